@@ -23,9 +23,14 @@ no data-path collective; the int64 error counters are summed with one all_reduce
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the predict recurrence):
 algorithmic FLOPs per launch (2 T [N_res (N_res+n_in+n_out) + n_out (N_res+n_in)]
-per frame) / mean launch duration measured with HIP events on the launch stream.  Beside the
-headline (fp16 operands, shared reservoir) the same line carries, measured in the same run on
-the same workload (N=1 only):
+per frame) / mean launch duration measured with HIP events on the launch stream.
+
+A plain run measures the headline alone: set-up, W warm-up steps, the K timed steps, the result line.
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0) as float64 .npy files
+after the timed steps: a fixed sample of the predicted outputs, a fixed sample of the readouts, and the
+per-block error / bit counters of that step; the inputs depend on the arguments only, so two builds can
+be compared output for output.  With `--full` (N=1 only) the line also carries, measured in the same run
+on the same workload:
     `precisions`   the step in float32 (exact f32 MFMA) and float64 (the reference's arithmetic)
     `reservoirs`   the fp16 step with one reservoir per coherence block (reference-faithful mode)
     `large_reservoir`  the fp16 step at N_res = 2048 (BASELINE configs[4]; one GEMM launch per timestep)
@@ -33,7 +38,7 @@ the same workload (N=1 only):
 this host on bounded samples of the same workload: one BLAS thread, default BLAS threads, and one
 single-threaded process per physical core over disjoint block shards (`value`).
 `sweep` is what a user of `DetectorSweep.run` gets: wall clock of an Eb/No sweep including the frame generator,
-training, detection and every host synchronisation.
+training, detection and every host synchronisation.  None of these run without `--full`.
 """
 import argparse
 import json
@@ -207,7 +212,8 @@ def spawn_ranks(n, argv):
 # one timed configuration of the step
 # ------------------------------------------------------------------------------------------------
 def run_config(torch, dist, params, *, precision, fit_precision, reservoirs, n_res, G, F, ebno, steps, warmup,
-               solve, rank, world, predict_only=False, pool=8):
+               solve, rank, world, predict_only=False, pool=8, capture=False):
+    """capture=True: the record also holds `outputs`, what the last timed step computed (see last_step_outputs)."""
     from esn_ofdm_mimo_amd.montecarlo import DetectorSweep, reduce_counters
     import numpy as np
     if fit_precision == "auto":
@@ -246,7 +252,10 @@ def run_config(torch, dist, params, *, precision, fit_precision, reservoirs, n_r
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    before_last = None
     for i in range(steps):
+        if capture and i == steps - 1:          # counters accumulate over the steps: keep those before the last one
+            before_last = (err.clone(), nb.clone())
         step(i, True)
     counters = torch.stack([err.sum(), nb.sum()]).view(1, 2)
     reduce_counters(counters, dist if world > 1 else None, world)
@@ -264,12 +273,41 @@ def run_config(torch, dist, params, *, precision, fit_precision, reservoirs, n_r
     fpf = flop_per_frame(n_res, sweep.n_in, sweep.n_out, T)
     achieved = fpf * frames / (kernel_ms * 1e-3) / 1e12
     c = counters.cpu().numpy()[0]
-    return dict(value=world * frames * steps / dt, ms_per_step=1e3 * dt / max(steps, 1),
+    outputs = last_step_outputs(torch, y_out, sweep.bank.W_out[:G], err, nb, before_last) if capture else None
+    return dict(outputs=outputs, value=world * frames * steps / dt, ms_per_step=1e3 * dt / max(steps, 1),
                 predict_kernel_ms=kernel_ms, predict_only_symbols_per_s=world * frames / (kernel_ms * 1e-3),
                 achieved_tflops=achieved, frac=achieved / PEAK_TFLOPS[precision], peak=PEAK_TFLOPS[precision],
                 ber=float(c[0]) / max(float(c[1]), 1.0), fit_groups_flagged=int(sweep.bank.fit_status.sum().item()),
                 frames_per_step=frames, blocks=G, fit_precision=fit_precision, flop_per_frame=fpf,
                 n_in=sweep.n_in, n_out=sweep.n_out, T=T)
+
+
+DUMP_FRAMES, DUMP_BLOCKS, DUMP_SEED = 2048, 128, 7
+
+
+def last_step_outputs(torch, y, w_out, err, nb, before_last):
+    """What a caller of the timed step receives from its last step, as float64 host arrays: a fixed, seeded sample
+    of the predicted outputs Y [frames, N, 2 n_t] and of the readouts W_out [blocks, n_out, N_res + n_in] (the whole
+    arrays are ~1.3 GB and ~70 MB), the row indices of both samples, and the per-block bit-error and bit counters."""
+    import numpy as np
+    rs = np.random.RandomState(DUMP_SEED)
+    fr = np.sort(rs.choice(y.shape[0], min(DUMP_FRAMES, y.shape[0]), replace=False))
+    bl = np.sort(rs.choice(w_out.shape[0], min(DUMP_BLOCKS, w_out.shape[0]), replace=False))
+
+    def pick(t, idx):
+        return t.index_select(0, torch.as_tensor(idx, device=t.device)).double().cpu().numpy()
+    if before_last is not None:
+        err, nb = err - before_last[0], nb - before_last[1]
+    return {"y_sample": pick(y, fr), "y_sample_frames": fr.astype(np.float64),
+            "w_out_sample": pick(w_out, bl), "w_out_sample_blocks": bl.astype(np.float64),
+            "bit_errors": err.double().cpu().numpy(), "bits": nb.double().cpu().numpy()}
+
+
+def dump_outputs(path, outputs):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def run_sweep(torch, params, *, precision, fit_precision, n_res, F, solve, reservoirs="shared", points=(6.0, 12.0, 18.0),
@@ -339,9 +377,13 @@ def main():
     ap.add_argument("--frames-per-block", type=int, default=0, help="0 = L of the reference (75 at N=128)")
     ap.add_argument("--ebno", type=float, default=12.0)
     ap.add_argument("--reservoirs", default="shared", choices=["shared", "per_block"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the f32 / f64 / per-block / N_res=2048 sub-records and the sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy (float64, ~21 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-blocks", type=int, default=24, help="cpu_baseline single-process sample: blocks of L frames (~10 s)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the f32 / f64 / per-block sub-records")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the f32 / f64 / per-block / N_res=2048 sub-records and the sweep")
     ap.add_argument("--predict-only", action="store_true", help="time the predict+detect leg only")
     ap.add_argument("--solve", default="auto", choices=["auto", "qr", "chol"])
     ap.add_argument("--dry-run", action="store_true",
@@ -366,7 +408,7 @@ def main():
     F = args.frames_per_block or params.coherence_symbols
 
     cpu = None
-    if not args.no_cpu_baseline and args.cpu_blocks > 0 and world == 1 and not profiler_attached():
+    if args.full and not args.no_cpu_baseline and args.cpu_blocks > 0 and world == 1 and not profiler_attached():
         # once, at N=1, before this process touches the GPU or BLAS
         cpu = cpu_baseline((params.n_t, params.n_r, params.n_sub, params.m), args.n_res, args.ebno, args.cpu_blocks, F)
 
@@ -384,10 +426,13 @@ def main():
     common = dict(n_res=args.n_res, F=F, ebno=args.ebno, solve=args.solve, rank=rank, world=world)
     head = run_config(torch, dist, params, precision=args.precision, fit_precision=args.fit_precision,
                       reservoirs=args.reservoirs, G=G, steps=args.steps, warmup=args.warmup,
-                      predict_only=args.predict_only, **common)
+                      predict_only=args.predict_only, capture=args.dump_outputs is not None and rank == 0, **common)
+    if head["outputs"] is not None:
+        dump_outputs(args.dump_outputs, head.pop("outputs"))
+    extra = args.full and not args.no_extra and world == 1 and not args.predict_only
 
     extra_prec, extra_res = {}, {}
-    if not args.no_extra and world == 1 and not args.predict_only:
+    if extra:
         def sub(rec, **note):
             keep = ("value", "ms_per_step", "predict_kernel_ms", "achieved_tflops", "peak", "frac", "ber", "blocks",
                     "frames_per_step", "fit_precision", "fit_groups_flagged")
@@ -408,7 +453,7 @@ def main():
                                                    "reservoirs; the reference draws one per block, SURVEY F5)")
 
     large = None
-    if not args.no_extra and world == 1 and not args.predict_only and args.n_res != 2048:
+    if extra and args.n_res != 2048:
         g_big = 512                                   # 512 x 80 slots = 160 frame tiles x 8 row tiles = 5 workgroups per CU
         rec = run_config(torch, dist, params, precision=args.precision, fit_precision=args.fit_precision,
                          reservoirs="shared", n_res=2048, G=g_big, steps=2, warmup=1, F=F, ebno=args.ebno,
@@ -421,7 +466,7 @@ def main():
                             "(predict_kernel_ms spans all of them)")
 
     sweep_rec = None
-    if not args.no_extra and world == 1 and not args.predict_only:
+    if extra:
         sweep_rec = run_sweep(torch, params, precision=args.precision, fit_precision=args.fit_precision,
                               n_res=args.n_res, F=F, solve=args.solve)
         sweep_rec["vs_headline"] = sweep_rec["value"] / head["value"]

@@ -1,6 +1,8 @@
 """bench.py prints ONE JSON line with the fields the driver and the judge read (task contract,
 section 4 of the tier framing): metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config.workload + roofline + cpu_baseline."""
+higher_is_better / scaling / vs_baseline / dtype / data / config.workload + roofline; with --full also
+cpu_baseline, sweep and the sub-records.  A plain run carries the headline alone and, with --dump-outputs,
+writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_small_run():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                          "--blocks", "64", "--cpu-blocks", "1"], capture_output=True, text=True, cwd=ROOT,
+                          "--blocks", "64", "--cpu-blocks", "1", "--full"], capture_output=True, text=True, cwd=ROOT,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -51,3 +53,29 @@ def test_bench_line_small_run():
     assert d["reservoirs"]["per_block"]["value"] > 0 and 0.15 < d["reservoirs"]["per_block"]["ber"] < 0.30
     # the detector works: BER of the 4x8 ESN at 12 dB is ~0.23 for both the GPU and the oracle sample
     assert 0.15 < d["ber"] < 0.30
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
+                          "--blocks", "64", "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                         cwd=ROOT, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 1 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "OFDM symbols/s"
+    assert abs(d["value"] - d["config"]["frames_per_step"] * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "sweep", "precisions", "reservoirs", "large_reservoir"):
+        assert k not in d, k
+    import numpy as np
+    a = {n: np.load(tmp_path / (n + ".npy")) for n in ("y_sample", "y_sample_frames", "w_out_sample",
+                                                        "w_out_sample_blocks", "bit_errors", "bits")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    frames = d["config"]["frames_per_step"]
+    assert a["y_sample"].shape == (len(a["y_sample_frames"]), 128, 8) and a["y_sample_frames"].max() < frames
+    assert a["w_out_sample"].shape[0] == len(a["w_out_sample_blocks"]) and a["w_out_sample"].shape[1] == 8
+    assert np.isfinite(a["y_sample"]).all() and np.isfinite(a["w_out_sample"]).all()
+    assert a["bit_errors"].shape == a["bits"].shape == (64,)
+    # one timed step: its counters are the line's BER
+    assert abs(a["bit_errors"].sum() / a["bits"].sum() - d["ber"]) < 1e-12
