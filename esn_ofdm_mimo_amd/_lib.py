@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("ESN_HIP_LIB") or os.path.join(_PKG, "libesn_hip.so") 
 F64, F32, F16, BF16 = 0, 1, 2, 3
 PRECISIONS = {"f64": F64, "f32": F32, "f16": F16, "bf16": BF16}
 NOISE_NONE, NOISE_TENSOR, NOISE_COUNTER = 0, 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 MEM_DEVICE, MEM_HOST = 0, 1
 
 
@@ -38,6 +38,9 @@ SIGNATURES = {
     "esn_predict_batch": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _vp, _dp, _dp, _dp, _dp, _dp,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
                                     C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _dp, _vp, C.c_size_t, _vp]),
+    "esn_predict_batch_f32": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _vp, _dp, _dp, _dp, _dp, _vp,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                        C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_size_t, _vp]),
     "esn_predict_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(Shape), C.c_int, C.c_int]),
     "esn_harvest_batch": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _dp, _dp, _dp, _dp, _dp, _dp,
                                     C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _dp,
@@ -58,6 +61,9 @@ SIGNATURES = {
                                C.c_uint64, C.c_uint64, _dp, _vp]),
     "esn_gen_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  _dp, _dp, C.c_double, _dp, _vp, _dp, C.c_uint64, C.c_uint64, _vp, _dp, _dp, _vp]),
+    "esn_gen_frames_c64": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, _dp, _dp, C.c_double, _dp, _vp, _dp, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
+                                     _vp]),
     "esn_channel_estimate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                        C.c_double, _vp, _dp, C.c_int, _dp, _vp]),
     "esn_mmse_detect_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
@@ -71,6 +77,8 @@ SIGNATURES = {
                                         C.c_double, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "esn_detect_count": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
                                    _vp, _vp, _dp, _vp]),
+    "esn_detect_count_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
+                                       _vp, _vp, _dp, _vp]),
 }
 # host-memory front ends: the arguments of esn_X behind a leading esn_mem_kind (include/esn_hip.h)
 for _name in ("esn_pack_weights", "esn_pack_readout", "esn_predict_batch", "esn_harvest_batch",

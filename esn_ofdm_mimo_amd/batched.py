@@ -254,11 +254,20 @@ class ReservoirBank:
 
     # ------------------------------------------------------------------ predict
     def predict(self, U, frames_per_group, T=None, transient=0, precision="f32", x0=None, y0=None,
-                noise_mode="counter", noise_u=None, seed=0, out=None, group_offset=0):
+                noise_mode="counter", noise_u=None, seed=0, out=None, group_offset=0, io="f64"):
         """U [B,T_in,n_in] (frames ordered by group) -> Y [B,T-transient,n_out] (device, unscaled).
-        group_offset: global index of group 0 (noise key and weight set follow the global group)."""
+        group_offset: global index of group 0 (noise key and weight set follow the global group).
+        io="f32": U and Y are float32 (esn_predict_batch_f32; a float32 U is used as it is, any other dtype is
+        converted once): Y is bitwise the float64 result rounded to float32.  Precisions f32 / f16 / bf16 only."""
         torch = self.torch
-        U = _as_dev(U, torch, self.device)
+        if io not in ("f64", "f32"):
+            raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
+        io32 = io == "f32"
+        if io32 and precision == "f64":
+            raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
+        U = _as_dev(U, torch, self.device, torch.float32 if io32 else None)
+        if io32 and U.data_ptr() % 16:          # (a view into a larger buffer: the kernels stage 16-byte chunks)
+            U = U.clone()
         b, t_in = U.shape[0], U.shape[1]
         T = t_in if T is None else int(T)
         if not (0 <= int(transient) < T and t_in <= T):
@@ -274,7 +283,10 @@ class ReservoirBank:
         nm, nz = self._noise_args(noise_mode, noise_u, (b, T, self.n_reservoir))
         with torch.cuda.device(self.device):
             if out is None:
-                out = torch.empty((b, T - transient, self.n_outputs), dtype=torch.float64, device=self.device)
+                out = torch.empty((b, T - transient, self.n_outputs), dtype=torch.float32 if io32 else torch.float64,
+                                  device=self.device)
+            elif out.dtype != (torch.float32 if io32 else torch.float64):
+                raise ValueError(f"out is {out.dtype}, io={io!r} writes {'float32' if io32 else 'float64'}")
             # reservoirs beyond 1024 units run one GEMM launch per step out of a caller-owned workspace
             wbytes = self.lib.esn_predict_workspace_bytes(PRECISIONS[precision], C.byref(self.shape), b,
                                                           int(frames_per_group))
@@ -283,12 +295,14 @@ class ReservoirBank:
                 ws = getattr(self, "_workspace", None)
                 if ws is None or ws.numel() < wbytes:
                     ws = self._workspace = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
-            check(self.lib.esn_predict_batch(
+            fn = self.lib.esn_predict_batch_f32 if io32 else self.lib.esn_predict_batch
+            check(fn(
                 PRECISIONS[precision], C.byref(self.shape), ptr(self.packed_weights(precision)),
                 ptr(self.packed_readout(precision)), ptr(self.in_scale), ptr(self.in_shift),
                 ptr(self.t_scale), ptr(self.t_shift), ptr(U), b, int(frames_per_group), t_in, T,
                 int(transient), ptr(x0), ptr(y0), self.noise, nm, ptr(nz), int(seed) & (2**64 - 1),
-                int(group_offset), ptr(out), ptr(ws), wbytes, _lib.stream_handle()), "esn_predict_batch")
+                int(group_offset), ptr(out), ptr(ws), wbytes, _lib.stream_handle()),
+                "esn_predict_batch_f32" if io32 else "esn_predict_batch")
             if wbytes and precision == "f64" and b == 1:
                 self._cluster_err = ws[wbytes - 64:wbytes - 60]      # error word of the single-sequence cluster kernel
         return out
@@ -307,9 +321,11 @@ class ReservoirBank:
     # ------------------------------------------------------------------ detector tail
     def detect_count(self, Y, tx_bits, p_i, frames_per_group, n_sub, n_t, bits_per_sym,
                      err=None, bits=None, want_xhat=False):
-        """Y [B,N,2 n_t] -> per-group int64 (errors, bits) accumulated into err/bits."""
+        """Y [B,N,2 n_t] -> per-group int64 (errors, bits) accumulated into err/bits.  A float32 Y (predict with
+        io="f32") is read as it is by esn_detect_count_f32: the counts and X_hat are those of the widened Y."""
         torch = self.torch
-        Y = _as_dev(Y, torch, self.device)
+        y32 = getattr(Y, "dtype", None) in (torch.float32, np.float32)
+        Y = _as_dev(Y, torch, self.device, torch.float32 if y32 else None)
         b = Y.shape[0]
         g = (b + frames_per_group - 1) // frames_per_group
         p_i = _as_dev(p_i, torch, self.device)
@@ -320,9 +336,10 @@ class ReservoirBank:
             if bits is None:
                 bits = torch.zeros(g, dtype=torch.int64, device=self.device)
             xh = torch.empty((b, n_sub, 2 * n_t), dtype=torch.float64, device=self.device) if want_xhat else None
-            check(self.lib.esn_detect_count(ptr(Y), b, int(frames_per_group), int(n_sub), int(n_t),
-                                            int(bits_per_sym), ptr(p_i), ptr(tx_bits), ptr(err), ptr(bits),
-                                            ptr(xh), _lib.stream_handle()), "esn_detect_count")
+            fn = self.lib.esn_detect_count_f32 if y32 else self.lib.esn_detect_count
+            check(fn(ptr(Y), b, int(frames_per_group), int(n_sub), int(n_t),
+                     int(bits_per_sym), ptr(p_i), ptr(tx_bits), ptr(err), ptr(bits),
+                     ptr(xh), _lib.stream_handle()), "esn_detect_count_f32" if y32 else "esn_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
     # ------------------------------------------------------------------ helpers

@@ -24,7 +24,8 @@ int launch_recur_rs(int precision, const RecurParams& p, size_t wo_rs_off, hipSt
 bool big_path_applies(int precision, const RecurParams& p);
 int big_slots(const RecurParams& p);
 size_t big_workspace_bytes(int n_slots, int Mp, int Kp);
-int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream);
+int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream,
+                     bool io32 = false);
 bool big_harvest_applies(int precision, const RecurParams& p);
 size_t big_harvest_workspace_bytes(int n_groups, int Kp);
 int launch_harvest_big(int precision, const RecurParams& p, void* workspace, hipStream_t stream);
@@ -34,13 +35,13 @@ size_t cluster_workspace_bytes(int n_res, int n_in, int n_out, bool harvest);
 int launch_recur_cluster(const RecurParams& p, void* workspace, hipStream_t stream);
 // esn_recur_mfma.hip
 bool mfma_geometry(int precision, int n_res, int n_in, int n_out, bool harvest, Geometry* g);
-int launch_recur_mfma(int precision, const RecurParams& p, hipStream_t stream);
+int launch_recur_mfma(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
 // esn_harvest_cluster.hip
 bool harvest_cluster_applies(int precision, const RecurParams& p);
 size_t harvest_cluster_workspace_bytes(int n_pilots, int C, int n_wsets);
 int launch_harvest_cluster(int precision, const RecurParams& p, int C, void* workspace, hipStream_t stream);
 // esn_recur_skew16.hip
-int launch_recur_skew16(int precision, const RecurParams& p, hipStream_t stream);
+int launch_recur_skew16(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
 // esn_pack.hip
 size_t packed_w_bytes(int precision, int n_res, int n_in, int n_out, const Geometry& g);
 size_t packed_wout_bytes(int precision, int n_res, int n_in, int n_out, const Geometry& g);
@@ -65,7 +66,7 @@ int launch_readout_chol_big(const double* E, const float* E32, const double* D, 
                             double* W_out, int* status, void* workspace, hipStream_t stream);
 // esn_gen.hip
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
-int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream);
+int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);
 // esn_baseline.hip
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);
 int launch_mmse_detect(const MmseParams& mp, hipStream_t stream);
@@ -75,7 +76,7 @@ int launch_ldpc_encode(const LdpcEncodeParams& ep, hipStream_t stream);
 int launch_qam_llr(const LlrParams& lp, hipStream_t stream);
 int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
 // esn_detect.hip
-int launch_detect_count(const DetectParams& dp, hipStream_t stream);
+int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
 }  // namespace esn
 
 using namespace esn;
@@ -184,7 +185,7 @@ extern "C" {
 
 const char* esn_last_error(void) { return g_err; }
 
-int esn_abi_version(void) { return 9; }
+int esn_abi_version(void) { return 10; }
 
 int esn_debug_set(const char* key, const char* value) {
     if (!key) return fail(-1, "esn_debug_set: null key");
@@ -307,21 +308,28 @@ static int fill_common(RecurParams& p, int precision, const esn_shape_t* shape, 
     return 0;
 }
 
-int esn_predict_batch(int precision, const esn_shape_t* shape, const void* packed_w, const void* packed_wout,
-                      const double* in_scale, const double* in_shift, const double* t_scale,
-                      const double* t_shift, const double* U, int n_frames, int frames_per_group, int T_in,
-                      int T, int transient, const double* x0, const double* y0, double noise, int noise_mode,
-                      const double* noise_u, uint64_t seed, uint64_t group_offset, double* Y, void* workspace,
-                      size_t workspace_bytes, void* stream) {
+// esn_predict_batch and esn_predict_batch_f32: io32 = float32 U / Y (fp32/fp16/bf16 precisions only)
+static int predict_common(const char* who, bool io32, int precision, const esn_shape_t* shape, const void* packed_w,
+                          const void* packed_wout, const double* in_scale, const double* in_shift,
+                          const double* t_scale, const double* t_shift, const void* U, int n_frames,
+                          int frames_per_group, int T_in, int T, int transient, const double* x0, const double* y0,
+                          double noise, int noise_mode, const double* noise_u, uint64_t seed, uint64_t group_offset,
+                          void* Y, void* workspace, size_t workspace_bytes, void* stream) {
+    if (io32 && precision == ESN_F64)
+        return fail(-2, "%s: float32 I/O is served for precisions f32 / f16 / bf16; ESN_F64 reads and writes float64 "
+                    "(esn_predict_batch)", who);
     RecurParams p;
-    int rc = fill_common(p, precision, shape, "esn_predict_batch");
+    int rc = fill_common(p, precision, shape, who);
     if (rc) return rc;
-    if (!packed_w || !packed_wout || !U || !Y) return fail(-1, "esn_predict_batch: null pointer");
+    if (!packed_w || !packed_wout || !U || !Y) return fail(-1, "%s: null pointer", who);
     if (n_frames <= 0 || frames_per_group <= 0 || T <= 0 || T_in < 0 || T_in > T || transient < 0 || transient >= T)
-        return fail(-1, "esn_predict_batch: invalid sizes (n_frames=%d F=%d T_in=%d T=%d transient=%d)",
-                    n_frames, frames_per_group, T_in, T, transient);
-    if (noise_mode == ESN_NOISE_TENSOR && !noise_u) return fail(-1, "esn_predict_batch: noise tensor missing");
-    if (noise_mode < ESN_NOISE_NONE || noise_mode > ESN_NOISE_COUNTER) return fail(-1, "esn_predict_batch: bad noise mode");
+        return fail(-1, "%s: invalid sizes (n_frames=%d F=%d T_in=%d T=%d transient=%d)",
+                    who, n_frames, frames_per_group, T_in, T, transient);
+    if (noise_mode == ESN_NOISE_TENSOR && !noise_u) return fail(-1, "%s: noise tensor missing", who);
+    if (noise_mode < ESN_NOISE_NONE || noise_mode > ESN_NOISE_COUNTER) return fail(-1, "%s: bad noise mode", who);
+    // (float32 rows are staged in 16-byte chunks of four inputs when n_in is a multiple of 4, else in 4-byte ones)
+    if (io32 && ((uintptr_t)U & ((shape->n_in & 3) == 0 ? 15 : 3)) != 0)
+        return fail(-1, "%s: U must be %d-byte aligned", who, (shape->n_in & 3) == 0 ? 16 : 4);
     p.n_frames = n_frames;
     p.F = frames_per_group;
     p.n_groups = (n_frames + frames_per_group - 1) / frames_per_group;
@@ -345,35 +353,36 @@ int esn_predict_batch(int precision, const esn_shape_t* shape, const void* packe
     p.T_in = T_in; p.S = T; p.in_row_off = 0; p.transient = transient; p.harvest = 0;
     p.packed_w = packed_w; p.packed_wout = packed_wout;
     p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift;
-    p.U = U; p.x0 = x0; p.y0 = y0; p.noise_u = noise_u;
+    if (io32) p.U32 = static_cast<const float*>(U); else p.U = static_cast<const double*>(U);
+    p.x0 = x0; p.y0 = y0; p.noise_u = noise_u;
     p.noise = noise; p.noise_mode = (noise == 0.0) ? ESN_NOISE_NONE : noise_mode; p.seed = seed;
     p.frame_off = (uint32_t)(group_offset * (uint64_t)frames_per_group);
     p.wset_rot = (int)(group_offset % (uint64_t)p.n_wsets);
-    if (((uintptr_t)Y & 15) != 0) return fail(-1, "esn_predict_batch: Y must be 16-byte aligned");
-    p.Y = Y;
+    if (((uintptr_t)Y & 15) != 0) return fail(-1, "%s: Y must be 16-byte aligned", who);
+    if (io32) p.Y32 = static_cast<float*>(Y); else p.Y = static_cast<double*>(Y);
     ESN_SET_STAMPS(p);
     // ONE float64 sequence (the reference's own call pattern): the matrix resident in the LDS of a cluster of
     // workgroups that exchange the state through L2 every step (esn_recur_cluster.hip), when a workspace is lent
     if (workspace && knobs().cluster && cluster_applies(precision, p)) {
         const size_t need = cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, false);
         if (workspace_bytes < need)
-            return fail(-1, "esn_predict_batch: workspace holds %zu bytes, esn_predict_workspace_bytes says %zu",
-                        workspace_bytes, need);
-        return hip_fail(launch_recur_cluster(p, workspace, (hipStream_t)stream), "esn_predict_batch");
+            return fail(-1, "%s: workspace holds %zu bytes, esn_predict_workspace_bytes says %zu",
+                        who, workspace_bytes, need);
+        return hip_fail(launch_recur_cluster(p, workspace, (hipStream_t)stream), who);
     }
     // large reservoirs: one GEMM launch per step when the caller lends a workspace (else the persistent kernel)
     if (workspace && knobs().big_gemm && p.g.big && big_path_applies(precision, p)) {
         const size_t need = big_workspace_bytes(big_slots(p), p.g.Mp, p.g.Kp);
         if (workspace_bytes < need)
-            return fail(-1, "esn_predict_batch: workspace holds %zu bytes, esn_predict_workspace_bytes says %zu",
-                        workspace_bytes, need);
+            return fail(-1, "%s: workspace holds %zu bytes, esn_predict_workspace_bytes says %zu",
+                        who, workspace_bytes, need);
         p.Fpad = round_up(p.F, 16);
         return hip_fail(launch_recur_big(precision, p, wout_big_offset(precision, p.n_out, p.g), workspace,
-                                         (hipStream_t)stream), "esn_predict_batch");
+                                         (hipStream_t)stream, io32), who);
     }
     // N_res 257..512, fp16/bf16: state in registers, one wave per SIMD (tiles of 128 slots like the skewed kernel)
 #ifdef ESN_WITH_RS
-    if (knobs().rs && rs_path_applies(precision, p) &&
+    if (!io32 && knobs().rs && rs_path_applies(precision, p) &&
         (size_t)n_frames * (T - transient) * p.n_out * 8 < 0x7fffffffu &&
         (size_t)p.n_groups * p.wout_stride < 0x7fffffffu)         // its buffer descriptors are 31-bit
         return hip_fail(launch_recur_rs(precision, p, wout_big_offset(precision, p.n_out, p.g), (hipStream_t)stream),
@@ -381,11 +390,33 @@ int esn_predict_batch(int precision, const esn_shape_t* shape, const void* packe
 #endif
     // N_res 257..512, fp16/bf16: the skewed schedule on 16x16x32 MFMAs (the chip holds a higher clock on that shape)
     if (p.g.s16 && p.g.skew && knobs().s16 && (precision == ESN_F16 || precision == ESN_BF16))
-        return hip_fail(launch_recur_skew16(precision, p, (hipStream_t)stream), "esn_predict_batch");
+        return hip_fail(launch_recur_skew16(precision, p, (hipStream_t)stream, io32), who);
     int e = m64 ? launch_recur_f64_mfma(p, (hipStream_t)stream)
             : (precision == ESN_F64) ? launch_recur_f64(p, (hipStream_t)stream)
-                                     : launch_recur_mfma(precision, p, (hipStream_t)stream);
-    return hip_fail(e, "esn_predict_batch");
+                                     : launch_recur_mfma(precision, p, (hipStream_t)stream, io32);
+    return hip_fail(e, who);
+}
+
+int esn_predict_batch(int precision, const esn_shape_t* shape, const void* packed_w, const void* packed_wout,
+                      const double* in_scale, const double* in_shift, const double* t_scale,
+                      const double* t_shift, const double* U, int n_frames, int frames_per_group, int T_in,
+                      int T, int transient, const double* x0, const double* y0, double noise, int noise_mode,
+                      const double* noise_u, uint64_t seed, uint64_t group_offset, double* Y, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return predict_common("esn_predict_batch", false, precision, shape, packed_w, packed_wout, in_scale, in_shift,
+                          t_scale, t_shift, U, n_frames, frames_per_group, T_in, T, transient, x0, y0, noise,
+                          noise_mode, noise_u, seed, group_offset, Y, workspace, workspace_bytes, stream);
+}
+
+int esn_predict_batch_f32(int precision, const esn_shape_t* shape, const void* packed_w, const void* packed_wout,
+                          const double* in_scale, const double* in_shift, const double* t_scale,
+                          const double* t_shift, const float* U, int n_frames, int frames_per_group, int T_in,
+                          int T, int transient, const double* x0, const double* y0, double noise, int noise_mode,
+                          const double* noise_u, uint64_t seed, uint64_t group_offset, float* Y, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return predict_common("esn_predict_batch_f32", true, precision, shape, packed_w, packed_wout, in_scale, in_shift,
+                          t_scale, t_shift, U, n_frames, frames_per_group, T_in, T, transient, x0, y0, noise,
+                          noise_mode, noise_u, seed, group_offset, Y, workspace, workspace_bytes, stream);
 }
 
 size_t esn_predict_workspace_bytes(int precision, const esn_shape_t* shape, int n_frames, int frames_per_group) {
@@ -560,22 +591,38 @@ int esn_readout_solve_chol_batch_f32(const float* E, const double* D, int n_grou
                        t_shift, W_out, status, workspace, workspace_bytes, stream);
 }
 
-int esn_detect_count(const double* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
-                     const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
-                     double* X_hat, void* stream) {
-    if (!Y || !p_i || !tx_bits || !err_count || !bit_count) return fail(-1, "esn_detect_count: null pointer");
-    if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0) return fail(-1, "esn_detect_count: invalid sizes");
+static int detect_common(const char* who, bool io32, const void* Y, int n_frames, int frames_per_group, int n_sub,
+                         int n_t, int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
+                         long long* bit_count, double* X_hat, void* stream) {
+    if (!Y || !p_i || !tx_bits || !err_count || !bit_count) return fail(-1, "%s: null pointer", who);
+    if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0) return fail(-1, "%s: invalid sizes", who);
     int log2n = 0;
     while ((1 << log2n) < n_sub) ++log2n;
     if ((1 << log2n) != n_sub || n_sub < 2 || n_sub > 2048)
-        return fail(-1, "esn_detect_count: N=%d must be a power of two in [2, 2048]", n_sub);
+        return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
     if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
-        return fail(-1, "esn_detect_count: bits_per_sym=%d must be even (square QAM)", bits_per_sym);
+        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
+    if (io32 && ((uintptr_t)Y & 7) != 0) return fail(-1, "%s: Y must be 8-byte aligned", who);
     DetectParams dp;
-    dp.Y = Y; dp.n_frames = n_frames; dp.frames_per_group = frames_per_group; dp.n_sub = n_sub;
+    if (io32) dp.Y32 = static_cast<const float*>(Y); else dp.Y = static_cast<const double*>(Y);
+    dp.n_frames = n_frames; dp.frames_per_group = frames_per_group; dp.n_sub = n_sub;
     dp.log2n = log2n; dp.n_t = n_t; dp.m = bits_per_sym; dp.p_i = p_i; dp.tx_bits = tx_bits;
     dp.err = err_count; dp.bits = bit_count; dp.X_hat = X_hat;
-    return hip_fail(launch_detect_count(dp, (hipStream_t)stream), "esn_detect_count");
+    return hip_fail(launch_detect_count(dp, (hipStream_t)stream, io32), who);
+}
+
+int esn_detect_count(const double* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                     const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                     double* X_hat, void* stream) {
+    return detect_common("esn_detect_count", false, Y, n_frames, frames_per_group, n_sub, n_t, bits_per_sym, p_i,
+                         tx_bits, err_count, bit_count, X_hat, stream);
+}
+
+int esn_detect_count_f32(const float* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                         const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                         double* X_hat, void* stream) {
+    return detect_common("esn_detect_count_f32", true, Y, n_frames, frames_per_group, n_sub, n_t, bits_per_sym, p_i,
+                         tx_bits, err_count, bit_count, X_hat, stream);
 }
 
 static const double kTdlbDelay[23] = {0.0000, 0.1072, 0.2155, 0.2095, 0.2870, 0.2986, 0.3752, 0.5055, 0.3681,
@@ -615,29 +662,49 @@ int esn_gen_taps(int kind, int n_blocks, int n_r, int n_t, int isi, double fs_hz
     return hip_fail(launch_gen_taps(tp, (hipStream_t)stream), "esn_gen_taps");
 }
 
-int esn_gen_frames(int n_frames, int frames_per_block, int n_sub, int cp, int n_t, int n_r, int isi,
-                   int bits_per_sym, int ls_pattern, const double* p_i, const double* a_clip, double no, const double* taps,
-                   const uint8_t* bits_in, const double* noise_in, uint64_t seed, uint64_t frame_offset,
-                   uint8_t* bits, double* x_cp, double* y_cp, void* stream) {
-    if (!p_i || !a_clip || !taps || !bits || !y_cp) return fail(-1, "esn_gen_frames: null pointer");
+static int gen_common(const char* who, bool c64, int n_frames, int frames_per_block, int n_sub, int cp, int n_t,
+                      int n_r, int isi, int bits_per_sym, int ls_pattern, const double* p_i, const double* a_clip,
+                      double no, const double* taps, const uint8_t* bits_in, const double* noise_in, uint64_t seed,
+                      uint64_t frame_offset, uint8_t* bits, void* x_cp, void* y_cp, void* stream) {
+    if (!p_i || !a_clip || !taps || !bits || !y_cp) return fail(-1, "%s: null pointer", who);
     int log2n = 0;
     while ((1 << log2n) < n_sub) ++log2n;
     if ((1 << log2n) != n_sub || n_sub < 2 || n_sub > 2048)
-        return fail(-1, "esn_gen_frames: N=%d must be a power of two in [2, 2048]", n_sub);
+        return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
     if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
-        return fail(-1, "esn_gen_frames: bits_per_sym=%d must be even (square QAM)", bits_per_sym);
+        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
     if (n_frames <= 0 || frames_per_block <= 0 || cp < 0 || cp >= n_sub || n_t <= 0 || n_r <= 0 || isi <= 0)
-        return fail(-1, "esn_gen_frames: invalid sizes");
+        return fail(-1, "%s: invalid sizes", who);
+    if (c64 && ((((uintptr_t)y_cp) | ((uintptr_t)x_cp)) & 7) != 0)
+        return fail(-1, "%s: x_cp / y_cp must be 8-byte aligned (complex64)", who);
     FrameGenParams fp;
     fp.n_frames = n_frames; fp.frames_per_block = frames_per_block; fp.n_sub = n_sub; fp.log2n = log2n;
     fp.cp = cp; fp.n_t = n_t; fp.n_r = n_r; fp.isi = isi; fp.m = bits_per_sym;
     fp.p_i = p_i; fp.a_clip = a_clip; fp.no = no; fp.taps = taps; fp.bits_in = bits_in; fp.noise_in = noise_in;
-    fp.seed = seed; fp.frame_offset = frame_offset; fp.bits = bits; fp.x_cp = x_cp; fp.y_cp = y_cp;
+    fp.seed = seed; fp.frame_offset = frame_offset; fp.bits = bits;
+    if (c64) { fp.x_cp32 = static_cast<float*>(x_cp); fp.y_cp32 = static_cast<float*>(y_cp); }
+    else { fp.x_cp = static_cast<double*>(x_cp); fp.y_cp = static_cast<double*>(y_cp); }
     fp.ls_pattern = ls_pattern ? 1 : 0;
     fp.ko = knobs().gen_ko;
-    int e = launch_gen_frames(fp, (hipStream_t)stream);
-    if (e == -1) return fail(-2, "esn_gen_frames: frame does not fit LDS");
-    return hip_fail(e, "esn_gen_frames");
+    int e = launch_gen_frames(fp, (hipStream_t)stream, c64);
+    if (e == -1) return fail(-2, "%s: frame does not fit LDS", who);
+    return hip_fail(e, who);
+}
+
+int esn_gen_frames(int n_frames, int frames_per_block, int n_sub, int cp, int n_t, int n_r, int isi,
+                   int bits_per_sym, int ls_pattern, const double* p_i, const double* a_clip, double no, const double* taps,
+                   const uint8_t* bits_in, const double* noise_in, uint64_t seed, uint64_t frame_offset,
+                   uint8_t* bits, double* x_cp, double* y_cp, void* stream) {
+    return gen_common("esn_gen_frames", false, n_frames, frames_per_block, n_sub, cp, n_t, n_r, isi, bits_per_sym,
+                      ls_pattern, p_i, a_clip, no, taps, bits_in, noise_in, seed, frame_offset, bits, x_cp, y_cp, stream);
+}
+
+int esn_gen_frames_c64(int n_frames, int frames_per_block, int n_sub, int cp, int n_t, int n_r, int isi,
+                       int bits_per_sym, int ls_pattern, const double* p_i, const double* a_clip, double no,
+                       const double* taps, const uint8_t* bits_in, const double* noise_in, uint64_t seed,
+                       uint64_t frame_offset, uint8_t* bits, float* x_cp, float* y_cp, void* stream) {
+    return gen_common("esn_gen_frames_c64", true, n_frames, frames_per_block, n_sub, cp, n_t, n_r, isi, bits_per_sym,
+                      ls_pattern, p_i, a_clip, no, taps, bits_in, noise_in, seed, frame_offset, bits, x_cp, y_cp, stream);
 }
 
 static int pow2_log(int n) { int l = 0; while ((1 << l) < n) ++l; return ((1 << l) == n) ? l : -1; }

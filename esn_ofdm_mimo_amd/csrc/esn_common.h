@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/esn_hip.h"
 
 namespace esn {
@@ -60,7 +61,8 @@ struct RecurParams {
     size_t w16_off, wo16_off;                     // g.s16: byte offset of the 16x16x32 kernel's images
     const double* in_scale; const double* in_shift;
     const double* t_scale;  const double* t_shift;
-    const double* U; const double* D;
+    union { const double* U; const float* U32; };   // U32: predict with float32 I/O (esn_predict_batch_f32)
+    const double* D;
     const double* x0; const double* y0;
     const double* noise_u;
     double noise; int noise_mode; uint64_t seed;
@@ -68,13 +70,15 @@ struct RecurParams {
     uint32_t frame_off;    // counter noise: global index of this launch's frame 0 (= group_offset * F, mod 2^32), so a
                            // frame draws the same noise whichever launch, chunk or rank it lands in
     int wset_rot;          // n_wsets > 1: group g uses weight set (g + wset_rot) % n_wsets (= group_offset % n_wsets)
-    double* Y; double* E;
+    union { double* Y; float* Y32; };               // Y32: predict with float32 I/O
+    double* E;
     float* E32;            // harvest: when set, the extended states are stored as float32 here (E unused)
     unsigned long long* stamps;   // diagnostic build (-DESN_STAMPS) only: [block0 wave][8] cycle sums
 };
 
 struct DetectParams {
-    const double* Y; int n_frames, frames_per_group, n_sub, log2n, n_t, m;
+    union { const double* Y; const float* Y32; };   // Y32: esn_detect_count_f32 (widened on load)
+    int n_frames, frames_per_group, n_sub, log2n, n_t, m;
     const double* p_i; const uint8_t* tx_bits;
     long long* err; long long* bits; double* X_hat;
     int na_wg;             // antennas per workgroup (set by the launcher: all of them unless LDS is short)
@@ -103,8 +107,8 @@ struct FrameGenParams {
     const double* noise_in;   // optional complex [B][T][n_r], unit-variance real and imaginary parts
     uint64_t seed; uint64_t frame_offset;
     uint8_t* bits;            // [B][N*m][n_t]
-    double* x_cp;             // optional complex [B][T][n_t] (pre-PA: the ESN teacher)
-    double* y_cp;             // complex [B][T][n_r]
+    union { double* x_cp; float* x_cp32; };   // optional complex [B][T][n_t] (pre-PA: the ESN teacher); x_cp32 complex64
+    union { double* y_cp; float* y_cp32; };   // complex [B][T][n_r]; y_cp32: complex64 (esn_gen_frames_c64)
     int ls_pattern;           // 1: sparse LS pilot, subcarrier sc carries only tx = sc % n_t (driver:330-333)
     int ko;                   // diagnostic (esn_debug_set "gen_ko"): bit0 no AWGN draw, bit1 no channel MACs, bit2 no IFFT, bit3 no PA
 };
@@ -185,6 +189,17 @@ __device__ __forceinline__ int slot_frame(const RecurParams& p, int slot, int& g
     grp = slot_group(p, slot, j);
     const int fr = grp * p.F + j;
     return (j < p.F && grp < p.n_groups && fr < p.n_frames) ? fr : -1;
+}
+
+// predict I/O element: float64 (esn_predict_batch) or float32 (esn_predict_batch_f32).  The kernels narrow every
+// input to float (or scale it in double) before any arithmetic, so a float32 input widened to double gives the same
+// recurrence; the float32 output is the rounded float64 one.
+template <bool IO32> using io_elem = typename std::conditional<IO32, float, double>::type;
+template <bool IO32> __device__ __forceinline__ const io_elem<IO32>* in_ptr(const RecurParams& p) {
+    if constexpr (IO32) return p.U32; else return p.U;
+}
+template <bool IO32> __device__ __forceinline__ io_elem<IO32>* out_ptr(const RecurParams& p) {
+    if constexpr (IO32) return p.Y32; else return p.Y;
 }
 
 inline __host__ __device__ int round_up(int x, int m) { return (x + m - 1) / m * m; }

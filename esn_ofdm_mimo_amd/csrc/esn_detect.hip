@@ -14,6 +14,9 @@ namespace esn {
 // (same sincospi arguments as the reference order).  The radix-2 stages are taken two at a time
 // on four points in registers -- the same butterflies in the same order, so the spectrum is
 // bit-identical to the plain radix-2 loop, with half the LDS round trips and barriers.
+// IO32: float32 Y (esn_detect_count_f32), widened on load into the same float64 buffer -- counts and X_hat are those
+// of the float64 entry point on the widened Y
+template <bool IO32>
 __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
     const int N = dp.n_sub, n_t = dp.n_t, tid = threadIdx.x, half = N >> 1;
@@ -29,6 +32,7 @@ __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
     const int na = (n_t - a0 < na_max) ? n_t - a0 : na_max;
     const int group = frame / dp.frames_per_group;
     const double2* y = reinterpret_cast<const double2*>(dp.Y) + (size_t)frame * N * n_t;
+    const float2* y32 = reinterpret_cast<const float2*>(dp.Y32) + (size_t)frame * N * n_t;
 
     // transmitted bits of the elements this thread will slice (the m x n_t bytes of a subcarrier are contiguous), fetched
     // NOW: the slicer at the end would otherwise pay a second global round trip behind the FFT
@@ -51,7 +55,12 @@ __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
     for (int i = tid; i < N * na; i += nthr) {               // bit-reversed load, element i = (row, antenna)
         const int row = i / na, ant = i - row * na;
         const int rv = (int)(__brev((unsigned)row) >> (32 - dp.log2n));
-        buf[ant * ld + rv] = y[(size_t)row * n_t + a0 + ant];
+        if constexpr (IO32) {
+            const float2 v = y32[(size_t)row * n_t + a0 + ant];
+            buf[ant * ld + rv] = make_double2((double)v.x, (double)v.y);
+        } else {
+            buf[ant * ld + rv] = y[(size_t)row * n_t + a0 + ant];
+        }
     }
     __syncthreads();
     const int lane = tid & 63, wv = tid >> 6;
@@ -134,7 +143,7 @@ __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
     }
 }
 
-int launch_detect_count(const DetectParams& dp_in, hipStream_t stream) {
+int launch_detect_count(const DetectParams& dp_in, hipStream_t stream, bool io32) {
     DetectParams dp = dp_in;
     int na = dp.n_t < 16 ? dp.n_t : 16;                      // antennas per workgroup
     auto lds_of = [&](int a) { return sizeof(double2) * ((size_t)a * (dp.n_sub + 1) + dp.n_sub / 2); };
@@ -143,10 +152,13 @@ int launch_detect_count(const DetectParams& dp_in, hipStream_t stream) {
     if (lds > 150 * 1024) return -1;
     const int n_chunks = (dp.n_t + na - 1) / na;
     dp.na_wg = na;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detect_count_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void* kern = io32 ? reinterpret_cast<const void*>(detect_count_kernel<true>)
+                            : reinterpret_cast<const void*>(detect_count_kernel<false>);
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(detect_count_kernel, dim3(dp.n_frames * n_chunks), dim3(32 * na < 64 ? 64 : 32 * na), lds, stream, dp);
+    const dim3 grid(dp.n_frames * n_chunks), block(32 * na < 64 ? 64 : 32 * na);
+    if (io32) hipLaunchKernelGGL(detect_count_kernel<true>, grid, block, lds, stream, dp);
+    else hipLaunchKernelGGL(detect_count_kernel<false>, grid, block, lds, stream, dp);
     return (int)hipGetLastError();
 }
 

@@ -113,6 +113,8 @@ __global__ void gen_taps_kernel(TapParams tp) {
 constexpr int GEN_RXG = 4;      // receive antennas per wave task
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
+// C64: complex64 x_cp / y_cp (esn_gen_frames_c64) -- the same float64 arithmetic, rounded at the store
+template <bool C64>
 __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
     const int N = fp.n_sub, T = N + fp.cp, n_t = fp.n_t, n_r = fp.n_r, isi = fp.isi, m = fp.m;
@@ -223,7 +225,9 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
         const int n = (t < fp.cp) ? (N - fp.cp + t) : (t - fp.cp);
         const double2 v = X[(size_t)tx * N + n];
         const double xr = v.x * sp, xi = v.y * sp;
-        if (fp.x_cp) {
+        if (C64 && fp.x_cp32) {
+            reinterpret_cast<float2*>(fp.x_cp32)[((size_t)frame * T + t) * n_t + tx] = make_float2((float)xr, (float)xi);
+        } else if (!C64 && fp.x_cp) {
             fp.x_cp[((size_t)frame * T + t) * n_t * 2 + 2 * tx] = xr;
             fp.x_cp[((size_t)frame * T + t) * n_t * 2 + 2 * tx + 1] = xi;
         }
@@ -305,11 +309,26 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
                 box_muller_fast(w[0], w[1], nr[0], ni[0]);
                 box_muller_fast(w[2], w[3], nr[1], ni[1]);
             }
+            if constexpr (C64) {
+                // complex64: the antenna pair is ONE 16-byte store (n_r even, y_cp 16-byte aligned: the pair starts on a boundary)
+                const size_t o = ((size_t)frame * T + t) * n_r + rx;
+                const float2 v0 = make_float2((float)(yr[q] + sig * nr[0]), (float)(yi[q] + sig * ni[0]));
+                if (rx + 1 < n_r && (n_r & 1) == 0 && ((uintptr_t)fp.y_cp32 & 15) == 0) {
+                    const float2 v1 = make_float2((float)(yr[q + 1] + sig * nr[1]), (float)(yi[q + 1] + sig * ni[1]));
+                    *reinterpret_cast<float4*>(fp.y_cp32 + 2 * o) = make_float4(v0.x, v0.y, v1.x, v1.y);
+                } else {
+                    reinterpret_cast<float2*>(fp.y_cp32)[o] = v0;
+                    if (rx + 1 < n_r)
+                        reinterpret_cast<float2*>(fp.y_cp32)[o + 1] =
+                            make_float2((float)(yr[q + 1] + sig * nr[1]), (float)(yi[q + 1] + sig * ni[1]));
+                }
+            } else {
 #pragma unroll
-            for (int d = 0; d < 2; ++d)
-                if (rx + d < n_r)
-                    reinterpret_cast<double2*>(fp.y_cp)[((size_t)frame * T + t) * n_r + rx + d] =
-                        make_double2(yr[q + d] + sig * nr[d], yi[q + d] + sig * ni[d]);
+                for (int d = 0; d < 2; ++d)
+                    if (rx + d < n_r)
+                        reinterpret_cast<double2*>(fp.y_cp)[((size_t)frame * T + t) * n_r + rx + d] =
+                            make_double2(yr[q + d] + sig * nr[d], yi[q + d] + sig * ni[d]);
+            }
         }
     }
 }
@@ -320,15 +339,17 @@ int launch_gen_taps(const TapParams& tp, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream) {
+int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64) {
     const int T = fp.n_sub + fp.cp;
     const size_t lds = sizeof(double2) * ((size_t)fp.n_t * fp.n_sub + (size_t)fp.n_t * T + fp.n_sub / 2 +
                                           (size_t)fp.n_r * fp.n_t * fp.isi);
     if (lds > 150 * 1024) return -1;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gen_frames_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void* kern = c64 ? reinterpret_cast<const void*>(gen_frames_kernel<true>)
+                           : reinterpret_cast<const void*>(gen_frames_kernel<false>);
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(gen_frames_kernel, dim3(fp.n_frames), dim3(256), lds, stream, fp);
+    if (c64) hipLaunchKernelGGL(gen_frames_kernel<true>, dim3(fp.n_frames), dim3(256), lds, stream, fp);
+    else hipLaunchKernelGGL(gen_frames_kernel<false>, dim3(fp.n_frames), dim3(256), lds, stream, fp);
     return (int)hipGetLastError();
 }
 

@@ -89,7 +89,8 @@ __global__ void big_init_kernel(BigParams bp, char* x0_img, char* x1_img) {
 //   s <  S:  [U_s ; F_s = Y_s] -> k-groups nkgS, nkgS+1 of the image GEMM launch s reads (bp.x_out here)
 // U_{s-1} is read back from the image of the previous step (bp.x_in), in the operand type -- the same
 // rounded inputs the persistent kernels multiply with W_out.
-template <typename TR>
+// IO32: float32 U / Y (esn_predict_batch_f32): U widened on load, Y rounded from the double the float64 path writes
+template <typename TR, bool IO32 = false>
 __global__ __launch_bounds__(256) void big_prep_kernel(BigParams bp) {
     __shared__ float wou[17 * 128];                       // (W_out gain)[:, inputs] of the block's groups
     __shared__ float inv_gain[17];
@@ -135,21 +136,24 @@ __global__ __launch_bounds__(256) void big_prep_kernel(BigParams bp) {
     const int row_c = row < p.T_in ? row : 0;
     const bool has_isc = p.in_scale != nullptr, has_ish = p.in_shift != nullptr, has_y0 = p.y0 != nullptr,
                has_tsc = p.t_scale != nullptr, has_tsh = p.t_shift != nullptr;
-    const double* sc_in = p.in_scale ? p.in_scale : p.U;       // (any valid address; the value is masked below)
-    const double* sh_in = p.in_shift ? p.in_shift : p.U;
+    // (any valid address; the value is masked below.  float32 I/O: U holds half the bytes it would as float64, so the
+    //  packed read-out stands in -- a group's image is far more than the 16 doubles per group read through it)
+    const double* dummy = IO32 ? reinterpret_cast<const double*>(p.packed_wout) : p.U;
+    const double* sc_in = p.in_scale ? p.in_scale : dummy;
+    const double* sh_in = p.in_shift ? p.in_shift : dummy;
     float uu[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int ic = i < n_in ? i : 0;
-        const double raw = p.U[(fr_c * p.T_in + row_c) * n_in + ic];
+        const double raw = (double)in_ptr<IO32>(p)[(fr_c * p.T_in + row_c) * n_in + ic];
         const float scv = (float)sc_in[grp_c * n_in + ic], shv = (float)sh_in[grp_c * n_in + ic];   // loaded, then masked
         const float sc = has_isc ? scv : 1.f, sh = has_ish ? shv : 0.f;
         const float v = fmaf(row < p.T_in ? (float)raw : 0.f, sc, sh);       // rows past T_in: zeros BEFORE scaling
         uu[i] = (live && i < n_in) ? v : 0.f;
     }
-    const double* y0p = p.y0 ? p.y0 : p.U;
-    const double* tsc = p.t_scale ? p.t_scale : p.U;
-    const double* tsh = p.t_shift ? p.t_shift : p.U;
+    const double* y0p = p.y0 ? p.y0 : dummy;
+    const double* tsc = p.t_scale ? p.t_scale : dummy;
+    const double* tsh = p.t_shift ? p.t_shift : dummy;
     const int orow = s - 1 - p.transient;
     const int out_rows = p.S - p.transient;
     float yy[8];
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(256) void big_prep_kernel(BigParams bp) {
         const double sc = has_tsc ? tscl : 1.0;
         const double sh = has_tsh ? tshl : 0.0;
         if (live && o < n_out && s > 0 && orow >= 0)
-            p.Y[((size_t)fr * out_rows + orow) * n_out + o] = ((double)y - sh) / sc;
+            out_ptr<IO32>(p)[((size_t)fr * out_rows + orow) * n_out + o] = (io_elem<IO32>)(((double)y - sh) / sc);
         yy[o] = (live && o < n_out) ? y : 0.f;
     }
     if (s < p.S) {
@@ -446,7 +450,7 @@ __global__ __launch_bounds__(1024 / NT) void big_step_kernel(BigParams bp) {
     }
 }
 
-template <typename TR>
+template <typename TR, bool IO32>
 static int launch_big_t(const RecurParams& rp, size_t wo_big_off, void* workspace, hipStream_t stream) {
     BigParams bp;
     bp.r = rp;
@@ -484,7 +488,7 @@ static int launch_big_t(const RecurParams& rp, size_t wo_big_off, void* workspac
         bp.x_in = X[(s + 1) & 1];          // previous step's image: its [U;F] group holds U_{s-1}
         bp.x_out = X[s & 1];
         bp.yp_in = YP[s & 1];
-        hipLaunchKernelGGL(big_prep_kernel<TR>, dim3(bp.n_slots / 256), dim3(256), 0, stream, bp);
+        hipLaunchKernelGGL((big_prep_kernel<TR, IO32>), dim3(bp.n_slots / 256), dim3(256), 0, stream, bp);
         if (s == rp.S) break;
         bp.x_in = X[s & 1]; bp.x_out = X[(s + 1) & 1];
         bp.yp_out = YP[(s + 1) & 1];
@@ -858,9 +862,14 @@ int launch_harvest_big(int precision, const RecurParams& p, void* workspace, hip
     return -1;
 }
 
-int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream) {
-    if (precision == ESN_F16) return launch_big_t<TraitsF16>(p, wo_big_off, workspace, stream);
-    if (precision == ESN_BF16) return launch_big_t<TraitsBF16>(p, wo_big_off, workspace, stream);
+int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream,
+                     bool io32) {
+    if (precision == ESN_F16)
+        return io32 ? launch_big_t<TraitsF16, true>(p, wo_big_off, workspace, stream)
+                    : launch_big_t<TraitsF16, false>(p, wo_big_off, workspace, stream);
+    if (precision == ESN_BF16)
+        return io32 ? launch_big_t<TraitsBF16, true>(p, wo_big_off, workspace, stream)
+                    : launch_big_t<TraitsBF16, false>(p, wo_big_off, workspace, stream);
     return -1;
 }
 

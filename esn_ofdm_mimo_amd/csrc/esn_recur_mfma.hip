@@ -6,9 +6,9 @@
 
 namespace esn {
 
-int launch_recur_mfma_f32(const RecurParams& p, hipStream_t stream);
-int launch_recur_mfma_f16(const RecurParams& p, hipStream_t stream);
-int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream);
+int launch_recur_mfma_f32(const RecurParams& p, hipStream_t stream, bool io32);
+int launch_recur_mfma_f16(const RecurParams& p, hipStream_t stream, bool io32);
+int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream, bool io32);
 
 // Tiling table: (NW, MT, NT) per precision and reservoir size.  Constraints:
 // Mp = 32*MT*NW >= n_res; LDS = 32*NT*Ks*ES <= 160 KiB; accumulators 16*MT*NT
@@ -84,10 +84,10 @@ bool mfma_geometry(int precision, int n_res, int n_in, int n_out, bool harvest, 
     return lds_bytes(g->skew) <= 160 * 1024;
 }
 
-int launch_recur_mfma(int precision, const RecurParams& p, hipStream_t stream) {
-    if (precision == ESN_F32) return launch_recur_mfma_f32(p, stream);
-    if (precision == ESN_F16) return launch_recur_mfma_f16(p, stream);
-    if (precision == ESN_BF16) return launch_recur_mfma_bf16(p, stream);
+int launch_recur_mfma(int precision, const RecurParams& p, hipStream_t stream, bool io32) {
+    if (precision == ESN_F32) return launch_recur_mfma_f32(p, stream, io32);
+    if (precision == ESN_F16) return launch_recur_mfma_f16(p, stream, io32);
+    if (precision == ESN_BF16) return launch_recur_mfma_bf16(p, stream, io32);
     return -1;
 }
 

@@ -2,10 +2,10 @@
 
 namespace esn {
 
-int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream) {
+int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream, bool io32) {
     const Geometry& g = p.g;
 #define ESN_CASE(NWv, MTv, NTv) \
-    if (g.NW == NWv && g.MT == MTv && g.NT == NTv) return launch_one<TraitsBF16, NWv, MTv, NTv>(p, stream);
+    if (g.NW == NWv && g.MT == MTv && g.NT == NTv) return launch_one<TraitsBF16, NWv, MTv, NTv>(p, stream, io32);
     ESN_CASE(4, 1, 2)
     ESN_CASE(8, 1, 4)
     ESN_CASE(8, 2, 4)

@@ -158,8 +158,10 @@ struct TraitsBF16 {
     static __device__ __forceinline__ float act_small(float z) { return tanh_prescaled(z); }
 };
 
-template <typename TR, int NW, int MT, int NT, bool HARVEST, int NOISE, bool SKEW>
+// IO32: predict with float32 U / Y (esn_predict_batch_f32); the float64-I/O instances are unchanged by it
+template <typename TR, int NW, int MT, int NT, bool HARVEST, int NOISE, bool SKEW, bool IO32 = false>
 __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
+    static_assert(!(HARVEST && IO32), "float32 I/O is a predict option");
     extern __shared__ __attribute__((aligned(16))) char zt[];   // Zt[Bt][Ks] elements, then tables
     constexpr int ES = TR::ES;
     constexpr int BT = 32 * NT;
@@ -276,7 +278,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
         float v = 0.f;
         if (fr >= 0 && ci < n_in) {
             const int row = s + p.in_row_off;
-            double raw = (row < p.T_in) ? p.U[(size_t)fr * in_stride + (size_t)row * n_in + ci] : 0.0;
+            double raw = (row < p.T_in) ? (double)in_ptr<IO32>(p)[(size_t)fr * in_stride + (size_t)row * n_in + ci] : 0.0;
             const float2 ss = tab_in[c * kin_p + ci];
             if (HARVEST) {
                 int pg;
@@ -324,8 +326,11 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
     };
     // LDS-DMA path for the per-step inputs (predict): every 16-byte chunk of the owned frames' input
     // row goes global -> LDS with no register staging; the owner wave converts it in phase E.
-    const int cpf = n_in / 2;                                   // 16-byte chunks per frame row
-    const bool in_dma = !HARVEST && (n_in % 2 == 0) && ((size_t)p.T_in * n_in % 2 == 0);
+    // float32 I/O: 16-byte chunks of four inputs when the rows tile into them (n_in % 4 == 0), else one 4-byte input
+    // per chunk (SISO: n_in = 2)
+    const bool in_w16 = !IO32 || (n_in & 3) == 0;      // (U is then 16-byte aligned: esn_predict_batch_f32)
+    const int cpf = IO32 ? (in_w16 ? n_in / 4 : n_in) : n_in / 2;      // 16-byte (4-byte) chunks per frame row
+    const bool in_dma = !HARVEST && (IO32 || ((n_in % 2 == 0) && ((size_t)p.T_in * n_in % 2 == 0)));
     auto dma_inputs = [&](int s) {
         const int row = s + p.in_row_off;
 #pragma unroll
@@ -337,12 +342,24 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                 const int f = e / cpf, ch = e % cpf;
                 const int fr = (e < 16 * cpf) ? tab_fr[c * 16 + f] : -1;
                 if (fr >= 0 && row < p.T_in) {
-                    const double* src = p.U + (size_t)fr * in_stride + (size_t)row * n_in + 2 * ch;
-                    // destination = wave-uniform base + lane*16 (hardware): chunk e of this tile
-                    char* dst = reinterpret_cast<char*>(in_raw + (size_t)c * 16 * n_in) + (size_t)e0 * 16;
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void*)src,
-                        (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                    if constexpr (IO32) {
+                        const float* src = p.U32 + (size_t)fr * in_stride + (size_t)row * n_in + (in_w16 ? 4 * ch : ch);
+                        // the tile's rows back to back, as in the float64 layout: chunk e at byte e * chunk size
+                        char* dst = reinterpret_cast<char*>(in_raw) + (size_t)c * 16 * n_in * 4 + (size_t)e0 * (in_w16 ? 16 : 4);
+                        if (in_w16)
+                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                        else
+                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                             (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+                    } else {
+                        const double* src = p.U + (size_t)fr * in_stride + (size_t)row * n_in + 2 * ch;
+                        // destination = wave-uniform base + lane*16 (hardware): chunk e of this tile
+                        char* dst = reinterpret_cast<char*>(in_raw + (size_t)c * 16 * n_in) + (size_t)e0 * 16;
+                        __builtin_amdgcn_global_load_lds(
+                            (const __attribute__((address_space(1))) void*)src,
+                            (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                    }
                 }
             }
         }
@@ -358,7 +375,8 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                 float v = 0.f;
                 if (tab_fr[c * 16 + f] >= 0 && ci < n_in) {
                     const float2 ss = tab_in[c * kin_p + ci];
-                    const double raw = (row < p.T_in) ? in_raw[((size_t)c * 16 + f) * n_in + ci] : 0.0;
+                    const double raw = (row < p.T_in)
+                        ? (double)reinterpret_cast<const io_elem<IO32>*>(in_raw)[((size_t)c * 16 + f) * n_in + ci] : 0.0;
                     v = fmaf((float)raw, ss.x, ss.y);
                 }
                 TR::store1(zt + (size_t)(c * 16 + f) * row_bytes + (size_t)(g.kin + ci) * ES, v);
@@ -445,7 +463,19 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             if (o0 < kfb_p) {
                 if (write_fb)
                     TR::store4(zt + (size_t)of * row_bytes + (size_t)(g.kfb + o0) * ES, y[0], y[1], y[2], y[3]);
-                if (orow >= 0 && fr >= 0) {
+                if (IO32 && orow >= 0 && fr >= 0) {
+                    float* yo = p.Y32 + ((size_t)fr * out_rows + orow) * n_out;
+                    if ((n_out & 3) == 0) {                                // whole quads: one 16-byte store
+                        *reinterpret_cast<float4*>(yo + o0) =
+                            make_float4((y[0] - u01.y) * u01.x, (y[1] - u01.w) * u01.z,
+                                        (y[2] - u23.y) * u23.x, (y[3] - u23.w) * u23.z);
+                    } else {
+                        const float2* un = tab_un + c * 16 + o0;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (o0 + j < n_out) yo[o0 + j] = (y[j] - un[j].y) * un[j].x;
+                    }
+                } else if (!IO32 && orow >= 0 && fr >= 0) {
                     double* yo = p.Y + ((size_t)fr * out_rows + orow) * n_out;
                     if ((n_out & 3) == 0) {                                // whole quads: two 16-byte stores
                         typedef double f64x2s __attribute__((ext_vector_type(2)));
@@ -785,7 +815,9 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
         constexpr int IN_TILES = NOWN / (NW / 2);          // column tiles staged per wave of set B
         const int in_c0 = IN_TILES * (wave - NW / 2);
         const int lcpf = __builtin_ctz(cpf), lkin = __builtin_ctz(kin_p);     // powers of two (mfma_geometry)
-        const size_t in_frame_bytes = (size_t)in_stride * 8;
+        const size_t in_frame_bytes = (size_t)in_stride * sizeof(io_elem<IO32>);
+        // float32 I/O: 16 cpf <= 64 chunks per tile -- one DMA instruction, of 16 or 4 bytes per lane (in_w16)
+        constexpr int IN_TRIPS = IO32 ? 1 : 2;
         // first frame of the tile (frames grow with the slot index): offsets stay below Bt frames' worth
         // of bytes however many frames a group has
         int j0;
@@ -819,11 +851,11 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             // past the tile (n_in < 8) has every lane out of range and fetches nothing
             int ln = lane;
             asm volatile("" : "+v"(ln));                       // opaque: derived per step, not kept across the GEMM phases
-            int off[IN_TILES][2];
+            int off[IN_TILES][IN_TRIPS];
 #pragma unroll
             for (int ti = 0; ti < IN_TILES; ++ti)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
+                for (int i = 0; i < IN_TRIPS; ++i) {
                     const int e = 64 * i + ln;
                     off[ti][i] = tab_off[(in_c0 + ti) * 16 + ((e >> lcpf) & 15)];
                 }
@@ -831,13 +863,22 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             for (int ti = 0; ti < IN_TILES; ++ti) {
                 const int c = in_c0 + ti;
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
+                for (int i = 0; i < IN_TRIPS; ++i) {
                     const int e = 64 * i + ln;
                     const bool on = off[ti][i] >= 0 && row_ok && e < 16 * cpf;
-                    const int voff = on ? off[ti][i] + ((e & (cpf - 1)) << 4) : OOB;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                        u_rsrc, (__attribute__((address_space(3))) void*)(in_slots + (size_t)(c * 2 + i) * 1024), 16,
-                        voff, row_ok ? row * n_in * 8 : 0, 0, 0);
+                    if constexpr (IO32) {
+                        auto* slot = (__attribute__((address_space(3))) void*)(in_slots + (size_t)(c * 2 + i) * 1024);
+                        const int voff = on ? off[ti][i] + ((e & (cpf - 1)) << (in_w16 ? 4 : 2)) : OOB;
+                        if (in_w16)
+                            __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rsrc, slot, 16, voff, row_ok ? row * n_in * 4 : 0, 0, 0);
+                        else
+                            __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rsrc, slot, 4, voff, row_ok ? row * n_in * 4 : 0, 0, 0);
+                    } else {
+                        const int voff = on ? off[ti][i] + ((e & (cpf - 1)) << 4) : OOB;
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                            u_rsrc, (__attribute__((address_space(3))) void*)(in_slots + (size_t)(c * 2 + i) * 1024), 16,
+                            voff, row_ok ? row * n_in * 8 : 0, 0, 0);
+                    }
                 }
             }
         };
@@ -858,8 +899,14 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                     const bool live = tab_fr[c * 16 + f] >= 0 && ci < n_in;          // (n_in is even: whole pairs)
                     const float4 ss = *reinterpret_cast<const float4*>(tab_in + c * kin_p + ci);
                     const int ch = (f << lcpf) + c2;                                  // < 128 for every lane
-                    const double2 raw = *reinterpret_cast<const double2*>(
-                        in_slots + (size_t)(c * 2 + (ch >> 6)) * 1024 + (size_t)(ch & 63) * 16);
+                    double2 raw;
+                    if constexpr (IO32) {       // the tile's 16 rows back to back from the slot's start
+                        const float2 r32 = *reinterpret_cast<const float2*>(in_slots + (size_t)c * 2048 + (size_t)(f * n_in + ci) * 4);
+                        raw = double2{(double)r32.x, (double)r32.y};
+                    } else {
+                        raw = *reinterpret_cast<const double2*>(
+                            in_slots + (size_t)(c * 2 + (ch >> 6)) * 1024 + (size_t)(ch & 63) * 16);
+                    }
                     const float v0 = live ? fmaf((float)(row_ok ? raw.x : 0.0), ss.x, ss.y) : 0.f;
                     const float v1 = live ? fmaf((float)(row_ok ? raw.y : 0.0), ss.z, ss.w) : 0.f;
                     if (e2 < 8 * kin_p)
@@ -1314,34 +1361,37 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
 
 // ---- host side: geometry choice and launch -------------------------------------
 
-template <typename TR, int NW, int MT, int NT, bool HARVEST, int NOISE, bool SKEW = false>
+template <typename TR, int NW, int MT, int NT, bool HARVEST, int NOISE, bool SKEW = false, bool IO32 = false>
 static int launch_k(const RecurParams& p, hipStream_t stream) {
     const int kin_p = p.g.kfb - p.g.kin, nown = p.g.Bt / 16;
     size_t lds = (size_t)p.g.Bt * p.g.Ks * TR::ES + 4 * (size_t)p.g.Bt + 8 * (size_t)nown * (kin_p + 16)
                  + (SKEW ? (size_t)nown * 2048 : 8 * (size_t)p.g.Bt * p.n_in) + 4 * (size_t)p.g.Bt;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(recur_mfma_kernel<TR, NW, MT, NT, HARVEST, NOISE, SKEW>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(recur_mfma_kernel<TR, NW, MT, NT, HARVEST, NOISE, SKEW, IO32>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((recur_mfma_kernel<TR, NW, MT, NT, HARVEST, NOISE, SKEW>), dim3(p.n_tiles), dim3(NW * 64), lds,
+    hipLaunchKernelGGL((recur_mfma_kernel<TR, NW, MT, NT, HARVEST, NOISE, SKEW, IO32>), dim3(p.n_tiles), dim3(NW * 64), lds,
                        stream, p);
     return (int)hipGetLastError();
 }
 
-template <typename TR, int NW, int MT, int NT, bool HARVEST, bool SKEW = false>
+template <typename TR, int NW, int MT, int NT, bool HARVEST, bool SKEW = false, bool IO32 = false>
 static int launch_n(const RecurParams& p, hipStream_t stream) {
     switch (p.noise_mode) {
-        case ESN_NOISE_NONE: return launch_k<TR, NW, MT, NT, HARVEST, ESN_NOISE_NONE, SKEW>(p, stream);
-        case ESN_NOISE_TENSOR: return launch_k<TR, NW, MT, NT, HARVEST, ESN_NOISE_TENSOR, SKEW>(p, stream);
-        default: return launch_k<TR, NW, MT, NT, HARVEST, ESN_NOISE_COUNTER, SKEW>(p, stream);
+        case ESN_NOISE_NONE: return launch_k<TR, NW, MT, NT, HARVEST, ESN_NOISE_NONE, SKEW, IO32>(p, stream);
+        case ESN_NOISE_TENSOR: return launch_k<TR, NW, MT, NT, HARVEST, ESN_NOISE_TENSOR, SKEW, IO32>(p, stream);
+        default: return launch_k<TR, NW, MT, NT, HARVEST, ESN_NOISE_COUNTER, SKEW, IO32>(p, stream);
     }
 }
 
+// io32: predict with float32 U / Y (never a harvest)
 template <typename TR, int NW, int MT, int NT>
-static int launch_one(const RecurParams& p, hipStream_t stream) {
+static int launch_one(const RecurParams& p, hipStream_t stream, bool io32) {
     // skewed schedule: instantiated for the 8-wave fp16 / bf16 predict tilings (mfma_geometry sets g.skew)
     if constexpr (NW == 8 && TR::ES == 2 && (NT == 2 || NT == 4)) {
-        if (!p.harvest && p.g.skew) return launch_n<TR, NW, MT, NT, false, true>(p, stream);
+        if (!p.harvest && p.g.skew)
+            return io32 ? launch_n<TR, NW, MT, NT, false, true, true>(p, stream) : launch_n<TR, NW, MT, NT, false, true>(p, stream);
     }
+    if (io32) return p.harvest ? -1 : launch_n<TR, NW, MT, NT, false, false, true>(p, stream);
     return p.harvest ? launch_n<TR, NW, MT, NT, true>(p, stream) : launch_n<TR, NW, MT, NT, false>(p, stream);
 }
 

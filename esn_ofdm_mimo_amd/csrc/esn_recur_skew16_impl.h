@@ -28,7 +28,8 @@ constexpr int S16_NKK = 17;            // 32-k groups: 16 of state rows + the [U
 constexpr int S16_NKH = 8;             // state groups per half
 constexpr int S16_MP = 512;
 
-template <typename TR, int NOISE>
+// IO32: float32 U / Y (esn_predict_batch_f32); the float64-I/O instances are unchanged by it
+template <typename TR, int NOISE, bool IO32 = false>
 __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     extern __shared__ __attribute__((aligned(16))) char zf[];
     constexpr int NW = 8, BT = 128, NOWN = 8, NKK = S16_NKK, NKH = S16_NKH;
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     uint32_t* tab_key = reinterpret_cast<uint32_t*>(tab_fr + BT);
     float2* tab_in = reinterpret_cast<float2*>(tab_key + BT);
     float2* tab_un = tab_in + NOWN * kin_p;
-    char* in_slots = reinterpret_cast<char*>(tab_un + NOWN * 16);       // [NOWN][2][1 KB] raw float64 input rows
+    char* in_slots = reinterpret_cast<char*>(tab_un + NOWN * 16);       // [NOWN][2][1 KB] raw input rows (float64 or float32)
     int* tab_off = reinterpret_cast<int*>(in_slots + (size_t)NOWN * 2048);
     // counter noise: the (frame, step) keys of the 128 frames, written once per step by the tile's own wave (sixteen
     // lanes, one mix32) instead of being re-derived by every lane of every wave for each of its eight tiles; two
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         float v = 0.f;
         if (fr >= 0 && ci < n_in) {
             const int row = p.in_row_off;
-            const double raw = (row < p.T_in) ? p.U[(size_t)fr * in_stride + (size_t)row * n_in + ci] : 0.0;
+            const double raw = (row < p.T_in) ? (double)in_ptr<IO32>(p)[(size_t)fr * in_stride + (size_t)row * n_in + ci] : 0.0;
             const float2 ss = tab_in[(f >> 4) * kin_p + ci];
             v = fmaf((float)raw, ss.x, ss.y);
         }
@@ -157,7 +158,18 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                 TR::store4(zf + ((size_t)(wave * NKK + 16) * 64 + (pos >> 3) * 16 + ofc) * 16 + 2 * (pos & 7),
                            y[0], y[1], y[2], y[3]);
             }
-            if (orow >= 0 && fr >= 0) {
+            if (IO32 && orow >= 0 && fr >= 0) {        // the float64 path's values, one 16-byte store per quad
+                float* yo = p.Y32 + ((size_t)fr * out_rows + orow) * n_out;
+                if ((n_out & 3) == 0) {
+                    *reinterpret_cast<float4*>(yo + o0) =
+                        make_float4((y[0] - u01.y) * u01.x, (y[1] - u01.w) * u01.z, (y[2] - u23.y) * u23.x, (y[3] - u23.w) * u23.z);
+                } else {
+                    const float2* un = tab_un + wave * 16 + o0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (o0 + j < n_out) yo[o0 + j] = (y[j] - un[j].y) * un[j].x;
+                }
+            } else if (!IO32 && orow >= 0 && fr >= 0) {
                 double* yo = p.Y + ((size_t)fr * out_rows + orow) * n_out;
                 if ((n_out & 3) == 0) {
                     typedef double f64x2s __attribute__((ext_vector_type(2)));
@@ -393,11 +405,16 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     const std::integral_constant<int, 8> n_hi;
 
     // ---- inputs: set B stages them for all column tiles, two tiles per wave (as in the 32x32x16 kernel) ----------
-    const int cpf = n_in / 2;                                   // 16-byte chunks per frame row
+    // float32 I/O: 16-byte chunks of four inputs (n_in % 4 == 0), else 4-byte chunks of one (n_in = 2: the skewed kernels
+    // take n_in in {2, 4, 8, 16}); either way 16 cpf <= 64 chunks per tile, ONE DMA instruction, the tile's rows back to
+    // back in its slot
+    const bool in_w16 = !IO32 || (n_in & 3) == 0;      // (U is then 16-byte aligned: esn_predict_batch_f32)
+    const int cpf = IO32 ? (in_w16 ? n_in / 4 : n_in) : n_in / 2;      // chunks per frame row
+    constexpr int IN_TRIPS = IO32 ? 1 : 2;
     constexpr int IN_TILES = NOWN / (NW / 2);
     const int in_c0 = IN_TILES * (wave - NW / 2);
     const int lcpf = __builtin_ctz(cpf), lkin = __builtin_ctz(kin_p);
-    const size_t in_frame_bytes = (size_t)in_stride * 8;
+    const size_t in_frame_bytes = (size_t)in_stride * sizeof(io_elem<IO32>);
     int j0;
     slot_group(p, slot0, j0);
     size_t u_base_frame = j0 < p.F ? (size_t)grp0 * p.F + j0 : ((size_t)grp0 + (p.spw ? p.n_wsets : 1)) * p.F;
@@ -416,11 +433,11 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         const bool row_ok = row < p.T_in;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        int off[IN_TILES][2];
+        int off[IN_TILES][IN_TRIPS];
 #pragma unroll
         for (int ti = 0; ti < IN_TILES; ++ti)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < IN_TRIPS; ++i) {
                 const int e = 64 * i + ln;
                 off[ti][i] = tab_off[(in_c0 + ti) * 16 + ((e >> lcpf) & 15)];
             }
@@ -428,13 +445,22 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         for (int ti = 0; ti < IN_TILES; ++ti) {
             const int c = in_c0 + ti;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < IN_TRIPS; ++i) {
                 const int e = 64 * i + ln;
                 const bool on = off[ti][i] >= 0 && row_ok && e < 16 * cpf;
-                const int voff = on ? off[ti][i] + ((e & (cpf - 1)) << 4) : OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                    u_rsrc, (__attribute__((address_space(3))) void*)(in_slots + (size_t)(c * 2 + i) * 1024), 16,
-                    voff, row_ok ? row * n_in * 8 : 0, 0, 0);
+                if constexpr (IO32) {
+                    auto* slot = (__attribute__((address_space(3))) void*)(in_slots + (size_t)(c * 2 + i) * 1024);
+                    const int voff = on ? off[ti][i] + ((e & (cpf - 1)) << (in_w16 ? 4 : 2)) : OOB;
+                    if (in_w16)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rsrc, slot, 16, voff, row_ok ? row * n_in * 4 : 0, 0, 0);
+                    else
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rsrc, slot, 4, voff, row_ok ? row * n_in * 4 : 0, 0, 0);
+                } else {
+                    const int voff = on ? off[ti][i] + ((e & (cpf - 1)) << 4) : OOB;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                        u_rsrc, (__attribute__((address_space(3))) void*)(in_slots + (size_t)(c * 2 + i) * 1024), 16,
+                        voff, row_ok ? row * n_in * 8 : 0, 0, 0);
+                }
             }
         }
     };
@@ -452,9 +478,15 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                 const int f = (e2 >> lk2) & 15, c2 = e2 & ((kin_p >> 1) - 1), ci = 2 * c2;
                 const bool live = tab_fr[c * 16 + f] >= 0 && ci < n_in;
                 const float4 ss = *reinterpret_cast<const float4*>(tab_in + c * kin_p + ci);
-                const int ch = (f << lcpf) + c2;
-                const double2 raw = *reinterpret_cast<const double2*>(
-                    in_slots + (size_t)(c * 2 + (ch >> 6)) * 1024 + (size_t)(ch & 63) * 16);
+                double2 raw;
+                if constexpr (IO32) {
+                    const float2 r32 = *reinterpret_cast<const float2*>(in_slots + (size_t)c * 2048 + (size_t)(f * n_in + ci) * 4);
+                    raw = double2{(double)r32.x, (double)r32.y};
+                } else {
+                    const int ch = (f << lcpf) + c2;
+                    raw = *reinterpret_cast<const double2*>(
+                        in_slots + (size_t)(c * 2 + (ch >> 6)) * 1024 + (size_t)(ch & 63) * 16);
+                }
                 const float v0 = live ? fmaf((float)(row_ok ? raw.x : 0.0), ss.x, ss.y) : 0.f;
                 const float v1 = live ? fmaf((float)(row_ok ? raw.y : 0.0), ss.z, ss.w) : 0.f;
                 if (e2 < 8 * kin_p)
@@ -545,7 +577,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     }
 }
 
-template <typename TR>
+template <typename TR, bool IO32>
 static int launch_skew16(const RecurParams& p, hipStream_t stream) {
     const int kin_p = p.g.kfb - p.g.kin;
     const size_t lds = (size_t)8 * S16_NKK * 1024 + 4 * 128 + 4 * 128 + 8 * (size_t)8 * (kin_p + 16) + 8 * 2048 + 4 * 128 + 8 * 128;
@@ -556,9 +588,9 @@ static int launch_skew16(const RecurParams& p, hipStream_t stream) {
         return (int)hipGetLastError();
     };
     switch (p.noise_mode) {
-        case ESN_NOISE_NONE: return go(recur_skew16_kernel<TR, ESN_NOISE_NONE>);
-        case ESN_NOISE_TENSOR: return go(recur_skew16_kernel<TR, ESN_NOISE_TENSOR>);
-        default: return go(recur_skew16_kernel<TR, ESN_NOISE_COUNTER>);
+        case ESN_NOISE_NONE: return go(recur_skew16_kernel<TR, ESN_NOISE_NONE, IO32>);
+        case ESN_NOISE_TENSOR: return go(recur_skew16_kernel<TR, ESN_NOISE_TENSOR, IO32>);
+        default: return go(recur_skew16_kernel<TR, ESN_NOISE_COUNTER, IO32>);
     }
 }
 

@@ -135,26 +135,31 @@ class FrameSource:
         return out
 
     def frames(self, taps, frames_per_block, ebno_db, snr_idx, first_frame, stream_id, want_x=False,
-               bits_in=None, noise_in=None, ls_pattern=False):
+               bits_in=None, noise_in=None, ls_pattern=False, io="c128"):
         """frames_per_block frames per block of `taps` -> (bits uint8 [B,N*m,n_t], x_cp or None, y_cp).
-        stream_id separates pilots (0) from data (1); first_frame is the global frame counter."""
+        stream_id separates pilots (0) from data (1); first_frame is the global frame counter.
+        io="c64": x_cp / y_cp complex64 (esn_gen_frames_c64), bitwise the complex128 frames rounded."""
         torch, p = self.torch, self.p
+        if io not in ("c128", "c64"):
+            raise ValueError(f"io must be 'c128' or 'c64', not {io!r}")
+        cdt = torch.complex64 if io == "c64" else torch.complex128
         g = taps.shape[0]
         b = g * frames_per_block
         with torch.cuda.device(self.device):
             p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=self.device)
             a_clip = torch.full((g,), p.a_clip(ebno_db), dtype=torch.float64, device=self.device)
             bits = torch.empty((b, p.n_sub * p.m, p.n_t), dtype=torch.uint8, device=self.device)
-            x_cp = torch.empty((b, p.t_frame, p.n_t), dtype=torch.complex128, device=self.device) if want_x else None
-            y_cp = torch.empty((b, p.t_frame, p.n_r), dtype=torch.complex128, device=self.device)
-            check(self.lib.esn_gen_frames(b, frames_per_block, p.n_sub, p.cp, p.n_t, p.n_r, p.isi, p.m,
+            x_cp = torch.empty((b, p.t_frame, p.n_t), dtype=cdt, device=self.device) if want_x else None
+            y_cp = torch.empty((b, p.t_frame, p.n_r), dtype=cdt, device=self.device)
+            name = "esn_gen_frames_c64" if io == "c64" else "esn_gen_frames"
+            check(getattr(self.lib, name)(b, frames_per_block, p.n_sub, p.cp, p.n_t, p.n_r, p.isi, p.m,
                                           1 if ls_pattern else 0, ptr(p_i),
                                           ptr(a_clip), p.no, ptr(taps), ptr(bits_in), ptr(noise_in),
                                           self._key(snr_idx, 2 + stream_id), int(first_frame), ptr(bits), ptr(x_cp),
-                                          ptr(y_cp), _lib.stream_handle()), "esn_gen_frames")
+                                          ptr(y_cp), _lib.stream_handle()), name)
         return bits, x_cp, y_cp
 
-    def blocks(self, ebno_db, snr_idx, block_ids, frames_per_block, with_ls_pilot=False):
+    def blocks(self, ebno_db, snr_idx, block_ids, frames_per_block, with_ls_pilot=False, io="c128"):
         """Pilot + data frames of the given coherence blocks (any subset, any order: every block is
         generated from its own global index, so the result does not depend on the rank that asks).
         Returns pilot_y [G,T,n_r], pilot_x [G,T,n_t] (pre-PA teacher), data_y [G*F,T,n_r], data_bits."""
@@ -164,14 +169,15 @@ class FrameSource:
         for i in range(1, len(ids) + 1):
             if i == len(ids) or ids[i] != ids[i - 1] + 1:
                 runs.append((ids[start], i - start)); start = i
-        outs = [self.blocks_fast(ebno_db, snr_idx, b0, n, frames_per_block, with_ls_pilot) for b0, n in runs]
+        outs = [self.blocks_fast(ebno_db, snr_idx, b0, n, frames_per_block, with_ls_pilot, io) for b0, n in runs]
         return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
 
-    def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False):
-        """Blocks first_block .. first_block + n_blocks - 1 in three launches (taps, pilots, data)."""
+    def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False, io="c128"):
+        """Blocks first_block .. first_block + n_blocks - 1 in three launches (taps, pilots, data).
+        io="c64": the DATA frames are complex64; pilots stay complex128 (training is unchanged)."""
         taps = self.taps(n_blocks, snr_idx, first_block)
         pbits, px, py = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, want_x=True)
-        bits, _, dy = self.frames(taps, frames_per_block, ebno_db, snr_idx, first_block * frames_per_block, 1)
+        bits, _, dy = self.frames(taps, frames_per_block, ebno_db, snr_idx, first_block * frames_per_block, 1, io=io)
         out = dict(pilot_y=py, pilot_x=px, pilot_bits=pbits, data_y=dy, data_bits=bits, taps=taps)
         if with_ls_pilot:     # same bits, same noise, sparse pattern (driver:330-356)
             _, _, out["pilot_y_ls"] = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, ls_pattern=True)
@@ -229,7 +235,8 @@ class FrameSource:
 
 
 def _view_real(z):
-    """complex128 [..., T, n] -> float64 view [..., T, 2n] (Re/Im interleaved; driver:433-436)."""
+    """complex128 [..., T, n] -> float64 view [..., T, 2n] (Re/Im interleaved; driver:433-436); complex64 ->
+    float32."""
     import torch
     z = z.contiguous()
     return torch.view_as_real(z).reshape(*z.shape[:-1], 2 * z.shape[-1])
@@ -274,7 +281,15 @@ class DetectorSweep:
 
     def __init__(self, params: LinkParams, n_reservoir=512, spectral_radius=0.9, sparsity=0.1, noise=0.001,
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
-                 rank=0, world_size=1, solve_method="auto", train_ebno=None):
+                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64"):
+        """io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
+        predict kernels see the same float inputs and write the same float outputs).  Pilots and training stay
+        float64.  Needs precision f32 / f16 / bf16."""
+        if io not in ("f64", "f32"):
+            raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
+        if io == "f32" and precision == "f64":
+            raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
+        self.io = io
         torch = _lib.require_gpu()
         self.torch, self.p = torch, params
         self.rank, self.world = rank, world_size
@@ -358,7 +373,7 @@ class DetectorSweep:
         x0, y0 = self._cont if (p.continuation and getattr(self, "_cont", None)) else (None, None)
         y = self.bank.predict(U, frames_per_block, T=p.t_frame + p.delay, transient=p.forget, x0=x0, y0=y0,
                               precision=self.precision, noise_mode="counter", seed=seed, out=out,
-                              group_offset=group_offset)
+                              group_offset=group_offset, io=self.io)
         self.bank.detect_count(y, data_bits, self.p_i, frames_per_block, p.n_sub, p.n_t, p.m, err=err, bits=bits)
         return y
 
@@ -375,7 +390,7 @@ class DetectorSweep:
         tensor [errors, bits, flagged fits] (int64) without synchronising the host unless `repair`."""
         torch = self.torch
         g = len(ids)
-        data = self.src.blocks_fast(ebno, si, ids[0], g, F)
+        data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128")
         self.set_snr(ebno, g)
         if self.train_ebno is not None:
             # the "train@fixed Eb/No" ESN of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:181-183,347-367):
@@ -435,7 +450,8 @@ def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=No
     (Demo_MIMO_4x8_Sionna_CDL_ESN_v2.py:283-530): LDPC-coded payloads on every data symbol, ESN and
     LS/MMSE detection, max-log LLRs, logistic LLR calibration fitted on the first `cal_frac` of the
     blocks (the reference: the first 30 % of the symbols, :266,:476-482,:513-523) and sum-product
-    decoding of the rest.  Returns dict(ESN_uncoded, MMSE_uncoded, ESN_coded, MMSE_coded, a_esn, ...)."""
+    decoding of the rest.  Returns dict(ESN_uncoded, MMSE_uncoded, ESN_coded, MMSE_coded, a_esn, ...).
+    Frames and the ESN leg stay float64 / complex128 whatever sweep.io says: the MMSE leg reads complex128."""
     torch, p, src = sweep.torch, sweep.p, sweep.src
     F = frames_per_block or p.coherence_symbols
     G = n_blocks
@@ -479,7 +495,9 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     ESN trained at a fixed Eb/No (`fixed_sweep`: a DetectorSweep built with train_ebno=12), LS-ZF,
     MMSE and Perfect-ZF (:450-460); uncoded BER over every data symbol, coded BER on every `decode_every`-th
     symbol of the run (kk % 4 == 1, :202,389) with the drivers' uncalibrated LLRs: per-stream decision-directed
-    sigma^2, x LLR_SCALE 1.5, clip +-20 (:478-485).  Returns the reference's holder names (BER_* / BERC_*)."""
+    sigma^2, x LLR_SCALE 1.5, clip +-20 (:478-485).  Returns the reference's holder names (BER_* / BERC_*).
+    Frames and the ESN legs stay float64 / complex128 whatever the sweeps' io says: the LS / MMSE / ZF legs read
+    complex128."""
     torch, p, src = sweep.torch, sweep.p, sweep.src
     L = p.coherence_symbols
     F, G = L - 1, n_blocks

@@ -172,6 +172,30 @@ int esn_predict_batch(int precision, const esn_shape_t* shape,
                       uint64_t seed, uint64_t group_offset,
                       double* Y, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Same predict with float32 I/O: U float [B][T_in][n_in] (16-byte aligned when n_in is a multiple of 4, else 4-byte),
+ * Y float [B][T-transient][n_out] (16-byte aligned); every
+ * other argument (scalings, x0 / y0, noise_u, workspace) as above.  Half the bytes of U and Y; no counterpart in the
+ * reference, whose arrays are float64.
+ *   Bitwise contract: Y equals (float) of the Y esn_predict_batch writes for the same call with U widened to double.
+ *   Every kernel that serves it narrows an input to float (or scales it in double) before any arithmetic, so the
+ *   recurrence is the same; the store rounds the value the float64 path would write (a float in the persistent
+ *   kernels, a double in the N_res > 1024 GEMM path).
+ *   Served: precisions ESN_F32 / ESN_F16 / ESN_BF16 on every path esn_predict_batch takes for them (the 16x16x32 and
+ *   32x32x16 skewed kernels, the in-step kernel, N_res > 1024 with or without a workspace), any n_in (n_in = 2 included).
+ *   Returns -2 for ESN_F64 (the vector-ALU, float64 matrix-pipe and single-sequence cluster kernels read and write
+ *   float64 only), -1 for null pointers, bad sizes or a misaligned U or Y; all of these
+ *   before any HIP call. */
+int esn_predict_batch_f32(int precision, const esn_shape_t* shape,
+                          const void* packed_w, const void* packed_wout,
+                          const double* in_scale, const double* in_shift,
+                          const double* t_scale, const double* t_shift,
+                          const float* U, int n_frames, int frames_per_group,
+                          int T_in, int T, int transient,
+                          const double* x0, const double* y0,
+                          double noise, int noise_mode, const double* noise_u,
+                          uint64_t seed, uint64_t group_offset,
+                          float* Y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Batched state harvest of ESN.fit: one training sequence per group.
  *
  *   U [n_groups][T][n_in], D [n_groups][T][n_out] (teacher, unscaled)
@@ -256,6 +280,14 @@ int esn_detect_count(const double* Y, int n_frames, int frames_per_group,
                      const double* p_i, const uint8_t* tx_bits,
                      long long* err_count, long long* bit_count,
                      double* X_hat, void* stream);
+/* Same with Y float [B][N][2 N_t] (8-byte aligned), as esn_predict_batch_f32 writes it: widened to double on load,
+ * then the float64 FFT and slicer of esn_detect_count -- counts and X_hat (still float64) are bitwise those of
+ * esn_detect_count on the widened Y.  Checks (-1) before any HIP call, as above. */
+int esn_detect_count_f32(const float* Y, int n_frames, int frames_per_group,
+                         int n_sub, int n_t, int bits_per_sym,
+                         const double* p_i, const uint8_t* tx_bits,
+                         long long* err_count, long long* bit_count,
+                         double* X_hat, void* stream);
 
 /* ---- Host-memory front ends ("caller-owned device or host pointers flagged by an enum").
  * The reference's callers hold C-contiguous float64 NumPy arrays on the host (pyESN.py:154,218); a binding that
@@ -335,6 +367,15 @@ int esn_gen_frames(int n_frames, int frames_per_block, int n_sub, int cp, int n_
                    const double* taps, const uint8_t* bits_in, const double* noise_in,
                    uint64_t seed, uint64_t frame_offset,
                    uint8_t* bits, double* x_cp, double* y_cp, void* stream);
+/* esn_gen_frames with complex64 outputs: x_cp (optional) and y_cp as float pairs [B][T][n] (8-byte aligned; a 16-byte
+ * aligned y_cp with even n_r is written one antenna pair per 16-byte store).  The arithmetic stays float64 and only
+ * the store rounds: bits are equal and x_cp / y_cp are bitwise the complex128 outputs of esn_gen_frames rounded to
+ * complex64, for the same seed and frame_offset, for supplied bits_in / noise_in and for ls_pattern = 1. */
+int esn_gen_frames_c64(int n_frames, int frames_per_block, int n_sub, int cp, int n_t, int n_r, int isi,
+                       int bits_per_sym, int ls_pattern, const double* p_i, const double* a_clip, double no,
+                       const double* taps, const uint8_t* bits_in, const double* noise_in,
+                       uint64_t seed, uint64_t frame_offset,
+                       uint8_t* bits, float* x_cp, float* y_cp, void* stream);
 
 /* ---- Baseline equaliser the reference compares the ESN with, float64.
  * esn_channel_estimate   pilot_bits [G][N*m][n_t], y_ls_cp complex [G][T][n_r] (received sparse LS
