@@ -22,6 +22,7 @@ struct SolveParams {
     int m, n, wide;
     int skip;   // diagnostic only (ESN_CHOL_SKIP env): bit0 Gram, bit1 Cholesky, bit2 solves, bit3 W_out
     int part_ok;   // big kernel: the three-partial-sums W_out pass fits the LDS the launcher allocated
+    int vec;       // LDS Cholesky kernel: E rows start 16-byte aligned and hold whole 16-byte runs (vector loads)
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -216,346 +217,455 @@ int launch_readout_solve(const double* E, const double* D, int n_groups, int T, 
 // Error ~ cond(A)^2 eps: with the model's state noise cond(A) ~ 1e3, i.e.
 // ~1e-10 -- far below the float32 harvest.  A non-positive / tiny pivot sets status=1 and
 // the caller re-solves that group with the QR kernel.
+//
+// Two systems per CU: 512 threads and 80 KiB of LDS per workgroup, so that one system's
+// serial phases (diagonal blocks, substitutions) run beside the other's Gram and E stream.
+// LDS holds only the 36 lower 16x16 tiles of the Gram matrix, packed (72 KiB), and the
+// right-hand sides (8 KiB).  A diagonal tile holds L11^-1 once factorised (L11 itself is not
+// needed again); the E staging of the Gram phase and the W_out partial sums alias the tiles.
 // ---------------------------------------------------------------------------------
 namespace esn {
 
-constexpr int CH_NP = 128;        // padded Gram dimension
-constexpr int CH_LD = CH_NP + 1;  // LDS row stride (doubles): conflict-free row-strided reads
-constexpr int CH_KC = 32;         // k-chunk staged per pass
+constexpr int CH_NP = 128;                  // padded Gram dimension
+constexpr int CH_NT = 512;                  // threads: 8 waves, two per SIMD
+constexpr int CH_NW = CH_NT / 64;
+constexpr int CH_TILES = 36;                // lower 16x16 tiles of the Gram matrix
+constexpr int CH_KC = 32;                   // k-chunk staged per pass
+constexpr int CH_AS_LD = CH_NP + 16;        // staging row stride (doubles): rows k and k+1 of an operand read
+                                            // fall on opposite halves of the 64 banks (no conflicts)
+constexpr int CH_RHS = 8;                   // right-hand side columns (n_out <= 8), Bs[i][CH_RHS]
+constexpr size_t CH_LDS = sizeof(double) * ((size_t)CH_TILES * 256 + (size_t)CH_NP * CH_RHS);   // 81 920 B
+static_assert(2 * CH_KC * CH_AS_LD <= CH_TILES * 256, "E staging aliases the Gram tiles");
 
-__global__ __launch_bounds__(1024) void readout_chol_kernel(SolveParams sp) {
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+// first double of lower tile (ti, tj), ti >= tj
+__device__ __forceinline__ int ch_tile(int ti, int tj) { return (ti * (ti + 1) / 2 + tj) * 256; }
+// element (r, c) of a tile: row-major, the column XORed with the row pair.  MFMA operand reads by row
+// (r = lane % 16, c = k + lane / 16) and by column (r = k + lane / 16, c = lane % 16), the 16-lane row
+// reads of the diagonal factorisation and the accumulator stores all hit 32 distinct 8-byte banks.
+__device__ __forceinline__ int ch_el(int r, int c) { return r * 16 + (c ^ (r & ~1)); }
+
+__device__ __forceinline__ void ch_load4(const float* p, float (&v)[4]) {
+    const float4 x = *reinterpret_cast<const float4*>(p);
+    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+}
+__device__ __forceinline__ void ch_load4(const double* p, double (&v)[4]) {
+    const double2 x = *reinterpret_cast<const double2*>(p), y = *reinterpret_cast<const double2*>(p + 2);
+    v[0] = x.x; v[1] = x.y; v[2] = y.x; v[3] = y.y;
+}
+__device__ __forceinline__ const float* ch_src(const SolveParams& sp, float*) { return sp.E32; }
+__device__ __forceinline__ const double* ch_src(const SolveParams& sp, double*) { return sp.E; }
+
+__device__ __forceinline__ double ch_bcast(double x, int src) {      // wave-uniform copy of lane `src` (constant)
+    const uint64_t u = __builtin_bit_cast(uint64_t, x);
+    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, src);
+    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), src);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// One wave: factorise the 16x16 diagonal tile at D in registers (lane r = row r, the pivots travel by
+// v_readlane) and overwrite it with L11^-1 (lane c = column c, by forward substitution).  A rejected pivot
+// (v <= tol) drops its direction, as pinv would: unit diagonal and zero column in L11, zero row in L11^-1,
+// so the panel column and the solution component vanish too.  Returns 1 if a live pivot was rejected.
+__device__ __forceinline__ int ch_factor_diag(double* D, int j0, int n, double piv_tol, int lane) {
+    const int r = lane & 15;                        // lanes 16..63 mirror lanes 0..15 (no divergence)
+    double a[16], x[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) a[c] = D[ch_el(r, c)];
+    double my_invd = 1.0;
+    unsigned rejected = 0, dropped = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const double v = ch_bcast(a[j], j);
+        const bool live = j0 + j < n;
+        const bool ok = live && v > piv_tol;
+        if (live && !ok) rejected |= 1u << j;
+        if (!ok) dropped |= 1u << j;
+        const double d = ok ? sqrt(v) : 1.0, inv_d = ok ? 1.0 / d : 0.0;
+        if (r == j) my_invd = ok ? inv_d : 1.0;
+        a[j] = (r == j) ? d : ((r > j) ? a[j] * inv_d : 0.0);          // column j of L11
+#pragma unroll
+        for (int k = j + 1; k < 16; ++k) {
+            const double lkj = ch_bcast(a[j], k);
+            if (r >= k) a[k] = fma(-a[j], lkj, a[k]);
+        }
+    }
+    // lane c: column c of L11^-1, L11[i][k] = a[k] of lane i
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        double sacc = (i == r) ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < i; ++k) sacc = fma(-ch_bcast(a[k], i), x[k], sacc);   // x[k] = 0 for k < c
+        const double idi = ch_bcast(my_invd, i);
+        x[i] = (i >= r && !((dropped >> i) & 1u)) ? sacc * idi : 0.0;
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) D[ch_el(i, r)] = x[i];
+    }
+    return rejected ? 1 : 0;
+}
+
+template <typename TE, bool wide>
+__global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void readout_chol_kernel(SolveParams sp) {
     extern __shared__ __attribute__((aligned(16))) char chol_smem[];
-    double* Gs = reinterpret_cast<double*>(chol_smem);            // [CH_NP][CH_LD]   (phase 2+)
-    double* As = Gs;                                               // [CH_KC][CH_NP+4] (phase 1, aliased)
-    double* Bs = Gs + CH_NP * CH_LD;                               // [nrhs][CH_NP] rhs / solution
-    __shared__ int sh_bad;
+    double* Gs = reinterpret_cast<double*>(chol_smem);             // 36 packed tiles            (phase 2-4)
+    double* As = Gs;                                                // [2][CH_KC][CH_AS_LD] staging (phase 1)
+    double* Bs = Gs + CH_TILES * 256;                               // [CH_NP][CH_RHS] rhs / solution
     const int g = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 15, lq = lane >> 4;
     const int rows = sp.T - sp.transient, cols = sp.cols, nrhs = sp.n_out;
-    const bool wide = rows < cols;
     const int n = wide ? rows : cols;      // Gram dimension (<= CH_NP)
     const int m = wide ? cols : rows;      // contraction length
-    const size_t a_off = ((size_t)g * sp.T + sp.transient) * cols;
-    const double* A = sp.E ? sp.E + a_off : nullptr;                     // [rows][cols]
-    const float* A32 = sp.E32 ? sp.E32 + a_off : nullptr;                //   ... or as float32
+    const int ntile = (n + 15) / 16;
+    const TE* A = ch_src(sp, (TE*)nullptr) + ((size_t)g * sp.T + sp.transient) * cols;    // [rows][cols]
     const double* Dg = sp.D + ((size_t)g * sp.T + sp.transient) * nrhs;
-    constexpr int AS_LD = CH_NP + 4;
 
     // ---- phase 1: G = sum_k a_k a_k^T on the float64 matrix pipe ------------------------------
     // v_mfma_f64_16x16x4_f64 (A[l%16][l/16], B[l/16][l%16], C reg i: row 4i + l/16, col l%16) runs at
-    // the vector-FMA rate on gfx950 (64 cycles, probe in tools/mfma_layout_probe.hip) but takes
-    // one LDS read per operand and 1024 FMAs, where a 4x4 register tile takes 8 reads per 16 FMAs
-    // per lane -- the old loop was LDS-bound at a tenth of the FMA rate.  Only the 36 lower 16x16
-    // tiles are formed (the factorisation reads nothing above the diagonal), dealt to the 16
-    // waves so that every SIMD (wave % 4) carries 9: waves 0-3 three tiles, the others two.
-    // lower tile t = ti (ti + 1) / 2 + tj goes to SIMD t % 4, slot t / 4 of its nine
-    const int wvu = __builtin_amdgcn_readfirstlane(wv);
-    const int g_cnt = (wvu >> 2) == 0 ? 3 : 2;
-    int g_ti[3], g_tj[3];
+    // the vector-FMA rate on gfx950 (64 cycles, probe in tools/mfma_layout_probe.hip).  Only the 36 lower
+    // 16x16 tiles are formed: tile t goes to wave t % 8, so waves w and w + 4 (one SIMD) carry 9 between them.
+    int g_ti[5], g_tj[5];
+    const int g_cnt = wv < 4 ? 5 : 4;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int m = wvu >> 2;
-        const int idx = m == 0 ? q : 2 * m + 1 + (q < 2 ? q : 0);
-        const int t = 4 * idx + (wvu & 3);
+    for (int q = 0; q < 5; ++q) {
+        const int t = wv + CH_NW * q < CH_TILES ? wv + CH_NW * q : 0;
         int ti = 0;
         while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
         g_ti[q] = ti;
         g_tj[q] = t - ti * (ti + 1) / 2;
     }
-    typedef double f64x4 __attribute__((ext_vector_type(4)));
-    f64x4 acc[3];
+    f64x4 acc[5];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) acc[q] = f64x4{0.0, 0.0, 0.0, 0.0};
-    const int fr_off = (lane >> 4) * (CH_NP + 4) + (lane & 15);      // operand element of this lane in a 4-row slab
-    // tall case also needs A^T B: thread (o, i) partial sums, o < nrhs, i < n  -> first nrhs*128 threads
-    double atb = 0.0;
-    const int ao = tid / CH_NP, ai = tid % CH_NP;
-    // chunk staging is register-prefetched one chunk ahead and double-buffered in LDS, so the
-    // global-load latency of chunk c+1 hides under the FMAs of chunk c (one barrier per chunk)
-    constexpr int EPT = CH_KC * CH_NP / 1024;          // staged elements per thread (4)
-    // two chunks in flight in registers (an HBM round trip is longer than the MFMAs of one chunk)
-    double stgA[EPT], stgB[EPT];
-    auto fetch = [&](double (&stg)[EPT], int k0) {
+    for (int q = 0; q < 5; ++q) acc[q] = f64x4{0.0, 0.0, 0.0, 0.0};
+    // tall case also needs A^T B: thread (o, i) = (e / 128, e % 128), e = tid + 512 p
+    double atb[2] = {0.0, 0.0};
+    // A chunk is 32 k x 128 i; each thread moves two runs of 4 elements that are contiguous in E (16-byte
+    // loads when sp.vec): 4 consecutive k of one Gram row (wide) or 4 consecutive Gram rows of one k (tall).
+    // Wide: a 16-lane group takes 16 rows, so the 8-byte LDS stores of a group hit 32 distinct banks.
+    auto run_of = [&](int p, int& i, int& kk) {
+        const int e = tid + CH_NT * p;
+        if (wide) { i = (e & 15) + 16 * ((e >> 7) & 7); kk = 4 * ((e >> 4) & 7); }
+        else      { kk = e >> 5; i = 4 * (e & 31); }
+    };
+    TE stg[2][4];
+    auto fetch = [&](int k0) {
 #pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int e = tid + 1024 * q;
-            int kk, i;
-            if (wide) { i = e / CH_KC; kk = e % CH_KC; } else { kk = e / CH_NP; i = e % CH_NP; }
+        for (int p = 0; p < 2; ++p) {
+            int i, kk;
+            run_of(p, i, kk);
             const int k = k0 + kk;
-            const size_t ai_ = wide ? (size_t)i * cols + k : (size_t)k * cols + i;
-            stg[q] = (i < n && k < m) ? (A32 ? (double)A32[ai_] : A[ai_]) : 0.0;
-        }
-    };
-    auto commit = [&](const double (&stg)[EPT], double* dst) {
+            int nv = wide ? (i < n ? m - k : 0) : (k < m ? n - i : 0);
+            nv = nv < 0 ? 0 : (nv > 4 ? 4 : nv);
+            const TE* src = A + (wide ? (size_t)i * cols + k : (size_t)k * cols + i);
+            if (nv == 4 && sp.vec) {
+                ch_load4(src, stg[p]);
+            } else {
 #pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int e = tid + 1024 * q;
-            int kk, i;
-            if (wide) { i = e / CH_KC; kk = e % CH_KC; } else { kk = e / CH_NP; i = e % CH_NP; }
-            dst[kk * AS_LD + i] = stg[q];
+                for (int j = 0; j < 4; ++j) stg[p][j] = j < nv ? src[j] : (TE)0;
+            }
         }
     };
-    double* Abuf[2] = {As, As + CH_KC * AS_LD};
+    auto commit = [&](double* dst) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            int i, kk;
+            run_of(p, i, kk);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (wide) dst[(kk + j) * CH_AS_LD + i] = (double)stg[p][j];
+                else      dst[kk * CH_AS_LD + i + j] = (double)stg[p][j];
+            }
+        }
+    };
+    double* Abuf[2] = {As, As + CH_KC * CH_AS_LD};
     const int m_run = (sp.skip & 1) ? CH_KC : m;
-    // chunk c is multiplied out of Abuf[c & 1]; `stg_next` holds chunk c+1, `stg_free` receives chunk c+2
-    auto chunk = [&](int k0, int cur, const double (&stg_next)[EPT], double (&stg_free)[EPT]) {
-        if (k0 + 2 * CH_KC < m_run) fetch(stg_free, k0 + 2 * CH_KC);
+    // chunk c is multiplied out of Abuf[c & 1] while chunk c+1 is in flight to registers (with two workgroups
+    // per CU, the partner's work covers what one chunk of MFMAs does not)
+    for (int k0 = 0, cur = 0; k0 < m_run; k0 += CH_KC, cur ^= 1) {
+        if (k0 == 0) {
+            fetch(0);
+            commit(Abuf[0]);
+            __syncthreads();
+        }
+        if (k0 + CH_KC < m_run) fetch(k0 + CH_KC);
         const double* Ac = Abuf[cur];
         const int kmax = (m - k0 < CH_KC) ? m - k0 : CH_KC;
         // (rows past m and columns past n of the chunk are zero-filled by fetch)
-#pragma unroll 2
-        for (int k4 = 0; k4 < CH_KC; k4 += 4) {
-            const double* slab = Ac + k4 * AS_LD + fr_off;
+        const double* slab0 = Ac + lq * CH_AS_LD + lr;
+        for (int k4 = 0; k4 < kmax; k4 += 4) {
+            const double* slab = slab0 + k4 * CH_AS_LD;
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
+            for (int q = 0; q < 5; ++q)
                 if (q < g_cnt)
                     acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(slab[g_ti[q] * 16], slab[g_tj[q] * 16], acc[q], 0, 0, 0);
         }
-        if (!wide && ao < nrhs) {
-            const double sc = sp.t_scale ? sp.t_scale[(size_t)g * nrhs + ao] : 1.0;
-            const double sh = sp.t_shift ? sp.t_shift[(size_t)g * nrhs + ao] : 0.0;
-            for (int kk = 0; kk < kmax; ++kk)
-                atb = fma(Ac[kk * AS_LD + ai], Dg[(size_t)(k0 + kk) * nrhs + ao] * sc + sh, atb);
-        }
-        if (k0 + CH_KC < m_run) commit(stg_next, Abuf[cur ^ 1]);
-        __syncthreads();
-    };
-    fetch(stgA, 0);
-    commit(stgA, Abuf[0]);
-    if (CH_KC < m_run) fetch(stgA, CH_KC);
-    __syncthreads();
-    for (int k0 = 0; k0 < m_run; k0 += 2 * CH_KC) {
-        chunk(k0, 0, stgA, stgB);
-        if (k0 + CH_KC < m_run) chunk(k0 + CH_KC, 1, stgB, stgA);
-    }
-    __syncthreads();
-    // ---- phase 2: G and the right-hand sides into LDS ----------------------------------
+        if constexpr (!wide) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-        if (q < g_cnt) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                Gs[(g_ti[q] * 16 + 4 * i + (lane >> 4)) * CH_LD + g_tj[q] * 16 + (lane & 15)] = acc[q][i];
-        }
-    if (tid == 0) sh_bad = 0;
-    for (int e = tid; e < nrhs * CH_NP; e += 1024) {
-        const int o = e / CH_NP, i = e % CH_NP;
-        double v = 0.0;
-        if (wide && i < n) {
-            const double sc = sp.t_scale ? sp.t_scale[(size_t)g * nrhs + o] : 1.0;
-            const double sh = sp.t_shift ? sp.t_shift[(size_t)g * nrhs + o] : 0.0;
-            v = Dg[(size_t)i * nrhs + o] * sc + sh;
-        }
-        if (wide) Bs[e] = v;
-    }
-    __syncthreads();
-    if (!wide && ao < nrhs) Bs[ao * CH_NP + ai] = (ai < n) ? atb : 0.0;
-    // largest diagonal entry (pivot tolerance)
-    double dmax = 0.0;
-    if (tid < n) dmax = Gs[tid * CH_LD + tid];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dmax = fmax(dmax, __shfl_down(dmax, off));
-    __shared__ double sh_max[2];
-    if (tid < 128 && lane == 0) sh_max[wv] = dmax;
-    __syncthreads();
-    const double piv_tol = fmax(sh_max[0], sh_max[1]) * 1e-14;
-
-    // ---- phase 3: blocked right-looking Cholesky, 16-column blocks --------------------------
-    // per block: (a) wave 0 factorises the 16x16 diagonal block in registers (lane r = row r, the
-    // pivots travel by v_readlane) and inverts it (lane c = column c of L11^-1); (b) the panel
-    // L21 = A21 L11^-T and (c) the trailing update A22 -= L21 L21^T are 16x16x4 float64 MFMAs out
-    // of / into the LDS image.  Three barriers per 16 columns instead of two per column.
-    // A rejected pivot (v <= tol) drops its direction, as pinv would: unit diagonal, zero column
-    // (row c of L11^-1 is zeroed so the panel column vanishes too) and the group is flagged.
-    __shared__ double sh_invd[CH_NP];
-    __shared__ double sh_linv[16][17];
-    auto bcast = [](double x, int src) -> double {       // wave-uniform copy of lane `src` (constant)
-        const uint64_t u = __builtin_bit_cast(uint64_t, x);
-        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, src);
-        const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), src);
-        return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-    };
-    const int nblk = (sp.skip & 2) ? 1 : (n + 15) / 16;
-    const int lr = lane & 15, lq = lane >> 4;
-    for (int kb = 0; kb < nblk; ++kb) {
-        const int j0 = 16 * kb;
-        if (wv == 0) {
-            const int r = lane & 15;                       // lanes 16..63 mirror lanes 0..15 (no divergence)
-            double a[16], x[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) a[c] = Gs[(j0 + r) * CH_LD + j0 + c];
-            double my_invd = 1.0;
-            unsigned rejected = 0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const double v = bcast(a[j], j);
-                const bool live = j0 + j < n;
-                const bool ok = live && v > piv_tol;
-                if (live && !ok) rejected |= 1u << j;
-                const double d = ok ? sqrt(v) : 1.0, inv_d = ok ? 1.0 / d : 0.0;
-                if (r == j) my_invd = ok ? inv_d : 1.0;
-                a[j] = (r == j) ? d : ((r > j) ? a[j] * inv_d : 0.0);          // column j of L11
-#pragma unroll
-                for (int k = j + 1; k < 16; ++k) {
-                    const double lkj = bcast(a[j], k);
-                    if (r >= k) a[k] = fma(-a[j], lkj, a[k]);
+            for (int p = 0; p < 2; ++p) {
+                const int e = tid + CH_NT * p, o = e / CH_NP, i = e % CH_NP;
+                if (o < nrhs) {
+                    const double sc = sp.t_scale ? sp.t_scale[(size_t)g * nrhs + o] : 1.0;
+                    const double sh = sp.t_shift ? sp.t_shift[(size_t)g * nrhs + o] : 0.0;
+                    for (int kk = 0; kk < kmax; ++kk)
+                        atb[p] = fma(Ac[kk * CH_AS_LD + i], Dg[(size_t)(k0 + kk) * nrhs + o] * sc + sh, atb[p]);
                 }
             }
-            if (lane < 16) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) Gs[(j0 + r) * CH_LD + j0 + c] = a[c];
-                sh_invd[j0 + r] = my_invd;
-            }
-            if (rejected && lane == 0) sh_bad = 1;
-            // lane c: column c of L11^-1 by forward substitution, L11[i][k] = a[k] of lane i
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                double sacc = (i == r) ? 1.0 : 0.0;
-#pragma unroll
-                for (int k = 0; k < i; ++k) sacc = fma(-bcast(a[k], i), x[k], sacc);   // x[k] = 0 for k < c
-                const double idi = bcast(my_invd, i);
-                x[i] = (i >= r && !((rejected >> i) & 1u)) ? sacc * idi : 0.0;
-            }
-            if (lane < 16) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh_linv[i][r] = x[i];
-            }
         }
+        if (k0 + CH_KC < m_run) commit(Abuf[cur ^ 1]);
         __syncthreads();
-        // (b) panel: row tile rt of L21 = A21[rt] * L11^-T  (B operand [k][n] = L11^-1[n][k])
-        const int ntile = (n + 15) / 16;
-        {
+    }
+
+    // ---- phase 2: G and the right-hand sides into LDS ----------------------------------------
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+        if (q < g_cnt) {
+            double* T = Gs + ch_tile(g_ti[q], g_tj[q]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) T[ch_el(4 * i + lq, lr)] = acc[q][i];
+        }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = tid + CH_NT * p;
+        if (wide) {
+            const int i = e / CH_RHS, o = e % CH_RHS;
+            double v = 0.0;
+            if (i < n && o < nrhs) {
+                const double sc = sp.t_scale ? sp.t_scale[(size_t)g * nrhs + o] : 1.0;
+                const double sh = sp.t_shift ? sp.t_shift[(size_t)g * nrhs + o] : 0.0;
+                v = Dg[(size_t)i * nrhs + o] * sc + sh;
+            }
+            Bs[e] = v;
+        } else {
+            const int o = e / CH_NP, i = e % CH_NP;
+            Bs[i * CH_RHS + o] = (o < nrhs && i < n) ? atb[p] : 0.0;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 3: blocked right-looking Cholesky, 16-column blocks ----------------------------
+    // per block kb: (b) panel L21 = A21 L11^-T, one tile per wave; (c) trailing update A22 -= L21 L21^T of
+    // the lower tiles, where wave 0 takes the next diagonal tile and goes on to factorise and invert it (a)
+    // while waves 1-7 update the rest.  Two barriers per 16 columns; all products are 16x16x4 float64
+    // MFMAs out of / into the packed tiles.
+    int bad = 0;                                                    // wave 0: a live pivot was rejected
+    const int nblk = (sp.skip & 2) ? 1 : ntile;
+    double piv_tol = 0.0;
+    if (wv == 0) {
+        double dmax = 0.0;                                          // largest diagonal entry
+        for (int i = lane; i < n; i += 64) dmax = fmax(dmax, Gs[ch_tile(i >> 4, i >> 4) + ch_el(i & 15, i & 15)]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) dmax = fmax(dmax, __shfl_xor(dmax, off));
+        piv_tol = dmax * 1e-14;
+    }
+    for (int kb = -1; kb < nblk; ++kb) {                            // kb = -1: the first diagonal block only
+        if (kb >= 0) {   // (b) panel: row tile rt of L21 = A21[rt] * L11^-T  (B operand [k][n] = L11^-1[n][k])
             const int rt = kb + 1 + wv;
             if (rt < ntile) {
+                const double* Li = Gs + ch_tile(kb, kb);
+
+                double* T = Gs + ch_tile(rt, kb);
                 f64x4 c = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int k0 = 0; k0 < 16; k0 += 4)
-                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(Gs[(rt * 16 + lr) * CH_LD + j0 + k0 + lq],
-                                                             sh_linv[lr][k0 + lq], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(T[ch_el(lr, k0 + lq)], Li[ch_el(lr, k0 + lq)], c, 0, 0, 0);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) Gs[(rt * 16 + 4 * i + lq) * CH_LD + j0 + lr] = c[i];
+                for (int i = 0; i < 4; ++i) T[ch_el(4 * i + lq, lr)] = c[i];
             }
         }
-        __syncthreads();
-        // (c) trailing update of the lower tiles (ti >= tj > kb): A22[ti][tj] -= L21[ti] L21[tj]^T
-        {
+        if (kb >= 0) {   // (c) trailing update of the lower tiles (ti >= tj > kb): A22[ti][tj] -= L21[ti] L21[tj]^T;
+            // t = 0 is the next diagonal tile (wave 0), waves 1..7 take t = 1, 2, ...
+            __syncthreads();
             const int mt = ntile - kb - 1, cnt = mt * (mt + 1) / 2;
-            for (int t = wv; t < cnt; t += 16) {
+            for (int t = wv; t < cnt; t += (wv == 0 ? cnt : CH_NW - 1)) {
                 int di = 0;
                 while ((di + 1) * (di + 2) / 2 <= t) ++di;
                 const int ti = kb + 1 + di, tj = kb + 1 + t - di * (di + 1) / 2;
+                double* C = Gs + ch_tile(ti, tj);
+                const double* La = Gs + ch_tile(ti, kb);
+                const double* Lb = Gs + ch_tile(tj, kb);
                 f64x4 c;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) c[i] = Gs[(ti * 16 + 4 * i + lq) * CH_LD + tj * 16 + lr];
+                for (int i = 0; i < 4; ++i) c[i] = C[ch_el(4 * i + lq, lr)];
 #pragma unroll
                 for (int k0 = 0; k0 < 16; k0 += 4)
-                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(-Gs[(ti * 16 + lr) * CH_LD + j0 + k0 + lq],
-                                                             Gs[(tj * 16 + lr) * CH_LD + j0 + k0 + lq], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(-La[ch_el(lr, k0 + lq)], Lb[ch_el(lr, k0 + lq)], c, 0, 0, 0);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) Gs[(ti * 16 + 4 * i + lq) * CH_LD + tj * 16 + lr] = c[i];
+                for (int i = 0; i < 4; ++i) C[ch_el(4 * i + lq, lr)] = c[i];
             }
         }
+        if (wv == 0 && kb + 1 < nblk) bad |= ch_factor_diag(Gs + ch_tile(kb + 1, kb + 1), 16 * (kb + 1), n, piv_tol, lane);
         __syncthreads();
     }
 
-    // ---- phase 4: L L^T x = b, column-oriented (no reductions), one wave per right-hand side --
-    for (int o = wv; o < ((sp.skip & 4) ? 0 : nrhs); o += 16) {
-        double* x = Bs + o * CH_NP;
-        double b0 = x[lane], b1 = x[lane + 64];       // rows lane and lane+64 of this rhs
-        for (int j = 0; j < n; ++j) {                 // forward: L z = b
-            const double own = (j < 64) ? b0 : b1;
-            const double zj = __shfl(own, j & 63) * sh_invd[j];
-            if (lane == (j & 63)) { if (j < 64) b0 = zj; else b1 = zj; }
-            const double l0 = (lane > j) ? Gs[lane * CH_LD + j] : 0.0;
-            const double l1 = (lane + 64 > j && lane + 64 < n) ? Gs[(lane + 64) * CH_LD + j] : 0.0;
-            b0 = fma(-l0, zj, b0);
-            b1 = fma(-l1, zj, b1);
-        }
-        for (int j = n - 1; j >= 0; --j) {            // backward: L^T x = z
-            const double own = (j < 64) ? b0 : b1;
-            const double xj = __shfl(own, j & 63) * sh_invd[j];
-            if (lane == (j & 63)) { if (j < 64) b0 = xj; else b1 = xj; }
-            const double* Lj = Gs + j * CH_LD;        // row j: L[j][i], i < j
-            const double l0 = (lane < j) ? Lj[lane] : 0.0;
-            const double l1 = (lane + 64 < j) ? Lj[lane + 64] : 0.0;
-            b0 = fma(-l0, xj, b0);
-            b1 = fma(-l1, xj, b1);
-        }
-        x[lane] = b0; x[lane + 64] = b1;
-    }
-    __syncthreads();
-
-    // ---- phase 5: W_out ---------------------------------------------------------------------
-    if (wide) {
-        // W_out[o][c] = sum_i A[i][c] alpha[i][o].  Every element of A is fetched once, by 16-byte
-        // loads: thread (third, pair) sums a third of the rows for columns 2 pair, 2 pair + 1 and all
-        // nrhs outputs; the three partial sums meet in LDS (the factor is no longer needed).  HBM
-        // latency-bound: ~12 waves x 8 loads x 1 KB in flight per CU.
-        const int npair = cols / 2;
-        if ((cols & 1) == 0 && 3 * npair <= 1024 && 3 * npair * 16 <= CH_NP * CH_LD && !(sp.skip & 8)) {
-            double* part = Gs;                               // [3][nrhs<=8][cols]
-            const int third = tid / npair, pr = tid - third * npair;
-            if (third < 3) {
-                const int per = (n + 2) / 3;
-                const int i0 = third * per, i1 = (i0 + per < n) ? i0 + per : n;
-                double w0[8], w1[8];
+    // ---- phase 4: L L^T alpha = B by 16-row tiles ---------------------------------------------
+    // Forward, step I: z_I = L_II^-1 b_I, then b_J -= L_JI z_I for J > I (wave J - I - 1).  Backward, step I:
+    // x_I = L_II^-T z_I, then z_J -= L_IJ^T x_I for J < I (wave J).  Each product is four 16x16x4 MFMAs
+    // (columns = right-hand sides, lanes with lr >= 8 carry zeros); the accumulator layout of z_I is the B
+    // operand layout of the update, so every updating wave forms z_I itself.  Wave 7 forms it as well and
+    // stores it one step later, when no wave reads those rows any more.  One barrier per tile step.
+    if (!(sp.skip & 4)) {
+        const bool bl = lr < CH_RHS;
+        f64x4 keep = {0.0, 0.0, 0.0, 0.0};
+        int keep_t = -1;
+        auto rhs_tile = [&](int I) -> f64x4 {                       // rows 16 I + 4 i + lq, column lr
+            f64x4 v;
 #pragma unroll
-                for (int o = 0; o < 8; ++o) { w0[o] = 0.0; w1[o] = 0.0; }
-                const size_t ac = 2 * (size_t)pr;
-#pragma unroll 8
-                for (int i = i0; i < i1; ++i) {
-                    double2 a;
-                    if (A32) {
-                        const float2 af = *reinterpret_cast<const float2*>(A32 + ac + (size_t)i * cols);
-                        a = double2{(double)af.x, (double)af.y};
-                    } else {
-                        a = *reinterpret_cast<const double2*>(A + ac + (size_t)i * cols);
-                    }
+            for (int i = 0; i < 4; ++i) v[i] = bl ? Bs[(16 * I + 4 * i + lq) * CH_RHS + lr] : 0.0;
+            return v;
+        };
+        auto put_tile = [&](int I, const f64x4& v) {
+            if (bl) {
 #pragma unroll
-                    for (int o = 0; o < 8; ++o)
-                        if (o < nrhs) {
-                            const double al = Bs[o * CH_NP + i];
-                            w0[o] = fma(a.x, al, w0[o]);
-                            w1[o] = fma(a.y, al, w1[o]);
-                        }
+                for (int i = 0; i < 4; ++i) Bs[(16 * I + 4 * i + lq) * CH_RHS + lr] = v[i];
+            }
+        };
+        auto flush = [&]() {
+            if (wv == CH_NW - 1 && keep_t >= 0) put_tile(keep_t, keep);
+            keep_t = -1;
+        };
+        for (int I = 0; I < ntile; ++I) {                           // forward: L z = b
+            flush();
+            const int J = I + 1 + wv;
+            const bool upd = J < ntile;
+            if (upd || wv == CH_NW - 1) {
+                const double* Li = Gs + ch_tile(I, I);
+                const f64x4 b = rhs_tile(I);
+                f64x4 z = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    z = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[ch_el(lr, 4 * s + lq)], b[s], z, 0, 0, 0);
+                if (upd) {
+                    const double* L = Gs + ch_tile(J, I);
+                    f64x4 c = rhs_tile(J);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        c = __builtin_amdgcn_mfma_f64_16x16x4f64(-L[ch_el(lr, 4 * s + lq)], z[s], c, 0, 0, 0);
+                    put_tile(J, c);
+                } else {
+                    keep = z;
+                    keep_t = I;
                 }
-#pragma unroll
-                for (int o = 0; o < 8; ++o)
-                    if (o < nrhs) {
-                        part[(third * 8 + o) * cols + 2 * pr] = w0[o];
-                        part[(third * 8 + o) * cols + 2 * pr + 1] = w1[o];
-                    }
             }
             __syncthreads();
-            for (int e = tid; e < nrhs * cols; e += 1024) {
-                const int o = e / cols, c = e - o * cols;
-                sp.W_out[((size_t)g * nrhs + o) * cols + c] =
-                    (part[o * cols + c] + part[(8 + o) * cols + c]) + part[(16 + o) * cols + c];
+        }
+        flush();
+        __syncthreads();
+        for (int I = ntile - 1; I >= 0; --I) {                      // backward: L^T x = z
+            flush();
+            const int J = wv;
+            const bool upd = J < I;
+            if (upd || wv == CH_NW - 1) {
+                const double* Li = Gs + ch_tile(I, I);
+                const f64x4 zi = rhs_tile(I);
+                f64x4 x = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    x = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[ch_el(4 * s + lq, lr)], zi[s], x, 0, 0, 0);
+                if (upd) {
+                    const double* L = Gs + ch_tile(I, J);
+                    f64x4 c = rhs_tile(J);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        c = __builtin_amdgcn_mfma_f64_16x16x4f64(-L[ch_el(4 * s + lq, lr)], x[s], c, 0, 0, 0);
+                    put_tile(J, c);
+                } else {
+                    keep = x;
+                    keep_t = I;
+                }
+            }
+            __syncthreads();
+        }
+        flush();
+        __syncthreads();
+    }
+
+    // ---- phase 5: W_out ---------------------------------------------------------------------
+    if constexpr (wide) {
+        // W_out[o][c] = sum_i A[i][c] alpha[i][o].  Every element of A is fetched once, by 16-byte loads:
+        // thread (part, unit) sums a third of the rows for the unit's CPT columns and all nrhs outputs;
+        // parts 1 and 2 leave their sums in LDS (the factor is no longer needed), part 0 adds them.
+        constexpr int CPT = 16 / sizeof(TE);
+        const int nunit = cols / CPT;
+        int parts = nunit > 0 ? CH_NT / nunit : 0;
+        parts = parts > 3 ? 3 : parts;
+        if (sp.vec && cols % CPT == 0 && parts > 0 && (parts - 1) * CH_RHS * cols <= CH_TILES * 256 && !(sp.skip & 8)) {
+            double* part = Gs;                               // [parts - 1][CH_RHS][cols]
+            const int pt = tid / nunit, un = tid - pt * nunit;
+            double w[CPT][CH_RHS];
+#pragma unroll
+            for (int c = 0; c < CPT; ++c)
+#pragma unroll
+                for (int o = 0; o < CH_RHS; ++o) w[c][o] = 0.0;
+            if (pt < parts) {
+                const int per = (n + parts - 1) / parts;
+                const int i0 = pt * per, i1 = (i0 + per < n) ? i0 + per : n;
+                const TE* ac = A + (size_t)CPT * un;
+#pragma unroll 4
+                for (int i = i0; i < i1; ++i) {
+                    TE a[CPT];
+                    if constexpr (CPT == 4) {
+                        ch_load4(ac + (size_t)i * cols, a);
+                    } else {
+                        const double2 ad = *reinterpret_cast<const double2*>(ac + (size_t)i * cols);
+                        a[0] = ad.x; a[1] = ad.y;
+                    }
+#pragma unroll
+                    for (int o = 0; o < CH_RHS; ++o)
+                        if (o < nrhs) {
+                            const double al = Bs[i * CH_RHS + o];
+#pragma unroll
+                            for (int c = 0; c < CPT; ++c) w[c][o] = fma((double)a[c], al, w[c][o]);
+                        }
+                }
+                if (pt > 0) {
+#pragma unroll
+                    for (int o = 0; o < CH_RHS; ++o)
+                        if (o < nrhs) {
+#pragma unroll
+                            for (int c = 0; c < CPT; ++c) part[((pt - 1) * CH_RHS + o) * cols + CPT * un + c] = w[c][o];
+                        }
+                }
+            }
+            __syncthreads();
+            if (pt == 0) {
+#pragma unroll
+                for (int o = 0; o < CH_RHS; ++o)
+                    if (o < nrhs) {
+#pragma unroll
+                        for (int c = 0; c < CPT; ++c) {
+                            double v = w[c][o];
+                            for (int q = 1; q < parts; ++q) v += part[((q - 1) * CH_RHS + o) * cols + CPT * un + c];
+                            sp.W_out[((size_t)g * nrhs + o) * cols + CPT * un + c] = v;
+                        }
+                    }
             }
         } else {
-            for (int c = tid; c < ((sp.skip & 8) ? 0 : cols); c += 1024) {
-                double w[8];
+            for (int c = tid; c < ((sp.skip & 8) ? 0 : cols); c += CH_NT) {
+                double w[CH_RHS];
 #pragma unroll
-                for (int o = 0; o < 8; ++o) w[o] = 0.0;
+                for (int o = 0; o < CH_RHS; ++o) w[o] = 0.0;
 #pragma unroll 8
                 for (int i = 0; i < n; ++i) {
-                    const double a = A32 ? (double)A32[(size_t)i * cols + c] : A[(size_t)i * cols + c];
+                    const double a = (double)A[(size_t)i * cols + c];
 #pragma unroll
-                    for (int o = 0; o < 8; ++o)
-                        if (o < nrhs) w[o] = fma(a, Bs[o * CH_NP + i], w[o]);
+                    for (int o = 0; o < CH_RHS; ++o)
+                        if (o < nrhs) w[o] = fma(a, Bs[i * CH_RHS + o], w[o]);
                 }
 #pragma unroll
-                for (int o = 0; o < 8; ++o)
+                for (int o = 0; o < CH_RHS; ++o)
                     if (o < nrhs) sp.W_out[((size_t)g * nrhs + o) * cols + c] = w[o];
             }
         }
     } else {
-        for (int e = tid; e < nrhs * cols; e += 1024) {
+        for (int e = tid; e < nrhs * cols; e += CH_NT) {
             const int o = e / cols, c = e % cols;
-            sp.W_out[((size_t)g * nrhs + o) * cols + c] = Bs[o * CH_NP + c];
+            sp.W_out[((size_t)g * nrhs + o) * cols + c] = Bs[c * CH_RHS + o];
         }
     }
-    if (tid == 0) sp.status[g] = sh_bad;
+    if (tid == 0) sp.status[g] = bad;
 }
 
 int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
@@ -565,17 +675,22 @@ int launch_readout_chol(const double* E, const float* E32, const double* D, int 
     sp.E32 = E32;
     const int rows = T - transient;
     const int n = rows < cols ? rows : cols;
-    if (n > CH_NP || n_out > 8) return -1;     // tall case stages A^T B with nrhs*128 <= 1024 threads
+    if (n > CH_NP || n_out > CH_RHS) return -1;
     sp.E = E; sp.D = D; sp.n_groups = n_groups; sp.T = T; sp.transient = transient;
     sp.cols = cols; sp.n_out = n_out; sp.t_scale = t_scale; sp.t_shift = t_shift;
     sp.W_out = W_out; sp.status = status; sp.work = nullptr; sp.work_stride = 0;
     sp.wide = rows < cols; sp.m = sp.wide ? cols : rows; sp.n = n;
     sp.skip = knobs().chol_skip;
-    const size_t lds = sizeof(double) * ((size_t)CH_NP * CH_LD + (size_t)n_out * CH_NP);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_chol_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    sp.part_ok = 0;
+    // 16-byte loads of 4 consecutive elements: every row of every group starts 16-byte aligned
+    const uintptr_t base = E32 ? (uintptr_t)E32 : (uintptr_t)E;
+    sp.vec = (base % 16 == 0) && (cols % (E32 ? 4 : 2) == 0);
+    void (*fn)(SolveParams) = E32 ? (sp.wide ? readout_chol_kernel<float, true> : readout_chol_kernel<float, false>)
+                                  : (sp.wide ? readout_chol_kernel<double, true> : readout_chol_kernel<double, false>);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)CH_LDS);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(readout_chol_kernel, dim3(n_groups), dim3(1024), lds, stream, sp);
+    hipLaunchKernelGGL(fn, dim3(n_groups), dim3(CH_NT), CH_LDS, stream, sp);
     return (int)hipGetLastError();
 }
 

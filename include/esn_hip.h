@@ -86,7 +86,9 @@ int esn_abi_version(void);
  *   "skew"          "0" = in-step schedule for the fp16/bf16 predict kernel, else skewed (default)
  *   "mfma_geom"     "NW,MT,NT" re-cuts the fp16/bf16 predict tiling; ignored unless 32*NW*MT equals
  *   "mfma_geom_f32" the table's padded row count, so a packed image never goes stale; NULL = table
- *   "chol_skip"     bit mask of Cholesky-solve phases to drop (timing only, wrong results)
+ *   "chol_skip"     bit mask of Cholesky-solve phases to drop (timing only, wrong results; Gram dimension <= 128):
+ *                   1 Gram over the first 32-wide k-chunk only, 2 factorisation of the first 16-column block
+ *                   only, 4 no blocked triangular solves, 8 no W_out = A^T alpha pass
  *   "f64_mfma"      "0" = ESN_F64 batches on the vector-ALU kernel instead of the float64 matrix pipe
  *   "rs"            "1" = fp16/bf16 predict at N_res 257..512 on the register-resident-state kernel
  *                   (esn_recur_rs.hip; an experiment kept for A/B runs, compiled only into ESN_WITH_RS=1 builds:
