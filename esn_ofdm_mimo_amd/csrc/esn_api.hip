@@ -116,6 +116,8 @@ Knobs& knobs() {
         x.hcluster = (v && (v[0] == '0' || v[0] == '4' || v[0] == '8')) ? v[0] - '0' : 1;
         v = getenv("ESN_S16");
         x.s16 = (v && v[0] == '0') ? 0 : 1;
+        v = getenv("ESN_CHOL_DMA");
+        x.chol_dma = (v && v[0] == '0') ? 0 : 1;
         v = getenv("ESN_BIG_PIPE");
         x.big_pipe = (v && v[0] == '0') ? 0 : 1;
         return x;
@@ -176,6 +178,7 @@ static bool geometry_for(int precision, const esn_shape_t* s, Geometry* g, bool 
 #ifdef ESN_STAMPS
 static unsigned long long* g_stamp_buf = nullptr;
 extern "C" void esn_debug_set_stamp_buffer(void* dev) { g_stamp_buf = (unsigned long long*)dev; }
+namespace esn { unsigned long long* stamp_buffer() { return g_stamp_buf; } }
 #define ESN_SET_STAMPS(p) (p).stamps = g_stamp_buf
 #else
 #define ESN_SET_STAMPS(p) (p).stamps = nullptr
@@ -213,6 +216,7 @@ int esn_debug_set(const char* key, const char* value) {
         return 0;
     }
     if (!strcmp(key, "s16")) { k.s16 = (value && value[0] == '0') ? 0 : 1; return 0; }
+    if (!strcmp(key, "chol_dma")) { k.chol_dma = (value && value[0] == '0') ? 0 : 1; return 0; }
     if (!strcmp(key, "big_pipe")) { k.big_pipe = (value && value[0] == '0') ? 0 : 1; return 0; }
     return fail(-1, "esn_debug_set: unknown key '%s'", key);
 }

@@ -223,6 +223,8 @@ struct Knobs {
     int geom16[3];         // fp16/bf16 predict tiling override {NW, MT, NT}; {0,0,0} = table
     int geom32[3];         // float32 predict tiling override
     int chol_skip;         // bit mask of Cholesky-solve phases to drop (tools/time_chol.py)
+    int chol_dma;          // 1 (default): the LDS Cholesky solve feeds its Gram and W_out passes of float32 E by LDS-DMA
+                           // rings; 0: the register-staged passes (A/B and bitwise tests)
     int f64_mfma;          // 1 (default): float64 batches run on the matrix pipe; 0: vector-ALU kernel (A/B tests)
     int rs;                // 1: fp16/bf16 predict at N_res 257..512 runs the register-resident-state kernel (default 0:
                            // correct but 17 % slower than the skewed LDS-state kernel on MI355X)

@@ -8,6 +8,7 @@
 // The working matrix is column-major in the caller's workspace (L2 resident);
 // reflector j is applied to the trailing columns one wave per column.
 #include <stdlib.h>
+#include <type_traits>
 #include "esn_common.h"
 
 namespace esn {
@@ -23,6 +24,8 @@ struct SolveParams {
     int skip;   // diagnostic only (ESN_CHOL_SKIP env): bit0 Gram, bit1 Cholesky, bit2 solves, bit3 W_out
     int part_ok;   // big kernel: the three-partial-sums W_out pass fits the LDS the launcher allocated
     int vec;       // LDS Cholesky kernel: E rows start 16-byte aligned and hold whole 16-byte runs (vector loads)
+    int dma;       // LDS Cholesky kernel, wide float32 E: Gram and W_out passes fed by LDS-DMA rings (knob chol_dma)
+    unsigned long long* stamps;   // diagnostic build (-DESN_STAMPS) only: [wave][8] cycle sums of workgroup 0
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -239,6 +242,55 @@ static_assert(2 * CH_KC * CH_AS_LD <= CH_TILES * 256, "E staging aliases the Gra
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+// LDS-DMA rings of the wide float32 instance (sp.dma): E goes global -> LDS by buffer_load ... lds, 16 B per
+// lane, with no register staging.  Both rings live in the tile area, which is dead in phases 1 and 5.
+constexpr int CH_RING = 4;                  // Gram: 4 buffers of one 32-k chunk (3 chunks in flight)
+constexpr int CH_RBUF = CH_KC * CH_NP * 4;  // 16 KB: 128 rows x 32 k as float32
+constexpr int CH_WRING = 3;                 // W_out: 3 buffers (2 chunks in flight) of three part segments
+constexpr int CH_WSEG = 8192;               // rows of one part per chunk, padded to whole 1 KB DMA pieces
+constexpr int CH_WROWS = 4;                 // at most 4 rows of a part per chunk (the row loop is unrolled)
+static_assert(CH_RING * CH_RBUF <= CH_TILES * 256 * 8, "Gram ring aliases the Gram tiles");
+static_assert(CH_WRING * 3 * CH_WSEG <= CH_TILES * 256 * 8, "W_out ring aliases the Gram tiles");
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ch_rsrc(const void* ptr, int bytes) {
+    const uint64_t a = (uint64_t)reinterpret_cast<uintptr_t>(ptr);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>((uintptr_t)(((uint64_t)hi << 32) | lo)), 0,
+                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+// 16 bytes per lane from E at byte offset voff (>= num_records: zeros, no traffic) to the 1 KB at dst
+__device__ __forceinline__ void ch_dma16(__amdgpu_buffer_rsrc_t rs, char* dst, int voff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, voff, 0, 0, 0);
+}
+constexpr int CH_OOR = 0x7ffffff0;          // byte offset past any E a launch accepts
+// this wave's DMA pieces, except the last `pending` issued, have landed in LDS; its LDS reads have returned
+__device__ __forceinline__ void ch_wait_dma(int pending) {
+    switch (pending) {
+        case 4: asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); break;
+        case 3: asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory"); break;
+        case 2: asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory"); break;
+        default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
+    }
+}
+
+// W_out ring: a thread's 16 B of one E row and the row's CH_RHS alpha values.  hipcc guards every LDS read it can
+// see with vmcnt(0) while an LDS-DMA is pending, which would drain the ring on each row; these reads are ordered
+// after the DMA by the ring's counted vmcnt and barrier instead, and waited for here.
+__device__ __forceinline__ void ch_wrow(const char* e, const double* al, float (&a)[4], double (&b)[8]) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    const uint32_t ea = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)e;
+    const uint32_t ba = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) double*)al;
+    f32x4 ev;
+    f64x2 b0, b1, b2, b3;
+    asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %6\n\tds_read_b128 %2, %6 offset:16\n\t"
+                 "ds_read_b128 %3, %6 offset:32\n\tds_read_b128 %4, %6 offset:48\n\ts_waitcnt lgkmcnt(0)"
+                 : "=v"(ev), "=v"(b0), "=v"(b1), "=v"(b2), "=v"(b3) : "v"(ea), "v"(ba) : "memory");
+    a[0] = ev.x; a[1] = ev.y; a[2] = ev.z; a[3] = ev.w;
+    b[0] = b0.x; b[1] = b0.y; b[2] = b1.x; b[3] = b1.y; b[4] = b2.x; b[5] = b2.y; b[6] = b3.x; b[7] = b3.y;
+}
+
 // first double of lower tile (ti, tj), ti >= tj
 __device__ __forceinline__ int ch_tile(int ti, int tj) { return (ti * (ti + 1) / 2 + tj) * 256; }
 // element (r, c) of a tile: row-major, the column XORed with the row pair.  MFMA operand reads by row
@@ -382,14 +434,104 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
     };
     double* Abuf[2] = {As, As + CH_KC * CH_AS_LD};
     const int m_run = (sp.skip & 1) ? CH_KC : m;
+    constexpr bool can_dma = wide && sizeof(TE) == 4;
+    const bool dma = can_dma && sp.dma && sp.vec;
+#ifdef ESN_STAMPS
+    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_ph[4] = {0, 0, 0, 0};
+    ESN_STAMP(st_k0);
+#endif
+    if constexpr (can_dma) {
+        if (dma) {
+            // Float32 chunks of 32 k x 128 rows through a ring of CH_RING buffers, CH_RING - 1 in flight.  DMA
+            // piece j of wave w covers rows 8 d .. 8 d + 7 (d = 2 w + j) and all eight k-quads of the chunk: lane l
+            // fetches the 16 B of row 8 d + (l & 7), k-quad l >> 3.  Byte (r, k) of a buffer is therefore
+            // 1024 (r >> 3) + 128 (k >> 2) + 16 (r & 7) + 4 (k & 3): an operand read (16 rows x 4 k) takes two LDS
+            // cycles per lane group, the least a 4-byte read of 16-byte runs allows, and steps k4 apart by a
+            // constant offset.  Rows >= n are past num_records, k-quads >= m get an out-of-range offset: both land
+            // as zeros.  The MFMA sequence and k order are those of the register-staged pass (bitwise the same G).
+            char* ring = chol_smem;
+            const __amdgpu_buffer_rsrc_t ers = ch_rsrc(A, n * cols * 4);
+            const int kq = lane >> 3;
+            int roff[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) roff[j] = ((16 * wv + 8 * j + (lane & 7)) * cols + 4 * kq) * 4;
+            const int nch = (m_run + CH_KC - 1) / CH_KC;
+            auto issue = [&](int c, int b) {
+                const int k0 = c * CH_KC;
+                const bool ok = k0 + 4 * kq < m;
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    ch_dma16(ers, ring + b * CH_RBUF + (2 * wv + j) * 1024, ok ? roff[j] + 4 * k0 : CH_OOR);
+            };
+#pragma unroll
+            for (int c = 0; c < CH_RING - 1; ++c)
+                if (c < nch) issue(c, c);
+            const int lbase = 1024 * (lr >> 3) + 16 * (lr & 7) + 4 * lq;
+            for (int c = 0, b = 0; c < nch; ++c, b = (b + 1 == CH_RING ? 0 : b + 1)) {
+#ifdef ESN_STAMPS
+                ESN_STAMP(s0);
+#endif
+                const int later = nch - 1 - c < CH_RING - 2 ? nch - 1 - c : CH_RING - 2;
+                ch_wait_dma(2 * later);
+#ifdef ESN_STAMPS
+                ESN_STAMP(s1);
+#endif
+                __builtin_amdgcn_s_barrier();                       // chunk c landed for all; chunk c-1 read by all
+                if (c + CH_RING - 1 < nch) issue(c + CH_RING - 1, b == 0 ? CH_RING - 1 : b - 1);
+                const char* buf = ring + b * CH_RBUF + lbase;
+                const float* pa[5];
+                const float* pb[5];
+#pragma unroll
+                for (int q = 0; q < 5; ++q) {
+                    pa[q] = reinterpret_cast<const float*>(buf + 2048 * g_ti[q]);
+                    pb[q] = reinterpret_cast<const float*>(buf + 2048 * g_tj[q]);
+                }
+#ifdef ESN_STAMPS
+                ESN_STAMP(s2);
+                {   // operand-read latency: one read of the chunk, waited for (the stamp waits lgkmcnt(0))
+                    float x = pa[0][0];
+                    asm volatile("" :: "v"(x));
+                }
+                ESN_STAMP(s3);
+#endif
+                // the tile count is hoisted out of the k4 steps: a full chunk is one straight block, so its
+                // operand reads run ahead of the MFMAs across steps
+                auto step = [&](int s, auto cnt) {
+#pragma unroll
+                    for (int q = 0; q < decltype(cnt)::value; ++q)
+                        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)pa[q][32 * s], (double)pb[q][32 * s], acc[q], 0, 0, 0);
+                };
+                const int kmax = (m - c * CH_KC < CH_KC) ? m - c * CH_KC : CH_KC;
+                if (kmax == CH_KC && g_cnt == 5) {
+#pragma unroll
+                    for (int s = 0; s < CH_KC / 4; ++s) step(s, std::integral_constant<int, 5>());
+                } else if (kmax == CH_KC) {
+#pragma unroll
+                    for (int s = 0; s < CH_KC / 4; ++s) step(s, std::integral_constant<int, 4>());
+                } else if (g_cnt == 5) {
+                    for (int s = 0; s < kmax / 4; ++s) step(s, std::integral_constant<int, 5>());
+                } else {
+                    for (int s = 0; s < kmax / 4; ++s) step(s, std::integral_constant<int, 4>());
+                }
+#ifdef ESN_STAMPS
+                ESN_STAMP(s4);
+                st_acc[0] += s1 - s0; st_acc[1] += s2 - s1; st_acc[2] += s3 - s2; st_acc[3] += s4 - s3;
+#endif
+            }
+            __syncthreads();                                        // every DMA waited for; the ring is read out
+        }
+    }
     // chunk c is multiplied out of Abuf[c & 1] while chunk c+1 is in flight to registers (with two workgroups
     // per CU, the partner's work covers what one chunk of MFMAs does not)
-    for (int k0 = 0, cur = 0; k0 < m_run; k0 += CH_KC, cur ^= 1) {
+    for (int k0 = 0, cur = 0; k0 < (dma ? 0 : m_run); k0 += CH_KC, cur ^= 1) {
         if (k0 == 0) {
             fetch(0);
             commit(Abuf[0]);
             __syncthreads();
         }
+#ifdef ESN_STAMPS
+        ESN_STAMP(s0);
+#endif
         if (k0 + CH_KC < m_run) fetch(k0 + CH_KC);
         const double* Ac = Abuf[cur];
         const int kmax = (m - k0 < CH_KC) ? m - k0 : CH_KC;
@@ -414,9 +556,22 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
                 }
             }
         }
+#ifdef ESN_STAMPS
+        ESN_STAMP(s1);
+#endif
         if (k0 + CH_KC < m_run) commit(Abuf[cur ^ 1]);
+#ifdef ESN_STAMPS
+        ESN_STAMP(s2);
+#endif
         __syncthreads();
+#ifdef ESN_STAMPS
+        ESN_STAMP(s3);
+        st_acc[3] += s1 - s0; st_acc[0] += s2 - s1; st_acc[1] += s3 - s2;    // MFMA issue | load wait + commit | barrier
+#endif
     }
+#ifdef ESN_STAMPS
+    ESN_STAMP(st_k1);
+#endif
 
     // ---- phase 2: G and the right-hand sides into LDS ----------------------------------------
 #pragma unroll
@@ -500,6 +655,9 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         __syncthreads();
     }
 
+#ifdef ESN_STAMPS
+    ESN_STAMP(st_k2);
+#endif
     // ---- phase 4: L L^T alpha = B by 16-row tiles ---------------------------------------------
     // Forward, step I: z_I = L_II^-1 b_I, then b_J -= L_JI z_I for J > I (wave J - I - 1).  Backward, step I:
     // x_I = L_II^-T z_I, then z_J -= L_IJ^T x_I for J < I (wave J).  Each product is four 16x16x4 MFMAs
@@ -582,6 +740,9 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         __syncthreads();
     }
 
+#ifdef ESN_STAMPS
+    ESN_STAMP(st_k3);
+#endif
     // ---- phase 5: W_out ---------------------------------------------------------------------
     if constexpr (wide) {
         // W_out[o][c] = sum_i A[i][c] alpha[i][o].  Every element of A is fetched once, by 16-byte loads:
@@ -599,8 +760,85 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
             for (int c = 0; c < CPT; ++c)
 #pragma unroll
                 for (int o = 0; o < CH_RHS; ++o) w[c][o] = 0.0;
-            if (pt < parts) {
-                const int per = (n + parts - 1) / parts;
+            const int per = (n + parts - 1) / parts;
+            int rw = CH_WSEG / (cols * 4);                   // rows of each part per W_out chunk
+            rw = rw > CH_WROWS ? CH_WROWS : rw;
+            bool wdma = false;
+            if constexpr (can_dma) {
+              wdma = dma && rw > 0;
+              if (wdma) {
+                // The same sums, E streamed through a ring of CH_WRING buffers: chunk c holds rows
+                // i0 + rw c .. i0 + rw c + rw - 1 of each part in that part's CH_WSEG segment (row-major as in E),
+                // so each thread reads its 16 B of a row with one conflict-free LDS read.  Wave w fetches 1 KB piece
+                // w of every segment; bytes past a segment's rows get an out-of-range offset and land as zeros.
+                // Row order per thread and the combine order of the parts are unchanged (bitwise the same W_out).
+                char* ring = chol_smem;
+                const __amdgpu_buffer_rsrc_t ers = ch_rsrc(A, n * cols * 4);
+                const int rowb = cols * 4;
+                const int nch = (per + rw - 1) / rw;
+                auto issue = [&](int c, int b) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        const int r0 = j * per + c * rw;
+                        int nr = (j < parts) ? ((j + 1) * per < n ? (j + 1) * per : n) - r0 : 0;
+                        nr = nr < 0 ? 0 : (nr > rw ? rw : nr);
+                        const int off = 1024 * wv + 16 * lane;
+                        ch_dma16(ers, ring + (b * 3 + j) * CH_WSEG + 1024 * wv, off < nr * rowb ? r0 * rowb + off : CH_OOR);
+                    }
+                };
+#pragma unroll
+                for (int c = 0; c < CH_WRING - 1; ++c)
+                    if (c < nch) issue(c, c);
+                const int i0 = pt * per, i1 = (i0 + per < n) ? i0 + per : n;
+                for (int c = 0, b = 0; c < nch; ++c, b = (b + 1 == CH_WRING ? 0 : b + 1)) {
+#ifdef ESN_STAMPS
+                    ESN_STAMP(s0);
+#endif
+                    ch_wait_dma(nch - 1 - c < CH_WRING - 2 ? 3 * (nch - 1 - c) : 3 * (CH_WRING - 2));
+#ifdef ESN_STAMPS
+                    ESN_STAMP(s1);
+#endif
+                    __builtin_amdgcn_s_barrier();
+                    if (c + CH_WRING - 1 < nch) issue(c + CH_WRING - 1, b == 0 ? CH_WRING - 1 : b - 1);
+#ifdef ESN_STAMPS
+                    ESN_STAMP(s2);
+#endif
+                    if (pt < parts) {
+                        const char* seg = ring + (b * 3 + pt) * CH_WSEG + CPT * sizeof(TE) * un;
+                        const int ib = i0 + c * rw;
+                        const int nr = ((ib + rw < i1) ? ib + rw : i1) - ib;
+#pragma unroll
+                        for (int rr = 0; rr < CH_WROWS; ++rr) {
+                            if (rr >= nr) break;
+                            const int i = ib + rr;
+                            float a[4];
+                            double al[CH_RHS];
+                            ch_wrow(seg + rr * rowb, Bs + i * CH_RHS, a, al);
+#pragma unroll
+                            for (int o = 0; o < CH_RHS; ++o)
+                                if (o < nrhs) {
+#pragma unroll
+                                    for (int cc = 0; cc < CPT; ++cc) w[cc][o] = fma((double)a[cc], al[o], w[cc][o]);
+                                }
+                        }
+                    }
+#ifdef ESN_STAMPS
+                    ESN_STAMP(s3);
+                    st_acc[4] += s1 - s0; st_acc[5] += s2 - s1; st_acc[6] += s3 - s2;
+#endif
+                }
+                __syncthreads();                             // the ring is read out: the part sums alias it
+                if (pt > 0 && pt < parts) {
+#pragma unroll
+                    for (int o = 0; o < CH_RHS; ++o)
+                        if (o < nrhs) {
+#pragma unroll
+                            for (int c = 0; c < CPT; ++c) part[((pt - 1) * CH_RHS + o) * cols + CPT * un + c] = w[c][o];
+                        }
+                }
+              }
+            }
+            if (!wdma && pt < parts) {
                 const int i0 = pt * per, i1 = (i0 + per < n) ? i0 + per : n;
                 const TE* ac = A + (size_t)CPT * un;
 #pragma unroll 4
@@ -666,7 +904,23 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         }
     }
     if (tid == 0) sp.status[g] = bad;
+#ifdef ESN_STAMPS
+    ESN_STAMP(st_k4);
+    // row wv: Gram wait | barrier | operand read | MFMA issue, W_out wait | barrier | rows; row 8 + wv: phase totals
+    if (sp.stamps && g == 0 && lane == 0) {
+        for (int i = 0; i < 7; ++i) sp.stamps[wv * 8 + i] = st_acc[i];
+        sp.stamps[(8 + wv) * 8 + 0] = st_k1 - st_k0;
+        sp.stamps[(8 + wv) * 8 + 1] = st_k2 - st_k1;
+        sp.stamps[(8 + wv) * 8 + 2] = st_k3 - st_k2;
+        sp.stamps[(8 + wv) * 8 + 3] = st_k4 - st_k3;
+        sp.stamps[(8 + wv) * 8 + 4] = st_k4 - st_k0;
+    }
+#endif
 }
+
+#ifdef ESN_STAMPS
+unsigned long long* stamp_buffer();     // esn_api.hip
+#endif
 
 int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
                         int cols, int n_out, const double* t_scale, const double* t_shift,
@@ -681,7 +935,13 @@ int launch_readout_chol(const double* E, const float* E32, const double* D, int 
     sp.W_out = W_out; sp.status = status; sp.work = nullptr; sp.work_stride = 0;
     sp.wide = rows < cols; sp.m = sp.wide ? cols : rows; sp.n = n;
     sp.skip = knobs().chol_skip;
+    sp.dma = knobs().chol_dma;
     sp.part_ok = 0;
+#ifdef ESN_STAMPS
+    sp.stamps = stamp_buffer();
+#else
+    sp.stamps = nullptr;
+#endif
     // 16-byte loads of 4 consecutive elements: every row of every group starts 16-byte aligned
     const uintptr_t base = E32 ? (uintptr_t)E32 : (uintptr_t)E;
     sp.vec = (base % 16 == 0) && (cols % (E32 ? 4 : 2) == 0);

@@ -81,7 +81,7 @@ const char* esn_last_error(void);
 int esn_abi_version(void);
 
 /* Tuning / diagnostic knobs for benchmarks and A/B tests (no counterpart in the reference).  The
- * library reads ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP and ESN_F64_MFMA from the environment
+ * library reads ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP, ESN_CHOL_DMA and ESN_F64_MFMA from the environment
  * ONCE, at its first call, as initial values; afterwards only this call changes them:
  *   "skew"          "0" = in-step schedule for the fp16/bf16 predict kernel, else skewed (default)
  *   "mfma_geom"     "NW,MT,NT" re-cuts the fp16/bf16 predict tiling; ignored unless 32*NW*MT equals
@@ -89,6 +89,8 @@ int esn_abi_version(void);
  *   "chol_skip"     bit mask of Cholesky-solve phases to drop (timing only, wrong results; Gram dimension <= 128):
  *                   1 Gram over the first 32-wide k-chunk only, 2 factorisation of the first 16-column block
  *                   only, 4 no blocked triangular solves, 8 no W_out = A^T alpha pass
+ *   "chol_dma"      "0" = the Cholesky solve (Gram dimension <= 128, float32 E, rows < cols) stages E through
+ *                   registers instead of LDS-DMA rings in its Gram and W_out passes (bitwise the same results; A/B runs)
  *   "f64_mfma"      "0" = ESN_F64 batches on the vector-ALU kernel instead of the float64 matrix pipe
  *   "rs"            "1" = fp16/bf16 predict at N_res 257..512 on the register-resident-state kernel
  *                   (esn_recur_rs.hip; an experiment kept for A/B runs, compiled only into ESN_WITH_RS=1 builds:
