@@ -9,10 +9,19 @@ per-subcarrier MMSE detector (``system_model_2/Demo_MIMO_4x8_Sionna_CDL_ESN_v2.p
   * time-domain MMSE refinement, truncation to IsiDuration taps ............ :373-378
   * per-subcarrier MMSE solve (H^H H + No/Pi I)^-1 H^H Y / sqrt(Pi) ........ :40-45, :444-448
 
-Parity pin: the driver cannot be imported (runs at import, needs pyldpc), so this file is pinned
-statistically only -- against column 3 (MMSE_uncoded) of the reference's own
-``results/results_4x8_cdl_coded_uncoded/CDLB_run_01/results_ber.csv`` -- which at the same time
-pins the frame recipe of ``ofdm_frames.py`` (tests/test_oracle_baseline_ber.py)."""
+and of the SISO driver's index-drawn pilot, scalar LS estimate and scalar ZF / LS / MMSE
+(``Demo_SISO_QPSK_AWGN_LDPC_ESN_with_ZF_LS.py:76-95,203-217``).
+
+Parity pin: the drivers cannot be imported (they run at import and need pyldpc), so their own loop
+statements are executed into tests/golden/loop_v2.npz / loop_nbf.npz / loop_siso.npz
+(tests/golden/make_golden.py, case_driver_loop).  tests/test_oracle_driver_loop.py holds
+``pilot_frames`` (one noise draw shared with the LS companion), ``estimate_channel`` (both
+``ls_only`` settings), ``mmse_detect`` / ``linear_detect`` (Perfect-ZF, LS-ZF), ``flat_pilot``,
+``flat_ls_estimate`` and ``flat_detect`` to the reference's ``X_LS``, ``y_LS_CP``, ``H_LS``,
+``H_MMSE`` and every ``X_hat_*`` within 1e-12 of max (measured 0 to 3e-14) and to its running error
+counters exactly.  The statistical check against column 3 (MMSE_uncoded) of the reference's own
+``results/results_4x8_cdl_coded_uncoded/CDLB_run_01/results_ber.csv`` stays
+(tests/test_oracle_baseline_ber.py)."""
 from __future__ import annotations
 
 import math
@@ -130,3 +139,32 @@ def linear_detect(cfg: LinkConfig, ebno_db, h, y_cp, reg=None):
 def mmse_detect(cfg: LinkConfig, ebno_db, h, y_cp):
     """X_hat [N, n_t] = (H^H H + No/Pi I)^-1 H^H Y / sqrt(Pi) per subcarrier (driver:40-45,444-448)."""
     return linear_detect(cfg, ebno_db, h, y_cp)
+
+
+def flat_pilot(cfg: LinkConfig, ebno_db, taps, rng):
+    """The SISO driver's one pilot: N constellation points drawn by index (randint, not bits), through
+    the same transmitter, the one-tap channel and AWGN (Demo_SISO_QPSK_AWGN_LDPC_ESN_with_ZF_LS.py:207-213).
+    Returns dict(X_p [N], x_cp [T] pre-PA teacher, y_cp [T])."""
+    const = unit_qam(cfg.m)
+    x_p = const[rng.randint(0, 2 ** cfg.m, size=cfg.n_sub)]
+    xt = cfg.n_sub * np.fft.ifft(x_p)
+    x_cp = (np.r_[xt[-cfg.cp:], xt] if cfg.cp > 0 else xt) * math.sqrt(cfg.p_i(ebno_db))
+    x_pa = x_cp / np.sqrt(1 + (np.abs(x_cp) / cfg.a_clip(ebno_db)) ** 2)
+    t = len(x_cp)
+    y = signal.lfilter(taps[0, 0], np.array([1]), x_pa)
+    y = y + math.sqrt(t * cfg.no / 2) * (rng.randn(t) + 1j * rng.randn(t))
+    return dict(X_p=x_p, x_cp=x_cp, y_cp=y)
+
+
+def flat_ls_estimate(cfg: LinkConfig, ebno_db, x_p, y_cp):
+    """Scalar LS estimate of a flat channel: mean over tones of Y / (X sqrt(Pi)) (SISO driver:216-217)."""
+    y = (1.0 / cfg.n_sub) * np.fft.fft(y_cp[cfg.cp:])
+    return np.mean(y / (x_p * math.sqrt(cfg.p_i(ebno_db))))
+
+
+def flat_detect(cfg: LinkConfig, ebno_db, h, y_cp, reg):
+    """X_hat [N] = conj(h) Y / (|h|^2 + reg + 1e-12) / sqrt(Pi) for a scalar channel: the SISO driver's
+    ZF and LS (reg = 0) and MMSE (reg = No/Pi) -- its MMSE keeps the 1e-12 floor on top of No/Pi, which
+    the matrix drivers' MMSE does not (SISO driver:76-95 against v2 driver:40-45)."""
+    y = (1.0 / cfg.n_sub) * np.fft.fft(y_cp[cfg.cp:])
+    return np.conj(h) * y / (abs(h) ** 2 + reg + 1e-12) / math.sqrt(cfg.p_i(ebno_db))

@@ -14,14 +14,19 @@ and the block-fading exponential-PDP taps of
 ``system_model_2/OFDM_MIMO_2-2_NBF_LDPC.py:162-164,272-279``.
 
 Parity pin: the constellation is checked against the reference's importable
-``HelpFunc.UnitQamConstellation``; the rest of the recipe lives in driver
+``HelpFunc.UnitQamConstellation``.  The rest of the recipe lives in driver
 scripts that cannot be imported (they run a whole simulation at import and
-need pyldpc), so it is "parity unpinned" at the sample level and pinned
-STATISTICALLY against the reference's own published curve: frames from this
-recipe through the restated LS/MMSE baseline (oracle/baselines.py) reproduce
+need pyldpc); it is pinned sample for sample by executing the drivers' own
+loop statements (tests/golden/make_golden.py, case_driver_loop) into
+tests/golden/loop_v2.npz, loop_nbf.npz and loop_siso.npz:
+tests/test_oracle_driver_loop.py feeds ``modulate``, ``channel``,
+``exp_pdp_taps``, ``flat_taps`` and ``tdlb_mimo_taps`` the fixtures' bits and
+taps and the noise replayed from the recorded NumPy stream states, and requires
+the reference's ``x_CP`` / ``y_CP`` / taps within 1e-12 of max (measured 0 to
+2e-16).  On top of that the recipe reproduces the reference's own published
+curve: frames from it through the LS/MMSE baseline (oracle/baselines.py) give
 column MMSE_uncoded of results/.../CDLB_run_01/results_ber.csv within 0-5 % at
-every Eb/No from 0 to 30 dB (tests/test_oracle_baseline_ber.py) -- a wrong power
-scaling, PA, noise variance or tap recipe moves that curve by dBs.
+every Eb/No from 0 to 30 dB (tests/test_oracle_baseline_ber.py).
 """
 from __future__ import annotations
 

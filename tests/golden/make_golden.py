@@ -25,6 +25,10 @@ Cases:
   driver_funcs  the top-level functions of the reference's driver SCRIPTS (hard-bit decision, per-tone MMSE/ZF
          equalisers, LLR demapper, TDL-B taps, logistic-regression detector, encoder): the scripts run a whole sweep
          at import, so only their `def`s (and the `_TDLB_*` tables) are compiled, via `ast` (driver_functions())
+  loop_v2 / loop_nbf / loop_siso  the main-loop STATEMENTS of three driver scripts (4x8 TDL-B; 2x2 block fading with its FAST
+         switch and uncoded bit source; SISO QPSK), shortened to two Eb/No points and a few symbols, cut before the first
+         LLR / decoder statement, run under np.random.seed: pilots, channel estimates, frames, every X_hat, running error
+         counters and the NumPy stream states before each ESN(...) / frame / predict (case_driver_loop())
 """
 import hashlib
 import os
@@ -387,6 +391,271 @@ def case_driver_funcs():
     save("driver_funcs", **out)
 
 
+# ------------------------------------------------------------------------------------------------
+# The drivers' own main loops.  Same technique as driver_functions(): the script is parsed, never
+# imported; this time every top-level statement up to and including the Eb/No loop is compiled,
+# except imports, the pyldpc matrix construction, seeding, directory creation and prints.  The
+# per-symbol body is cut right after the statement that advances the uncoded bit counter, i.e.
+# before the first LLR / decoder / calibrator statement.  Values are recorded by wrapping names in
+# the namespace (ESN, trainMIMOESN_generic, the instance's fit / predict) and by one appended call
+# `_frame_done(jj, kk)`; no driver text is edited or copied.
+LOOP_SPECS = {
+    # esns_per_block: ESN(...) constructions per pilot (the first one of a pilot opens a new block).
+    # h_ls_points: Eb/No points whose blocks keep H_LS (loop_v2 drops it at the second point for size).
+    # overrides: re-assigned right after the driver's own assignment of that name, so that every
+    # derived vector (Ptotal, Pi, var_x, ...) follows from the driver's own statements.
+    "v2": dict(path=DRIVERS["v2"], ebno=(12, 21), overrides={"NumOfdmSymbols": "3"},
+               bit_counter="TotalBits_uncoded_MMSE", k_info=256, n_code=512, esns_per_block=1, h_ls_points=(0,),
+               frames={0: (1, 2, 3), 1: (1,)}, layout="one block per point (L = 75): three frames at the first, one at the second",
+               xhat=("X_hat_ESN", "X_hat_MMSE"),
+               counters=("Err_uncoded_ESN", "Err_uncoded_MMSE", "TotalBits_uncoded_ESN", "TotalBits_uncoded_MMSE")),
+    # FAST is the driver's own switch (N = 128, 80 symbols): with it L = 75 and two blocks fit.
+    # USE_LDPC = False selects the driver's uncoded bit source (rand > 0.5).
+    "nbf": dict(path=DRIVERS["nbf"], ebno=(12, 18), overrides={"FAST": "True", "NumOfdmSymbols": "77", "USE_LDPC": "False"},
+                bit_counter="TotalBits", k_info=256, n_code=512, esns_per_block=2, h_ls_points=(0, 1),
+                frames={0: (2,), 1: (2, 77)}, layout="two blocks at the second point (pilots at kk = 1 and 76), one frame per recorded block",
+                xhat=("X_hat_ESN_m", "X_hat_ESN_f", "X_hat_PerfZF", "X_hat_LS_ZF", "X_hat_MMSE"),
+                counters=("TotalErr_ESN_matched", "TotalErr_ESN_trainFixed", "TotalErr_PerfectZF", "TotalErr_LS_ZF",
+                          "TotalErr_MMSE", "TotalBits")),
+    "siso": dict(path=DRIVERS["siso"], ebno=(9, 18), overrides={"NumOfdmSymbols": "3"},
+                 bit_counter="TotalBits", k_info=512, n_code=1024, esns_per_block=1, h_ls_points=(),
+                 frames={0: (1,), 1: (2,)}, layout="one pilot per point, one recorded frame each: symbol 1 at the first, symbol 2 at the second (predict restarts from the state fit() left)",
+                 xhat=("X_hat_ESN", "X_hat_MMSE", "X_hat_ZF", "X_hat_LS"),
+                 counters=("TotalErr_ESN", "TotalErr_MMSE", "TotalErr_ZF", "TotalErr_LS", "TotalBits")),
+}
+G_SEED = 5
+DECODER_CALLS = {"make_ldpc", "ldpc_decode", "get_message", "qam_llrs_maxlog", "est_sigma2_from_decision", "fit_logreg_1d"}
+TOL_SAMPLE = 1e-9            # loosest relative sample tolerance a test applies to a recorded X_hat
+MARGIN_FACTOR = 1e3
+
+
+class MarginTooSmall(Exception):
+    """A recorded X_hat component lies too close to a decision boundary for this seed."""
+
+
+def pack_state(st):
+    """np.random.get_state() -> (keys uint32[624], [pos, has_gauss] int64, cached_gaussian float64)."""
+    return np.asarray(st[1], dtype=np.uint32), np.array([st[2], st[3]], dtype=np.int64), np.float64(st[4])
+
+
+def decision_margin(x, m):
+    """Smallest distance of any real / imaginary part of x from a decision boundary of the
+    unit-power 2^m-QAM grid (midpoints between neighbouring levels).  Uses the REFERENCE's
+    constellation: the generator does not depend on the oracle.  oracle/driver_loop.py has a second
+    copy on the oracle's constellation, with which the CPU test cross-checks the stored margins."""
+    lv = np.unique(np.round(np.asarray(RefHelp.UnitQamConstellation(m)).real, 12))
+    b = (lv[1:] + lv[:-1]) / 2
+    x = np.asarray(x).ravel()
+    parts = np.r_[x.real, x.imag]
+    return float(np.abs(parts[:, None] - b[None, :]).min())
+
+
+def _assigned_names(node):
+    import ast
+    return {t.id for n in ast.walk(node) if isinstance(n, (ast.Assign, ast.AugAssign))
+            for t in (n.targets if isinstance(n, ast.Assign) else [n.target]) if isinstance(t, ast.Name)}
+
+
+def _cut_after_counter(stmts, counter, hook):
+    """Truncate the statement list that holds `counter += ...` right after it (and every enclosing
+    list after the statement that encloses it); append `hook` there.  True if found."""
+    import ast
+    for i, s in enumerate(stmts):
+        if isinstance(s, ast.AugAssign) and isinstance(s.target, ast.Name) and s.target.id == counter:
+            del stmts[i + 1:]
+            stmts.append(hook)
+            return True
+        for field in ("body", "orelse"):
+            sub = getattr(s, field, None)
+            if isinstance(sub, list) and sub and _cut_after_counter(sub, counter, hook):
+                del stmts[i + 1:]
+                return True
+    return False
+
+
+def driver_loop_module(spec):
+    """The statements of one driver up to the end of its (shortened) symbol loop, as an ast.Module."""
+    import ast
+    tree = ast.parse(open(spec["path"]).read(), filename=spec["path"])
+    overrides = dict(spec["overrides"], EbNoDB="np.array(%r, dtype=np.int32)" % (list(spec["ebno"]),))
+    body = []
+    for node in tree.body:
+        if isinstance(node, (ast.Import, ast.ImportFrom)):
+            continue
+        src = ast.unparse(node)
+        if isinstance(node, ast.Assign) and "make_ldpc(" in src:
+            continue
+        if isinstance(node, ast.Expr) and src.startswith(("os.makedirs", "print(", "np.random.seed")):
+            continue
+        if isinstance(node, ast.For):
+            kk = [n for n in node.body if isinstance(n, ast.For)][0]
+            hook = ast.parse("_frame_done(jj, kk)").body[0]
+            assert _cut_after_counter(kk.body, spec["bit_counter"], hook), spec["bit_counter"]
+            del node.body[node.body.index(kk) + 1:]
+            calls = {n.func.id for n in ast.walk(node) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name)}
+            assert not (calls & DECODER_CALLS), calls & DECODER_CALLS
+            body.append(node)
+            break
+        body.append(node)
+        for name in _assigned_names(node) & set(overrides):
+            body.extend(ast.parse(f"{name} = {overrides.pop(name)}").body)
+    assert not overrides, overrides
+    return ast.fix_missing_locations(ast.Module(body=body, type_ignores=[]))
+
+
+def run_driver_loop(tag, seed):
+    """Execute one driver's shortened loop under np.random.seed(seed); returns the fixture dict."""
+    import math
+    import time
+    import warnings
+    import scipy.sparse as sp
+    from scipy import interpolate, signal
+    spec = LOOP_SPECS[tag]
+    rs = np.random.RandomState(G_SEED)
+    k, n = spec["k_info"], spec["n_code"]
+    g = sp.csr_matrix(np.vstack([np.eye(k, dtype=np.int8), (rs.rand(n - k, k) < 0.02).astype(np.int8)]))
+    out = dict(seed=seed, g_seed=G_SEED, g_shape=np.array(g.shape), ebno_db=np.array(spec["ebno"]),
+               layout=np.array(spec["layout"]), counter_names=np.array(spec["counters"]),
+               xhat_names=np.array(spec["xhat"]),
+               overrides=np.array([f"{k_} = {v}" for k_, v in sorted(spec["overrides"].items())] +
+                                  ["EbNoDB = %r" % (list(spec["ebno"]),), "G, H = test-made systematic G, None",
+                                   "np.random.seed(%d) in place of the driver's own seeding, if any" % seed]))
+    ns = {}
+    cur = dict(block=-1, esn=0, last_state=None, pred_states=[], prev_counts={}, pilots=[], frames=[], jj=None)
+
+    def put_state(key, st):
+        out[key + "_keys"], out[key + "_pos"], out[key + "_gauss"] = pack_state(st)
+
+    def new_block(jj):
+        if cur["jj"] != jj:
+            cur.update(jj=jj, block=-1)
+        cur["block"] += 1
+        cur["esn"] = 0
+        cur["pilots"].append((jj, cur["block"], int(ns.get("kk", 0))))
+        put_state(f"p{jj}_b{cur['block']}_state", cur["last_state"])     # before the block's first draw (taps / pilot bits)
+        return f"p{jj}_b{cur['block']}_"
+
+    def esn_rec(*a, **kw):
+        jj = int(ns["jj"])
+        if cur["esn"] >= spec["esns_per_block"] or cur["jj"] != jj:
+            pre = new_block(jj)
+        else:
+            pre = f"p{jj}_b{cur['block']}_"
+        put_state(pre + f"esn{cur['esn']}_state", np.random.get_state())
+        e = ref_pyesn.ESN(*a, **kw)
+        e._idx = cur["esn"]
+        cur["esn"] += 1
+        orig_predict, orig_fit = e.predict, e.fit
+
+        def predict(u, *pa, **pk):
+            if cur.get("recording", True):
+                cur["pred_states"].append((e._idx, np.random.get_state()))
+            return orig_predict(u, *pa, **pk)
+        e.predict = predict
+        if tag == "siso":
+            def fit(ein, eout, *fa, **fk):
+                r = orig_fit(ein, eout, *fa, **fk)
+                h = np.zeros((1, 1, 1), dtype=complex)
+                h[0, 0, 0] = ns["H_true"]
+                out.update({pre + "taps": h, pre + "H_est": np.complex128(ns["H_est"]),
+                            pre + "X_pilot": np.array(ns["X_pilot"]), pre + "pilot_x": np.array(ns["x_cp"]),
+                            pre + "pilot_y": np.array(ns["y_td"])})
+                cur["last_state"] = np.random.get_state()
+                return r
+            e.fit = fit
+        return e
+
+    def train_rec(esn, *a):
+        jj = int(ns["jj"])
+        pre = f"p{jj}_b{cur['block']}_"
+        cur["recording"] = False           # the helper's own predict calls are not data frames
+        ret = ref_train(esn, *a)
+        cur["recording"] = True
+        i = esn._idx
+        out[pre + f"esn{i}_helper"] = np.r_[np.asarray(ret[3]).ravel(), ret[4], ret[5], ret[6], ret[7]].astype(np.int64)
+        out[pre + f"esn{i}_nmse"] = np.float64(ret[8])
+        if i == 0:
+            out.update({pre + "pilot_bits": np.packbits(np.asarray(ns["TxBitsPilot"], dtype=np.uint8)),
+                        pre + "pilot_bits_shape": np.array(ns["TxBitsPilot"].shape),
+                        pre + "X_LS": np.array(ns["X_LS"]), pre + "pilot_x": np.array(a[-1]),
+                        pre + "pilot_y": np.array(a[-2]), pre + "pilot_y_ls": np.array(ns["y_LS_CP"]),
+                        pre + "taps": np.array(ns["c"]).astype(complex), pre + "H_MMSE": np.array(ns["H_MMSE"])})
+            if jj in spec["h_ls_points"]:
+                out[pre + "H_LS"] = np.array(ns["H_LS"])
+            if "H_true" in ns:                  # the block-fading driver's perfect-CSI channel (Perfect-ZF)
+                out[pre + "H_true"] = np.array(ns["H_true"])
+        else:                               # the fixed-SNR ESN's own pilot (a fresh noise draw)
+            out.update({pre + "pilot_x_fixed": np.array(a[-1]), pre + "pilot_y_fixed": np.array(a[-2])})
+        cur["last_state"] = np.random.get_state()
+        return ret
+
+    def frame_done(jj, kk):
+        jj, kk = int(jj), int(kk)
+        counts = np.array([int(ns[c]) for c in spec["counters"]], dtype=np.int64)
+        before = cur["prev_counts"].get(jj, np.zeros_like(counts))
+        if kk in spec["frames"][jj]:
+            pre = f"p{jj}_f{kk}_"
+            bits = np.asarray(ns["TxBits"], dtype=np.uint8)
+            out.update({pre + "bits": np.packbits(bits), pre + "bits_shape": np.array(bits.shape),
+                        pre + "x_cp": np.array(ns["x_CP" if tag != "siso" else "x_cp"]),
+                        pre + "y_cp": np.array(ns["y_CP" if tag != "siso" else "y_td"]),
+                        pre + "counts_before": before, pre + "counts": counts})
+            put_state(pre + "state", cur["last_state"])
+            for i, st in cur["pred_states"]:
+                put_state(pre + f"predict{i}_state", st)
+            for name in spec["xhat"]:
+                x = np.array(ns[name])
+                out[pre + name] = x
+                margin, top = decision_margin(x, int(ns["m"])), float(np.abs(x).max())
+                out[pre + name + "_margin"] = margin
+                if margin < MARGIN_FACTOR * TOL_SAMPLE * top:
+                    raise MarginTooSmall(f"{pre + name}: margin {margin:.3g} at max {top:.3g}")
+            cur["frames"].append((jj, kk, cur["block"]))
+        cur["prev_counts"][jj] = counts
+        cur["pred_states"] = []
+        cur["last_state"] = np.random.get_state()
+
+    ns.update({"np": np, "math": math, "os": os, "time": time, "warnings": warnings, "sp": sp, "signal": signal, "interpolate": interpolate,
+               "ESN": esn_rec, "trainMIMOESN_generic": train_rec, "G": g, "H": None, "_frame_done": frame_done,
+               "__name__": "driver_loop"})
+    code = compile(driver_loop_module(spec), spec["path"], "exec")
+    np.random.seed(seed)
+    cur["last_state"] = np.random.get_state()
+    exec(code, ns)
+    used = {(j, b) for j, _, b in cur["frames"]}                    # blocks no recorded frame belongs to are dropped
+    for j, b, _ in cur["pilots"]:
+        if (j, b) not in used:
+            for key in [k_ for k_ in out if k_.startswith(f"p{j}_b{b}_")]:
+                del out[key]
+    out["blocks"] = np.array([p for p in cur["pilots"] if (p[0], p[1]) in used], dtype=np.int64)   # (point, block, pilot kk)
+    out["frames"] = np.array(cur["frames"], dtype=np.int64)        # (point, kk, block)
+    out["coherence_symbols"] = int(ns.get("L", 0))
+    out["min_margin"] = min(float(v) for k_, v in out.items() if k_.endswith("_margin"))
+    for name in ("N", "m", "N_t", "N_r", "IsiDuration", "nInternalUnits", "CP"):
+        if name in ns:
+            out["param_" + name] = int(ns[name])
+    return out
+
+
+def case_driver_loop():
+    """loop_v2 / loop_nbf / loop_siso: the reference drivers' own loop statements, shortened, run
+    under a seed; the first seed from 7 upwards whose every recorded X_hat component keeps
+    MARGIN_FACTOR * TOL_SAMPLE * max|X_hat| away from a decision boundary is taken."""
+    for tag in LOOP_SPECS:
+        for seed in range(7, 40):
+            try:
+                out = run_driver_loop(tag, seed)
+            except MarginTooSmall as e:
+                print(f"loop_{tag}: seed {seed} rejected, {e}")
+                continue
+            break
+        else:
+            raise RuntimeError(f"loop_{tag}: no seed in 7..39 keeps the decision margin")
+        print(f"loop_{tag}: seed {seed}, min margin {out['min_margin']:.3g}, blocks {out['blocks'].tolist()}, "
+              f"frames {out['frames'].tolist()}")
+        save("loop_" + tag, **out)
+
+
 def main():
     only = set(sys.argv[1:])          # e.g. `make_golden.py mackey scan` regenerates just those
     if only:
@@ -399,6 +668,7 @@ def main():
     case_scan()
     case_legacy()
     case_driver_funcs()
+    case_driver_loop()
     case_plain("tiny", 3, 2, 8, 12, seed=42, transient=2,
                kw=dict(spectral_radius=0.9, sparsity=0.25, input_scaling=[0.3, 0.2, 0.1],
                        input_shift=[0.0, 0.1, -0.1], teacher_scaling=0.5, teacher_shift=0.05))

@@ -5,10 +5,10 @@ configs[1] and [2]):
         point, `fit(Ein, Eout)` with transient 0 and no output delay, `predict(x)` = continuation=True, CP = 0
   block fading, exponential PDP  OFDM_MIMO_2-2_NBF_LDPC.py:162-164,272-279
 
-The frame recipe restatement (oracle/ofdm_frames.py) is parity-unpinned at the sample level (driver
-scripts are not importable); what is pinned here: the HIP tap generator kinds 1 / 2 equal it with supplied
-gains (1e-12), and the harness driven in the SISO semantics equals the pinned ESN oracle on the same
-frames (float64 kernels: outputs 1e-8, bit-error counts exact)."""
+The frame recipe restatement (oracle/ofdm_frames.py) is pinned to both drivers' own loop statements by
+tests/test_oracle_driver_loop.py (loop_nbf.npz, loop_siso.npz); what is pinned here: the HIP tap generator
+kinds 1 / 2 equal it with supplied gains (1e-12), and the harness driven in the SISO semantics equals the
+pinned ESN oracle on the same frames (float64 kernels: outputs 1e-8, bit-error counts exact)."""
 import numpy as np
 import pytest
 
