@@ -11,6 +11,8 @@ PRECISIONS = {"f64": F64, "f32": F32, "f16": F16, "bf16": BF16}
 NOISE_NONE, NOISE_TENSOR, NOISE_COUNTER = 0, 1, 2
 ABI_VERSION = 10
 MEM_DEVICE, MEM_HOST = 0, 1
+# enum esn_path, by value: the recurrence kernel a call dispatches to (recur_path below)
+PATHS = ("mfma", "skew16", "f64_valu", "f64_mfma", "cluster_f64", "big_predict", "big_harvest", "harvest_cluster", "rs")
 
 
 class Shape(C.Structure):
@@ -28,6 +30,7 @@ SIGNATURES = {
     "esn_last_error": (C.c_char_p, []),
     "esn_abi_version": (C.c_int, []),
     "esn_debug_set": (C.c_int, [C.c_char_p, C.c_char_p]),
+    "esn_recur_path": (C.c_int, [C.c_int, C.c_int, C.POINTER(Shape), C.c_int, C.c_int, C.c_int]),
     "esn_device_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.c_char_p, C.c_int]),
     "esn_tile_frames": (C.c_int, [C.c_int, C.POINTER(Shape)]),
@@ -143,6 +146,16 @@ def stream_handle():
 def debug_set(key, value):
     """Tuning knob of the library (benchmarks / A-B tests): see esn_debug_set in include/esn_hip.h."""
     check(load().esn_debug_set(key.encode(), None if value is None else str(value).encode()), "esn_debug_set")
+
+
+def recur_path(harvest, precision, shape, n_sequences, frames_per_group=1, have_workspace=True):
+    """Name (PATHS) of the kernel esn_harvest_batch (harvest) / esn_predict_batch runs for this call under the current
+    knobs: esn_recur_path in include/esn_hip.h.  `precision` is a key of PRECISIONS."""
+    rc = load().esn_recur_path(int(bool(harvest)), PRECISIONS[precision], C.byref(shape), int(n_sequences),
+                               int(frames_per_group), int(bool(have_workspace)))
+    if rc < 0:
+        check(rc, "esn_recur_path")
+    return PATHS[rc]
 
 
 def device_info():

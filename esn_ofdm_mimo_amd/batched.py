@@ -143,23 +143,18 @@ class ReservoirBank:
             fn = self.lib.esn_harvest_batch_f32 if f32 else self.lib.esn_harvest_batch
             E = torch.empty((g, t, self.n_reservoir + self.n_inputs),
                             dtype=torch.float32 if f32 else torch.float64, device=self.device)
-            # reservoirs beyond 1024 units harvest as one GEMM launch per step out of a caller-owned workspace
+            # some kernels run out of a caller-owned workspace (include/esn_hip.h: enum esn_path)
             wbytes = self.lib.esn_harvest_workspace_bytes(PRECISIONS[precision], C.byref(self.shape), g)
-            ws = None
-            if wbytes:
-                ws = getattr(self, "_harvest_ws", None)
-                if ws is None or ws.numel() < wbytes:
-                    ws = self._harvest_ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+            ws = self._scratch("_harvest_ws", wbytes)
             check(fn(PRECISIONS[precision], C.byref(self.shape), ptr(self.packed_weights(precision)),
                      ptr(self.in_scale), ptr(self.in_shift), ptr(self.t_scale), ptr(self.t_shift),
                      ptr(U), ptr(D), g, t, self.noise, nm, ptr(nz), int(seed) & (2**64 - 1), int(group_offset),
                      ptr(E), ptr(ws), wbytes, _lib.stream_handle()), "esn_harvest_batch")
-            if wbytes and precision == "f64" and g == 1:
-                self._cluster_err = ws[wbytes - 64:wbytes - 60]      # error word of the single-sequence cluster kernel
-            # fp16/bf16 at 257..512 units: clusters of eight workgroups with the matrix resident in LDS
-            # (csrc/esn_harvest_cluster.hip); their bounded waits raise the same kind of error word
-            self.harvest_timeout = (ws[wbytes - 64:wbytes - 60].view(torch.int32)
-                                    if wbytes and precision in ("f16", "bf16") and self.n_reservoir <= 512 else None)
+            # the two cluster kernels wait for their peers with bounded spins and raise an error word instead of hanging
+            path = _lib.recur_path(True, precision, self.shape, g, have_workspace=wbytes > 0)
+            if path == "cluster_f64":
+                self._cluster_err = ws[wbytes - 64:wbytes - 60]
+            self.harvest_timeout = ws[wbytes - 64:wbytes - 60].view(torch.int32) if path == "harvest_cluster" else None
         return E
 
     def raise_if_harvest_timed_out(self):
@@ -200,11 +195,7 @@ class ReservoirBank:
                 status = torch.empty(g, dtype=torch.int32, device=self.device)
                 fn = self.lib.esn_readout_solve_chol_batch_f32 if e32 else self.lib.esn_readout_solve_chol_batch
                 wbytes = self.lib.esn_readout_chol_workspace_bytes(g, rows, cols)
-                ws = None
-                if wbytes:
-                    ws = getattr(self, "_chol_ws", None)
-                    if ws is None or ws.numel() < wbytes:
-                        ws = self._chol_ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+                ws = self._scratch("_chol_ws", wbytes)
                 check(fn(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale),
                          ptr(self.t_shift), ptr(W_out), ptr(status), ptr(ws), wbytes, _lib.stream_handle()),
                       "esn_readout_solve_chol_batch")
@@ -287,14 +278,10 @@ class ReservoirBank:
                                   device=self.device)
             elif out.dtype != (torch.float32 if io32 else torch.float64):
                 raise ValueError(f"out is {out.dtype}, io={io!r} writes {'float32' if io32 else 'float64'}")
-            # reservoirs beyond 1024 units run one GEMM launch per step out of a caller-owned workspace
+            # some kernels run out of a caller-owned workspace (include/esn_hip.h: enum esn_path)
             wbytes = self.lib.esn_predict_workspace_bytes(PRECISIONS[precision], C.byref(self.shape), b,
                                                           int(frames_per_group))
-            ws = None
-            if wbytes:
-                ws = getattr(self, "_workspace", None)
-                if ws is None or ws.numel() < wbytes:
-                    ws = self._workspace = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+            ws = self._scratch("_workspace", wbytes)
             fn = self.lib.esn_predict_batch_f32 if io32 else self.lib.esn_predict_batch
             check(fn(
                 PRECISIONS[precision], C.byref(self.shape), ptr(self.packed_weights(precision)),
@@ -303,7 +290,7 @@ class ReservoirBank:
                 int(transient), ptr(x0), ptr(y0), self.noise, nm, ptr(nz), int(seed) & (2**64 - 1),
                 int(group_offset), ptr(out), ptr(ws), wbytes, _lib.stream_handle()),
                 "esn_predict_batch_f32" if io32 else "esn_predict_batch")
-            if wbytes and precision == "f64" and b == 1:
+            if _lib.recur_path(False, precision, self.shape, b, frames_per_group, wbytes > 0) == "cluster_f64":
                 self._cluster_err = ws[wbytes - 64:wbytes - 60]      # error word of the single-sequence cluster kernel
         return out
 
@@ -343,6 +330,16 @@ class ReservoirBank:
         return (err, bits, xh) if want_xhat else (err, bits)
 
     # ------------------------------------------------------------------ helpers
+    def _scratch(self, name, nbytes):
+        """The bank's device scratch `name`, grown on demand to nbytes (None for 0).  Called under the device guard."""
+        if not nbytes:
+            return None
+        ws = getattr(self, name, None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
+            setattr(self, name, ws)
+        return ws
+
     def _check_groups(self, g):
         for name in ("in_scale", "in_shift", "t_scale", "t_shift"):
             t = getattr(self, name)

@@ -6,133 +6,11 @@
 #include <stdlib.h>
 #include <math.h>
 #include <string.h>
-#include "esn_common.h"
-
-namespace esn {
-// esn_recur_f64.hip
-int launch_recur_f64(const RecurParams& p, hipStream_t stream);
-size_t recur_f64_lds_bytes(int FB, int n_res, int n_in, int n_out);
-// esn_recur_f64_mfma.hip
-bool f64_mfma_geometry(int n_res, int n_in, int n_out, bool harvest, Geometry* g);
-int launch_recur_f64_mfma(const RecurParams& p, hipStream_t stream);
-#ifdef ESN_WITH_RS
-// esn_recur_rs.hip (a kept negative result, DESIGN.md 3.1b: only in builds made with ESN_WITH_RS=1)
-bool rs_path_applies(int precision, const RecurParams& p);
-int launch_recur_rs(int precision, const RecurParams& p, size_t wo_rs_off, hipStream_t stream);
-#endif
-// esn_recur_big.hip
-bool big_path_applies(int precision, const RecurParams& p);
-int big_slots(const RecurParams& p);
-size_t big_workspace_bytes(int n_slots, int Mp, int Kp);
-int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream,
-                     bool io32 = false);
-bool big_harvest_applies(int precision, const RecurParams& p);
-size_t big_harvest_workspace_bytes(int n_groups, int Kp);
-int launch_harvest_big(int precision, const RecurParams& p, void* workspace, hipStream_t stream);
-// esn_recur_cluster.hip
-bool cluster_applies(int precision, const RecurParams& p);
-size_t cluster_workspace_bytes(int n_res, int n_in, int n_out, bool harvest);
-int launch_recur_cluster(const RecurParams& p, void* workspace, hipStream_t stream);
-// esn_recur_mfma.hip
-bool mfma_geometry(int precision, int n_res, int n_in, int n_out, bool harvest, Geometry* g);
-int launch_recur_mfma(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
-// esn_harvest_cluster.hip
-bool harvest_cluster_applies(int precision, const RecurParams& p);
-size_t harvest_cluster_workspace_bytes(int n_pilots, int C, int n_wsets);
-int launch_harvest_cluster(int precision, const RecurParams& p, int C, void* workspace, hipStream_t stream);
-// esn_recur_skew16.hip
-int launch_recur_skew16(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
-// esn_pack.hip
-size_t packed_w_bytes(int precision, int n_res, int n_in, int n_out, const Geometry& g);
-size_t packed_wout_bytes(int precision, int n_res, int n_in, int n_out, const Geometry& g);
-size_t wout_big_offset(int precision, int n_out, const Geometry& g);
-size_t f64_w_offset(int n_res, int n_in, int n_out);
-size_t f64_wout_offset(int n_res, int n_in, int n_out);
-int launch_pack_weights(int precision, const esn_shape_t* sh, const Geometry& g, const double* W,
-                        const double* Win, const double* Wfb, void* packed, hipStream_t stream);
-int launch_pack_readout(int precision, const esn_shape_t* sh, const Geometry& g, int n_groups,
-                        const double* Wout, void* packed, hipStream_t stream);
-// esn_solve.hip
-size_t solve_work_doubles(int rows, int cols, int n_out);
-int launch_readout_solve(const double* E, const double* D, int n_groups, int T, int transient,
-                         int cols, int n_out, const double* t_scale, const double* t_shift,
-                         double* W_out, int* status, void* workspace, hipStream_t stream);
-int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
-                        int cols, int n_out, const double* t_scale, const double* t_shift,
-                        double* W_out, int* status, hipStream_t stream);
-size_t chol_big_work_doubles(int n);
-int launch_readout_chol_big(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
-                            int cols, int n_out, const double* t_scale, const double* t_shift,
-                            double* W_out, int* status, void* workspace, hipStream_t stream);
-// esn_gen.hip
-int launch_gen_taps(const TapParams& tp, hipStream_t stream);
-int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);
-// esn_baseline.hip
-int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);
-int launch_mmse_detect(const MmseParams& mp, hipStream_t stream);
-int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream);
-// esn_coded.hip
-int launch_ldpc_encode(const LdpcEncodeParams& ep, hipStream_t stream);
-int launch_qam_llr(const LlrParams& lp, hipStream_t stream);
-int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
-// esn_detect.hip
-int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
-}  // namespace esn
+#include "esn_launch.h"
 
 using namespace esn;
 
 static thread_local char g_err[512] = "";
-
-namespace esn {
-static bool parse3(const char* v, int (&out)[3]) {
-    int a, b, c;
-    if (v && sscanf(v, "%d,%d,%d", &a, &b, &c) == 3 && a > 0 && b > 0 && c > 0) { out[0] = a; out[1] = b; out[2] = c; return true; }
-    out[0] = out[1] = out[2] = 0;
-    return false;
-}
-Knobs& knobs() {
-    static Knobs k = [] {
-        Knobs x;
-        const char* v = getenv("ESN_SKEW");
-        x.skew = (v && v[0] == '0') ? 0 : 1;
-        parse3(getenv("ESN_MFMA_GEOM"), x.geom16);
-        parse3(getenv("ESN_MFMA_GEOM_F32"), x.geom32);
-        v = getenv("ESN_CHOL_SKIP");
-        x.chol_skip = v ? atoi(v) : 0;
-        v = getenv("ESN_F64_MFMA");
-        x.f64_mfma = (v && v[0] == '0') ? 0 : 1;
-        v = getenv("ESN_RS");
-        x.rs = (v && v[0] == '1') ? 1 : 0;          // opt-in: measured slower than the skewed LDS-state kernel
-        v = getenv("ESN_BIG_GEMM");
-        x.big_gemm = (v && v[0] == '0') ? 0 : 1;
-        v = getenv("ESN_CLUSTER");
-        x.cluster = (v && v[0] == '0') ? 0 : 1;
-        x.gen_ko = 0;
-        v = getenv("ESN_HARVEST_GEMM");
-        x.harvest_gemm = (v && v[0] == '1') ? 1 : 0;
-        v = getenv("ESN_BIG_NT");
-        x.big_nt = (v && v[0] == '4') ? 4 : 2;
-        v = getenv("ESN_HCLUSTER");
-        x.hcluster = (v && (v[0] == '0' || v[0] == '4' || v[0] == '8')) ? v[0] - '0' : 1;
-        v = getenv("ESN_S16");
-        x.s16 = (v && v[0] == '0') ? 0 : 1;
-        v = getenv("ESN_CHOL_DMA");
-        x.chol_dma = (v && v[0] == '0') ? 0 : 1;
-        v = getenv("ESN_BIG_PIPE");
-        x.big_pipe = (v && v[0] == '0') ? 0 : 1;
-        return x;
-    }();
-    return k;
-}
-}  // namespace esn
-
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 namespace esn {
 // for esn_host.hip: same error string, same conventions
@@ -142,6 +20,69 @@ int api_fail(int code, const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+}  // namespace esn
+static int (&fail)(int, const char*, ...) = api_fail;
+
+// ---- the knobs (esn_common.h: Knobs): ONE row each, walked by knobs() (initial values from the environment, read
+// once) and by esn_debug_set.  How a value string becomes the knob:
+enum KnobRule {
+    KNOB_FLAG,       // first character '0' / '1', whichever the default is not, flips it; anything else: the default
+    KNOB_INT,        // atoi
+    KNOB_TRIPLE,     // "a,b,c", all positive; anything else: {0, 0, 0}
+    KNOB_BIG_NT,     // "4": 4; anything else: 2
+    KNOB_HCLUSTER    // "0" off, "4" / "8" members per cluster; anything else: 1 (on, pairs)
+};
+struct KnobRow {
+    const char* key;     // esn_debug_set
+    const char* env;     // environment variable, or nullptr
+    size_t field;        // offset in Knobs (an int; three for KNOB_TRIPLE)
+    KnobRule rule;
+    int dflt;            // value without a string (variable unset, esn_debug_set(key, NULL)) where the rule names none
+};
+static const KnobRow kKnobTable[] = {
+    {"skew", "ESN_SKEW", offsetof(Knobs, skew), KNOB_FLAG, 1},
+    {"mfma_geom", "ESN_MFMA_GEOM", offsetof(Knobs, geom16), KNOB_TRIPLE, 0},
+    {"mfma_geom_f32", "ESN_MFMA_GEOM_F32", offsetof(Knobs, geom32), KNOB_TRIPLE, 0},
+    {"chol_skip", "ESN_CHOL_SKIP", offsetof(Knobs, chol_skip), KNOB_INT, 0},
+    {"chol_dma", "ESN_CHOL_DMA", offsetof(Knobs, chol_dma), KNOB_FLAG, 1},
+    {"f64_mfma", "ESN_F64_MFMA", offsetof(Knobs, f64_mfma), KNOB_FLAG, 1},
+    // opt-in: measured slower than the skewed LDS-state kernel; read by ESN_WITH_RS=1 builds only
+    {"rs", "ESN_RS", offsetof(Knobs, rs), KNOB_FLAG, 0},
+    {"big_gemm", "ESN_BIG_GEMM", offsetof(Knobs, big_gemm), KNOB_FLAG, 1},
+    {"cluster", "ESN_CLUSTER", offsetof(Knobs, cluster), KNOB_FLAG, 1},
+    {"big_nt", "ESN_BIG_NT", offsetof(Knobs, big_nt), KNOB_BIG_NT, 2},
+    {"big_pipe", "ESN_BIG_PIPE", offsetof(Knobs, big_pipe), KNOB_FLAG, 1},
+    {"harvest_gemm", "ESN_HARVEST_GEMM", offsetof(Knobs, harvest_gemm), KNOB_FLAG, 0},
+    {"gen_ko", nullptr, offsetof(Knobs, gen_ko), KNOB_INT, 0},
+    {"s16", "ESN_S16", offsetof(Knobs, s16), KNOB_FLAG, 1},
+    {"hcluster", "ESN_HCLUSTER", offsetof(Knobs, hcluster), KNOB_HCLUSTER, 1},
+};
+
+static void knob_parse(const KnobRow& r, const char* v, Knobs& k) {
+    int* out = reinterpret_cast<int*>(reinterpret_cast<char*>(&k) + r.field);
+    switch (r.rule) {
+        case KNOB_FLAG: *out = (v && v[0] == '0' + !r.dflt) ? !r.dflt : r.dflt; break;
+        case KNOB_INT: *out = v ? atoi(v) : r.dflt; break;
+        case KNOB_TRIPLE: {
+            int t[3];
+            const bool ok = v && sscanf(v, "%d,%d,%d", &t[0], &t[1], &t[2]) == 3 && t[0] > 0 && t[1] > 0 && t[2] > 0;
+            for (int i = 0; i < 3; ++i) out[i] = ok ? t[i] : 0;
+            break;
+        }
+        case KNOB_BIG_NT: *out = (v && v[0] == '4') ? 4 : 2; break;
+        case KNOB_HCLUSTER: *out = (v && (v[0] == '0' || v[0] == '4' || v[0] == '8')) ? v[0] - '0' : 1; break;
+    }
+}
+
+namespace esn {
+Knobs& knobs() {
+    static Knobs k = [] {
+        Knobs x{};
+        for (const KnobRow& r : kKnobTable) knob_parse(r, r.env ? getenv(r.env) : nullptr, x);
+        return x;
+    }();
+    return k;
 }
 }  // namespace esn
 
@@ -192,32 +133,13 @@ int esn_abi_version(void) { return 10; }
 
 int esn_debug_set(const char* key, const char* value) {
     if (!key) return fail(-1, "esn_debug_set: null key");
-    Knobs& k = knobs();
-    if (!strcmp(key, "skew")) { k.skew = (value && value[0] == '0') ? 0 : 1; return 0; }
-    if (!strcmp(key, "mfma_geom")) { parse3(value, k.geom16); return 0; }
-    if (!strcmp(key, "mfma_geom_f32")) { parse3(value, k.geom32); return 0; }
-    if (!strcmp(key, "chol_skip")) { k.chol_skip = value ? atoi(value) : 0; return 0; }
-    if (!strcmp(key, "f64_mfma")) { k.f64_mfma = (value && value[0] == '0') ? 0 : 1; return 0; }
-    if (!strcmp(key, "rs")) {
-#ifdef ESN_WITH_RS
-        k.rs = (value && value[0] == '1') ? 1 : 0; return 0;
-#else
-        if (value && value[0] == '1') return fail(-3, "esn_debug_set: the register-state kernel is not in this build (ESN_WITH_RS=1)");
-        return 0;
+#ifndef ESN_WITH_RS
+    if (!strcmp(key, "rs"))
+        return (value && value[0] == '1')
+                   ? fail(-3, "esn_debug_set: the register-state kernel is not in this build (ESN_WITH_RS=1)") : 0;
 #endif
-    }
-    if (!strcmp(key, "big_gemm")) { k.big_gemm = (value && value[0] == '0') ? 0 : 1; return 0; }
-    if (!strcmp(key, "cluster")) { k.cluster = (value && value[0] == '0') ? 0 : 1; return 0; }
-    if (!strcmp(key, "gen_ko")) { k.gen_ko = value ? atoi(value) : 0; return 0; }
-    if (!strcmp(key, "harvest_gemm")) { k.harvest_gemm = (value && value[0] == '1') ? 1 : 0; return 0; }
-    if (!strcmp(key, "big_nt")) { k.big_nt = (value && value[0] == '4') ? 4 : 2; return 0; }
-    if (!strcmp(key, "hcluster")) {       // "0" off, "4" / "8" members per cluster (A/B), anything else: the default (2)
-        k.hcluster = (value && (value[0] == '0' || value[0] == '4' || value[0] == '8')) ? value[0] - '0' : 1;
-        return 0;
-    }
-    if (!strcmp(key, "s16")) { k.s16 = (value && value[0] == '0') ? 0 : 1; return 0; }
-    if (!strcmp(key, "chol_dma")) { k.chol_dma = (value && value[0] == '0') ? 0 : 1; return 0; }
-    if (!strcmp(key, "big_pipe")) { k.big_pipe = (value && value[0] == '0') ? 0 : 1; return 0; }
+    for (const KnobRow& r : kKnobTable)
+        if (!strcmp(key, r.key)) { knob_parse(r, value, knobs()); return 0; }
     return fail(-1, "esn_debug_set: unknown key '%s'", key);
 }
 
@@ -277,18 +199,10 @@ int esn_pack_readout(int precision, const esn_shape_t* shape, int n_groups, cons
                     "esn_pack_readout");
 }
 
-// float64 kernel: every frame slot of a tile costs its share of FMAs whether it holds a frame or not,
-// so a batch smaller than the tile (the 2-D drop-in is ONE sequence) gets a smaller tile
-static void shrink_f64_tile(int precision, RecurParams& p) {
-    if (precision != ESN_F64) return;
-    const long long slots = (long long)p.n_groups * p.Fpad;
-    while (p.g.Bt > 1 && p.g.Bt / 2 >= slots) p.g.Bt >>= 1;
-}
-
 // float64: the matrix-pipe kernel for batches (more slots than one vector-ALU tile holds), the
 // vector-ALU kernel for the 2-D drop-in's single sequence and for shapes the MFMA tiling does not cover
-static bool use_f64_mfma(int precision, const RecurParams& p, long long sequences) {
-    return precision == ESN_F64 && p.g.m64 && sequences > 8 && knobs().f64_mfma;
+static bool use_f64_mfma(int precision, const RecurParams& p) {
+    return precision == ESN_F64 && p.g.m64 && p.n_frames > 8 && knobs().f64_mfma;
 }
 
 static int fill_common(RecurParams& p, int precision, const esn_shape_t* shape, const char* who,
@@ -309,7 +223,119 @@ static int fill_common(RecurParams& p, int precision, const esn_shape_t* shape, 
     p.wo16_off = wout_big_offset(precision, p.n_out, p.g);
     p.w64_off = f64_w_offset(p.n_res, p.n_in, p.n_out);
     p.wo64_off = f64_wout_offset(p.n_res, p.n_in, p.n_out);
+    p.harvest = harvest ? 1 : 0;
     return 0;
+}
+
+// The batch of one call and its slot axis (esn_common.h: Fpad, spw, n_tiles), after fill_common.  Predict: n_frames
+// sequences in groups of F.  Harvest: one pilot per group (n_frames = n_groups, F = 1), tiles span groups.
+static void fill_batch(RecurParams& p, int precision, int n_frames, int frames_per_group) {
+    p.n_frames = n_frames;
+    p.F = frames_per_group;
+    p.n_groups = (n_frames + frames_per_group - 1) / frames_per_group;
+    const bool m64 = use_f64_mfma(precision, p);
+    // slots per group: one pilot (harvest); the readout's 16-frame column granularity (MFMA kernels) or no padding at
+    // all (float64 vector-ALU kernel)
+    p.Fpad = p.harvest ? 1 : (precision == ESN_F64 && !m64) ? p.F : round_up(p.F, 16);
+    // float64 vector-ALU kernel: every frame slot of a tile costs its share of FMAs whether it holds a frame or not,
+    // so a batch smaller than the tile (the 2-D drop-in is ONE sequence) gets a smaller tile
+    // (Tried for the harvest: leaving slots empty so that 2048 pilots spread over 256 tiles of 8 instead of 64 tiles of
+    //  32 -- the harvest is bound by the AGGREGATE L2 weight stream, 4x the workgroups stream 4x the bytes: 1.14 -> 1.23 ms.)
+    if (precision == ESN_F64 && !m64 && (!p.harvest || p.n_wsets == 1)) {
+        const long long slots = (long long)p.n_groups * p.Fpad;
+        while (p.g.Bt > 1 && p.g.Bt / 2 >= slots) p.g.Bt >>= 1;
+    }
+    const int tile = m64 ? p.g.Bt64 : p.g.Bt;
+    // with several weight sets the slot axis is set-major (esn_common.h: spw), so a tile packs the groups of ONE set
+    // back to back instead of padding every group to a whole tile
+    if (p.n_wsets > 1) {
+        const int gpw = (p.n_groups + p.n_wsets - 1) / p.n_wsets;
+        p.spw = round_up(gpw * p.Fpad, tile);
+        p.n_tiles = p.n_wsets * (p.spw / tile);
+    } else {
+        p.n_tiles = (int)(((long long)p.n_groups * p.Fpad + tile - 1) / tile);
+    }
+}
+
+// ---- THE dispatch rule: which kernel serves a recurrence call (an esn_path) and how much workspace the size
+// queries advertise for it.  The launches, esn_*_workspace_bytes and esn_recur_path all ask here; the order of the
+// ladder is the specification.  `p` is filled by fill_common + fill_batch (+ noise_mode, S, transient on a launch;
+// zero in a query: only the ESN_WITH_RS experiment reads them).
+struct Plan {
+    int path;                  // enum esn_path
+    size_t workspace_bytes;    // what the size query answers; the path reads that many bytes iff path_uses_workspace
+    int hc_members;            // ESN_PATH_HARVEST_CLUSTER: workgroups per cluster
+};
+static bool path_uses_workspace(int path) {
+    return path == ESN_PATH_CLUSTER_F64 || path == ESN_PATH_BIG_PREDICT || path == ESN_PATH_BIG_HARVEST ||
+           path == ESN_PATH_HARVEST_CLUSTER;
+}
+
+static Plan plan_recur(int precision, const RecurParams& p, bool io32, bool workspace_lent) {
+    const Knobs& k = knobs();
+    const bool half = precision == ESN_F16 || precision == ESN_BF16;
+    Plan pl = {ESN_PATH_MFMA, 0, 0};
+    if (workspace_lent) {
+        // ONE float64 sequence (the reference's own call pattern): the matrix resident in the LDS of a cluster of
+        // workgroups that exchange the state through L2 every step (esn_recur_cluster.hip)
+        if (k.cluster && cluster_applies(precision, p))
+            return {ESN_PATH_CLUSTER_F64, cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, p.harvest != 0), 0};
+        // harvest, 257..512 units, fp16/bf16: clusters of workgroups with the matrix resident in registers / LDS
+        if (p.harvest && k.hcluster && harvest_cluster_applies(precision, p)) {
+            const int members = k.hcluster == 1 ? 2 : k.hcluster;
+            return {ESN_PATH_HARVEST_CLUSTER, harvest_cluster_workspace_bytes(p.n_groups, members, p.n_wsets), members};
+        }
+        // large reservoirs: one GEMM launch per step
+        if (p.harvest ? big_harvest_applies(precision, p) : (p.g.big && big_path_applies(precision, p))) {
+            pl.workspace_bytes = p.harvest ? big_harvest_workspace_bytes(p.n_groups, p.g.Kp)
+                                           : big_workspace_bytes(big_slots(p), p.g.Mp, p.g.Kp);
+            if (k.big_gemm) { pl.path = p.harvest ? ESN_PATH_BIG_HARVEST : ESN_PATH_BIG_PREDICT; return pl; }
+            // Kept as found: with big_gemm = 0 the size queries still advertise the GEMM paths' workspace although
+            // the persistent kernel below serves the call and reads none of it (tests/test_dispatch_cpu.py names
+            // this exception).  Making the queries follow the knob changes their answers: a change of its own.
+        }
+    }
+    if (!p.harvest) {
+#ifdef ESN_WITH_RS
+        // N_res 257..512, fp16/bf16: state in registers, one wave per SIMD (tiles of 128 slots like the skewed kernel);
+        // its buffer descriptors are 31-bit
+        if (!io32 && k.rs && rs_path_applies(precision, p) &&
+            (size_t)p.n_frames * (p.S - p.transient) * p.n_out * 8 < 0x7fffffffu &&
+            (size_t)p.n_groups * p.wout_stride < 0x7fffffffu) { pl.path = ESN_PATH_RS; return pl; }
+#endif
+        // N_res 257..512, fp16/bf16: the skewed schedule on 16x16x32 MFMAs (the chip holds a higher clock on that shape)
+        if (p.g.s16 && p.g.skew && k.s16 && half) { pl.path = ESN_PATH_SKEW16; return pl; }
+    }
+    (void)io32;
+    pl.path = use_f64_mfma(precision, p) ? ESN_PATH_F64_MFMA : precision == ESN_F64 ? ESN_PATH_F64_VALU : ESN_PATH_MFMA;
+    return pl;
+}
+
+// plan, the ONE workspace check, launch
+static int launch_plan(const char* who, const char* size_query, int precision, RecurParams& p, bool io32,
+                       void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const Plan pl = plan_recur(precision, p, io32, workspace != nullptr);
+    if (path_uses_workspace(pl.path) && workspace_bytes < pl.workspace_bytes)
+        return fail(-1, "%s: workspace holds %zu bytes, %s says %zu", who, workspace_bytes, size_query,
+                    pl.workspace_bytes);
+    int e = -1;
+    switch (pl.path) {
+        case ESN_PATH_CLUSTER_F64: e = launch_recur_cluster(p, workspace, stream); break;
+        case ESN_PATH_HARVEST_CLUSTER: e = launch_harvest_cluster(precision, p, pl.hc_members, workspace, stream); break;
+        case ESN_PATH_BIG_HARVEST: e = launch_harvest_big(precision, p, workspace, stream); break;
+        case ESN_PATH_BIG_PREDICT:
+            p.Fpad = round_up(p.F, 16);
+            e = launch_recur_big(precision, p, wout_big_offset(precision, p.n_out, p.g), workspace, stream, io32);
+            break;
+#ifdef ESN_WITH_RS
+        case ESN_PATH_RS: e = launch_recur_rs(precision, p, wout_big_offset(precision, p.n_out, p.g), stream); break;
+#endif
+        case ESN_PATH_SKEW16: e = launch_recur_skew16(precision, p, stream, io32); break;
+        case ESN_PATH_F64_MFMA: e = launch_recur_f64_mfma(p, stream); break;
+        case ESN_PATH_F64_VALU: e = launch_recur_f64(p, stream); break;
+        case ESN_PATH_MFMA: e = launch_recur_mfma(precision, p, stream, io32); break;   // in-step or 32x32x16 skewed: g.skew
+    }
+    return hip_fail(e, who);
 }
 
 // esn_predict_batch and esn_predict_batch_f32: io32 = float32 U / Y (fp32/fp16/bf16 precisions only)
@@ -334,27 +360,8 @@ static int predict_common(const char* who, bool io32, int precision, const esn_s
     // (float32 rows are staged in 16-byte chunks of four inputs when n_in is a multiple of 4, else in 4-byte ones)
     if (io32 && ((uintptr_t)U & ((shape->n_in & 3) == 0 ? 15 : 3)) != 0)
         return fail(-1, "%s: U must be %d-byte aligned", who, (shape->n_in & 3) == 0 ? 16 : 4);
-    p.n_frames = n_frames;
-    p.F = frames_per_group;
-    p.n_groups = (n_frames + frames_per_group - 1) / frames_per_group;
-    // slots per group: whole tiles when each group has its own weight set, else the readout's
-    // 16-frame column granularity (MFMA kernels) or no padding at all (float64 kernel)
-    const bool m64 = use_f64_mfma(precision, p, n_frames);
-    const int tile = m64 ? p.g.Bt64 : p.g.Bt;
-    // slots per group: the readout's 16-frame column granularity (MFMA kernels) or no padding at all (float64
-    // vector-ALU kernel); with several weight sets the slot axis is set-major (esn_common.h: spw), so a tile
-    // packs the groups of ONE set back to back instead of padding every group to a whole tile
-    p.Fpad = (precision == ESN_F64 && !m64) ? p.F : round_up(p.F, 16);
-    if (!m64) shrink_f64_tile(precision, p);
-    const int tslots = m64 ? tile : p.g.Bt;
-    if (p.n_wsets > 1) {
-        const int gpw = (p.n_groups + p.n_wsets - 1) / p.n_wsets;
-        p.spw = round_up(gpw * p.Fpad, tslots);
-        p.n_tiles = p.n_wsets * (p.spw / tslots);
-    } else {
-        p.n_tiles = (int)(((long long)p.n_groups * p.Fpad + tslots - 1) / tslots);
-    }
-    p.T_in = T_in; p.S = T; p.in_row_off = 0; p.transient = transient; p.harvest = 0;
+    fill_batch(p, precision, n_frames, frames_per_group);
+    p.T_in = T_in; p.S = T; p.in_row_off = 0; p.transient = transient;
     p.packed_w = packed_w; p.packed_wout = packed_wout;
     p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift;
     if (io32) p.U32 = static_cast<const float*>(U); else p.U = static_cast<const double*>(U);
@@ -365,40 +372,8 @@ static int predict_common(const char* who, bool io32, int precision, const esn_s
     if (((uintptr_t)Y & 15) != 0) return fail(-1, "%s: Y must be 16-byte aligned", who);
     if (io32) p.Y32 = static_cast<float*>(Y); else p.Y = static_cast<double*>(Y);
     ESN_SET_STAMPS(p);
-    // ONE float64 sequence (the reference's own call pattern): the matrix resident in the LDS of a cluster of
-    // workgroups that exchange the state through L2 every step (esn_recur_cluster.hip), when a workspace is lent
-    if (workspace && knobs().cluster && cluster_applies(precision, p)) {
-        const size_t need = cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, false);
-        if (workspace_bytes < need)
-            return fail(-1, "%s: workspace holds %zu bytes, esn_predict_workspace_bytes says %zu",
-                        who, workspace_bytes, need);
-        return hip_fail(launch_recur_cluster(p, workspace, (hipStream_t)stream), who);
-    }
-    // large reservoirs: one GEMM launch per step when the caller lends a workspace (else the persistent kernel)
-    if (workspace && knobs().big_gemm && p.g.big && big_path_applies(precision, p)) {
-        const size_t need = big_workspace_bytes(big_slots(p), p.g.Mp, p.g.Kp);
-        if (workspace_bytes < need)
-            return fail(-1, "%s: workspace holds %zu bytes, esn_predict_workspace_bytes says %zu",
-                        who, workspace_bytes, need);
-        p.Fpad = round_up(p.F, 16);
-        return hip_fail(launch_recur_big(precision, p, wout_big_offset(precision, p.n_out, p.g), workspace,
-                                         (hipStream_t)stream, io32), who);
-    }
-    // N_res 257..512, fp16/bf16: state in registers, one wave per SIMD (tiles of 128 slots like the skewed kernel)
-#ifdef ESN_WITH_RS
-    if (!io32 && knobs().rs && rs_path_applies(precision, p) &&
-        (size_t)n_frames * (T - transient) * p.n_out * 8 < 0x7fffffffu &&
-        (size_t)p.n_groups * p.wout_stride < 0x7fffffffu)         // its buffer descriptors are 31-bit
-        return hip_fail(launch_recur_rs(precision, p, wout_big_offset(precision, p.n_out, p.g), (hipStream_t)stream),
-                        "esn_predict_batch");
-#endif
-    // N_res 257..512, fp16/bf16: the skewed schedule on 16x16x32 MFMAs (the chip holds a higher clock on that shape)
-    if (p.g.s16 && p.g.skew && knobs().s16 && (precision == ESN_F16 || precision == ESN_BF16))
-        return hip_fail(launch_recur_skew16(precision, p, (hipStream_t)stream, io32), who);
-    int e = m64 ? launch_recur_f64_mfma(p, (hipStream_t)stream)
-            : (precision == ESN_F64) ? launch_recur_f64(p, (hipStream_t)stream)
-                                     : launch_recur_mfma(precision, p, (hipStream_t)stream, io32);
-    return hip_fail(e, who);
+    return launch_plan(who, "esn_predict_workspace_bytes", precision, p, io32, workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
 int esn_predict_batch(int precision, const esn_shape_t* shape, const void* packed_w, const void* packed_wout,
@@ -427,23 +402,28 @@ size_t esn_predict_workspace_bytes(int precision, const esn_shape_t* shape, int 
     RecurParams p;
     if (n_frames <= 0 || frames_per_group <= 0) return 0;
     if (fill_common(p, precision, shape, "esn_predict_workspace_bytes")) return 0;
-    p.harvest = 0; p.F = frames_per_group; p.n_frames = n_frames;
-    p.n_groups = (n_frames + frames_per_group - 1) / frames_per_group;
-    if (knobs().cluster && cluster_applies(precision, p)) return cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, false);
-    if (!p.g.big || !big_path_applies(precision, p)) return 0;
-    return big_workspace_bytes(big_slots(p), p.g.Mp, p.g.Kp);
+    fill_batch(p, precision, n_frames, frames_per_group);
+    return plan_recur(precision, p, false, true).workspace_bytes;
 }
 
 size_t esn_harvest_workspace_bytes(int precision, const esn_shape_t* shape, int n_groups) {
     RecurParams p;
     if (n_groups <= 0) return 0;
     if (fill_common(p, precision, shape, "esn_harvest_workspace_bytes", true)) return 0;
-    p.harvest = 1; p.n_groups = n_groups; p.n_frames = n_groups; p.F = 1;
-    if (knobs().cluster && cluster_applies(precision, p)) return cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, true);
-    if (knobs().hcluster && harvest_cluster_applies(precision, p))
-        return harvest_cluster_workspace_bytes(n_groups, knobs().hcluster == 1 ? 2 : knobs().hcluster, p.n_wsets);
-    if (!big_harvest_applies(precision, p)) return 0;
-    return big_harvest_workspace_bytes(n_groups, p.g.Kp);
+    fill_batch(p, precision, n_groups, 1);
+    return plan_recur(precision, p, false, true).workspace_bytes;
+}
+
+int esn_recur_path(int harvest, int precision, const esn_shape_t* shape, int n_sequences, int frames_per_group,
+                   int have_workspace) {
+    RecurParams p;
+    int rc = fill_common(p, precision, shape, "esn_recur_path", harvest != 0);
+    if (rc) return rc;
+    if (harvest) frames_per_group = 1;
+    if (n_sequences <= 0 || frames_per_group <= 0)
+        return fail(-1, "esn_recur_path: invalid sizes (n_sequences=%d F=%d)", n_sequences, frames_per_group);
+    fill_batch(p, precision, n_sequences, frames_per_group);
+    return plan_recur(precision, p, false, have_workspace != 0).path;
 }
 
 static int harvest_common(int precision, const esn_shape_t* shape, const void* packed_w, const double* in_scale,
@@ -459,24 +439,8 @@ static int harvest_common(int precision, const esn_shape_t* shape, const void* p
     if (n_groups <= 0 || T < 2) return fail(-1, "esn_harvest_batch: invalid sizes (n_groups=%d T=%d)", n_groups, T);
     if (noise_mode == ESN_NOISE_TENSOR && !noise_u) return fail(-1, "esn_harvest_batch: noise tensor missing");
     if (noise_mode < ESN_NOISE_NONE || noise_mode > ESN_NOISE_COUNTER) return fail(-1, "esn_harvest_batch: bad noise mode");
-    p.n_frames = n_groups;
-    p.n_groups = n_groups;
-    p.F = 1;
-    const bool m64 = use_f64_mfma(precision, p, n_groups);
-    const int tile = m64 ? p.g.Bt64 : p.g.Bt;
-    p.Fpad = 1;                             // one pilot per group; tiles span groups (of one weight set: spw)
-    // (Tried: leaving slots empty so that 2048 pilots spread over 256 tiles of 8 instead of 64 tiles of 32 -- the
-    //  harvest is bound by the AGGREGATE L2 weight stream, 4x the workgroups stream 4x the bytes: 1.14 -> 1.23 ms.)
-    if (p.n_wsets == 1 && !m64) shrink_f64_tile(precision, p);
-    const int tslots = m64 ? tile : p.g.Bt;
-    if (p.n_wsets > 1) {
-        const int gpw = (n_groups + p.n_wsets - 1) / p.n_wsets;
-        p.spw = round_up(gpw, tslots);
-        p.n_tiles = p.n_wsets * (p.spw / tslots);
-    } else {
-        p.n_tiles = (int)(((long long)n_groups + tslots - 1) / tslots);
-    }
-    p.T_in = T; p.S = T - 1; p.in_row_off = 1; p.transient = 0; p.harvest = 1;
+    fill_batch(p, precision, n_groups, 1);
+    p.T_in = T; p.S = T - 1; p.in_row_off = 1; p.transient = 0;
     p.packed_w = packed_w;
     p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift;
     p.U = U; p.D = D; p.noise_u = noise_u;
@@ -486,34 +450,8 @@ static int harvest_common(int precision, const esn_shape_t* shape, const void* p
     if ((((uintptr_t)E) | ((uintptr_t)E32)) & 15) return fail(-1, "esn_harvest_batch: E must be 16-byte aligned");
     p.E = E; p.E32 = E32;
     ESN_SET_STAMPS(p);
-    if (workspace && knobs().cluster && !E32 && cluster_applies(precision, p)) {          // one float64 sequence
-        const size_t need = cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, true);
-        if (workspace_bytes < need)
-            return fail(-1, "esn_harvest_batch: workspace holds %zu bytes, esn_harvest_workspace_bytes says %zu",
-                        workspace_bytes, need);
-        return hip_fail(launch_recur_cluster(p, workspace, (hipStream_t)stream), "esn_harvest_batch");
-    }
-    // 257..512 units, fp16/bf16, shared reservoir: clusters of eight workgroups with the matrix resident in LDS
-    if (workspace && knobs().hcluster && harvest_cluster_applies(precision, p)) {
-        const int hc_c = knobs().hcluster == 1 ? 2 : knobs().hcluster;           // members per cluster
-        const size_t need = harvest_cluster_workspace_bytes(n_groups, hc_c, p.n_wsets);
-        if (workspace_bytes < need)
-            return fail(-1, "esn_harvest_batch: workspace holds %zu bytes, esn_harvest_workspace_bytes says %zu",
-                        workspace_bytes, need);
-        return hip_fail(launch_harvest_cluster(precision, p, hc_c, workspace, (hipStream_t)stream), "esn_harvest_batch");
-    }
-    // large reservoirs: one GEMM launch per step when the caller lends a workspace (else the persistent kernel)
-    if (workspace && knobs().big_gemm && big_harvest_applies(precision, p)) {
-        const size_t need = big_harvest_workspace_bytes(n_groups, p.g.Kp);
-        if (workspace_bytes < need)
-            return fail(-1, "esn_harvest_batch: workspace holds %zu bytes, esn_harvest_workspace_bytes says %zu",
-                        workspace_bytes, need);
-        return hip_fail(launch_harvest_big(precision, p, workspace, (hipStream_t)stream), "esn_harvest_batch");
-    }
-    int e = m64 ? launch_recur_f64_mfma(p, (hipStream_t)stream)
-            : (precision == ESN_F64) ? launch_recur_f64(p, (hipStream_t)stream)
-                                     : launch_recur_mfma(precision, p, (hipStream_t)stream);
-    return hip_fail(e, "esn_harvest_batch");
+    return launch_plan("esn_harvest_batch", "esn_harvest_workspace_bytes", precision, p, false, workspace,
+                       workspace_bytes, (hipStream_t)stream);
 }
 
 int esn_harvest_batch(int precision, const esn_shape_t* shape, const void* packed_w, const double* in_scale,

@@ -8,6 +8,7 @@
 //       X = (H^H H + No/Pi I)^-1 H^H Y / sqrt(Pi)  (:40-45, :444-448); nearest QAM point, natural
 //       binary LSB-first bits, error count vs TxBits (:95-103, :451-456)
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 

@@ -7,6 +7,7 @@
 //                        Lc = 2 y / var, stop on zero syndrome or maxiter; systematic message = first k
 //                        bits (get_message); info-bit errors accumulated per group (:495-511)
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 

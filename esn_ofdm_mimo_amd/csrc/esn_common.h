@@ -215,8 +215,8 @@ inline __host__ __device__ int s16_nat(int pos) {       // inverse of s16_pos
 }
 
 // Tuning / diagnostic knobs (benchmarks and A/B tests only).  Read ONCE per process from the
-// environment (ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP) and changed afterwards only
-// through the debug entry point esn_debug_set (esn_api.hip) -- never re-read per launch.  None of
+// environment and changed afterwards only through the debug entry point esn_debug_set -- never re-read per
+// launch; keys, variables and parse rules are the rows of ONE table (esn_api.hip: kKnobTable).  None of
 // them changes a packed image: the weight image depends on (precision, n_res, n_in, n_out) alone.
 struct Knobs {
     int skew;              // 1 (default): skewed schedule where it applies; 0: in-step schedule

@@ -5,6 +5,7 @@
 //   bits = natural binary of idx, LSB first; errors vs TxBits  (driver :30-32, :451-456)
 // float64 throughout, radix-2 FFT in LDS.
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 

@@ -10,6 +10,7 @@
 //   gen_frames_kernel  bits -> QAM (:406-411) -> N*ifft (:416) -> CP (:417) -> sqrt(Pi) -> PA (:419)
 //                      -> per-link FIR, zero initial state (:422-425) -> AWGN (:426)
 #include "esn_common.h"
+#include "esn_launch.h"
 #include <type_traits>
 
 namespace esn {

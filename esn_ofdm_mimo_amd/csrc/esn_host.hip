@@ -12,10 +12,8 @@
 #include <stdio.h>
 #include <vector>
 #include "esn_common.h"
+#include "esn_launch.h"
 
-namespace esn {
-int api_fail(int code, const char* fmt, ...);      // esn_api.hip: sets esn_last_error()
-}
 using namespace esn;
 
 namespace {

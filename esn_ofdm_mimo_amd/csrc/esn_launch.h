@@ -1,0 +1,87 @@
+// Host-side functions one translation unit of the library offers the others: geometry, size and "applies"
+// predicates and the kernel launchers, grouped by the file that defines them.  Included by the callers
+// (esn_api.hip, esn_host.hip) AND by every defining file, so a definition is compiled against the declaration its
+// caller sees; default arguments live here only.  Launchers return 0, a hipError_t (> 0), or -1 for "no kernel
+// instance for this shape".
+#pragma once
+#include "esn_common.h"
+
+namespace esn {
+// esn_api.hip: sets esn_last_error(), returns `code`
+int api_fail(int code, const char* fmt, ...);
+#ifdef ESN_STAMPS
+unsigned long long* stamp_buffer();
+#endif
+// esn_recur_f64.hip
+int launch_recur_f64(const RecurParams& p, hipStream_t stream);
+size_t recur_f64_lds_bytes(int FB, int n_res, int n_in, int n_out);
+// esn_recur_f64_mfma.hip
+bool f64_mfma_geometry(int n_res, int n_in, int n_out, bool harvest, Geometry* g);
+int launch_recur_f64_mfma(const RecurParams& p, hipStream_t stream);
+#ifdef ESN_WITH_RS
+// esn_recur_rs.hip (a kept negative result, DESIGN.md 3.1b: only in builds made with ESN_WITH_RS=1)
+bool rs_path_applies(int precision, const RecurParams& p);
+int launch_recur_rs(int precision, const RecurParams& p, size_t wo_rs_off, hipStream_t stream);
+#endif
+// esn_recur_big.hip
+bool big_path_applies(int precision, const RecurParams& p);
+int big_slots(const RecurParams& p);
+size_t big_workspace_bytes(int n_slots, int Mp, int Kp);
+size_t big_wout_image_bytes(int Mp);
+int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream,
+                     bool io32 = false);
+bool big_harvest_applies(int precision, const RecurParams& p);
+size_t big_harvest_workspace_bytes(int n_groups, int Kp);
+int launch_harvest_big(int precision, const RecurParams& p, void* workspace, hipStream_t stream);
+// esn_recur_cluster.hip
+bool cluster_applies(int precision, const RecurParams& p);
+size_t cluster_workspace_bytes(int n_res, int n_in, int n_out, bool harvest);
+int launch_recur_cluster(const RecurParams& p, void* workspace, hipStream_t stream);
+// esn_recur_mfma.hip, and the per-precision instantiations it dispatches to (esn_recur_mfma_{f32,f16,bf16}.hip)
+bool mfma_geometry(int precision, int n_res, int n_in, int n_out, bool harvest, Geometry* g);
+int launch_recur_mfma(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
+int launch_recur_mfma_f32(const RecurParams& p, hipStream_t stream, bool io32);
+int launch_recur_mfma_f16(const RecurParams& p, hipStream_t stream, bool io32);
+int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream, bool io32);
+// esn_harvest_cluster.hip
+bool harvest_cluster_applies(int precision, const RecurParams& p);
+size_t harvest_cluster_workspace_bytes(int n_pilots, int C, int n_wsets);
+int launch_harvest_cluster(int precision, const RecurParams& p, int C, void* workspace, hipStream_t stream);
+// esn_recur_skew16.hip
+int launch_recur_skew16(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
+// esn_pack.hip
+size_t packed_w_bytes(int precision, int n_res, int n_in, int n_out, const Geometry& g);
+size_t packed_wout_bytes(int precision, int n_res, int n_in, int n_out, const Geometry& g);
+size_t wout_big_offset(int precision, int n_out, const Geometry& g);
+size_t f64_w_offset(int n_res, int n_in, int n_out);
+size_t f64_wout_offset(int n_res, int n_in, int n_out);
+int launch_pack_weights(int precision, const esn_shape_t* sh, const Geometry& g, const double* W,
+                        const double* Win, const double* Wfb, void* packed, hipStream_t stream);
+int launch_pack_readout(int precision, const esn_shape_t* sh, const Geometry& g, int n_groups,
+                        const double* Wout, void* packed, hipStream_t stream);
+// esn_solve.hip
+size_t solve_work_doubles(int rows, int cols, int n_out);
+int launch_readout_solve(const double* E, const double* D, int n_groups, int T, int transient,
+                         int cols, int n_out, const double* t_scale, const double* t_shift,
+                         double* W_out, int* status, void* workspace, hipStream_t stream);
+int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
+                        int cols, int n_out, const double* t_scale, const double* t_shift,
+                        double* W_out, int* status, hipStream_t stream);
+size_t chol_big_work_doubles(int n);
+int launch_readout_chol_big(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
+                            int cols, int n_out, const double* t_scale, const double* t_shift,
+                            double* W_out, int* status, void* workspace, hipStream_t stream);
+// esn_gen.hip
+int launch_gen_taps(const TapParams& tp, hipStream_t stream);
+int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);
+// esn_baseline.hip
+int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);
+int launch_mmse_detect(const MmseParams& mp, hipStream_t stream);
+int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream);
+// esn_coded.hip
+int launch_ldpc_encode(const LdpcEncodeParams& ep, hipStream_t stream);
+int launch_qam_llr(const LlrParams& lp, hipStream_t stream);
+int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
+// esn_detect.hip
+int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
+}  // namespace esn

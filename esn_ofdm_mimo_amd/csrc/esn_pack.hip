@@ -1,6 +1,7 @@
 // Weight packing: float64 row-major reference matrices (pyESN.py:93-109,191-192)
 // -> device images in the exact order the recurrence kernels consume them.
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 
@@ -140,7 +141,6 @@ __host__ __device__ inline size_t packed_wout_persistent_bytes(int es, int n_out
     const int n_ot = (n_out + 15) / 16;
     return (size_t)g.ro_parts * n_ot * 16 * g.Kp * es + 16;
 }
-size_t big_wout_image_bytes(int Mp);
 // (defined in esn_recur_rs.hip in ESN_WITH_RS=1 builds; g.rs is 0 otherwise, so this is never called)
 static inline size_t rs_wout_image_bytes(int Kp) { return (size_t)(Kp / 16) * 1024 + 16; }
 

@@ -20,6 +20,7 @@
 // and so does everybody else (the host call then reports the failure instead of hanging).
 // N_res small enough for one workgroup (C = 1) keeps the state in LDS and exchanges nothing.
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 

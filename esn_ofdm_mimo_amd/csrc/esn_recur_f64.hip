@@ -4,6 +4,7 @@
 // Weights are read K-major (Wk[k][n_res]) so a wave's loads are coalesced and
 // the LDS operand Z[f][k] is a wave-wide broadcast.
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 

@@ -23,6 +23,7 @@
 //       harvest: E row s+1 -> HBM
 #include <type_traits>
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 

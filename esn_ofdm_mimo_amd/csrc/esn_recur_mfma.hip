@@ -3,12 +3,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
-
-int launch_recur_mfma_f32(const RecurParams& p, hipStream_t stream, bool io32);
-int launch_recur_mfma_f16(const RecurParams& p, hipStream_t stream, bool io32);
-int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream, bool io32);
 
 // Tiling table: (NW, MT, NT) per precision and reservoir size.  Constraints:
 // Mp = 32*MT*NW >= n_res; LDS = 32*NT*Ks*ES <= 160 KiB; accumulators 16*MT*NT

@@ -1,4 +1,5 @@
 #include "esn_recur_mfma_impl.h"
+#include "esn_launch.h"
 
 namespace esn {
 

@@ -1,5 +1,6 @@
 // Instantiations of the 16x16x32 skewed predict kernel (esn_recur_skew16_impl.h).
 #include "esn_recur_skew16_impl.h"
+#include "esn_launch.h"
 
 namespace esn {
 

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "esn_common.h"
+#include "esn_launch.h"
 
 namespace esn {
 
@@ -917,10 +918,6 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
     }
 #endif
 }
-
-#ifdef ESN_STAMPS
-unsigned long long* stamp_buffer();     // esn_api.hip
-#endif
 
 int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
                         int cols, int n_out, const double* t_scale, const double* t_shift,

@@ -81,8 +81,10 @@ const char* esn_last_error(void);
 int esn_abi_version(void);
 
 /* Tuning / diagnostic knobs for benchmarks and A/B tests (no counterpart in the reference).  The
- * library reads ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP, ESN_CHOL_DMA and ESN_F64_MFMA from the environment
- * ONCE, at its first call, as initial values; afterwards only this call changes them:
+ * library reads the initial value of every key but "gen_ko" from the environment ONCE, at its first call -- the
+ * variable is ESN_ + the key in capitals: ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP, ESN_CHOL_DMA,
+ * ESN_F64_MFMA, ESN_RS, ESN_S16, ESN_BIG_GEMM, ESN_CLUSTER, ESN_BIG_PIPE, ESN_BIG_NT, ESN_HARVEST_GEMM, ESN_HCLUSTER
+ * (one table in csrc/esn_api.hip serves both) -- and afterwards only this call changes them:
  *   "skew"          "0" = in-step schedule for the fp16/bf16 predict kernel, else skewed (default)
  *   "mfma_geom"     "NW,MT,NT" re-cuts the fp16/bf16 predict tiling; ignored unless 32*NW*MT equals
  *   "mfma_geom_f32" the table's padded row count, so a packed image never goes stale; NULL = table
@@ -108,6 +110,39 @@ int esn_abi_version(void);
  *   "gen_ko"        frame-generator knock-out mask for tools/time_gen.py (timing only, wrong frames)
  * Returns 0, or -1 for an unknown key. */
 int esn_debug_set(const char* key, const char* value);
+
+/* The recurrence kernels behind esn_predict_batch / esn_harvest_batch.  Which one serves a call is decided in ONE
+ * place (plan_recur, csrc/esn_api.hip) from the precision, the shape, the batch, the knobs above and whether the
+ * caller lends a workspace; the first that applies, in this order:
+ *   workspace lent:  CLUSTER_F64      ESN_F64, ONE sequence ("cluster")
+ *                    HARVEST_CLUSTER  harvest, fp16/bf16, 257..512 units, n_in 2/4/8/16, n_out <= 8 ("hcluster")
+ *                    BIG_PREDICT /    fp16/bf16, one weight set, n_in <= 16, n_out <= 8, beyond 1024 units ("big_gemm";
+ *                    BIG_HARVEST      harvests of 257..1024 units and >= 64 pilots with "harvest_gemm")
+ *   predict:         RS               the register-state experiment (ESN_WITH_RS=1 builds, "rs")
+ *                    SKEW16           fp16/bf16, 257..512 units, n_in 2/4/8/16, n_out <= 8 ("s16", "skew")
+ *   otherwise:       F64_MFMA         ESN_F64, more than 8 sequences, where the matrix-pipe tiling fits ("f64_mfma")
+ *                    F64_VALU         ESN_F64
+ *                    MFMA             ESN_F32 / ESN_F16 / ESN_BF16: in-step or 32x32x16 skewed schedule ("skew") */
+enum esn_path {
+    ESN_PATH_MFMA = 0,             /* persistent MFMA kernel (esn_recur_mfma_impl.h)                         */
+    ESN_PATH_SKEW16 = 1,           /* 16x16x32 skewed predict kernel (esn_recur_skew16_impl.h)               */
+    ESN_PATH_F64_VALU = 2,         /* float64 on the vector ALU (esn_recur_f64.hip)                          */
+    ESN_PATH_F64_MFMA = 3,         /* float64 matrix pipe (esn_recur_f64_mfma.hip)                           */
+    ESN_PATH_CLUSTER_F64 = 4,      /* single float64 sequence, workgroup cluster (esn_recur_cluster.hip)     */
+    ESN_PATH_BIG_PREDICT = 5,      /* one GEMM launch per step, predict (esn_recur_big.hip)                  */
+    ESN_PATH_BIG_HARVEST = 6,      /* one GEMM launch per step, harvest (esn_recur_big.hip)                  */
+    ESN_PATH_HARVEST_CLUSTER = 7,  /* fp16/bf16 harvest, workgroup clusters (esn_harvest_cluster.hip)        */
+    ESN_PATH_RS = 8                /* register-resident state, experiment builds only (esn_recur_rs.hip)     */
+};
+/* Which kernel esn_predict_batch (harvest = 0) / esn_harvest_batch (harvest = 1) runs for this call when a
+ * workspace of the advertised size is lent (have_workspace = 1) or not (0), under the current knobs: the answer of
+ * the same function the calls dispatch through.  n_sequences = n_frames (predict) or n_groups (harvest, where
+ * frames_per_group is ignored).  The paths CLUSTER_F64, BIG_PREDICT, BIG_HARVEST and HARVEST_CLUSTER read the
+ * workspace; of these CLUSTER_F64 and HARVEST_CLUSTER keep an error word in its last 64 bytes.  In ESN_WITH_RS=1
+ * experiment builds the answer assumes float64 I/O and no tensor noise (the RS kernel serves neither float32 I/O nor
+ * ESN_NOISE_TENSOR).  Returns an esn_path value >= 0, or a negative error as the calls themselves would.  Diagnostic. */
+int esn_recur_path(int harvest, int precision, const esn_shape_t* shape, int n_sequences,
+                   int frames_per_group, int have_workspace);
 
 /* Device facts used for roofline reporting (any pointer may be NULL). */
 int esn_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz,
@@ -155,8 +190,9 @@ int esn_pack_readout(int precision, const esn_shape_t* shape, int n_groups,
  *                 output (continuation=True: laststate/lastoutput, :234-237) or NULL (zeros)
  *   noise_u       [B][T][n_res] uniforms when noise_mode == ESN_NOISE_TENSOR
  *   Y             [B][T-transient][n_out], unscaled (:255); 16-byte aligned (rows are written as 16-byte pairs)
- *   workspace     device scratch of esn_predict_workspace_bytes(...) bytes, or NULL.  Two shapes use it:
- *                 reservoirs beyond 1024 units in fp16/bf16 (the recurrence runs as one tiled GEMM launch
+ *   workspace     device scratch of esn_predict_workspace_bytes(...) bytes, or NULL.  The paths BIG_PREDICT and
+ *                 CLUSTER_F64 use it (enum esn_path; esn_recur_path tells which one a call takes): reservoirs
+ *                 beyond 1024 units in fp16/bf16 (the recurrence runs as one tiled GEMM launch
  *                 per timestep with the state images in the workspace), and ONE float64 sequence (n_frames = 1:
  *                 the reference's own call pattern) -- the matrix then stays resident in the LDS of a cluster of
  *                 co-resident workgroups that exchange the state through the workspace every step
@@ -208,7 +244,8 @@ int esn_predict_batch_f32(int precision, const esn_shape_t* shape,
  *   noise_u [n_groups][T-1][n_res] when noise_mode == ESN_NOISE_TENSOR.
  *   group_offset: as in esn_predict_batch (noise key and weight set follow the GLOBAL group index);
  *   E is 16-byte aligned.
- *   workspace: device scratch of esn_harvest_workspace_bytes(...) bytes, or NULL.  Three shapes use it: reservoirs
+ *   workspace: device scratch of esn_harvest_workspace_bytes(...) bytes, or NULL.  The paths BIG_HARVEST,
+ *   HARVEST_CLUSTER and CLUSTER_F64 use it (enum esn_path; esn_recur_path tells which one a call takes): reservoirs
  *   beyond 1024 units in fp16/bf16 (one tiled GEMM launch per timestep, 128 x 64 tiles: a fit has one sequence per
  *   trained ESN, so the tile is cut for workgroup count); fp16/bf16 at 257..512 units (pairs
  *   of co-resident workgroups keep the weight matrix in registers and exchange their state slices through the

@@ -122,17 +122,26 @@ def test_big_gemm_harvest_matches_persistent_kernel(mods, n_res, n_in, n_out, G,
         kw["noise_u"] = rs.rand(G, t - 1, n_res)
     from esn_ofdm_mimo_amd._lib import PRECISIONS
     import ctypes as C
-    lib.debug_set("harvest_gemm", "1")          # (reservoirs of 257..1024 units take the GEMM path only on request: it is slower)
+    # below 1025 units the harvest cluster kernel comes first in the dispatch order and reads neither knob used here:
+    # it is switched off around BOTH runs, or they would be the same kernel compared with itself
+    if n_res < 1025:
+        lib.debug_set("hcluster", "0")
     try:
-        assert lib.load().esn_harvest_workspace_bytes(PRECISIONS[precision], C.byref(bank.shape), G) > 0
-        big = bank.harvest(u, d, **kw).double().cpu().numpy()
+        lib.debug_set("harvest_gemm", "1")          # (reservoirs of 257..1024 units take the GEMM path only on request: it is slower)
+        try:
+            assert lib.load().esn_harvest_workspace_bytes(PRECISIONS[precision], C.byref(bank.shape), G) > 0
+            assert lib.recur_path(True, precision, bank.shape, G) == "big_harvest"
+            big = bank.harvest(u, d, **kw).double().cpu().numpy()
+        finally:
+            lib.debug_set("harvest_gemm", "0")
+        lib.debug_set("big_gemm", "0")
+        try:
+            assert lib.recur_path(True, precision, bank.shape, G) == "mfma"
+            persistent = bank.harvest(u, d, **kw).double().cpu().numpy()
+        finally:
+            lib.debug_set("big_gemm", "1")
     finally:
-        lib.debug_set("harvest_gemm", "0")
-    lib.debug_set("big_gemm", "0")
-    try:
-        persistent = bank.harvest(u, d, **kw).double().cpu().numpy()
-    finally:
-        lib.debug_set("big_gemm", "1")
+        lib.debug_set("hcluster", "1")
     assert big.shape == persistent.shape == (G, t, n_res + n_in)
     # same operand rounding, same k order, same noise stream: the two kernels agree to accumulation round-off
     tol = 2e-3 if precision == "f16" else 2e-2

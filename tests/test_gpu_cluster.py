@@ -66,9 +66,11 @@ def test_cluster_kernel_matches_vector_kernel_and_oracle(mods, n_res, n_in, n_ou
         bank.raise_if_cluster_timed_out()
         return fresh, cont, e
 
+    assert [lib.recur_path(h, "f64", bank.shape, 1) for h in (0, 1)] == ["cluster_f64"] * 2
     got = run()
     lib.debug_set("cluster", "0")
     try:
+        assert [lib.recur_path(h, "f64", bank.shape, 1) for h in (0, 1)] == ["f64_valu"] * 2
         ref = run()
     finally:
         lib.debug_set("cluster", "1")

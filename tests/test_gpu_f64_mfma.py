@@ -55,6 +55,8 @@ def test_predict_f64_matrix_pipe(mods, n_res, n_in, n_out, G, F, noise_mode, noi
         kw["noise_u"] = rs.rand(B, t, n_res)
     got = bank.predict(u, F, **kw).cpu().numpy()
     assert got.shape == (B, t - tr, n_out)
+    assert lib.recur_path(False, "f64", bank.shape, B, F) == "f64_mfma"
+    assert _valu(lib, lambda: lib.recur_path(False, "f64", bank.shape, B, F)) == "f64_valu"
     ref = _valu(lib, lambda: bank.predict(u, F, **kw).cpu().numpy())
     assert rel_err(got, ref) < 1e-11, rel_err(got, ref)             # same arithmetic, same noise, other k order
     if noise_mode != "counter":
@@ -90,6 +92,8 @@ def test_harvest_f64_matrix_pipe(mods, n_res, n_in, n_out, G, noise):
     u, d = rs.randn(G, t, n_in), rs.randn(G, t, n_out) * 0.3
     mode = "counter" if noise else "none"
     E = bank.harvest(u, d, precision="f64", noise_mode=mode, seed=3).cpu().numpy()
+    assert lib.recur_path(True, "f64", bank.shape, G) == "f64_mfma"
+    assert _valu(lib, lambda: lib.recur_path(True, "f64", bank.shape, G)) == "f64_valu"
     ref = _valu(lib, lambda: bank.harvest(u, d, precision="f64", noise_mode=mode, seed=3).cpu().numpy())
     assert E.shape == (G, t, n_res + n_in)
     assert rel_err(E, ref) < 1e-12

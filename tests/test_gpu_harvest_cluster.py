@@ -41,6 +41,7 @@ def test_cluster_harvest_matches_persistent_kernel_and_oracle(mods, n_res, n_in,
     if noise_mode == "tensor":
         kw["noise_u"] = rs.rand(G, t - 1, n_res)
     assert L.load().esn_harvest_workspace_bytes(L.F16, C.byref(bank.shape), G) == ((G + 15) // 16) * 32768 + 64
+    assert L.recur_path(True, "f16", bank.shape, G) == "harvest_cluster"
     e32 = bank.harvest(u, d, e_dtype="f32", **kw)
     bank.raise_if_harvest_timed_out()
     e64 = bank.harvest(u, d, **kw)
@@ -48,6 +49,7 @@ def test_cluster_harvest_matches_persistent_kernel_and_oracle(mods, n_res, n_in,
     L.debug_set("hcluster", "0")
     try:
         assert L.load().esn_harvest_workspace_bytes(L.F16, C.byref(bank.shape), G) == 0
+        assert L.recur_path(True, "f16", bank.shape, G) == "mfma"
         ref = bank.harvest(u, d, **kw).cpu().numpy()
     finally:
         L.debug_set("hcluster", "1")
@@ -81,10 +83,12 @@ def test_cluster_harvest_bf16_and_fit(mods):
     bank.set_scaling(np.full((G, n_in), 0.15), None, np.full((G, n_out), 0.8), None)
     u, d = rs.randn(G, t, n_in), np.tanh(rs.randn(G, t, n_out))
     for precision in ("bf16", "f16"):
+        assert L.recur_path(True, precision, bank.shape, G) == "harvest_cluster"
         e = bank.harvest(u, d, precision=precision, noise_mode="counter", seed=2, e_dtype="f32")
         bank.raise_if_harvest_timed_out()
         L.debug_set("hcluster", "0")
         try:
+            assert L.recur_path(True, precision, bank.shape, G) == "mfma"
             ref = bank.harvest(u, d, precision=precision, noise_mode="counter", seed=2, e_dtype="f32")
         finally:
             L.debug_set("hcluster", "1")
@@ -113,10 +117,12 @@ def test_cluster_harvest_with_several_weight_sets(mods):
     u, d = rs.randn(G, t, n_in), np.tanh(rs.randn(G, t, n_out))
     for off in (0, 5):
         kw = dict(precision="f16", noise_mode="counter", seed=8, group_offset=off)
+        assert L.recur_path(True, "f16", bank.shape, G) == "harvest_cluster"
         e = bank.harvest(u, d, **kw).cpu().numpy()
         bank.raise_if_harvest_timed_out()
         L.debug_set("hcluster", "0")
         try:
+            assert L.recur_path(True, "f16", bank.shape, G) == "mfma"
             ref = bank.harvest(u, d, **kw).cpu().numpy()
         finally:
             L.debug_set("hcluster", "1")

@@ -58,6 +58,8 @@ PATHS = [
     ("big_persistent_2048", "f16", 2048, 16, 8, {"big_gemm": "0"}),
 ]
 RESTORE = {"s16": "1", "skew": "1", "big_gemm": "1"}
+# what esn_recur_path answers for each row ("mfma" is the in-step and the 32x32x16 skewed schedule alike)
+KERNEL = {"skew16_f16": "skew16", "skew16_bf16": "skew16", "skew16_siso_shape": "skew16", "big_gemm_2048": "big_predict"}
 
 
 # every path with and without counter noise; the slow 2048 shapes with counter noise only
@@ -74,6 +76,7 @@ def test_predict_f32_is_rounded_f64(mods, name, precision, n_res, n_in, n_out, k
     try:
         for k, v in knobs.items():
             _lib.debug_set(k, v)
+        assert _lib.recur_path(False, precision, bank.shape, G * F, F) == KERNEL.get(name, "mfma")
         y32, y64 = predict_both(torch, bank, U32, F, T, transient, precision, noise_mode=noise_mode, seed=7)
     finally:
         for k in knobs:

@@ -192,6 +192,7 @@ def test_skewed_schedule_matches_in_step_schedule(amd, noise_mode, noise, n_res,
         kw["noise_u"] = rs.rand(u.shape[0], t, n_res)
     from esn_ofdm_mimo_amd import _lib
     assert os.environ.get("ESN_SKEW") is None
+    assert _lib.recur_path(False, "f16", bank.shape, u.shape[0], F) == ("skew16" if 256 < n_res <= 512 else "mfma")
     skew = bank.predict(u, F, **kw).cpu().numpy()
     _lib.debug_set("skew", "0")
     try:
@@ -203,6 +204,7 @@ def test_skewed_schedule_matches_in_step_schedule(amd, noise_mode, noise, n_res,
     # order and LDS layout); knob s16=0 selects the 32x32x16 skewed kernel on the same inputs and noise draws
     _lib.debug_set("s16", "0")
     try:
+        assert _lib.recur_path(False, "f16", bank.shape, u.shape[0], F) == "mfma"
         skew32 = bank.predict(u, F, **kw).cpu().numpy()
     finally:
         _lib.debug_set("s16", "1")
