@@ -88,7 +88,11 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         tab_un[i] = v;
     }
     // byte offset of natural column k of frame f in the state image
-    auto zoff = [&](int f, int k) -> size_t {
+    // (every lambda of this kernel is S16_INLINE: the step loop below exists once per wave set, and without the
+    //  attribute the compiler outlines the lambdas that now have two callers into real functions -- s_swappc, the
+    //  accumulators through 1-1.4 KB of scratch)
+#define S16_INLINE __attribute__((always_inline))
+    auto zoff = [&](int f, int k) S16_INLINE -> size_t {
         const int pos = s16_pos(k);
         return ((size_t)((f >> 4) * NKK + (pos >> 5)) * 64 + ((pos >> 3) & 3) * 16 + (f & 15)) * 16 + 2 * (pos & 7);
     };
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     constexpr int OOB = 0x7ffffff0;
 
     // Y complete: feedback columns into the image, unscaled output row `orow` to HBM, reset yacc
-    auto finish_readout = [&](int orow, bool write_fb) {
+    auto finish_readout = [&](int orow, bool write_fb) S16_INLINE {
         int ofc = ofc_w, oq = oq_w;
         asm volatile("" : "+v"(ofc), "+v"(oq));              // derived per step, not kept across the GEMM phases
         if (!has_ro) return;
@@ -195,7 +199,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     const int lag = wave >= NW / 2 ? 1 : 0;
     f32x4 acc[4][8];
     u32x4 abuf[2][4], b[4], ra[4];
-    auto zero_acc = [&]() {
+    auto zero_acc = [&]() S16_INLINE {
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -205,7 +209,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         const_cast<char*>(reinterpret_cast<const char*>(p.packed_w) + (size_t)wset * p.wset_stride + p.w16_off), 0,
         S16_MP * NKK * 64, 0x00020000);
     const int w_frag0 = wave * NKK * 4;                    // fragment (wave, kk, m) at ((wave NKK + kk) 4 + m) KB
-    auto loadA = [&](u32x4 (&a)[4], int kk) {             // kk >= NKK: zeros, no traffic
+    auto loadA = [&](u32x4 (&a)[4], int kk) S16_INLINE {  // kk >= NKK: zeros, no traffic
         const bool live = kk < NKK;
         const int voff = live ? lane16 : OOB;
 #pragma unroll
@@ -219,19 +223,20 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         0, NKK * 1024 + 16, 0x00020000);
     // W_out fragments of one trip (two groups): ra[2j] = group kk0 + i + j (the half being multiplied),
     // ra[2j+1] = group (kk0 + i + j) ^ 8 (the other half); `on` false: zeros, no traffic
-    auto load_ra = [&](int j, int kk, bool on) {
+    auto load_ra = [&](int j, int kk, bool on) S16_INLINE {
         on = on && kk < 2 * NKH;
         const int voff = on ? lane16 : OOB;
         ra[2 * j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wo_rsrc, voff, on ? kk * 1024 : 0, 0));
         ra[2 * j + 1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wo_rsrc, voff, on ? (kk ^ 8) * 1024 : 0, 0));
     };
-    auto ro_prefetch = [&](int kk0, bool on) { load_ra(0, kk0, on); load_ra(1, kk0 + 1, on); };
+    auto ro_prefetch = [&](int kk0, bool on) S16_INLINE { load_ra(0, kk0, on); load_ra(1, kk0 + 1, on); };
     typedef const __attribute__((address_space(3))) u32x4* lds_frag_t;
     // State groups [kk0, kk0 + 8) out of abuf, two per trip; abuf[j] holds group kk0 + j on entry and kk0 + 8 + j on
     // exit.  B ring: slot n & 3 holds column tile n's fragment and is refilled behind that tile's four MFMAs with
     // tile n + 4's (n < 4: same group; else tile n - 4 of the next group) -- twelve MFMAs of look-ahead, 16 registers.
-    // RO: the read-out of the own tile rides along, both halves of k per group position.
-    auto gemm_half = [&](int kk0, auto ro_tag, bool ro_on) {
+    // RO: the read-out of the own tile rides along, both halves of k per group position (a wave reads out in ONE of its
+    // two halves per step, see run_set; the other half is instantiated without it).
+    auto gemm_half = [&](int kk0, auto ro_tag, bool ro_on) S16_INLINE {
         constexpr bool RO = decltype(ro_tag)::value;
         const int voff_ro = ro_on ? lane16 : OOB;      // (step 0 and tiles of padding: zero fragments, no traffic)
         // (addresses re-derived from the lane id per call, opaque to the optimiser: kept live across the step loop they
@@ -248,7 +253,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         uint32_t xp = zb + (uint32_t)(wave * TILE_B) + (uint32_t)(kk0 ^ 8) * 1024;
         int sA = (w_frag0 + (kk0 + 2) * 4) * 1024;        // weight fragments two groups ahead
         int sR = (kk0 + 2) * 1024;                        // W_out fragments one trip ahead
-        auto trip = [&](int i, auto tail_tag) {
+        auto trip = [&](int i, auto tail_tag) S16_INLINE {
             constexpr bool TAIL = decltype(tail_tag)::value;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -264,15 +269,18 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                                        // fragments of the next trip go out right behind the read-out MFMA that used them
                             if (u == 0) rb0 = *reinterpret_cast<lds_frag_t>((uintptr_t)(rp + j * 1024));
                             if (u == 1) rbx = *reinterpret_cast<lds_frag_t>((uintptr_t)(xp + j * 1024));
+                            // (none in the last trip: the next reader of ra is behind the next ro_prefetch)
                             if (u == 8) {
                                 TR::mma16(yacc, ra[2 * j], rb0);
-                                ra[2 * j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                    wo_rsrc, TAIL ? OOB : voff_ro, TAIL ? 0 : sR + j * 1024, 0));
+                                if (!TAIL)
+                                    ra[2 * j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                        wo_rsrc, voff_ro, sR + j * 1024, 0));
                             }
                             if (u == 10) {
                                 TR::mma16(yacc, ra[2 * j + 1], rbx);
-                                ra[2 * j + 1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                    wo_rsrc, TAIL ? OOB : voff_ro, TAIL ? 0 : (sR ^ 8192) + j * 1024, 0));
+                                if (!TAIL)
+                                    ra[2 * j + 1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                        wo_rsrc, voff_ro, (sR ^ 8192) + j * 1024, 0));
                             }
                         }
                         if (n == 7) {                     // weight fragment m of the group two ahead
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         trip(NKH - 2, std::true_type{});
     };
     // [U ; F] group: abuf[0] holds group 16 on entry
-    auto uf_group = [&](u32x4 ra_u) {
+    auto uf_group = [&](u32x4 ra_u) S16_INLINE {
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const uint32_t up = (uint32_t)(uintptr_t)zf + (uint32_t)(ln << 4) + 16 * 1024;
@@ -323,7 +331,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto next_step_A = [&]() { loadA(abuf[0], 0); loadA(abuf[1], 1); };
+    auto next_step_A = [&]() S16_INLINE { loadA(abuf[0], 0); loadA(abuf[1], 1); };
 
     // phase E for tile positions [N0, N1): eight values per lane and row-tile pair -> one 16-byte store
     constexpr bool PK_NOISE = NOISE == ESN_NOISE_COUNTER && std::is_same<TR, TraitsF16>::value;
@@ -333,7 +341,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     const h16x2 c1h = {c1s, c1s};
     const float t_bias = 1.0f + n_c0 - (float)c1s;
     const uint32_t seed_hi = (uint32_t)(p.seed >> 32);
-    auto activate = [&](int s, auto n0_tag, auto n1_tag, int ln) {
+    auto activate = [&](int s, auto n0_tag, auto n1_tag, int ln) S16_INLINE {
         constexpr int N0 = decltype(n0_tag)::value, N1 = decltype(n1_tag)::value;
         const int g4 = ln >> 4, col = ln & 15;
         uint32_t k1[N1 - N0];
@@ -428,7 +436,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(reinterpret_cast<const char*>(p.U) + u_base_frame * in_frame_bytes), 0,
         (int)(u_left < 0x7fffffffu ? u_left : 0x7fffffffu), 0x00020000);
-    auto dma_inputs_b = [&](int s) {
+    auto dma_inputs_b = [&](int s) S16_INLINE {
         const int row = s + p.in_row_off;
         const bool row_ok = row < p.T_in;
         int ln = lane;
@@ -464,7 +472,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
             }
         }
     };
-    auto commit_inputs_b = [&](int s) {
+    auto commit_inputs_b = [&](int s) S16_INLINE {
         const bool row_ok = s + p.in_row_off < p.T_in;
         const int lk2 = lkin - 1;
         int ln = lane;
@@ -503,61 +511,91 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
 #define ESN_SK_ADD(i, a, b)
 #endif
     const uint32_t key1_own = tab_key[wave * 16 + (lane & 15)];
-    next_step_A();
-    ro_prefetch(0, false);
-    if (lag) __syncthreads();                                      // slot 0: set A alone
-    for (int s = 0; s < p.S; ++s) {
-        const bool ro = has_ro && s > 0;
-        ESN_STAMP(t0)
-        zero_acc();
-        // ---- P0 (set A: slot 3s; set B: slot 3s+1 with the read-out of Y_s).  ONE code path for both sets: a
-        // branch around the MFMAs makes the compiler shuffle the accumulators between its arms (hundreds of spills);
-        // where a wave does not read out, its W_out fragments are zero (no traffic) and the MFMAs add nothing
-        if (lag) __builtin_amdgcn_s_setprio(1);
-        if (NOISE == ESN_NOISE_COUNTER) {      // keys of step s for the own tile's frames: read from slot 3s+2 on
-            const uint32_t k = mix32(key1_own ^ seed_hi ^ ((uint32_t)s * 0x85EBCA6BU + 0x27d4eb2fU));
-            if (lane < 16) tab_ks[(s & 1) * BT + wave * 16 + lane] = k;
-        }
-        if (lag && s > 0) commit_inputs_b(s);
-        gemm_half(0, std::true_type{}, ro && lag);
-        if (lag) { if (ro) finish_readout(s - 1 - p.transient, true); }
-        if (lag) __builtin_amdgcn_s_setprio(0);
-        ro_prefetch(NKH, ro && !lag);                              // set A: for P1, in flight over the barrier
-        ESN_STAMP(t1)
-        __syncthreads();
-        ESN_STAMP(t2)
-        // ---- P1 (set A: slot 3s+1 with the read-out; set B: slot 3s+2)
-        gemm_half(NKH, std::true_type{}, ro && !lag);
-        if (!lag) { if (ro) finish_readout(s - 1 - p.transient, true); }
-        ESN_STAMP(t3)
-        __syncthreads();
-        ESN_STAMP(t4)
-        // ---- P2: [U ; F] group + phase E
-        __builtin_amdgcn_s_setprio(2);
-        const u32x4 ra_u = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            wo_rsrc, has_ro ? lane16 : OOB, has_ro ? 16 * 1024 : 0, 0));
-        int ln_e = lane;
-        asm volatile("" : "+v"(ln_e));
-        uf_group(ra_u);
-        ESN_STAMP(u1)
-        activate(s, n_lo, n_mid, ln_e);
-        ESN_STAMP(u2)
+    // The step loop, once per wave set, entered by ONE wave-uniform branch: inside a body LAG is a constant, so a wave's
+    // half without the read-out is gemm_half<RO = false> (no read-out MFMAs on zero fragments, no ds_read of the own
+    // tile, no out-of-bounds W_out loads: about 100 instructions per wave and step, 16 of them MFMAs) and every
+    // per-set choice (input commit, LDS-DMA launches, priorities, which phase finishes the read-out) is compile-time
+    // code.  No accumulator is live across the branch, which is what a branch around the MFMAs inside ONE loop could
+    // not have (the compiler shuffled the accumulators between its arms: 290 spilled registers).
+    // Results are bitwise those of the one-path loop: the MFMAs that are gone added 0 * x to yacc for finite x, and
+    // yacc is never -0.0 (it starts at +0.0, and under round-to-nearest a sum with a +0.0 term, or one that cancels
+    // exactly, is +0.0), so yacc + (+-0.0) == yacc bit for bit.
+    // Barriers: both bodies execute three s_barrier per step; set B one more before its loop (slot 0 is set A's alone)
+    // and set A one more behind it (slot 3S: set B finishes X_B(S)).
+    auto run_set = [&](auto lag_tag) S16_INLINE {
+        constexpr bool LAG = decltype(lag_tag)::value;
         next_step_A();
-        ro_prefetch(0, lag && has_ro && s + 1 < p.S);              // set B: for P0(s+1)
-        ESN_STAMP(u3)
-        if (lag && s + 1 < p.S) dma_inputs_b(s + 1);               // last LDS read of the phase is behind us
-        ESN_STAMP(u4)
-        activate(s, n_mid, n_hi, ln_e);
-        ESN_STAMP(u5)
-        __builtin_amdgcn_s_setprio(0);
-        ESN_STAMP(t5)
-        __syncthreads();
-        ESN_STAMP(t6)
-        ESN_SK_ADD(0, t0, t1) ESN_SK_ADD(1, t1, t2) ESN_SK_ADD(2, t2, t3)
-        ESN_SK_ADD(3, t3, t4) ESN_SK_ADD(4, t4, t5) ESN_SK_ADD(5, t5, t6)
-        ESN_SK_ADD(6, t4, u1) ESN_SK_ADD(7, u1, u2) ESN_SK_ADD(8, u2, u3) ESN_SK_ADD(9, u3, u4)
-        ESN_SK_ADD(10, u4, u5) ESN_SK_ADD(11, u5, t5)
-    }
+        if (LAG) {
+            ro_prefetch(0, false);                                 // step 0 reads nothing out: zero fragments
+            __syncthreads();                                       // slot 0: set A alone
+        }
+        for (int s = 0; s < p.S; ++s) {
+            const bool ro = has_ro && s > 0;
+            ESN_STAMP(t0)
+            zero_acc();
+            // ---- P0 (set A: slot 3s; set B: slot 3s+1 with the read-out of Y_s)
+            if (LAG) __builtin_amdgcn_s_setprio(1);
+            if (NOISE == ESN_NOISE_COUNTER) {      // keys of step s for the own tile's frames: read from slot 3s+2 on
+                const uint32_t k = mix32(key1_own ^ seed_hi ^ ((uint32_t)s * 0x85EBCA6BU + 0x27d4eb2fU));
+                if (lane < 16) tab_ks[(s & 1) * BT + wave * 16 + lane] = k;
+            }
+            if (LAG) {
+                if (s > 0) commit_inputs_b(s);
+                gemm_half(0, std::true_type{}, ro);
+                if (ro) finish_readout(s - 1 - p.transient, true);
+                __builtin_amdgcn_s_setprio(0);
+            } else {
+                gemm_half(0, std::false_type{}, false);
+                ro_prefetch(NKH, ro);                              // for P1, in flight over the barrier
+            }
+            ESN_STAMP(t1)
+            __syncthreads();
+            ESN_STAMP(t2)
+#ifdef ESN_STAMPS
+            unsigned long long u3 = 0, u4 = 0;                     // around set B's LDS-DMA launches, inside its P1
+#endif
+            // ---- P1 (set A: slot 3s+1 with the read-out; set B: slot 3s+2)
+            if (LAG) {
+                gemm_half(NKH, std::false_type{}, false);
+                // inputs of step s + 1, launched into the time set B waits for set A's phase E (slot 3s+2 is bound by
+                // it); the staging slots are free, their last reader was this wave's commit_inputs_b(s).  Inside
+                // phase E the launches held the wave for a thousand cycles: the LDS reads behind them wait for the DMA
+                ESN_STAMP_SET(u3)
+                if (s + 1 < p.S) dma_inputs_b(s + 1);
+                ESN_STAMP_SET(u4)
+            } else {
+                gemm_half(NKH, std::true_type{}, ro);
+                if (ro) finish_readout(s - 1 - p.transient, true);
+            }
+            ESN_STAMP(t3)
+            __syncthreads();
+            ESN_STAMP(t4)
+            // ---- P2: [U ; F] group + phase E
+            __builtin_amdgcn_s_setprio(2);
+            const u32x4 ra_u = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                wo_rsrc, has_ro ? lane16 : OOB, has_ro ? 16 * 1024 : 0, 0));
+            int ln_e = lane;
+            asm volatile("" : "+v"(ln_e));
+            uf_group(ra_u);
+            ESN_STAMP(u1)
+            activate(s, n_lo, n_mid, ln_e);
+            ESN_STAMP(u2)
+            next_step_A();
+            if (LAG) ro_prefetch(0, has_ro && s + 1 < p.S);        // for P0(s+1)
+            ESN_STAMP(u2b)
+            activate(s, n_mid, n_hi, ln_e);
+            ESN_STAMP(u5)
+            __builtin_amdgcn_s_setprio(0);
+            ESN_STAMP(t5)
+            __syncthreads();
+            ESN_STAMP(t6)
+            ESN_SK_ADD(0, t0, t1) ESN_SK_ADD(1, t1, t2) ESN_SK_ADD(2, t2, t3)
+            ESN_SK_ADD(3, t3, t4) ESN_SK_ADD(4, t4, t5) ESN_SK_ADD(5, t5, t6)
+            ESN_SK_ADD(6, t4, u1) ESN_SK_ADD(7, u1, u2) ESN_SK_ADD(8, u2, u2b) ESN_SK_ADD(9, u3, u4)
+            ESN_SK_ADD(10, u2b, u5) ESN_SK_ADD(11, u5, t5)
+        }
+    };
+    if (lag) run_set(std::true_type{}); else run_set(std::false_type{});
 #undef ESN_SK_ADD
 #ifdef ESN_STAMPS
     if (p.stamps && blockIdx.x == 0 && lane == 0) {
@@ -576,6 +614,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         finish_readout(p.S - 1 - p.transient, false);
     }
 }
+#undef S16_INLINE
 
 template <typename TR, bool IO32>
 static int launch_skew16(const RecurParams& p, hipStream_t stream) {

@@ -76,6 +76,7 @@ print("mean " + " ".join(f"{v:13.0f}" for v in st.mean(0)) + f" {st.mean(0).sum(
 
 if raw[8:, :6].any():
     sub = raw[8:16, :6].astype(float) / T
-    print("inside P2 (skewed schedule): uf_groups, E first half, prefetch issue, E second half, yU, input fetch")
+    print("inside P2 (skewed schedule): [U;F] group, E first half, prefetch issue, input LDS-DMA launches "
+          "(16x16x32 kernel: at the tail of set B's P1, part of its G2 column), E second half, tail")
     for w in range(8):
         print(f"{w:4d} " + " ".join(f"{v:13.0f}" for v in sub[w]))
