@@ -35,6 +35,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     constexpr int NW = 8, BT = 128, NOWN = 8, NKK = S16_NKK, NKH = S16_NKH;
     constexpr int NTHREADS = NW * 64;
     constexpr int TILE_B = NKK * 1024;                    // bytes of one column tile's image
+    ESN_STAMP(t_entry)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -61,15 +62,30 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     // lanes, one mix32) instead of being re-derived by every lane of every wave for each of its eight tiles; two
     // buffers by step parity (set B reads step s while set A already writes step s + 1)
     uint32_t* tab_ks = reinterpret_cast<uint32_t*>(tab_off + BT);
+    // group of every slot, for the prologue alone: it borrows the head of the input staging slots, whose first writer is
+    // the LDS-DMA of step 1, barriers later.  Every per-slot division of the prologue is done here, once per slot
+    int* tab_grp = reinterpret_cast<int*>(in_slots);
+    const int lkin = __builtin_ctz(kin_p);                 // kin_p = round4(n_in) is 4, 8 or 16
     for (int i = tid; i < BT; i += NTHREADS) {
         int gtmp;
         const int fr = slot_frame(p, slot0 + i, gtmp);
         tab_fr[i] = fr;
+        tab_grp[i] = gtmp;
         tab_key[i] = mix32((uint32_t)p.seed ^ (((uint32_t)fr + p.frame_off) * 0x9E3779B9U));   // noise_key, stage 1
     }
+    // ---- LDS init: zeros over the whole state image (state rows and the [U ; F] group of every column tile), linear
+    // 16-byte stores; the bench and every detector call without a continuation start from exactly this image
+    {
+        constexpr int CHUNKS = NOWN * TILE_B / 16;
+        static_assert(CHUNKS % NTHREADS == 0, "whole passes");
+#pragma unroll
+        for (int i = 0; i < CHUNKS / NTHREADS; ++i)
+            *reinterpret_cast<u32x4*>(zf + (size_t)(i * NTHREADS + tid) * 16) = u32x4{0u, 0u, 0u, 0u};
+    }
+    __syncthreads();
     for (int i = tid; i < NOWN * kin_p; i += NTHREADS) {
-        const int c16 = i / kin_p, c = i % kin_p;
-        const int cg = slot_group(p, slot0 + c16 * 16);
+        const int c16 = i >> lkin, c = i & (kin_p - 1);
+        const int cg = tab_grp[c16 * 16];
         float2 v = make_float2(0.f, 0.f);
         if (cg < p.n_groups && c < n_in) {
             v.x = p.in_scale ? (float)p.in_scale[(size_t)cg * n_in + c] : 1.f;
@@ -79,7 +95,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     }
     for (int i = tid; i < NOWN * 16; i += NTHREADS) {
         const int c16 = i / 16, o = i % 16;
-        const int cg = slot_group(p, slot0 + c16 * 16);
+        const int cg = tab_grp[c16 * 16];
         float2 v = make_float2(1.f, 0.f);
         if (cg < p.n_groups && o < n_out) {
             if (p.t_scale) v.x = (float)(1.0 / p.t_scale[(size_t)cg * n_out + o]);
@@ -87,34 +103,49 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         }
         tab_un[i] = v;
     }
-    // byte offset of natural column k of frame f in the state image
     // (every lambda of this kernel is S16_INLINE: the step loop below exists once per wave set, and without the
     //  attribute the compiler outlines the lambdas that now have two callers into real functions -- s_swappc, the
     //  accumulators through 1-1.4 KB of scratch)
 #define S16_INLINE __attribute__((always_inline))
-    auto zoff = [&](int f, int k) S16_INLINE -> size_t {
-        const int pos = s16_pos(k);
-        return ((size_t)((f >> 4) * NKK + (pos >> 5)) * 64 + ((pos >> 3) & 3) * 16 + (f & 15)) * 16 + 2 * (pos & 7);
-    };
-    // ---- LDS init: x0 in the state rows, y0 in the feedback columns, zeros elsewhere --------------
-    for (int i = tid; i < BT * g.Kp; i += NTHREADS) {
-        const int f = i / g.Kp, k = i % g.Kp;
-        float v = 0.f;
-        int pg;
-        const int fr = slot_frame(p, slot0 + f, pg);
-        if (fr >= 0) {
-            if (k < n_res) {
-                if (p.x0) v = (float)p.x0[(size_t)pg * n_res + k];
-            } else if (k >= g.kfb && k < g.kfb + n_out) {
-                if (p.y0) v = (float)p.y0[(size_t)pg * n_out + (k - g.kfb)];
+    // x0 into the state rows: one 16-byte chunk (frame f, group kk, k-chunk q) per trip = the natural rows
+    // 32 kk + 16 t + 4 q + e (t = 0, 1; e = 0..3) of s16_pos, rows past n_res and padding frames as zeros
+    if (p.x0) {
+        for (int i = tid; i < BT * 2 * NKH * 4; i += NTHREADS) {
+            const int f = i & (BT - 1), kq = i >> 7, kk = kq >> 2, q = kq & 3;
+            const bool live = tab_fr[f] >= 0;
+            const double* xr = p.x0 + (size_t)(live ? tab_grp[f] : 0) * n_res;
+            uint32_t w[4];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int k = 32 * kk + 16 * t + 4 * q;
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = (live && k + e < n_res) ? (float)xr[k + e] : 0.f;
+                w[2 * t] = TR::pack2(v[0], v[1]);
+                w[2 * t + 1] = TR::pack2(v[2], v[3]);
             }
+            *reinterpret_cast<u32x4*>(zf + ((size_t)((f >> 4) * NKK + kk) * 64 + q * 16 + (f & 15)) * 16) = u32x4{w[0], w[1], w[2], w[3]};
         }
-        TR::store1(zf + zoff(f, k), v);
+    }
+    // y0 into the feedback columns: one quad of outputs per (frame, quad), as finish_readout stores them
+    if (p.y0) {
+        for (int i = tid; i < BT * 2; i += NTHREADS) {
+            const int f = i & (BT - 1), o0 = 4 * (i >> 7);
+            const bool live = tab_fr[f] >= 0;
+            const double* yr = p.y0 + (size_t)(live ? tab_grp[f] : 0) * n_out;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (live && o0 + e < n_out) ? (float)yr[o0 + e] : 0.f;
+            const int pos = g.kfb - S16_MP + o0;                         // position inside the [U ; F] group
+            if (o0 < kfb_p)
+                TR::store4(zf + ((size_t)((f >> 4) * NKK + 16) * 64 + (pos >> 3) * 16 + (f & 15)) * 16 + 2 * (pos & 7),
+                           v[0], v[1], v[2], v[3]);
+        }
     }
     __syncthreads();
 
     // ---- the wave's own column tile (tile `wave`): read-out lane view = output rows 4 oq .. 4 oq + 3 of frame ofc
-    const int oq_w = lane >> 4, ofc_w = lane & 15;
+    // (oq = lane >> 4, ofc = lane & 15: finish_readout)
     const int own_grp = __builtin_amdgcn_readfirstlane(slot_group(p, slot0 + wave * 16));
     const bool has_ro = own_grp < p.n_groups;                 // wave-uniform
     float wo_inv = 1.f;
@@ -123,8 +154,9 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                                                  + (size_t)own_grp * p.wout_stride + p.wo16_off + (size_t)NKK * 1024);
     const uint32_t in_stride = (uint32_t)(p.T_in * n_in);
     // inputs of step 0, straight from HBM (every later step arrives by LDS-DMA)
+    // (the [U ; F] group keeps natural order: input ci of frame f at position ci of group 16)
     for (int e = tid; e < BT * kin_p; e += NTHREADS) {
-        const int f = e / kin_p, ci = e % kin_p;
+        const int f = e >> lkin, ci = e & (kin_p - 1);
         const int fr = tab_fr[f];
         float v = 0.f;
         if (fr >= 0 && ci < n_in) {
@@ -133,7 +165,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
             const float2 ss = tab_in[(f >> 4) * kin_p + ci];
             v = fmaf((float)raw, ss.x, ss.y);
         }
-        TR::store1(zf + zoff(f, g.kin + ci), v);
+        TR::store1(zf + ((size_t)((f >> 4) * NKK + 16) * 64 + (ci >> 3) * 16 + (f & 15)) * 16 + 2 * (ci & 7), v);
     }
 
     const float noise = (float)p.noise;
@@ -144,8 +176,9 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
 
     // Y complete: feedback columns into the image, unscaled output row `orow` to HBM, reset yacc
     auto finish_readout = [&](int orow, bool write_fb) S16_INLINE {
-        int ofc = ofc_w, oq = oq_w;
-        asm volatile("" : "+v"(ofc), "+v"(oq));              // derived per step, not kept across the GEMM phases
+        int ln_ro = lane;
+        asm volatile("" : "+v"(ln_ro));                      // derived per step, not kept across the GEMM phases
+        const int ofc = ln_ro & 15, oq = ln_ro >> 4;
         if (!has_ro) return;
         const int of = wave * 16 + ofc;
         f32x4 y = yacc;
@@ -396,8 +429,13 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                             v[3] = fmaf((float)(sq >> 24), n_c1, v[3] + n_c0);
                         } else if (NOISE == ESN_NOISE_TENSOR) {
 #pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                if (nz && row + j < n_res) v[j] += noise * ((float)nz[row + j] - 0.5f);
+                            for (int j = 0; j < 4; ++j) {      // branch-free: a lane without noise (padding frame, row
+                                                               // past n_res) reads element 0 of the tensor and drops it
+                                const bool on = nz && row + j < n_res;
+                                const double u = (on ? nz : p.noise_u)[on ? row + j : 0];
+                                const float w = v[j] + noise * ((float)u - 0.5f);
+                                v[j] = on ? w : v[j];
+                            }
                         }
                         out[2 * tt] = TR::pack2(v[0], v[1]);
                         out[2 * tt + 1] = TR::pack2(v[2], v[3]);
@@ -421,7 +459,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     constexpr int IN_TRIPS = IO32 ? 1 : 2;
     constexpr int IN_TILES = NOWN / (NW / 2);
     const int in_c0 = IN_TILES * (wave - NW / 2);
-    const int lcpf = __builtin_ctz(cpf), lkin = __builtin_ctz(kin_p);
+    const int lcpf = __builtin_ctz(cpf);
     const size_t in_frame_bytes = (size_t)in_stride * sizeof(io_elem<IO32>);
     int j0;
     slot_group(p, slot0, j0);
@@ -433,9 +471,15 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
     }
     __syncthreads();
     const size_t u_left = ((size_t)p.n_frames - u_base_frame) * in_frame_bytes;
+    // The base and the record count are uniform (kernel arguments and the tile's first slot), but they come out of
+    // integer divisions, which run on the vector ALU: built from them as they are, the descriptor sits in four VGPRs
+    // and every LDS-DMA launch of dma_inputs_b is wrapped in a readfirstlane loop.  One readfirstlane set here instead
+    const uintptr_t u_base = reinterpret_cast<uintptr_t>(p.U) + u_base_frame * in_frame_bytes;
+    const uint32_t u_base_lo = __builtin_amdgcn_readfirstlane((uint32_t)u_base);
+    const uint32_t u_base_hi = __builtin_amdgcn_readfirstlane((uint32_t)(u_base >> 32));
+    const int u_records = __builtin_amdgcn_readfirstlane((int)(u_left < 0x7fffffffu ? u_left : 0x7fffffffu));
     const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.U) + u_base_frame * in_frame_bytes), 0,
-        (int)(u_left < 0x7fffffffu ? u_left : 0x7fffffffu), 0x00020000);
+        reinterpret_cast<char*>(((uintptr_t)u_base_hi << 32) | u_base_lo), 0, u_records, 0x00020000);
     auto dma_inputs_b = [&](int s) S16_INLINE {
         const int row = s + p.in_row_off;
         const bool row_ok = row < p.T_in;
@@ -504,13 +548,19 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         }
     };
 
+    // stamped build: a barrier split into its fence (the wave's own stores and LDS-DMA draining) and the s_barrier
+    // itself (waiting for the other waves), with a stamp between the two
 #ifdef ESN_STAMPS
-    unsigned long long sk_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long sk_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define ESN_SK_ADD(i, a, b) sk_acc[i] += (b) - (a);
+#define ESN_SYNC_SPLIT(mid) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); ESN_STAMP(mid) \
+    __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #else
 #define ESN_SK_ADD(i, a, b)
+#define ESN_SYNC_SPLIT(mid) __syncthreads();
 #endif
     const uint32_t key1_own = tab_key[wave * 16 + (lane & 15)];
+    ESN_STAMP(t_prologue)
     // The step loop, once per wave set, entered by ONE wave-uniform branch: inside a body LAG is a constant, so a wave's
     // half without the read-out is gemm_half<RO = false> (no read-out MFMAs on zero fragments, no ds_read of the own
     // tile, no out-of-bounds W_out loads: about 100 instructions per wave and step, 16 of them MFMAs) and every
@@ -549,14 +599,22 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                 ro_prefetch(NKH, ro);                              // for P1, in flight over the barrier
             }
             ESN_STAMP(t1)
-            __syncthreads();
+            ESN_SYNC_SPLIT(m1)
             ESN_STAMP(t2)
 #ifdef ESN_STAMPS
             unsigned long long u3 = 0, u4 = 0;                     // around set B's LDS-DMA launches, inside its P1
 #endif
             // ---- P1 (set A: slot 3s+1 with the read-out; set B: slot 3s+2)
+            // W_out fragment of the [U ; F] group, consumed by the first MFMA group of P2: launched here so that it is in
+            // flight across the barrier (the ra[] registers are dead from here to the next ro_prefetch in both sets)
+            auto load_ra_u = [&]() S16_INLINE {
+                return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                    wo_rsrc, has_ro ? lane16 : OOB, has_ro ? 16 * 1024 : 0, 0));
+            };
+            u32x4 ra_u;
             if (LAG) {
                 gemm_half(NKH, std::false_type{}, false);
+                ra_u = load_ra_u();
                 // inputs of step s + 1, launched into the time set B waits for set A's phase E (slot 3s+2 is bound by
                 // it); the staging slots are free, their last reader was this wave's commit_inputs_b(s).  Inside
                 // phase E the launches held the wave for a thousand cycles: the LDS reads behind them wait for the DMA
@@ -566,14 +624,13 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
             } else {
                 gemm_half(NKH, std::true_type{}, ro);
                 if (ro) finish_readout(s - 1 - p.transient, true);
+                ra_u = load_ra_u();
             }
             ESN_STAMP(t3)
-            __syncthreads();
+            ESN_SYNC_SPLIT(m3)
             ESN_STAMP(t4)
             // ---- P2: [U ; F] group + phase E
             __builtin_amdgcn_s_setprio(2);
-            const u32x4 ra_u = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                wo_rsrc, has_ro ? lane16 : OOB, has_ro ? 16 * 1024 : 0, 0));
             int ln_e = lane;
             asm volatile("" : "+v"(ln_e));
             uf_group(ra_u);
@@ -592,13 +649,16 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
             ESN_SK_ADD(0, t0, t1) ESN_SK_ADD(1, t1, t2) ESN_SK_ADD(2, t2, t3)
             ESN_SK_ADD(3, t3, t4) ESN_SK_ADD(4, t4, t5) ESN_SK_ADD(5, t5, t6)
             ESN_SK_ADD(6, t4, u1) ESN_SK_ADD(7, u1, u2) ESN_SK_ADD(8, u2, u2b) ESN_SK_ADD(9, u3, u4)
-            ESN_SK_ADD(10, u2b, u5) ESN_SK_ADD(11, u5, t5)
+            ESN_SK_ADD(10, u2b, u5) ESN_SK_ADD(11, u5, t5) ESN_SK_ADD(12, t1, m1) ESN_SK_ADD(13, t3, m3)
         }
     };
     if (lag) run_set(std::true_type{}); else run_set(std::false_type{});
 #undef ESN_SK_ADD
+#undef ESN_SYNC_SPLIT
 #ifdef ESN_STAMPS
     if (p.stamps && blockIdx.x == 0 && lane == 0) {
+        p.stamps[wave * 8 + 7] = t_prologue - t_entry;                // kernel entry to the first step
+        for (int i = 0; i < 2; ++i) p.stamps[(8 + wave) * 8 + 6 + i] = sk_acc[12 + i];   // fence share of "wait Ba" / "wait Bb"
         for (int i = 0; i < 6; ++i) p.stamps[wave * 8 + i] = sk_acc[i];
         for (int i = 0; i < 6; ++i) p.stamps[(8 + wave) * 8 + i] = sk_acc[6 + i];    // inside P2
         p.stamps[wave * 8 + 6] = (unsigned long long)__builtin_amdgcn_s_getreg(63492);   // HW_ID

@@ -80,3 +80,11 @@ if raw[8:, :6].any():
           "(16x16x32 kernel: at the tail of set B's P1, part of its G2 column), E second half, tail")
     for w in range(8):
         print(f"{w:4d} " + " ".join(f"{v:13.0f}" for v in sub[w]))
+if raw[:8, 7].any():         # 16x16x32 kernel: the prologue, and the barriers split at the s_barrier instruction
+    fence = raw[8:16, 6:8].astype(float) / T
+    print("16x16x32 kernel: prologue (kernel entry to the first step, cycles per LAUNCH), then per timestep the wait columns "
+          "split into the wave's own fence (stores / LDS-DMA draining) and the s_barrier (waiting for the others)")
+    print("wave      prologue   Ba fence Ba barrier   Bb fence Bb barrier")
+    for w in range(8):
+        print(f"{w:4d} {int(raw[w, 7]):13d} {fence[w, 0]:10.0f} {st[w, 1] - fence[w, 0]:10.0f} {fence[w, 1]:10.0f} {st[w, 3] - fence[w, 1]:10.0f}")
+    print(f"prologue share of workgroup 0's stamped life: {raw[:8, 7].mean() / (raw[:8, 7].mean() + st.mean(0).sum() * T):.4f}")

@@ -33,6 +33,7 @@ PASSES = [
     ["TCC_HIT_sum", "TCC_MISS_sum", "TCC_REQ_sum", "TCP_TCC_READ_REQ_sum"],
     ["SQC_ICACHE_REQ", "SQC_ICACHE_HITS", "SQC_ICACHE_MISSES", "SQ_IFETCH", "SQ_WAIT_INST_LDS", "SQ_ACTIVE_INST_LDS",
      "SQ_INSTS_LDS", "SQ_WAVE_CYCLES"],
+    ["SQ_INSTS_SALU", "SQ_INSTS_SMEM", "SQ_INSTS_VALU", "SQ_INSTS_MFMA", "SQ_WAVE_CYCLES"],
 ]
 
 
@@ -42,17 +43,23 @@ def main():
     ap.add_argument("--tag", default="r02")
     ap.add_argument("--blocks", default="2048")
     ap.add_argument("--extra", default="", help="extra bench.py arguments (quoted)")
+    ap.add_argument("--passes", default="", help="comma-separated indices into PASSES (default: all)")
     a = ap.parse_args()
+    chosen = [int(x) for x in a.passes.split(",")] if a.passes else list(range(len(PASSES)))
     bench_args = ["--precision", a.precision, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra",
                   "--blocks", a.blocks, *a.extra.split()]
     acc = collections.defaultdict(lambda: collections.defaultdict(list))
     for i, counters in enumerate(PASSES):
+        if i not in chosen:
+            continue
         d = os.path.join(ROOT, "gpurun_out", f"pmc_pass{i}_{a.precision}")
         shutil.rmtree(d, ignore_errors=True)
         try:
             rows = run_pass(counters, d, bench_args)
         except Exception as e:          # noqa: BLE001  (a counter the driver refuses: keep the other passes)
             print(f"pass {i} failed: {e}")
+            if getattr(e, "returncode", 1) in (124, 134, 137, 139, -6, -9, -11):     # the program died: start nothing more
+                raise
             continue
         for r in rows:
             kc = kernel_class(r.get("Kernel_Name", ""))

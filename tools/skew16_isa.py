@@ -5,7 +5,9 @@ Compiles esn_recur_skew16.hip to gfx950 assembly with the product flags of esn_o
 per selected instance: VGPRs, spilled VGPRs / SGPRs, scratch bytes, s_barrier / s_swappc / scratch-instruction counts
 of the whole kernel and of its step loops, and per Depth=2 loop (the GEMM trip loops; the short ones are the
 readfirstlane loops of a buffer descriptor) the counts of instructions, MFMAs, ds_read, buffer_load, s_waitcnt,
-scratch operations and the vmcnt values waited for.
+scratch operations and the vmcnt values waited for; and the structure counters of structure() below (readfirstlane-loop
+latches between the barriers of the step loops, element-wise LDS fill loops in front of them, scratch inside trip loops),
+which tests/test_skew16_structure.py holds to bounds.
 
     python tools/skew16_isa.py                      # headline instance: TraitsF16, counter noise, float64 I/O
     python tools/skew16_isa.py --all                # all twelve, one summary line each
@@ -113,14 +115,46 @@ def loops(body):
     return sorted(found, key=lambda t: t[1])
 
 
+def step_loops(body, lp):
+    return [(a, b) for d, a, b in lp if d == 1 and count(body[a:b + 1])["mfma"] > 100]
+
+
+def ops(body, a, b):
+    return [(i, body[i].split()[0]) for i in range(a, b + 1) if is_inst(body[i])]
+
+
+def structure(body, meta):
+    """What surrounds the recurrence slots, as numbers (tests/test_skew16_structure.py holds them to bounds):
+    execnz_in_steps   s_cbranch_execnz (the latch of a readfirstlane loop around a buffer operation whose descriptor the
+                      compiler holds in VGPRs) between the first and the last s_barrier of a step loop, summed over both
+    b16_loops_before  loops in front of the first step loop that hold a ds_write_b16 (element-wise LDS fills)
+    spilled_vgprs     of the whole kernel
+    trip_scratch      scratch instructions inside the GEMM trip loops (Depth=2 loops with MFMAs)"""
+    lp = loops(body)
+    steps = step_loops(body, lp)
+    execnz = 0
+    for a, b in steps:
+        bars = [i for i, op in ops(body, a, b) if op == "s_barrier"]
+        execnz += sum(op == "s_cbranch_execnz" for _, op in ops(body, bars[0], bars[-1])) if bars else 0
+    first = min((a for a, _ in steps), default=len(body))
+    b16 = sum(1 for _, a, b in lp if b < first and any(op.startswith("ds_write_b16") for _, op in ops(body, a, b)))
+    trip = sum(count(body[x:y + 1])["scratch"] for d, x, y in lp
+               if d == 2 and any(a <= x and y <= b for a, b in steps) and count(body[x:y + 1])["mfma"])
+    return dict(step_loops=len(steps), execnz_in_steps=execnz, b16_loops_before=b16,
+                spilled_vgprs=meta.get("vgpr_spill_count"), trip_scratch=trip)
+
+
 def report(name, body, meta, brief):
     whole = count(body)
     lp = loops(body)
-    steps = [(a, b) for d, a, b in lp if d == 1 and count(body[a:b + 1])["mfma"] > 100]
+    steps = step_loops(body, lp)
     head = (f"{name}\n  VGPRs {meta.get('vgpr_count')}  spilled VGPRs {meta.get('vgpr_spill_count')}  spilled SGPRs "
             f"{meta.get('sgpr_spill_count')}  scratch bytes {meta.get('private_segment_fixed_size')}  instructions "
             f"{whole['inst']}  s_barrier {whole['barrier']}  s_swappc {whole['swappc']}  scratch instructions {whole['scratch']}")
     print(head)
+    st = structure(body, meta)
+    print(f"  s_cbranch_execnz between the barriers of the step loops {st['execnz_in_steps']}  loops with ds_write_b16 in front "
+          f"of the step loops {st['b16_loops_before']}  scratch instructions inside the trip loops {st['trip_scratch']}")
     if brief:
         for a, b in steps:
             c = count(body[a:b + 1])
