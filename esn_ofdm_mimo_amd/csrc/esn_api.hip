@@ -711,6 +711,19 @@ int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const d
     return hip_fail(launch_taps_to_freq(tp, (hipStream_t)stream), "esn_taps_to_freq");
 }
 
+int esn_channel_metrics(int n_blocks, int n_sub, int n_t, int n_r, const double* H, const double* p_i, double no,
+                        double* S, double* cond, uint8_t* rank, double* cap, void* stream) {
+    if (!H || !p_i || !cond || !rank || !cap) return fail(-1, "esn_channel_metrics: null pointer");
+    if (n_blocks <= 0 || n_sub <= 0 || n_t <= 0 || n_r <= 0) return fail(-1, "esn_channel_metrics: invalid sizes");
+    if (!((n_t <= 4 && n_r <= 8) || (n_r <= 4 && n_t <= 8)))
+        return fail(-1, "esn_channel_metrics: unsupported n_t=%d n_r=%d (needs min <= 4 and max <= 8)", n_t, n_r);
+    if ((uintptr_t)H & 15) return fail(-1, "esn_channel_metrics: H must be 16-byte aligned");
+    ChanStatParams c;
+    c.n_blocks = n_blocks; c.n_sub = n_sub; c.n_t = n_t; c.n_r = n_r; c.H = H; c.p_i = p_i; c.no = no;
+    c.S = S; c.cond = cond; c.rank = rank; c.cap = cap;
+    return hip_fail(launch_channel_metrics(c, (hipStream_t)stream), "esn_channel_metrics");
+}
+
 int esn_ldpc_encode(int n_frames, int n_t, int k, int n, const uint8_t* P, const uint8_t* u, uint8_t* bits,
                     void* stream) {
     if (!P || !u || !bits) return fail(-1, "esn_ldpc_encode: null pointer");

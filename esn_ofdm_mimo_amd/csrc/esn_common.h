@@ -127,6 +127,16 @@ struct TapsFreqParams {
     const double* taps;          // complex [G][n_r][n_t][isi]
     double* H;                   // complex [G][N][n_r][n_t]
 };
+// channel rank / condition / capacity record (esn_chanstat.hip)
+struct ChanStatParams {
+    int n_blocks, n_sub, n_t, n_r;
+    const double* H;             // complex [G][N][n_r][n_t]
+    const double* p_i; double no;
+    double* S;                   // optional [G][N][min(n_t, n_r)], descending
+    double* cond;                // [G][N]
+    uint8_t* rank;               // [G][N]
+    double* cap;                 // [G]
+};
 struct MmseParams {
     int n_frames, frames_per_group, n_sub, log2n, cp, n_t, n_r, m;
     int zf;                      // 1: zero forcing, G = H^H H + 1e-12 I (driver :34-39); 0: MMSE, G = H^H H + No/Pi I

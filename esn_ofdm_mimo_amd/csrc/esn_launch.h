@@ -78,6 +78,8 @@ int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = f
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);
 int launch_mmse_detect(const MmseParams& mp, hipStream_t stream);
 int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream);
+// esn_chanstat.hip
+int launch_channel_metrics(const ChanStatParams& cp, hipStream_t stream);
 // esn_coded.hip
 int launch_ldpc_encode(const LdpcEncodeParams& ep, hipStream_t stream);
 int launch_qam_llr(const LlrParams& lp, hipStream_t stream);

@@ -233,6 +233,56 @@ class FrameSource:
                                                      _lib.stream_handle()), "esn_mmse_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
+    def channel_metrics(self, H, ebno_db, want_s=False):
+        """Per-subcarrier SVD metrics of H [G, N, n_r, n_t] (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; esn_channel_metrics):
+        cond [G, N] float64, rank [G, N] uint8, cap [G] float64 (the block's mean capacity per subcarrier), and with
+        want_s the singular values S [G, N, min(n_t, n_r)], descending.  Device tensors; nothing is read back."""
+        torch, p = self.torch, self.p
+        g, n = H.shape[0], H.shape[1]
+        if H.dtype != torch.complex128 or tuple(H.shape[2:]) != (p.n_r, p.n_t):
+            raise ValueError(f"H must be complex128 [G, N, {p.n_r}, {p.n_t}], not {H.dtype} {tuple(H.shape)}")
+        with torch.cuda.device(self.device):
+            p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=self.device)
+            cond = torch.empty((g, n), dtype=torch.float64, device=self.device)
+            rank = torch.empty((g, n), dtype=torch.uint8, device=self.device)
+            cap = torch.empty((g,), dtype=torch.float64, device=self.device)
+            S = torch.empty((g, n, min(p.n_t, p.n_r)), dtype=torch.float64, device=self.device) if want_s else None
+            check(self.lib.esn_channel_metrics(g, n, p.n_t, p.n_r, ptr(H.contiguous()), ptr(p_i), p.no, ptr(S),
+                                               ptr(cond), ptr(rank), ptr(cap), _lib.stream_handle()),
+                  "esn_channel_metrics")
+        return (cond, rank, cap, S) if want_s else (cond, rank, cap)
+
+
+def percentiles_linear(x, qs):
+    """np.percentile(x, qs) with its default linear rule, on the tensor's own device: sorted value at the virtual index
+    (n - 1) q / 100, interpolated between its two neighbours as NumPy does (a + (b - a) t below the midpoint,
+    b - (b - a)(1 - t) from it on).  One torch.sort, no torch.quantile (which refuses large inputs).  Returns a float64
+    tensor [len(qs)]."""
+    import torch
+    v = torch.sort(x.reshape(-1).to(torch.float64)).values
+    n = v.numel()
+    if n == 0:
+        raise ValueError("percentiles of an empty tensor")
+    q = torch.tensor([float(a) for a in qs], dtype=torch.float64) / 100.0
+    vi = q * (n - 1)                                  # host arithmetic, as NumPy's: the index must not depend on the device
+    lo = torch.floor(vi).clamp(0, n - 1)
+    t = (vi - lo).to(v.device)
+    lo = lo.to(torch.int64).to(v.device)
+    hi = (lo + 1).clamp(max=n - 1)
+    a, b = v[lo], v[hi]
+    d = b - a
+    return torch.where(t >= 0.5, b - d * (1 - t), a + d * t)
+
+
+def summarize_channel_metrics(cond, rank, cap, n_t, n_r):
+    """The per-Eb/No channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:515-521) from the outputs
+    of FrameSource.channel_metrics, reduced on the device; only these four floats are read back."""
+    import torch
+    pct = percentiles_linear(cond, (50, 90))
+    full = rank.reshape(-1).ge(min(n_t, n_r)).to(torch.float64).mean()
+    vals = torch.stack([cap.to(torch.float64).mean(), full, pct[0], pct[1]]).cpu().tolist()
+    return dict(zip(("capacity_bits_per_sc", "frac_rank_ge_full", "cond_p50", "cond_p90"), vals))
+
 
 def _view_real(z):
     """complex128 [..., T, n] -> float64 view [..., T, 2n] (Re/Im interleaved; driver:433-436); complex64 ->
@@ -488,7 +538,7 @@ def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=No
 
 
 def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None, decode_every=4, llr_scale=1.5,
-                       seed=0):
+                       seed=0, channel_metrics=False):
     """One Eb/No point of the block-fading drivers' comparison (OFDM_{SISO,SIMO_1-2,MIMO_2-2}_NBF_LDPC.py /
     Demo_MIMO_4x8_ChannelRank_..._fast.py :266-521), batched on the device: per coherence block one pilot and
     L - 1 LDPC-coded data symbols (the pilot symbol carries no data here, :387); detectors ESN (SNR-matched),
@@ -496,6 +546,8 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     MMSE and Perfect-ZF (:450-460); uncoded BER over every data symbol, coded BER on every `decode_every`-th
     symbol of the run (kk % 4 == 1, :202,389) with the drivers' uncalibrated LLRs: per-stream decision-directed
     sigma^2, x LLR_SCALE 1.5, clip +-20 (:478-485).  Returns the reference's holder names (BER_* / BERC_*).
+    channel_metrics=True adds the drivers' channel record of this Eb/No point (:369-385,515-521) as plain floats:
+    capacity_bits_per_sc, frac_rank_ge_full, cond_p50, cond_p90 (FrameSource.channel_metrics on H_true).
     Frames and the ESN legs stay float64 / complex128 whatever the sweeps' io says: the LS / MMSE / ZF legs read
     complex128."""
     torch, p, src = sweep.torch, sweep.p, sweep.src
@@ -549,4 +601,6 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
         e, nb = code.decode_count(llr.view(xs.shape[0], p.n_t, -1), a, b, u[sel], max(1, xs.shape[0] * p.n_t), p.m)
         out["BERC_" + name] = float(e.sum()) / max(float(nb.sum()), 1.0)
     out["decoded_symbols"] = int(sel.numel())
+    if channel_metrics:
+        out.update(summarize_channel_metrics(*src.channel_metrics(H_true, ebno_db), p.n_t, p.n_r))
     return out

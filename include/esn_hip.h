@@ -445,6 +445,21 @@ int esn_zf_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, i
                         long long* err_count, long long* bit_count, double* X_hat, void* stream);
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream);
 
+/* ---- Channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; the 4x8 ChannelRank driver is
+ * named after it), float64.  H complex [G][N][n_r][n_t] in the layout of the function above, 16-byte aligned; p_i [G]
+ * on the device as in the detectors; per subcarrier k the singular values s_1 >= ... of H_k by one-sided complex
+ * Jacobi (no H^H H: its eigenvalues square the condition number), then
+ *     rank [G][N]  = #{ s_i^2 >= max(1e-2 s_1^2, 10 No / Pi) }                                    (:379-380)
+ *     cond [G][N]  = s_1 / max(s_min, 1e-12)                                                      (:381)
+ *     cap  [G]     = mean over k of sum_i log2(1 + (Pi / No / n_t) s_i^2)                         (:372,382-383)
+ *     S    [G][N][min(n_t, n_r)]  optional (NULL), descending                                     (:376)
+ * min(n_t, n_r) <= 4 and max(n_t, n_r) <= 8, else -1 ("unsupported").  A zero matrix gives S = 0, rank 0, cond 0;
+ * non-finite entries give NaN for that subcarrier; the iteration count is bounded for every input.  A block's outputs
+ * are bitwise the same alone or inside any batch (cap is reduced in a fixed order).  The per-Eb/No aggregates of
+ * :515-521 (mean, fraction of full rank, percentiles) are the caller's. */
+int esn_channel_metrics(int n_blocks, int n_sub, int n_t, int n_r, const double* H, const double* p_i, double no,
+                        double* S, double* cond, uint8_t* rank, double* cap, void* stream);
+
 /* ---- Coded leg of the north-star driver, float64.  The reference delegates the code
  * to the un-vendored package pyldpc (requirements-sm2.txt:5); these entry points restate its
  * published algorithms at the reference's call sites (parity unpinned, see oracle/ldpc_oracle.py).
