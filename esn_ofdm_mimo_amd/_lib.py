@@ -60,6 +60,15 @@ SIGNATURES = {
                                                _dp, _dp, _dp, _ip, _vp, C.c_size_t, _vp]),
     "esn_readout_solve_chol_batch_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    _dp, _dp, _dp, _ip, _vp, C.c_size_t, _vp]),
+    # ridge read-out (extension): lambda [G][L] between t_shift and W_out; W_out [G][L][n_out][cols], status [G][L]
+    "esn_readout_solve_ridge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "esn_readout_solve_ridge_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                _dp, _dp, _dp, C.c_int, _dp, _ip, _vp, _vp]),
+    "esn_readout_chol_ridge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "esn_readout_solve_chol_ridge_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     _dp, _dp, _dp, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
+    "esn_readout_solve_chol_ridge_batch_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         _dp, _dp, _dp, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
     "esn_gen_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp,
                                C.c_uint64, C.c_uint64, _dp, _vp]),
     "esn_gen_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -169,8 +169,32 @@ class ReservoirBank:
         up to 512 out of a workspace."""
         return min(rows, cols) <= 512 and self.n_outputs <= 8
 
-    def solve(self, E, D, transient, method="qr"):
+    def _ridge_arg(self, ridge, g):
+        """ridge (float, [G] or [G, L] array / tensor) -> (device float64 [G, L], whether the caller gave no L axis)."""
+        torch = self.torch
+        flat = (ridge.ndim if isinstance(ridge, torch.Tensor) else np.ndim(ridge)) < 2
+        if isinstance(ridge, torch.Tensor):
+            r = ridge.to(device=self.device, dtype=torch.float64)
+        elif np.ndim(ridge) == 0:
+            r = torch.full((g, 1), float(ridge), dtype=torch.float64, device=self.device)   # (no host copy)
+        else:
+            r = torch.as_tensor(np.array(ridge, dtype=np.float64), device=self.device)
+        if r.ndim == 0:
+            r = r.reshape(1, 1).expand(g, 1)
+        elif r.ndim == 1:
+            r = r[:, None]
+        if r.ndim != 2 or r.shape[0] != g or r.shape[1] < 1:
+            raise ValueError(f"ridge must be a scalar, [G] or [G, L] with G = {g}, not {tuple(r.shape)}")
+        return r.contiguous(), flat
+
+    def solve(self, E, D, transient, method="qr", ridge=None):
         """W_out[g] = (pinv(E[g][transient:]) @ scale(D[g][transient:])).T ; returns (W_out, status).
+
+        ridge (extension, the reference has none; None = the pinv solve above, untouched): lambda >= 0 of
+        W_out = argmin |E W^T - D_s|^2 + lambda |W|^2, absolute, in the units of the Gram matrix of the scaled states.
+        A float or a [G] array / tensor gives W_out [G, n_out, cols] and status [G]; a [G, L] one solves L lambdas
+        per group in one launch and gives W_out [G, L, n_out, cols] and status [G, L].  lambda = 0 is the pinv solve
+        bit for bit; a negative or non-finite lambda gives status 2 and a zero W_out for that entry.
 
         method "qr": float64 Householder QR (accurate to cond(E) eps; the drop-in's choice).
         method "chol": float64 normal equations on the float64 matrix pipe (min(rows, cols) <= 512, n_out <= 8;
@@ -187,9 +211,35 @@ class ReservoirBank:
             method = "chol" if fits else "qr"
         if e32 and method != "chol":
             E = E.double()                                                  # the QR kernel works in place on float64
+        if method == "chol" and not fits:
+            raise ValueError("method='chol' needs min(rows, cols) <= 512 and n_outputs <= 8")
+        if ridge is not None:
+            lam, flat = self._ridge_arg(ridge, g)
+            nl = lam.shape[1]
+            with torch.cuda.device(self.device):
+                W_out = torch.empty((g, nl, self.n_outputs, cols), dtype=torch.float64, device=self.device)
+                status = torch.empty((g, nl), dtype=torch.int32, device=self.device)
+                if method == "chol":
+                    fn, name = (self.lib.esn_readout_solve_chol_ridge_batch_f32, "esn_readout_solve_chol_ridge_batch_f32") \
+                        if e32 else (self.lib.esn_readout_solve_chol_ridge_batch, "esn_readout_solve_chol_ridge_batch")
+                    wbytes = self.lib.esn_readout_chol_ridge_workspace_bytes(g, nl, rows, cols)
+                    ws = self._scratch("_chol_ws", wbytes)
+                    check(fn(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale),
+                             ptr(self.t_shift), ptr(lam), nl, ptr(W_out), ptr(status), ptr(ws), wbytes,
+                             _lib.stream_handle()), name)
+                else:
+                    wbytes = self.lib.esn_readout_solve_ridge_workspace_bytes(g, nl, rows, cols, self.n_outputs)
+                    work = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+                    check(self.lib.esn_readout_solve_ridge_batch(
+                        ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale),
+                        ptr(self.t_shift), ptr(lam), nl, ptr(W_out), ptr(status), ptr(work), _lib.stream_handle()),
+                        "esn_readout_solve_ridge_batch")
+            if flat:
+                W_out, status = W_out[:, 0], status[:, 0]       # (L = 1: contiguous views)
+            if method == "chol":
+                self.last_solve_status = status
+            return W_out, status
         if method == "chol":
-            if not fits:
-                raise ValueError("method='chol' needs min(rows, cols) <= 512 and n_outputs <= 8")
             with torch.cuda.device(self.device):
                 W_out = torch.empty((g, self.n_outputs, cols), dtype=torch.float64, device=self.device)
                 status = torch.empty(g, dtype=torch.int32, device=self.device)
@@ -212,12 +262,34 @@ class ReservoirBank:
                   "esn_readout_solve_batch")
         return W_out, status
 
-    def resolve_failed(self, E, D, transient, W_out, status):
-        """Re-solve with QR (on the GPU) the groups a "chol" solve flagged; returns their count."""
+    def resolve_failed(self, E, D, transient, W_out, status, ridge=None):
+        """Re-solve with QR (on the GPU) the groups a "chol" solve flagged; returns their count.  `ridge` as given to
+        that solve: each flagged entry is re-solved with its own lambda, so a repaired group is a ridge solution too."""
         torch = self.torch
-        bad = torch.nonzero(status).flatten()
+        if ridge is not None and status.ndim == 2:
+            idx = torch.nonzero(status)
+            bad, bad_l = idx[:, 0], idx[:, 1]
+        else:
+            bad, bad_l = torch.nonzero(status).flatten(), None
         nbad = int(bad.numel())
-        if nbad:
+        if nbad and ridge is not None:
+            lam, _ = self._ridge_arg(ridge, status.shape[0])
+            lam = lam[bad, bad_l if bad_l is not None else 0].contiguous()
+            keep = (self.t_scale, self.t_shift)
+            self.t_scale = None if keep[0] is None else keep[0][bad].contiguous()
+            self.t_shift = None if keep[1] is None else keep[1][bad].contiguous()
+            try:
+                w2, st2 = self.solve(E[bad].contiguous(), _as_dev(D, torch, self.device)[bad].contiguous(),
+                                     transient, method="qr", ridge=lam)
+            finally:
+                self.t_scale, self.t_shift = keep
+            if bad_l is None:
+                W_out[bad] = w2
+                status[bad] = st2
+            else:
+                W_out[bad, bad_l] = w2
+                status[bad, bad_l] = st2
+        elif nbad:
             keep = (self.t_scale, self.t_shift)
             self.t_scale = None if keep[0] is None else keep[0][bad].contiguous()
             self.t_shift = None if keep[1] is None else keep[1][bad].contiguous()
@@ -231,9 +303,13 @@ class ReservoirBank:
         return nbad
 
     def fit(self, U, D, transient=0, precision="f64", noise_mode="counter", noise_u=None, seed=0,
-            method="qr", e_dtype="f64", group_offset=0):
+            method="qr", e_dtype="f64", group_offset=0, ridge=None):
+        """harvest + solve + set_readout.  ridge: None (pinv), a float or one lambda per group [G] -- see solve."""
+        if ridge is not None and np.ndim(ridge) > 1:
+            raise ValueError("fit takes one lambda per group (a scalar or [G]); solve() takes [G, L]")
         E = self.harvest(U, D, precision, noise_mode, noise_u, seed, e_dtype=e_dtype, group_offset=group_offset)
-        W_out, status = self.solve(E, D, transient, method=method)
+        W_out, status = self.solve(E, D, transient, method=method, ridge=ridge)
+        self.fit_ridge = ridge
         self.set_readout(W_out)
         ht = getattr(self, "harvest_timeout", None)
         if ht is not None:

@@ -533,6 +533,68 @@ int esn_readout_solve_chol_batch_f32(const float* E, const double* D, int n_grou
                        t_shift, W_out, status, workspace, workspace_bytes, stream);
 }
 
+// ---- ridge read-out (an extension: the reference fits with pinv only) --------------------------------------------
+size_t esn_readout_solve_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols, int n_out) {
+    if (n_groups <= 0 || n_ridge <= 0 || rows <= 0 || cols <= 0 || n_out <= 0) return 0;
+    return sizeof(double) * solve_ridge_work_doubles(rows, cols, n_out) * (size_t)n_groups * (size_t)n_ridge;
+}
+
+int esn_readout_solve_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
+                                  int n_out, const double* t_scale, const double* t_shift, const double* ridge,
+                                  int n_ridge, double* W_out, int* status, void* workspace, void* stream) {
+    if (!E || !D || !ridge || !W_out || !status || !workspace)
+        return fail(-1, "esn_readout_solve_ridge_batch: null pointer");
+    if (n_groups <= 0 || n_ridge <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
+        return fail(-1, "esn_readout_solve_ridge_batch: invalid sizes");
+    return hip_fail(launch_readout_solve(E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out, status,
+                                         workspace, (hipStream_t)stream, ridge, n_ridge),
+                    "esn_readout_solve_ridge_batch");
+}
+
+size_t esn_readout_chol_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols) {
+    if (n_ridge <= 0) return 0;
+    return esn_readout_chol_workspace_bytes(n_groups, rows, cols) * (size_t)n_ridge;
+}
+
+static int chol_ridge_common(const char* who, const double* E, const float* E32, const double* D, int n_groups, int T,
+                             int transient, int cols, int n_out, const double* t_scale, const double* t_shift,
+                             const double* ridge, int n_ridge, double* W_out, int* status, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    if ((!E && !E32) || !D || !ridge || !W_out || !status) return fail(-1, "%s: null pointer", who);
+    if (n_groups <= 0 || n_ridge <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
+        return fail(-1, "%s: invalid sizes", who);
+    const int rows = T - transient, n = rows < cols ? rows : cols;
+    if (n > 512 || n_out > 8) return fail(-2, "%s: no kernel instance for this shape", who);
+    if (n > 128) {            // one Gram matrix / factor per (group, lambda) in the caller's workspace
+        const size_t need = esn_readout_chol_ridge_workspace_bytes(n_groups, n_ridge, rows, cols);
+        if (!workspace || workspace_bytes < need)
+            return fail(-1, "%s: workspace holds %zu bytes, esn_readout_chol_ridge_workspace_bytes says %zu", who,
+                        workspace ? workspace_bytes : (size_t)0, need);
+        if (((uintptr_t)(E ? (const void*)E : (const void*)E32) & 15) || ((uintptr_t)workspace & 15))
+            return fail(-1, "%s: E and the workspace must be 16-byte aligned", who);
+        return hip_fail(launch_readout_chol_big(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
+                                                status, workspace, (hipStream_t)stream, ridge, n_ridge), who);
+    }
+    return hip_fail(launch_readout_chol(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
+                                        status, (hipStream_t)stream, ridge, n_ridge), who);
+}
+
+int esn_readout_solve_chol_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
+                                       int n_out, const double* t_scale, const double* t_shift, const double* ridge,
+                                       int n_ridge, double* W_out, int* status, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return chol_ridge_common("esn_readout_solve_chol_ridge_batch", E, nullptr, D, n_groups, T, transient, cols, n_out,
+                             t_scale, t_shift, ridge, n_ridge, W_out, status, workspace, workspace_bytes, stream);
+}
+
+int esn_readout_solve_chol_ridge_batch_f32(const float* E, const double* D, int n_groups, int T, int transient,
+                                           int cols, int n_out, const double* t_scale, const double* t_shift,
+                                           const double* ridge, int n_ridge, double* W_out, int* status,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    return chol_ridge_common("esn_readout_solve_chol_ridge_batch_f32", nullptr, E, D, n_groups, T, transient, cols,
+                             n_out, t_scale, t_shift, ridge, n_ridge, W_out, status, workspace, workspace_bytes, stream);
+}
+
 static int detect_common(const char* who, bool io32, const void* Y, int n_frames, int frames_per_group, int n_sub,
                          int n_t, int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
                          long long* bit_count, double* X_hat, void* stream) {

@@ -60,17 +60,23 @@ int launch_pack_weights(int precision, const esn_shape_t* sh, const Geometry& g,
 int launch_pack_readout(int precision, const esn_shape_t* sh, const Geometry& g, int n_groups,
                         const double* Wout, void* packed, hipStream_t stream);
 // esn_solve.hip
+// ridge != nullptr (device, [n_groups][n_ridge]): the ridge instances, one workgroup per (group, lambda);
+// W_out, status and the workspace then hold n_groups * n_ridge entries
 size_t solve_work_doubles(int rows, int cols, int n_out);
+size_t solve_ridge_work_doubles(int rows, int cols, int n_out);
 int launch_readout_solve(const double* E, const double* D, int n_groups, int T, int transient,
                          int cols, int n_out, const double* t_scale, const double* t_shift,
-                         double* W_out, int* status, void* workspace, hipStream_t stream);
+                         double* W_out, int* status, void* workspace, hipStream_t stream,
+                         const double* ridge = nullptr, int n_ridge = 1);
 int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
                         int cols, int n_out, const double* t_scale, const double* t_shift,
-                        double* W_out, int* status, hipStream_t stream);
+                        double* W_out, int* status, hipStream_t stream,
+                        const double* ridge = nullptr, int n_ridge = 1);
 size_t chol_big_work_doubles(int n);
 int launch_readout_chol_big(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
                             int cols, int n_out, const double* t_scale, const double* t_shift,
-                            double* W_out, int* status, void* workspace, hipStream_t stream);
+                            double* W_out, int* status, void* workspace, hipStream_t stream,
+                            const double* ridge = nullptr, int n_ridge = 1);
 // esn_gen.hip
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);

@@ -7,6 +7,13 @@
 //
 // The working matrix is column-major in the caller's workspace (L2 resident);
 // reflector j is applied to the trailing columns one wave per column.
+//
+// Ridge (an extension, the reference has none): W_out = argmin |E W^T - D_s|^2 + lambda |W|^2, lambda >= 0 absolute.
+// The <true> instances of the three kernels run one workgroup per (group, lambda): workgroup `slot` reads E of group
+// slot / n_ridge and lambda = ridge[slot], and writes W_out[slot], status[slot].  The QR kernel solves the augmented
+// problem (tall: [A ; sqrt(lambda) I] w = [B ; 0]; wide: minimum norm of [A  sqrt(lambda) I] [w ; z] = B, first
+// `cols` entries kept); the Cholesky kernels add lambda to the live Gram diagonal.  lambda = 0 takes the pinv path
+// instruction for instruction; a negative or non-finite lambda gives status 2 and a zero W_out.
 #include <stdlib.h>
 #include <type_traits>
 #include "esn_common.h"
@@ -27,7 +34,18 @@ struct SolveParams {
     int vec;       // LDS Cholesky kernel: E rows start 16-byte aligned and hold whole 16-byte runs (vector loads)
     int dma;       // LDS Cholesky kernel, wide float32 E: Gram and W_out passes fed by LDS-DMA rings (knob chol_dma)
     unsigned long long* stamps;   // diagnostic build (-DESN_STAMPS) only: [wave][8] cycle sums of workgroup 0
+    const double* ridge; int n_ridge;   // ridge instances only: lambda [n_groups][n_ridge]
 };
+
+// ridge instances: workgroup `slot` with a negative or non-finite lambda writes status 2 and a zero W_out
+__device__ __forceinline__ bool ridge_rejects(const SolveParams& sp, int slot) {
+    const double lam = sp.ridge[slot];
+    if (lam >= 0.0 && lam <= 1.7976931348623157e308) return false;
+    double* wo = sp.W_out + (size_t)slot * sp.n_out * sp.cols;
+    for (int i = threadIdx.x; i < sp.n_out * sp.cols; i += blockDim.x) wo[i] = 0.0;
+    if (threadIdx.x == 0) sp.status[slot] = 2;
+    return true;
+}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -35,15 +53,25 @@ __device__ __forceinline__ double wave_sum(double v) {
     return __shfl(v, 0);
 }
 
+template <bool RG>
 __global__ __launch_bounds__(1024) void readout_qr_kernel(SolveParams sp) {
     __shared__ double red[16];
     __shared__ double bc[4];
-    const int g = blockIdx.x;
+    const int slot = blockIdx.x;                            // RG: one workgroup per (group, lambda)
+    const int g = RG ? slot / sp.n_ridge : slot;
     const int tid = threadIdx.x, nth = blockDim.x;
     const int lane = tid & 63, wv = tid >> 6, nwv = nth >> 6;
-    const int m = sp.m, n = sp.n, nrhs = sp.n_out;
+    const int n = sp.n, nrhs = sp.n_out;
     const int rows = sp.T - sp.transient, cols = sp.cols;
-    double* M = sp.work + (size_t)g * sp.work_stride;       // [n + (wide?0:nrhs)][m] column-major
+    int m = sp.m;
+    double sq = 0.0;                                        // sqrt(lambda) > 0: the augmented problem, m grows by n
+    if constexpr (RG) {
+        if (ridge_rejects(sp, slot)) return;
+        const double lam = sp.ridge[slot];
+        if (lam > 0.0) { sq = sqrt(lam); m = sp.m + n; }
+    }
+    const bool aug = RG && sq > 0.0;
+    double* M = sp.work + (size_t)slot * sp.work_stride;    // [n + (wide?0:nrhs)][m] column-major
     const int ncol_tot = sp.wide ? n : n + nrhs;
     double* R = M + (size_t)ncol_tot * m;                    // rhs / solution block [nrhs][m]
     double* rdiag = R + (size_t)nrhs * m;                    // [n]
@@ -53,8 +81,15 @@ __global__ __launch_bounds__(1024) void readout_qr_kernel(SolveParams sp) {
 
     // ---- load -----------------------------------------------------------------
     if (sp.wide) {
-        // M = A^T: column j = row j of A (contiguous in E)
-        for (size_t i = tid; i < (size_t)n * m; i += nth) M[i] = Eg[i];
+        // M = A^T: column j = row j of A (contiguous in E); augmented: [A  sq I]^T
+        if (aug) {
+            for (size_t i = tid; i < (size_t)n * m; i += nth) {
+                const int c = (int)(i / m), rr = (int)(i % m);
+                M[i] = rr < cols ? Eg[(size_t)c * cols + rr] : (rr - cols == c ? sq : 0.0);
+            }
+        } else {
+            for (size_t i = tid; i < (size_t)n * m; i += nth) M[i] = Eg[i];
+        }
         for (int i = tid; i < nrhs * m; i += nth) {
             int o = i / m, j = i % m;
             double v = 0.0;
@@ -66,16 +101,18 @@ __global__ __launch_bounds__(1024) void readout_qr_kernel(SolveParams sp) {
             R[i] = v;
         }
     } else {
-        // M = [A | B]: column c of A is strided in E
+        // M = [A | B]: column c of A is strided in E; augmented: [A ; sq I | B ; 0]
         for (size_t i = tid; i < (size_t)n * m; i += nth) {
             int c = (int)(i / m), rr = (int)(i % m);
-            M[i] = Eg[(size_t)rr * cols + c];
+            if (aug && rr >= rows) M[i] = (rr - rows == c) ? sq : 0.0;
+            else M[i] = Eg[(size_t)rr * cols + c];
         }
         for (int i = tid; i < nrhs * m; i += nth) {
             int o = i / m, rr = i % m;
             double sc = sp.t_scale ? sp.t_scale[(size_t)g * nrhs + o] : 1.0;
             double sh = sp.t_shift ? sp.t_shift[(size_t)g * nrhs + o] : 0.0;
-            M[(size_t)(n + o) * m + rr] = Dg[(size_t)rr * nrhs + o] * sc + sh;
+            if (aug && rr >= rows) M[(size_t)(n + o) * m + rr] = 0.0;
+            else M[(size_t)(n + o) * m + rr] = Dg[(size_t)rr * nrhs + o] * sc + sh;
         }
     }
     __syncthreads();
@@ -129,7 +166,7 @@ __global__ __launch_bounds__(1024) void readout_qr_kernel(SolveParams sp) {
         bc[1] = r * 1e-13;
         int bad = 0;
         for (int j = 0; j < n; ++j) bad |= (fabs(rdiag[j]) <= r * 1e-13);
-        sp.status[g] = bad ? 1 : 0;
+        sp.status[slot] = bad ? 1 : 0;
     }
     __syncthreads();
     const double tol = bc[1];
@@ -162,8 +199,8 @@ __global__ __launch_bounds__(1024) void readout_qr_kernel(SolveParams sp) {
                 __builtin_amdgcn_s_waitcnt(0);
                 __builtin_amdgcn_wave_barrier();
             }
-            double* wo = sp.W_out + ((size_t)g * nrhs + o) * cols;
-            for (int i = lane; i < m; i += 64) wo[i] = z[i];
+            double* wo = sp.W_out + ((size_t)slot * nrhs + o) * cols;
+            for (int i = lane; i < cols; i += 64) wo[i] = z[i];
         }
     } else {
         // back substitution R x = (Q^T b)[0:n], one wave per right-hand side
@@ -180,7 +217,7 @@ __global__ __launch_bounds__(1024) void readout_qr_kernel(SolveParams sp) {
                 __builtin_amdgcn_s_waitcnt(0);
                 __builtin_amdgcn_wave_barrier();
             }
-            double* wo = sp.W_out + ((size_t)g * nrhs + o) * cols;
+            double* wo = sp.W_out + ((size_t)slot * nrhs + o) * cols;
             for (int i = lane; i < n; i += 64) wo[i] = c[i];
         }
     }
@@ -194,20 +231,30 @@ size_t solve_work_doubles(int rows, int cols, int n_out) {
     return (d + 1) & ~(size_t)1;
 }
 
+size_t solve_ridge_work_doubles(int rows, int cols, int n_out) {
+    const bool wide = rows < cols;
+    const size_t m = (size_t)rows + cols, n = wide ? rows : cols;      // the augmented matrix has rows + cols rows
+    size_t d = (n + (wide ? 0 : n_out)) * m + (size_t)n_out * m + 2 * n;
+    return (d + 1) & ~(size_t)1;
+}
+
 int launch_readout_solve(const double* E, const double* D, int n_groups, int T, int transient,
                          int cols, int n_out, const double* t_scale, const double* t_shift,
-                         double* W_out, int* status, void* workspace, hipStream_t stream) {
+                         double* W_out, int* status, void* workspace, hipStream_t stream,
+                         const double* ridge, int n_ridge) {
     SolveParams sp;
     const int rows = T - transient;
+    sp.ridge = ridge; sp.n_ridge = n_ridge;
     sp.E = E; sp.E32 = nullptr; sp.D = D; sp.n_groups = n_groups; sp.T = T; sp.transient = transient;
     sp.cols = cols; sp.n_out = n_out; sp.t_scale = t_scale; sp.t_shift = t_shift;
     sp.W_out = W_out; sp.status = status;
     sp.work = reinterpret_cast<double*>(workspace);
-    sp.work_stride = solve_work_doubles(rows, cols, n_out);
+    sp.work_stride = ridge ? solve_ridge_work_doubles(rows, cols, n_out) : solve_work_doubles(rows, cols, n_out);
     sp.wide = rows < cols;
     sp.m = sp.wide ? cols : rows;
     sp.n = sp.wide ? rows : cols;
-    hipLaunchKernelGGL(readout_qr_kernel, dim3(n_groups), dim3(1024), 0, stream, sp);
+    if (ridge) hipLaunchKernelGGL(readout_qr_kernel<true>, dim3(n_groups * n_ridge), dim3(1024), 0, stream, sp);
+    else hipLaunchKernelGGL(readout_qr_kernel<false>, dim3(n_groups), dim3(1024), 0, stream, sp);
     return (int)hipGetLastError();
 }
 
@@ -360,13 +407,17 @@ __device__ __forceinline__ int ch_factor_diag(double* D, int j0, int n, double p
     return rejected ? 1 : 0;
 }
 
-template <typename TE, bool wide>
+template <typename TE, bool wide, bool RG>
 __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void readout_chol_kernel(SolveParams sp) {
     extern __shared__ __attribute__((aligned(16))) char chol_smem[];
     double* Gs = reinterpret_cast<double*>(chol_smem);             // 36 packed tiles            (phase 2-4)
     double* As = Gs;                                                // [2][CH_KC][CH_AS_LD] staging (phase 1)
     double* Bs = Gs + CH_TILES * 256;                               // [CH_NP][CH_RHS] rhs / solution
-    const int g = blockIdx.x, tid = threadIdx.x;
+    const int slot = blockIdx.x, tid = threadIdx.x;                 // RG: one workgroup per (group, lambda)
+    const int g = RG ? slot / sp.n_ridge : slot;
+    if constexpr (RG) {
+        if (ridge_rejects(sp, slot)) return;
+    }
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
     const int rows = sp.T - sp.transient, cols = sp.cols, nrhs = sp.n_out;
@@ -600,6 +651,13 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         }
     }
     __syncthreads();
+    if constexpr (RG) {
+        // ridge: lambda on the live diagonal only (the padding rows of a ragged last tile stay as they are), before
+        // dmax / piv_tol are taken; + 0.0 leaves a non-negative diagonal bitwise as it is
+        const double lam = sp.ridge[slot];
+        for (int i = tid; i < n; i += CH_NT) Gs[ch_tile(i >> 4, i >> 4) + ch_el(i & 15, i & 15)] += lam;
+        __syncthreads();
+    }
 
     // ---- phase 3: blocked right-looking Cholesky, 16-column blocks ----------------------------
     // per block kb: (b) panel L21 = A21 L11^-T, one tile per wave; (c) trailing update A22 -= L21 L21^T of
@@ -877,7 +935,7 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
                         for (int c = 0; c < CPT; ++c) {
                             double v = w[c][o];
                             for (int q = 1; q < parts; ++q) v += part[((q - 1) * CH_RHS + o) * cols + CPT * un + c];
-                            sp.W_out[((size_t)g * nrhs + o) * cols + CPT * un + c] = v;
+                            sp.W_out[((size_t)slot * nrhs + o) * cols + CPT * un + c] = v;
                         }
                     }
             }
@@ -895,20 +953,20 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
                 }
 #pragma unroll
                 for (int o = 0; o < CH_RHS; ++o)
-                    if (o < nrhs) sp.W_out[((size_t)g * nrhs + o) * cols + c] = w[o];
+                    if (o < nrhs) sp.W_out[((size_t)slot * nrhs + o) * cols + c] = w[o];
             }
         }
     } else {
         for (int e = tid; e < nrhs * cols; e += CH_NT) {
             const int o = e / cols, c = e % cols;
-            sp.W_out[((size_t)g * nrhs + o) * cols + c] = Bs[c * CH_RHS + o];
+            sp.W_out[((size_t)slot * nrhs + o) * cols + c] = Bs[c * CH_RHS + o];
         }
     }
-    if (tid == 0) sp.status[g] = bad;
+    if (tid == 0) sp.status[slot] = bad;
 #ifdef ESN_STAMPS
     ESN_STAMP(st_k4);
     // row wv: Gram wait | barrier | operand read | MFMA issue, W_out wait | barrier | rows; row 8 + wv: phase totals
-    if (sp.stamps && g == 0 && lane == 0) {
+    if (sp.stamps && slot == 0 && lane == 0) {
         for (int i = 0; i < 7; ++i) sp.stamps[wv * 8 + i] = st_acc[i];
         sp.stamps[(8 + wv) * 8 + 0] = st_k1 - st_k0;
         sp.stamps[(8 + wv) * 8 + 1] = st_k2 - st_k1;
@@ -921,9 +979,10 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
 
 int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
                         int cols, int n_out, const double* t_scale, const double* t_shift,
-                        double* W_out, int* status, hipStream_t stream) {
+                        double* W_out, int* status, hipStream_t stream, const double* ridge, int n_ridge) {
     SolveParams sp;
     sp.E32 = E32;
+    sp.ridge = ridge; sp.n_ridge = n_ridge;
     const int rows = T - transient;
     const int n = rows < cols ? rows : cols;
     if (n > CH_NP || n_out > CH_RHS) return -1;
@@ -942,12 +1001,17 @@ int launch_readout_chol(const double* E, const float* E32, const double* D, int 
     // 16-byte loads of 4 consecutive elements: every row of every group starts 16-byte aligned
     const uintptr_t base = E32 ? (uintptr_t)E32 : (uintptr_t)E;
     sp.vec = (base % 16 == 0) && (cols % (E32 ? 4 : 2) == 0);
-    void (*fn)(SolveParams) = E32 ? (sp.wide ? readout_chol_kernel<float, true> : readout_chol_kernel<float, false>)
-                                  : (sp.wide ? readout_chol_kernel<double, true> : readout_chol_kernel<double, false>);
+    void (*fn)(SolveParams);
+    if (ridge)
+        fn = E32 ? (sp.wide ? readout_chol_kernel<float, true, true> : readout_chol_kernel<float, false, true>)
+                 : (sp.wide ? readout_chol_kernel<double, true, true> : readout_chol_kernel<double, false, true>);
+    else
+        fn = E32 ? (sp.wide ? readout_chol_kernel<float, true, false> : readout_chol_kernel<float, false, false>)
+                 : (sp.wide ? readout_chol_kernel<double, true, false> : readout_chol_kernel<double, false, false>);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)CH_LDS);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fn, dim3(n_groups), dim3(CH_NT), CH_LDS, stream, sp);
+    hipLaunchKernelGGL(fn, dim3(ridge ? n_groups * n_ridge : n_groups), dim3(CH_NT), CH_LDS, stream, sp);
     return (int)hipGetLastError();
 }
 
@@ -985,6 +1049,7 @@ size_t chol_big_work_doubles(int n) {
     return np * np;
 }
 
+template <bool RG>
 __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp) {
     extern __shared__ __attribute__((aligned(16))) char cb_smem[];
     typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -992,7 +1057,11 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
     __shared__ double sh_invd[CB_NMAX];
     __shared__ double sh_linv[16][17];
     __shared__ double sh_red[CB_NW];
-    const int g = blockIdx.x, tid = threadIdx.x;
+    const int slot = blockIdx.x, tid = threadIdx.x;                     // RG: one workgroup per (group, lambda)
+    const int g = RG ? slot / sp.n_ridge : slot;
+    if constexpr (RG) {
+        if (ridge_rejects(sp, slot)) return;
+    }
     const int lane = tid & 63, wv = tid >> 6;
     const int wvu = __builtin_amdgcn_readfirstlane(wv);
     const int rows = sp.T - sp.transient, cols = sp.cols, nrhs = sp.n_out;
@@ -1001,7 +1070,7 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
     const int m = wide ? cols : rows;      // contraction length
     const int np = round_up(n, 16), ntile = np / 16;
     const int ld = np;
-    double* Gw = sp.work + (size_t)g * sp.work_stride;                  // [np][np] column-major, lower part
+    double* Gw = sp.work + (size_t)slot * sp.work_stride;                  // [np][np] column-major, lower part
     const size_t a_off = ((size_t)g * sp.T + sp.transient) * cols;
     const double* A = sp.E ? sp.E + a_off : nullptr;
     const float* A32 = sp.E32 ? sp.E32 + a_off : nullptr;
@@ -1114,6 +1183,11 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
                 }
                 Bs[e] = acc_b;
             }
+        }
+        if constexpr (RG) {
+            // ridge: lambda on the live diagonal only (rows >= n of the last tile are padding), before dmax / piv_tol
+            const double lam = sp.ridge[slot];
+            for (int i = tid; i < n; i += CB_NT) Gw[(size_t)i * ld + i] += lam;
         }
     }
     __threadfence_block();
@@ -1324,7 +1398,7 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
                 const int o = e / cols, c = e - o * cols;
                 double v = part[o * cols + c];
                 for (int q = 1; q < parts; ++q) v += part[(q * 8 + o) * cols + c];
-                sp.W_out[((size_t)g * nrhs + o) * cols + c] = v;
+                sp.W_out[((size_t)slot * nrhs + o) * cols + c] = v;
             }
         } else {
             for (int c = tid; c < cols; c += CB_NT) {
@@ -1339,16 +1413,16 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
                 }
 #pragma unroll
                 for (int o = 0; o < 8; ++o)
-                    if (o < nrhs) sp.W_out[((size_t)g * nrhs + o) * cols + c] = w[o];
+                    if (o < nrhs) sp.W_out[((size_t)slot * nrhs + o) * cols + c] = w[o];
             }
         }
     } else {
         for (int e = tid; e < nrhs * cols; e += CB_NT) {
             const int o = e / cols, c = e % cols;
-            sp.W_out[((size_t)g * nrhs + o) * cols + c] = Bs[o * np + c];
+            sp.W_out[((size_t)slot * nrhs + o) * cols + c] = Bs[o * np + c];
         }
     }
-    if (tid == 0) sp.status[g] = sh_bad;
+    if (tid == 0) sp.status[slot] = sh_bad;
 }
 
 static int chol_big_parts(int cols, bool f32) {          // 0 = the partial-sums pass does not apply
@@ -1370,8 +1444,10 @@ static size_t chol_big_lds_bytes(int cols, bool f32) {
 
 int launch_readout_chol_big(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
                             int cols, int n_out, const double* t_scale, const double* t_shift,
-                            double* W_out, int* status, void* workspace, hipStream_t stream) {
+                            double* W_out, int* status, void* workspace, hipStream_t stream,
+                            const double* ridge, int n_ridge) {
     SolveParams sp;
+    sp.ridge = ridge; sp.n_ridge = n_ridge;
     const int rows = T - transient;
     const int n = rows < cols ? rows : cols;
     if (n > CB_NMAX || n_out > 8) return -1;
@@ -1382,10 +1458,11 @@ int launch_readout_chol_big(const double* E, const float* E32, const double* D, 
     sp.W_out = W_out; sp.status = status;
     sp.work = reinterpret_cast<double*>(workspace); sp.work_stride = chol_big_work_doubles(n);
     sp.wide = rows < cols; sp.m = sp.wide ? cols : rows; sp.n = n; sp.skip = 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(readout_chol_big_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    void (*fn)(SolveParams) = ridge ? readout_chol_big_kernel<true> : readout_chol_big_kernel<false>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(readout_chol_big_kernel, dim3(n_groups), dim3(CB_NT), lds, stream, sp);
+    hipLaunchKernelGGL(fn, dim3(ridge ? n_groups * n_ridge : n_groups), dim3(CB_NT), lds, stream, sp);
     return (int)hipGetLastError();
 }
 

@@ -79,11 +79,13 @@ def complex_frames_as_esn_io(z):
     return z.view(np.float64).reshape(*z.shape[:-1], 2 * z.shape[-1])
 
 
-def trainMIMOESN_batch(bank, y_CP, x_CP, d, CyclicPrefixLen, precision="f64", noise_mode="counter", seed=0):
+def trainMIMOESN_batch(bank, y_CP, x_CP, d, CyclicPrefixLen, precision="f64", noise_mode="counter", seed=0,
+                       ridge=None):
     """G pilots at once: y_CP [G,T,N_r], x_CP [G,T,N_t] complex -> bank.W_out (one harvest + one
     solve launch).  Returns (E, nForget).  Teacher rows are delayed by d; the d trailing input rows
     are the zeros the kernel synthesises beyond T_in -- here materialised because harvest takes
-    equal-length U and D."""
+    equal-length U and D.  ridge: None = the reference's pinv fit, else lambda (scalar or [G]) of
+    ReservoirBank.solve."""
     y = complex_frames_as_esn_io(y_CP)
     x = complex_frames_as_esn_io(x_CP)
     g, t = y.shape[0], y.shape[1]
@@ -92,5 +94,6 @@ def trainMIMOESN_batch(bank, y_CP, x_CP, d, CyclicPrefixLen, precision="f64", no
     U[:, :t] = y
     D[:, d:d + t] = x
     n_forget = d + CyclicPrefixLen
-    E = bank.fit(U, D, transient=n_forget, precision=precision, noise_mode=noise_mode, seed=seed)
+    E = bank.fit(U, D, transient=n_forget, precision=precision, noise_mode=noise_mode, seed=seed,
+                 ridge=ridge)
     return E, n_forget

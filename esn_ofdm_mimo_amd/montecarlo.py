@@ -331,8 +331,11 @@ class DetectorSweep:
 
     def __init__(self, params: LinkParams, n_reservoir=512, spectral_radius=0.9, sparsity=0.1, noise=0.001,
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
-                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64"):
-        """io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
+                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None):
+        """ridge (extension; None = the reference's pinv fit): lambda of the ridge read-out (ReservoirBank.solve), a
+        float or a callable ebno_db -> float (the best lambda moves with Eb/No and n_reservoir).
+
+        io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
         predict kernels see the same float inputs and write the same float outputs).  Pilots and training stay
         float64.  Needs precision f32 / f16 / bf16."""
         if io not in ("f64", "f32"):
@@ -345,6 +348,7 @@ class DetectorSweep:
         self.rank, self.world = rank, world_size
         self.precision, self.fit_precision = precision, fit_precision
         self.solve_method = solve_method
+        self.ridge = ridge
         self.train_ebno = train_ebno      # not None: every ESN is trained at this fixed Eb/No
         self.n_in, self.n_out, self.n_res = 2 * params.n_r, 2 * params.n_t, n_reservoir
         self.seed = seed
@@ -364,6 +368,13 @@ class DetectorSweep:
         ones_out = torch.ones((n_groups, self.n_out), dtype=torch.float64, device=self.device)
         self.bank.set_scaling(ones_in * p.input_scaling(ebno_db), None, ones_out * p.teacher_scale, None)
         self.p_i = torch.full((n_groups,), p.p_i(ebno_db), dtype=torch.float64, device=self.device)
+        self._ebno = ebno_db
+
+    def ridge_at(self, ebno_db):
+        """lambda of the fits at this Eb/No (None: pinv)."""
+        if self.ridge is None:
+            return None
+        return float(self.ridge(ebno_db)) if callable(self.ridge) else float(self.ridge)
 
     def stream_seed(self, snr_idx, leg):
         """64-bit seed of the state-noise stream of one Eb/No point; leg 0 = training (harvest), 1 = detection.
@@ -395,7 +406,8 @@ class DetectorSweep:
         chol = self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
         e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
         E = self.bank.fit(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
-                          seed=seed, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset)
+                          seed=seed, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
+                          ridge=self.ridge_at(getattr(self, "_ebno", None)))
         self._cont = None
         if p.continuation:      # laststate / lastoutput of pyESN.py:195-197: training-final state, scaled teacher
             y_last = D[:, -1, :]
@@ -410,7 +422,8 @@ class DetectorSweep:
         """Host-synchronising check of the last fit: groups the Cholesky path flagged are re-solved
         with the QR kernel (GPU).  Returns how many were."""
         U, D, tr = self._fit_io
-        n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status)
+        n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status,
+                                     ridge=getattr(self.bank, "fit_ridge", None))
         if n:
             self.bank.set_readout(self.bank.W_out)
         return n

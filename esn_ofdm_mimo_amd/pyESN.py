@@ -50,7 +50,8 @@ class ESN:
                  input_scaling=None, teacher_forcing=True, feedback_scaling=None,
                  teacher_scaling=None, teacher_shift=None,
                  out_activation=identity, inverse_out_activation=identity,
-                 random_state=None, silent=True, *, precision="f32", device=None, leak_rate=1.0):
+                 random_state=None, silent=True, *, precision="f32", device=None, leak_rate=1.0,
+                 ridge=0.0):
         self.n_inputs = n_inputs
         self.n_reservoir = n_reservoir
         self.n_outputs = n_outputs
@@ -85,6 +86,10 @@ class ESN:
         self.leak_rate = float(leak_rate)
         if self.leak_rate != 1.0:
             self.precision = "f64"
+        # extension (the reference fits with pinv only): W_out = argmin |E W^T - D_s|^2 + ridge |W|^2; 0.0 = pinv
+        self.ridge = float(ridge)
+        if not (self.ridge >= 0.0 and np.isfinite(self.ridge)):
+            raise ValueError("ridge must be a finite number >= 0")
         self.device = device
         _lib.load()
         _lib.require_gpu()
@@ -149,7 +154,7 @@ class ESN:
         E = bank.harvest(inputs[None], outputs[None], precision="f64",
                          noise_mode="tensor" if self.noise else "none", noise_u=noise_u[None])
         self._report("fitting...")
-        W_out, status = bank.solve(E, outputs[None], transient)
+        W_out, status = bank.solve(E, outputs[None], transient, ridge=self.ridge if self.ridge else None)
         bank.set_readout(W_out)
         self.fit_status = int(status[0].item())
         self.W_out = W_out[0].cpu().numpy()

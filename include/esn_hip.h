@@ -311,6 +311,44 @@ int esn_readout_solve_chol_batch_f32(const float* E, const double* D, int n_grou
                                      const double* t_scale, const double* t_shift,
                                      double* W_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Ridge-regression read-out -- an extension, OFF unless these entry points are called: the reference has no
+ * counterpart (its ESN.fit is the pinv solve above, :191-192, and pinv stays this library's default and its
+ * reference-parity mode).  For every trained ESN g and every l < n_ridge, over rows [transient, T) of E[g] and the
+ * scaled teacher D_s = D[g]*t_scale + t_shift:
+ *
+ *     W_out[g][l] = argmin_W |E W^T - D_s|^2 + lambda |W|^2,     lambda = ridge[g][l] >= 0
+ *
+ * lambda is absolute, in the units of the Gram matrix of the (scaled) extended states: it is added to the diagonal
+ * of E E^T (rows < cols: W^T = E^T (E E^T + lambda I)^-1 D_s) or E^T E (W^T = (E^T E + lambda I)^-1 E^T D_s); the
+ * two forms are the same solution.  lambda = 0 is the pinv solve of the entry points above, bit for bit.
+ *   ridge   [n_groups][n_ridge] float64, device: several lambda per pilot are solved in one launch
+ *   W_out   [n_groups][n_ridge][n_out][cols];  status [n_groups][n_ridge]
+ *   status  as in the pinv solves (0 ok, 1 rank deficient / pivot rejected), and 2 = lambda negative or not
+ *           finite: that entry's W_out is all zero, the other entries are unaffected
+ * The QR solve factorises the augmented matrix ([A ; sqrt(lambda) I], or [A  sqrt(lambda) I]^T when rows < cols),
+ * so its workspace per entry holds rows + cols matrix rows; the Cholesky solves add lambda to the Gram diagonal
+ * (same shapes as the pinv Cholesky solves: min(rows, cols) <= 512 and n_out <= 8, else -2; one workspace slice per
+ * (group, lambda) beyond 128). */
+size_t esn_readout_solve_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols, int n_out);
+int esn_readout_solve_ridge_batch(const double* E, const double* D, int n_groups, int T,
+                                  int transient, int cols, int n_out,
+                                  const double* t_scale, const double* t_shift,
+                                  const double* ridge, int n_ridge,
+                                  double* W_out, int* status, void* workspace, void* stream);
+size_t esn_readout_chol_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols);
+int esn_readout_solve_chol_ridge_batch(const double* E, const double* D, int n_groups, int T,
+                                       int transient, int cols, int n_out,
+                                       const double* t_scale, const double* t_shift,
+                                       const double* ridge, int n_ridge,
+                                       double* W_out, int* status, void* workspace, size_t workspace_bytes,
+                                       void* stream);
+int esn_readout_solve_chol_ridge_batch_f32(const float* E, const double* D, int n_groups, int T,
+                                           int transient, int cols, int n_out,
+                                           const double* t_scale, const double* t_shift,
+                                           const double* ridge, int n_ridge,
+                                           double* W_out, int* status, void* workspace, size_t workspace_bytes,
+                                           void* stream);
+
 /* Fused detector tail: Y [B][N][2 N_t] time-domain ESN outputs
  * -> (1/N) FFT_N / sqrt(Pi[group]) -> nearest unit-power square-QAM point ->
  * natural-binary LSB-first bits -> compare with tx_bits [B][N*m][N_t] (uint8) ->
