@@ -357,49 +357,121 @@ __device__ __forceinline__ void ch_load4(const double* p, double (&v)[4]) {
 __device__ __forceinline__ const float* ch_src(const SolveParams& sp, float*) { return sp.E32; }
 __device__ __forceinline__ const double* ch_src(const SolveParams& sp, double*) { return sp.E; }
 
-__device__ __forceinline__ double ch_bcast(double x, int src) {      // wave-uniform copy of lane `src` (constant)
-    const uint64_t u = __builtin_bit_cast(uint64_t, x);
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, src);
-    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), src);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+// copy of lane SRC of this lane's 16-lane row, by DPP: the value stays in the vector pipe (a v_readlane would take
+// it through an SGPR pair, and what is decided from it through the scalar unit and a branch).  The wait states of
+// a DPP read behind a VALU write of its source or of EXEC open the string, as in ch_dpp_fmac.
+template <int SRC>
+__device__ __forceinline__ double ch_row_bcast(double x) {
+    double v;
+    asm("s_nop 4\n\tv_mov_b64_dpp %0, %1 row_newbcast:%c2 row_mask:0xf bank_mask:0xf" : "=v"(v) : "v"(x), "i"(SRC));
+    return v;
 }
 
-// One wave: factorise the 16x16 diagonal tile at D in registers (lane r = row r, the pivots travel by
-// v_readlane) and overwrite it with L11^-1 (lane c = column c, by forward substitution).  A rejected pivot
-// (v <= tol) drops its direction, as pinv would: unit diagonal and zero column in L11, zero row in L11^-1,
-// so the panel column and the solution component vanish too.  Returns 1 if a live pivot was rejected.
-__device__ __forceinline__ int ch_factor_diag(double* D, int j0, int n, double piv_tol, int lane) {
-    const int r = lane & 15;                        // lanes 16..63 mirror lanes 0..15 (no divergence)
-    double a[16], x[16];
+// acc[t] = fma(-(d of lane L0 + t of this lane's 16-lane row), o, acc[t]) for t < N, N = 8, 4, 2 or 1: the
+// double-precision DPP form v_fmac_f64_dpp with row_newbcast takes the cross-lane factor as src0, so no value
+// travels through SGPRs.  One statement per group: the compiler sees neither the broadcasts (it cannot keep the
+// 120 of the factorisation alive for the inversion, which needs the same values) nor the DPP reads, so the wait
+// states a DPP read needs after a VALU write of its source (2) or of EXEC (5) open the string.
+#define CH_DPP_FMAC(t) "v_fmac_f64_dpp %" #t ", -%[d], %[o] row_newbcast:%c[l" #t "] row_mask:0xf bank_mask:0xf\n\t"
+template <int L0, int N>
+__device__ __forceinline__ void ch_dpp_fmac(double* acc, double d, double o) {
+    static_assert(N == 8 || N == 4 || N == 2 || N == 1, "group sizes");
+    static_assert(L0 >= 0 && L0 + N <= 16, "lanes of one row");
+    if constexpr (N == 8) {
+        asm("s_nop 4\n\t" CH_DPP_FMAC(0) CH_DPP_FMAC(1) CH_DPP_FMAC(2) CH_DPP_FMAC(3)
+            CH_DPP_FMAC(4) CH_DPP_FMAC(5) CH_DPP_FMAC(6) CH_DPP_FMAC(7)
+            : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7])
+            : [d] "v"(d), [o] "v"(o), [l0] "i"(L0), [l1] "i"(L0 + 1), [l2] "i"(L0 + 2), [l3] "i"(L0 + 3),
+              [l4] "i"(L0 + 4), [l5] "i"(L0 + 5), [l6] "i"(L0 + 6), [l7] "i"(L0 + 7));
+    } else if constexpr (N == 4) {
+        asm("s_nop 4\n\t" CH_DPP_FMAC(0) CH_DPP_FMAC(1) CH_DPP_FMAC(2) CH_DPP_FMAC(3)
+            : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])
+            : [d] "v"(d), [o] "v"(o), [l0] "i"(L0), [l1] "i"(L0 + 1), [l2] "i"(L0 + 2), [l3] "i"(L0 + 3));
+    } else if constexpr (N == 2) {
+        asm("s_nop 4\n\t" CH_DPP_FMAC(0) CH_DPP_FMAC(1)
+            : "+v"(acc[0]), "+v"(acc[1]) : [d] "v"(d), [o] "v"(o), [l0] "i"(L0), [l1] "i"(L0 + 1));
+    } else {
+        asm("s_nop 4\n\t" CH_DPP_FMAC(0) : "+v"(acc[0]) : [d] "v"(d), [o] "v"(o), [l0] "i"(L0));
+    }
+}
+#undef CH_DPP_FMAC
+// acc[i] = fma(-(d of lane i), o, acc[i]) for FROM <= i < 16, in groups of 8, 4, 2 and 1
+template <int FROM>
+__device__ __forceinline__ void ch_dpp_fmac_from(double (&acc)[16], double d, double o) {
+    constexpr int cnt = 16 - FROM;
+    if constexpr (cnt & 8) ch_dpp_fmac<FROM, 8>(acc + FROM, d, o);
+    if constexpr (cnt & 4) ch_dpp_fmac<FROM + (cnt & 8), 4>(acc + FROM + (cnt & 8), d, o);
+    if constexpr (cnt & 2) ch_dpp_fmac<FROM + (cnt & 12), 2>(acc + FROM + (cnt & 12), d, o);
+    if constexpr (cnt & 1) ch_dpp_fmac<15, 1>(acc + 15, d, o);
+}
+
+// One wave, every lane active, lanes 16..63 mirroring lanes 0..15 (r = lane % 16): the 16x16 diagonal tile whose
+// row r lane r holds in a[] is factorised in place (a[k] of lane i > k becomes L11[i][k]) and x[] of lane c
+// receives column c of L11^-1 by forward substitution.  Nothing travels through SGPRs: the pivot is a DPP row
+// broadcast (every lane takes the same accept / reject decision), the 120 updates a[k] -= a[j] L11[k][j] and
+// the 120 of the inversion take their cross-lane factor by DPP.  The updates run on every lane: rows r < k of
+// column k hold no tile entry and nothing reads them.  FULL_L: the caller stores L11, so a finalised column
+// gets its diagonal and 0.0 above it; otherwise only the rows below the diagonal are meaningful afterwards.
+// The inversion shares the column loop: once column j and x[j] are final, every x[i], i > j, takes its term;
+// each x[i] still sums in ascending k.
+// A rejected pivot (v <= tol) drops its direction, as pinv would: unit diagonal and zero column in L11, zero
+// row in L11^-1, so the panel column and the solution component vanish too; a padding pivot (past n) is not
+// a rejection, and DROP_PAD says whether its row of L11^-1 is zeroed as well.  my_invd (FULL_L only):
+// 1 / L11[r][r], 1.0 for a pivot that was not taken.  Returns the mask of rejected live pivots.
+template <bool DROP_PAD, bool FULL_L>
+__device__ __forceinline__ unsigned ch_diag_regs(double (&a)[16], double (&x)[16], double& my_invd, int j0, int n,
+                                                 double piv_tol, int r) {
+    my_invd = 1.0;
+    unsigned rejected = 0;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) a[c] = D[ch_el(r, c)];
-    double my_invd = 1.0;
-    unsigned rejected = 0, dropped = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const double v = ch_bcast(a[j], j);
+    for (int i = 0; i < 16; ++i) x[i] = (i == r) ? 1.0 : 0.0;           // x[] holds the running sums until final
+    double v = ch_row_bcast<0>(a[0]);                                   // the pivot of the column to come
+    auto column = [&](auto jc) {
+        constexpr int j = decltype(jc)::value;
         const bool live = j0 + j < n;
         const bool ok = live && v > piv_tol;
         if (live && !ok) rejected |= 1u << j;
-        if (!ok) dropped |= 1u << j;
-        const double d = ok ? sqrt(v) : 1.0, inv_d = ok ? 1.0 / d : 0.0;
-        if (r == j) my_invd = ok ? inv_d : 1.0;
-        a[j] = (r == j) ? d : ((r > j) ? a[j] * inv_d : 0.0);          // column j of L11
-#pragma unroll
-        for (int k = j + 1; k < 16; ++k) {
-            const double lkj = ch_bcast(a[j], k);
-            if (r >= k) a[k] = fma(-a[j], lkj, a[k]);
+        // (selects around the square root and the quotient, not a branch over them: sqrt(1.0) and 1.0 / 1.0 are
+        // exact, and the 16 columns stay one block the scheduler can overlap)
+        const double d = sqrt(ok ? v : 1.0), inv_1 = 1.0 / d, inv_d = ok ? inv_1 : 0.0;
+        if constexpr (FULL_L) {
+            if (r == j) my_invd = inv_1;
+            a[j] = (r == j) ? d : ((r > j) ? a[j] * inv_d : 0.0);      // column j of L11
+        } else {
+            a[j] *= inv_d;                                              // rows > j of column j of L11
         }
-    }
-    // lane c: column c of L11^-1, L11[i][k] = a[k] of lane i
+        // a[k] = fma(-a[j], L11[k][j], a[k]), k > j: the next column first, its pivot is what the chain waits for
+        if constexpr (j < 15) {
+            ch_dpp_fmac<j + 1, 1>(a + j + 1, a[j], a[j]);
+            v = ch_row_bcast<j + 1>(a[j + 1]);
+        }
+        if constexpr (j < 14) ch_dpp_fmac_from<j + 2>(a, a[j], a[j]);
+        const bool zero = DROP_PAD ? !ok : live && !ok;
+        x[j] = (j >= r && !zero) ? x[j] * inv_1 : 0.0;                  // row j of L11^-1
+        if constexpr (j < 15) ch_dpp_fmac_from<j + 1>(x, a[j], x[j]);   // x[i] = fma(-L11[i][j], x[j], x[i]), i > j
+    };
+    column(std::integral_constant<int, 0>()); column(std::integral_constant<int, 1>());
+    column(std::integral_constant<int, 2>()); column(std::integral_constant<int, 3>());
+    column(std::integral_constant<int, 4>()); column(std::integral_constant<int, 5>());
+    column(std::integral_constant<int, 6>()); column(std::integral_constant<int, 7>());
+    column(std::integral_constant<int, 8>()); column(std::integral_constant<int, 9>());
+    column(std::integral_constant<int, 10>()); column(std::integral_constant<int, 11>());
+    column(std::integral_constant<int, 12>()); column(std::integral_constant<int, 13>());
+    column(std::integral_constant<int, 14>()); column(std::integral_constant<int, 15>());
+    return rejected;
+}
+
+// One wave: factorise the 16x16 diagonal tile at D in registers and overwrite it with L11^-1 (ch_diag_regs).
+// Returns 1 if a live pivot was rejected.
+__device__ __forceinline__ int ch_factor_diag(double* D, int j0, int n, double piv_tol, int lane) {
+    int r = lane & 15;                              // lanes 16..63 mirror lanes 0..15 (no divergence)
+    // opaque per call: what depends on r alone (the 16 swizzled tile addresses, the row predicates of every
+    // column) would be hoisted out of the block loop and held in registers this kernel does not have
+    asm volatile("" : "+v"(r));
+    double a[16], x[16], my_invd;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        double sacc = (i == r) ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < i; ++k) sacc = fma(-ch_bcast(a[k], i), x[k], sacc);   // x[k] = 0 for k < c
-        const double idi = ch_bcast(my_invd, i);
-        x[i] = (i >= r && !((dropped >> i) & 1u)) ? sacc * idi : 0.0;
-    }
+    for (int c = 0; c < 16; ++c) a[c] = D[ch_el(r, c)];
+    const unsigned rejected = ch_diag_regs<true, false>(a, x, my_invd, j0, n, piv_tol, r);
     if (lane < 16) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) D[ch_el(i, r)] = x[i];
@@ -675,6 +747,10 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         piv_tol = dmax * 1e-14;
     }
     for (int kb = -1; kb < nblk; ++kb) {                            // kb = -1: the first diagonal block only
+#ifdef ESN_STAMPS
+        ESN_STAMP(f0);
+        unsigned long long f1 = f0, f2 = f0;
+#endif
         if (kb >= 0) {   // (b) panel: row tile rt of L21 = A21[rt] * L11^-T  (B operand [k][n] = L11^-1[n][k])
             const int rt = kb + 1 + wv;
             if (rt < ntile) {
@@ -691,7 +767,13 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         }
         if (kb >= 0) {   // (c) trailing update of the lower tiles (ti >= tj > kb): A22[ti][tj] -= L21[ti] L21[tj]^T;
             // t = 0 is the next diagonal tile (wave 0), waves 1..7 take t = 1, 2, ...
+#ifdef ESN_STAMPS
+            ESN_STAMP_SET(f1);
+#endif
             __syncthreads();
+#ifdef ESN_STAMPS
+            ESN_STAMP_SET(f2);
+#endif
             const int mt = ntile - kb - 1, cnt = mt * (mt + 1) / 2;
             for (int t = wv; t < cnt; t += (wv == 0 ? cnt : CH_NW - 1)) {
                 int di = 0;
@@ -710,8 +792,19 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
                 for (int i = 0; i < 4; ++i) C[ch_el(4 * i + lq, lr)] = c[i];
             }
         }
+#ifdef ESN_STAMPS
+        ESN_STAMP(f3);
+#endif
         if (wv == 0 && kb + 1 < nblk) bad |= ch_factor_diag(Gs + ch_tile(kb + 1, kb + 1), 16 * (kb + 1), n, piv_tol, lane);
+#ifdef ESN_STAMPS
+        ESN_STAMP(f4);
+#endif
         __syncthreads();
+#ifdef ESN_STAMPS
+        ESN_STAMP(f5);
+        // panel + trailing update | the two barrier waits | the diagonal tile (wave 0)
+        st_ph[0] += (f1 - f0) + (f3 - f2); st_ph[1] += (f2 - f1) + (f5 - f4); st_ph[2] += f4 - f3;
+#endif
     }
 
 #ifdef ESN_STAMPS
@@ -973,6 +1066,7 @@ __global__ __launch_bounds__(CH_NT) __attribute__((amdgpu_waves_per_eu(4))) void
         sp.stamps[(8 + wv) * 8 + 2] = st_k3 - st_k2;
         sp.stamps[(8 + wv) * 8 + 3] = st_k4 - st_k3;
         sp.stamps[(8 + wv) * 8 + 4] = st_k4 - st_k0;
+        for (int i = 0; i < 3; ++i) sp.stamps[(8 + wv) * 8 + 5 + i] = st_ph[i];      // the factor phase, split
     }
 #endif
 }
@@ -1205,12 +1299,6 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
     for (int w = 0; w < CB_NW; ++w) piv_tol = fmax(piv_tol, sh_red[w]);
     piv_tol *= 1e-14;
 
-    auto bcast = [](double x, int src) -> double {
-        const uint64_t u = __builtin_bit_cast(uint64_t, x);
-        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, src);
-        const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), src);
-        return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-    };
     // ---- phase 3: left-looking panel Cholesky ---------------------------------------------------------
     for (int j = 0; j < ntile; ++j) {
         const int j0 = 16 * j;
@@ -1231,40 +1319,16 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
         // (2) diagonal block: factorise and invert in registers (wave 0), as in the LDS kernel
         if (wv == 0) {
             const int r = lane & 15;
-            double a[16], x[16];
+            double a[16], x[16], my_invd;
 #pragma unroll
             for (int c = 0; c < 16; ++c) a[c] = P[(j0 + r) * CB_PLD + c];
-            double my_invd = 1.0;
-            unsigned rejected = 0;
-#pragma unroll
-            for (int jj = 0; jj < 16; ++jj) {
-                const double v = bcast(a[jj], jj);
-                const bool live = j0 + jj < n;
-                const bool ok = live && v > piv_tol;
-                if (live && !ok) rejected |= 1u << jj;
-                const double d = ok ? sqrt(v) : 1.0, inv_d = ok ? 1.0 / d : 0.0;
-                if (r == jj) my_invd = ok ? inv_d : 1.0;
-                a[jj] = (r == jj) ? d : ((r > jj) ? a[jj] * inv_d : 0.0);
-#pragma unroll
-                for (int k = jj + 1; k < 16; ++k) {
-                    const double lkj = bcast(a[jj], k);
-                    if (r >= k) a[k] = fma(-a[jj], lkj, a[k]);
-                }
-            }
+            const unsigned rejected = ch_diag_regs<false, true>(a, x, my_invd, j0, n, piv_tol, r);
             if (lane < 16) {
 #pragma unroll
                 for (int c = 0; c < 16; ++c) P[(j0 + r) * CB_PLD + c] = a[c];
                 sh_invd[j0 + r] = my_invd;
             }
             if (rejected && lane == 0) sh_bad = 1;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                double sacc = (i == r) ? 1.0 : 0.0;
-#pragma unroll
-                for (int k = 0; k < i; ++k) sacc = fma(-bcast(a[k], i), x[k], sacc);
-                const double idi = bcast(my_invd, i);
-                x[i] = (i >= r && !((rejected >> i) & 1u)) ? sacc * idi : 0.0;
-            }
             if (lane < 16) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) sh_linv[i][r] = x[i];

@@ -4,7 +4,8 @@ Loads the -DESN_STAMPS build (libesn_hip_stamps.so), solves the headline shape (
 per arm of the `chol_dma` knob and prints, per wave of workgroup 0, the summed s_memtime cycles of
   Gram:  DMA / load wait | barrier | operand-read latency (dma arm) | MFMA issue
   W_out: DMA wait | barrier | rows (dma arm only)
-and the phase totals.  Shares only: every stamp waits lgkmcnt(0), which the real kernel does not.
+the phase totals, and the factor phase split into panel + trailing-update MFMAs | its two barrier waits per 16
+columns | the diagonal-tile factorisation and inversion (wave 0 only).  Shares only: every stamp waits lgkmcnt(0), which the real kernel does not.
 
     python tools/chol_stamps.py [--groups 2048]
 """
@@ -52,10 +53,11 @@ def main():
         else:
             names = ["G ld+commit", "G barrier", "-", "G mfma", "-", "-", "-"]
         print("wave " + " ".join(f"{n:>11s}" for n in names) + " |" +
-              " ".join(f"{n:>9s}" for n in ["gram", "factor", "solves", "w_out", "total"]))
+              " ".join(f"{n:>9s}" for n in ["gram", "factor", "solves", "w_out", "total"]) + " |" +
+              " ".join(f"{n:>9s}" for n in ["F mfma", "F barrier", "F diag"]))
         for w in range(8):
             print(f"{w:4d} " + " ".join(f"{x:11d}" for x in raw[w, :7]) + " |" +
-                  " ".join(f"{x:9d}" for x in raw[8 + w, :5]))
+                  " ".join(f"{x:9d}" for x in raw[8 + w, :5]) + " |" + " ".join(f"{x:9d}" for x in raw[8 + w, 5:8]))
     _lib.debug_set("chol_dma", "1")
 
 
