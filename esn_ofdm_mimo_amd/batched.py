@@ -187,7 +187,56 @@ class ReservoirBank:
             raise ValueError(f"ridge must be a scalar, [G] or [G, L] with G = {g}, not {tuple(r.shape)}")
         return r.contiguous(), flat
 
-    def solve(self, E, D, transient, method="qr", ridge=None):
+    LOO_MAX_GRAM, LOO_MAX_GRID = 128, 16      # esn_readout_ridge_loo_batch: Gram dimension, candidates per group
+
+    def _solve_ridge_grid(self, E, D, transient, ridge_grid):
+        """solve(ridge_grid=...): leave-one-out choice among the candidates, one Gram pass per group."""
+        torch = self.torch
+        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32
+        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
+        D = _as_dev(D, torch, self.device)
+        g, t, cols = E.shape
+        rows = t - transient
+        if isinstance(ridge_grid, torch.Tensor):
+            lam = ridge_grid.to(device=self.device, dtype=torch.float64)
+        else:
+            lam = torch.as_tensor(np.array(ridge_grid, dtype=np.float64), device=self.device)
+        if lam.ndim == 1:
+            lam = lam[None, :].expand(g, lam.shape[0])
+        if lam.ndim != 2 or lam.shape[0] != g:
+            raise ValueError(f"ridge_grid must hold L candidates or be [G, L] with G = {g}, not {tuple(lam.shape)}")
+        nl = lam.shape[1]
+        if not 1 <= nl <= self.LOO_MAX_GRID:
+            raise ValueError(f"ridge_grid holds {nl} candidates per group, the kernel takes 1 to {self.LOO_MAX_GRID}")
+        if min(rows, cols) > self.LOO_MAX_GRAM:
+            raise ValueError(f"ridge_grid needs min(rows, cols) <= {self.LOO_MAX_GRAM}, not {min(rows, cols)}")
+        if self.n_outputs > 8:
+            raise ValueError(f"ridge_grid needs n_outputs <= 8, not {self.n_outputs}")
+        lam = lam.contiguous()
+        with torch.cuda.device(self.device):
+            W_out = torch.empty((g, self.n_outputs, cols), dtype=torch.float64, device=self.device)
+            scores = torch.empty((g, nl), dtype=torch.float64, device=self.device)
+            choice = torch.empty(g, dtype=torch.int32, device=self.device)
+            status_l = torch.empty((g, nl), dtype=torch.int32, device=self.device)
+            fn, name = (self.lib.esn_readout_ridge_loo_batch_f32, "esn_readout_ridge_loo_batch_f32") if e32 \
+                else (self.lib.esn_readout_ridge_loo_batch, "esn_readout_ridge_loo_batch")
+            wbytes = self.lib.esn_readout_ridge_loo_workspace_bytes(g, nl, rows, cols)
+            ws = self._scratch("_loo_ws", wbytes)
+            check(fn(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale), ptr(self.t_shift),
+                     ptr(lam), nl, ptr(W_out), ptr(scores), ptr(choice), ptr(status_l), ptr(ws), wbytes,
+                     _lib.stream_handle()), name)
+            self.last_ridge_choice = choice
+            self.last_ridge_scores = scores
+            self.last_ridge_status = status_l
+            self.last_ridge_grid = lam
+            # (device-side gather; NaN where no candidate survived)
+            picked = lam.gather(1, choice.clamp(min=0).long()[:, None])[:, 0]
+            self.last_ridge_lambda = torch.where(choice >= 0, picked, torch.full_like(picked, float("nan")))
+            status = (choice < 0).to(torch.int32)
+        self.last_solve_status = status
+        return W_out, status
+
+    def solve(self, E, D, transient, method="qr", ridge=None, ridge_grid=None):
         """W_out[g] = (pinv(E[g][transient:]) @ scale(D[g][transient:])).T ; returns (W_out, status).
 
         ridge (extension, the reference has none; None = the pinv solve above, untouched): lambda >= 0 of
@@ -199,7 +248,18 @@ class ReservoirBank:
         method "qr": float64 Householder QR (accurate to cond(E) eps; the drop-in's choice).
         method "chol": float64 normal equations on the float64 matrix pipe (min(rows, cols) <= 512, n_out <= 8;
         Gram + factor in LDS up to 128, in a workspace beyond), an order of magnitude faster; groups whose pivot test fails are re-solved
-        with QR on the GPU.  "auto" = "chol" when the shape fits."""
+        with QR on the GPU.  "auto" = "chol" when the shape fits.
+
+        ridge_grid (extension): a sequence of L candidates, or a [G, L] array / tensor of them.  Each group takes the
+        candidate with the smallest leave-one-out score of its own pilot (esn_readout_ridge_loo_batch: one Gram pass,
+        min(rows, cols) <= 128, n_out <= 8, L <= 16; `method` does not apply) and the result is (W_out [G, n_out, cols],
+        status [G]) with status 0 where a choice was made and 1 where no candidate survived (W_out zero; see
+        resolve_failed).  last_ridge_choice (int32 [G], -1 = none), last_ridge_lambda (float64 [G]) and
+        last_ridge_scores ([G, L]) stay on the device."""
+        if ridge_grid is not None:
+            if ridge is not None:
+                raise ValueError("give ridge or ridge_grid, not both")
+            return self._solve_ridge_grid(E, D, transient, ridge_grid)
         torch = self.torch
         e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32       # as written by harvest(e_dtype="f32")
         E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
@@ -262,10 +322,34 @@ class ReservoirBank:
                   "esn_readout_solve_batch")
         return W_out, status
 
-    def resolve_failed(self, E, D, transient, W_out, status, ridge=None):
+    def resolve_failed(self, E, D, transient, W_out, status, ridge=None, ridge_grid=None):
         """Re-solve with QR (on the GPU) the groups a "chol" solve flagged; returns their count.  `ridge` as given to
-        that solve: each flagged entry is re-solved with its own lambda, so a repaired group is a ridge solution too."""
+        that solve: each flagged entry is re-solved with its own lambda, so a repaired group is a ridge solution too.
+        `ridge_grid` as given to a solve(ridge_grid=...): a group left without a choice (choice == -1, status 1) is
+        re-solved by QR at its largest finite candidate -- the most regularised fit the caller was willing to accept --
+        and last_ridge_lambda takes that value; the choice stays -1."""
         torch = self.torch
+        if ridge_grid is not None:
+            if ridge is not None:
+                raise ValueError("give ridge or ridge_grid, not both")
+            bad = torch.nonzero(status).flatten()
+            nbad = int(bad.numel())
+            if nbad:
+                if isinstance(ridge_grid, torch.Tensor):
+                    lam = ridge_grid.to(device=self.device, dtype=torch.float64)
+                else:
+                    lam = torch.as_tensor(np.array(ridge_grid, dtype=np.float64), device=self.device)
+                if lam.ndim == 1:
+                    lam = lam[None, :].expand(status.shape[0], lam.shape[0])
+                lam = lam[bad]
+                lam = torch.where(torch.isfinite(lam), lam, torch.full_like(lam, -1.0)).max(dim=1).values
+                # (no finite candidate at all: lambda stays negative, the QR solve answers status 2 and a zero W_out)
+                w2 = self.resolve_failed_at(E, D, transient, bad, lam.contiguous())
+                W_out[bad] = w2[0]
+                status[bad] = w2[1]
+                if getattr(self, "last_ridge_lambda", None) is not None and self.last_ridge_lambda.shape[0] == status.shape[0]:
+                    self.last_ridge_lambda[bad] = lam
+            return nbad
         if ridge is not None and status.ndim == 2:
             idx = torch.nonzero(status)
             bad, bad_l = idx[:, 0], idx[:, 1]
@@ -302,14 +386,30 @@ class ReservoirBank:
             status[bad] = st2
         return nbad
 
+    def resolve_failed_at(self, E, D, transient, bad, lam):
+        """QR ridge solve of the groups `bad` (device index tensor) at lam [len(bad)]; returns (W_out, status)."""
+        torch = self.torch
+        keep = (self.t_scale, self.t_shift)
+        self.t_scale = None if keep[0] is None else keep[0][bad].contiguous()
+        self.t_shift = None if keep[1] is None else keep[1][bad].contiguous()
+        try:
+            return self.solve(E[bad].contiguous(), _as_dev(D, torch, self.device)[bad].contiguous(), transient,
+                              method="qr", ridge=lam)
+        finally:
+            self.t_scale, self.t_shift = keep
+
     def fit(self, U, D, transient=0, precision="f64", noise_mode="counter", noise_u=None, seed=0,
-            method="qr", e_dtype="f64", group_offset=0, ridge=None):
-        """harvest + solve + set_readout.  ridge: None (pinv), a float or one lambda per group [G] -- see solve."""
+            method="qr", e_dtype="f64", group_offset=0, ridge=None, ridge_grid=None):
+        """harvest + solve + set_readout.  ridge: None (pinv), a float or one lambda per group [G] -- see solve.
+        ridge_grid: candidates (L or [G, L]); each group's lambda is chosen by leave-one-out on its own pilot and
+        fit_ridge becomes the chosen per-group lambda tensor (float64 [G], device)."""
+        if ridge is not None and ridge_grid is not None:
+            raise ValueError("give ridge or ridge_grid, not both")
         if ridge is not None and np.ndim(ridge) > 1:
             raise ValueError("fit takes one lambda per group (a scalar or [G]); solve() takes [G, L]")
         E = self.harvest(U, D, precision, noise_mode, noise_u, seed, e_dtype=e_dtype, group_offset=group_offset)
-        W_out, status = self.solve(E, D, transient, method=method, ridge=ridge)
-        self.fit_ridge = ridge
+        W_out, status = self.solve(E, D, transient, method=method, ridge=ridge, ridge_grid=ridge_grid)
+        self.fit_ridge = ridge if ridge_grid is None else self.last_ridge_lambda
         self.set_readout(W_out)
         ht = getattr(self, "harvest_timeout", None)
         if ht is not None:

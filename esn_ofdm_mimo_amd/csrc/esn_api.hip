@@ -595,6 +595,50 @@ int esn_readout_solve_chol_ridge_batch_f32(const float* E, const double* D, int 
                              n_out, t_scale, t_shift, ridge, n_ridge, W_out, status, workspace, workspace_bytes, stream);
 }
 
+// ---- leave-one-out choice of the ridge parameter (esn_loo.hip) -----------------------------------------------------
+size_t esn_readout_ridge_loo_workspace_bytes(int n_groups, int n_ridge, int rows, int cols) {
+    if (n_groups <= 0 || n_ridge <= 0 || rows <= 0 || cols <= 0) return 0;
+    return sizeof(double) * ridge_loo_work_doubles() * (size_t)n_groups;
+}
+
+static int ridge_loo_common(const char* who, const double* E, const float* E32, const double* D, int n_groups, int T,
+                            int transient, int cols, int n_out, const double* t_scale, const double* t_shift,
+                            const double* ridge, int n_ridge, double* W_out, double* score, int* choice, int* status,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if ((!E && !E32) || !D || !ridge || !W_out || !score || !choice || !status) return fail(-1, "%s: null pointer", who);
+    if (n_groups <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
+        return fail(-1, "%s: invalid sizes", who);
+    if (n_ridge < 1 || n_ridge > 16) return fail(-1, "%s: n_ridge = %d, 1 to 16 candidates are served", who, n_ridge);
+    if (n_out > 8) return fail(-1, "%s: n_out = %d, at most 8 outputs are served", who, n_out);
+    const int rows = T - transient, n = rows < cols ? rows : cols;
+    if (n > 128)
+        return fail(-2, "%s: min(rows, cols) = %d, the limit is 128 (the factor stays in LDS)", who, n);
+    const size_t need = esn_readout_ridge_loo_workspace_bytes(n_groups, n_ridge, rows, cols);
+    if (!workspace || workspace_bytes < need)
+        return fail(-1, "%s: workspace holds %zu bytes, esn_readout_ridge_loo_workspace_bytes says %zu", who,
+                    workspace ? workspace_bytes : (size_t)0, need);
+    if ((uintptr_t)workspace & 7) return fail(-1, "%s: the workspace must be 8-byte aligned", who);
+    return hip_fail(launch_ridge_loo(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge,
+                                     W_out, score, choice, status, workspace, (hipStream_t)stream), who);
+}
+
+int esn_readout_ridge_loo_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
+                                int n_out, const double* t_scale, const double* t_shift, const double* ridge,
+                                int n_ridge, double* W_out, double* score, int* choice, int* status, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    return ridge_loo_common("esn_readout_ridge_loo_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
+                            t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes, stream);
+}
+
+int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols,
+                                    int n_out, const double* t_scale, const double* t_shift, const double* ridge,
+                                    int n_ridge, double* W_out, double* score, int* choice, int* status,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    return ridge_loo_common("esn_readout_ridge_loo_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out,
+                            t_scale, t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes,
+                            stream);
+}
+
 static int detect_common(const char* who, bool io32, const void* Y, int n_frames, int frames_per_group, int n_sub,
                          int n_t, int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
                          long long* bit_count, double* X_hat, void* stream) {

@@ -77,6 +77,12 @@ int launch_readout_chol_big(const double* E, const float* E32, const double* D, 
                             int cols, int n_out, const double* t_scale, const double* t_shift,
                             double* W_out, int* status, void* workspace, hipStream_t stream,
                             const double* ridge = nullptr, int n_ridge = 1);
+// esn_loo.hip: leave-one-out choice among n_ridge candidates per group; the workspace holds ridge_loo_work_doubles()
+// doubles per group (the un-factored Gram matrix, the right-hand side and the best solution so far)
+size_t ridge_loo_work_doubles();
+int launch_ridge_loo(const double* E, const float* E32, const double* D, int n_groups, int T, int transient, int cols,
+                     int n_out, const double* t_scale, const double* t_shift, const double* ridge, int n_ridge,
+                     double* W_out, double* score, int* choice, int* status, void* workspace, hipStream_t stream);
 // esn_gen.hip
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);

@@ -80,12 +80,13 @@ def complex_frames_as_esn_io(z):
 
 
 def trainMIMOESN_batch(bank, y_CP, x_CP, d, CyclicPrefixLen, precision="f64", noise_mode="counter", seed=0,
-                       ridge=None):
+                       ridge=None, ridge_grid=None):
     """G pilots at once: y_CP [G,T,N_r], x_CP [G,T,N_t] complex -> bank.W_out (one harvest + one
     solve launch).  Returns (E, nForget).  Teacher rows are delayed by d; the d trailing input rows
     are the zeros the kernel synthesises beyond T_in -- here materialised because harvest takes
     equal-length U and D.  ridge: None = the reference's pinv fit, else lambda (scalar or [G]) of
-    ReservoirBank.solve."""
+    ReservoirBank.solve.  ridge_grid: candidates (L or [G, L]); every pilot takes the one with the smallest
+    leave-one-out score (bank.last_ridge_choice / last_ridge_lambda say which)."""
     y = complex_frames_as_esn_io(y_CP)
     x = complex_frames_as_esn_io(x_CP)
     g, t = y.shape[0], y.shape[1]
@@ -95,5 +96,5 @@ def trainMIMOESN_batch(bank, y_CP, x_CP, d, CyclicPrefixLen, precision="f64", no
     D[:, d:d + t] = x
     n_forget = d + CyclicPrefixLen
     E = bank.fit(U, D, transient=n_forget, precision=precision, noise_mode=noise_mode, seed=seed,
-                 ridge=ridge)
+                 ridge=ridge, ridge_grid=ridge_grid)
     return E, n_forget

@@ -331,9 +331,14 @@ class DetectorSweep:
 
     def __init__(self, params: LinkParams, n_reservoir=512, spectral_radius=0.9, sparsity=0.1, noise=0.001,
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
-                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None):
+                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None):
         """ridge (extension; None = the reference's pinv fit): lambda of the ridge read-out (ReservoirBank.solve), a
         float or a callable ebno_db -> float (the best lambda moves with Eb/No and n_reservoir).
+
+        ridge_grid (extension): a sequence of L candidates; every block takes the one with the smallest
+        leave-one-out score of its own pilot (ReservoirBank.solve(ridge_grid=)), no data frame touched.  After run(),
+        ridge_choice_counts is {ebno: int64 [L]}: how many of this rank's blocks took each candidate (summed on the
+        device, read once per Eb/No point).
 
         io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
         predict kernels see the same float inputs and write the same float outputs).  Pilots and training stay
@@ -349,6 +354,10 @@ class DetectorSweep:
         self.precision, self.fit_precision = precision, fit_precision
         self.solve_method = solve_method
         self.ridge = ridge
+        if ridge is not None and ridge_grid is not None:
+            raise ValueError("give ridge or ridge_grid, not both")
+        self.ridge_grid = None if ridge_grid is None else np.array(ridge_grid, dtype=np.float64).reshape(-1)
+        self.ridge_choice_counts = {}
         self.train_ebno = train_ebno      # not None: every ESN is trained at this fixed Eb/No
         self.n_in, self.n_out, self.n_res = 2 * params.n_r, 2 * params.n_t, n_reservoir
         self.seed = seed
@@ -375,6 +384,14 @@ class DetectorSweep:
         if self.ridge is None:
             return None
         return float(self.ridge(ebno_db)) if callable(self.ridge) else float(self.ridge)
+
+    def _grid_dev(self):
+        """ridge_grid on the device, copied once (None without one)."""
+        if self.ridge_grid is None:
+            return None
+        if getattr(self, "_grid_t", None) is None:
+            self._grid_t = self.torch.as_tensor(self.ridge_grid, device=self.device)
+        return self._grid_t
 
     def stream_seed(self, snr_idx, leg):
         """64-bit seed of the state-noise stream of one Eb/No point; leg 0 = training (harvest), 1 = detection.
@@ -407,7 +424,7 @@ class DetectorSweep:
         e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
         E = self.bank.fit(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
                           seed=seed, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
-                          ridge=self.ridge_at(getattr(self, "_ebno", None)))
+                          ridge=self.ridge_at(getattr(self, "_ebno", None)), ridge_grid=self._grid_dev())
         self._cont = None
         if p.continuation:      # laststate / lastoutput of pyESN.py:195-197: training-final state, scaled teacher
             y_last = D[:, -1, :]
@@ -422,8 +439,11 @@ class DetectorSweep:
         """Host-synchronising check of the last fit: groups the Cholesky path flagged are re-solved
         with the QR kernel (GPU).  Returns how many were."""
         U, D, tr = self._fit_io
-        n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status,
-                                     ridge=getattr(self.bank, "fit_ridge", None))
+        if self.ridge_grid is not None:
+            n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status, ridge_grid=self._grid_dev())
+        else:
+            n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status,
+                                         ridge=getattr(self.bank, "fit_ridge", None))
         if n:
             self.bank.set_readout(self.bank.W_out)
         return n
@@ -450,7 +470,8 @@ class DetectorSweep:
 
     def _chunk(self, ebno, si, ids, F, repair):
         """One launch group: generate, train, detect the contiguous global blocks `ids`; returns the device
-        tensor [errors, bits, flagged fits] (int64) without synchronising the host unless `repair`."""
+        tensor [errors, bits, flagged fits] (int64) without synchronising the host unless `repair`; with a ridge_grid,
+        L more entries: how many blocks took each candidate."""
         torch = self.torch
         g = len(ids)
         data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128")
@@ -464,6 +485,11 @@ class DetectorSweep:
             ones_in = torch.ones((g, self.n_in), dtype=torch.float64, device=self.device)
             self.bank.in_scale = ones_in * self.p.input_scaling(self.train_ebno)
         E = self.train(data["pilot_y"], data["pilot_x"], seed=self.stream_seed(si, 0), group_offset=ids[0])
+        picks = None
+        if self.ridge_grid is not None:     # (before a repair: a block without a choice is in no bin)
+            ch = self.bank.last_ridge_choice
+            picks = torch.bincount(ch.clamp(min=0).long(), weights=ch.ge(0).double(),
+                                   minlength=len(self.ridge_grid)).to(torch.int64)
         if repair:
             self.repair_fit(E)
         err = torch.zeros(g, dtype=torch.int64, device=self.device)
@@ -479,7 +505,8 @@ class DetectorSweep:
                 self.bank.raise_if_harvest_timed_out()
             else:
                 flagged = flagged + ht.ne(0).sum().to(torch.int64)
-        return torch.stack([err.sum(), nb.sum(), flagged])
+        head = torch.stack([err.sum(), nb.sum(), flagged])
+        return head if picks is None else torch.cat([head, picks])
 
     def run(self, ebno_list, blocks_per_snr, frames_per_block=None, chunk_blocks=None, dist=None):
         """Returns (BER[n_snr], counters [n_snr, 2]) -- identical on every rank and for every world size and
@@ -503,6 +530,8 @@ class DetectorSweep:
                     self.fits_repaired += int(res[ci, 2].item())
                     res[ci] = self._chunk(ebno, si, chunks[ci], F, repair=True)
             counters[si] += res[:, :2].sum(dim=0)
+            if self.ridge_grid is not None:
+                self.ridge_choice_counts[ebno] = res[:, 3:].sum(dim=0).cpu().numpy()
         reduce_counters(counters, dist, self.world)
         c = counters.cpu().numpy()
         return c[:, 0] / np.maximum(c[:, 1], 1), c

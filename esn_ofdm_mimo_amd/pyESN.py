@@ -51,7 +51,7 @@ class ESN:
                  teacher_scaling=None, teacher_shift=None,
                  out_activation=identity, inverse_out_activation=identity,
                  random_state=None, silent=True, *, precision="f32", device=None, leak_rate=1.0,
-                 ridge=0.0):
+                 ridge=0.0, ridge_grid=None):
         self.n_inputs = n_inputs
         self.n_reservoir = n_reservoir
         self.n_outputs = n_outputs
@@ -90,6 +90,14 @@ class ESN:
         self.ridge = float(ridge)
         if not (self.ridge >= 0.0 and np.isfinite(self.ridge)):
             raise ValueError("ridge must be a finite number >= 0")
+        # extension: candidates among which fit() picks lambda by the leave-one-out score of its own training rows
+        # (ReservoirBank.solve(ridge_grid=)); the chosen lambda is ridge_ after fit
+        self.ridge_grid = None if ridge_grid is None else np.array(ridge_grid, dtype=float).reshape(-1)
+        if self.ridge_grid is not None:
+            if self.ridge:
+                raise ValueError("give ridge or ridge_grid, not both")
+            if not 1 <= self.ridge_grid.size <= ReservoirBank.LOO_MAX_GRID:
+                raise ValueError(f"ridge_grid takes 1 to {ReservoirBank.LOO_MAX_GRID} candidates")
         self.device = device
         _lib.load()
         _lib.require_gpu()
@@ -154,7 +162,16 @@ class ESN:
         E = bank.harvest(inputs[None], outputs[None], precision="f64",
                          noise_mode="tensor" if self.noise else "none", noise_u=noise_u[None])
         self._report("fitting...")
-        W_out, status = bank.solve(E, outputs[None], transient, ridge=self.ridge if self.ridge else None)
+        if self.ridge_grid is not None:
+            W_out, status = bank.solve(E, outputs[None], transient, ridge_grid=self.ridge_grid)
+            if int(status[0].item()):       # no candidate survived: QR at the largest finite one
+                bank.resolve_failed(E, outputs[None], transient, W_out, status, ridge_grid=self.ridge_grid)
+            self.ridge_ = float(bank.last_ridge_lambda[0].item())
+            self.ridge_choice_ = int(bank.last_ridge_choice[0].item())
+            self.ridge_scores_ = bank.last_ridge_scores[0].cpu().numpy()
+        else:
+            W_out, status = bank.solve(E, outputs[None], transient, ridge=self.ridge if self.ridge else None)
+            self.ridge_ = self.ridge
         bank.set_readout(W_out)
         self.fit_status = int(status[0].item())
         self.W_out = W_out[0].cpu().numpy()

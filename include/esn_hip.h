@@ -349,6 +349,36 @@ int esn_readout_solve_chol_ridge_batch_f32(const float* E, const double* D, int 
                                            double* W_out, int* status, void* workspace, size_t workspace_bytes,
                                            void* stream);
 
+/* Leave-one-out choice of the ridge parameter (an extension, like the ridge solves above).  For every trained ESN g,
+ * over rows [transient, T) of E[g] and the scaled teacher D_s (n = rows, c = cols), and for each candidate
+ * lambda = ridge[g][l]: loo[i][o] is the residual of fit row i, output o, under the ridge fit on the other n - 1
+ * rows, in closed form:
+ *     n <= c:  K = E E^T + lambda I,  A = K^-1 D_s,                      loo[i][o] = A[i][o] / (K^-1)[i][i]
+ *     n >  c:  G = E^T E + lambda I,  W^T = G^-1 E^T D_s,  R = D_s - E W^T,  loo[i][o] = R[i][o] / (1 - e_i^T G^-1 e_i)
+ *     score[g][l] = sum_i sum_o loo[i][o]^2          (one lambda for all outputs; scaled-teacher units)
+ * The Gram matrix is formed once per pilot, not once per candidate.
+ *   ridge   [n_groups][n_ridge] float64, device; 1 <= n_ridge <= 16
+ *   status  [n_groups][n_ridge]: 0 ok, 1 a pivot of the factorisation was rejected, 2 lambda negative or not finite;
+ *           score is +inf where status is not 0
+ *   choice  [n_groups]: the lowest l with the smallest finite score among the entries with status 0, -1 if none
+ *   W_out   [n_groups][n_out][cols]: the ridge solution at ridge[g][choice[g]], all zero where choice is -1
+ * A group's score, choice and W_out are bitwise the same alone and inside any batch.
+ * Shapes: min(rows, cols) <= 128 (else -2, esn_last_error() names the limit), n_out <= 8 and n_ridge <= 16 (else -1).
+ * The workspace (esn_readout_ridge_loo_workspace_bytes, 8-byte aligned) is always needed. */
+size_t esn_readout_ridge_loo_workspace_bytes(int n_groups, int n_ridge, int rows, int cols);
+int esn_readout_ridge_loo_batch(const double* E, const double* D, int n_groups, int T,
+                                int transient, int cols, int n_out,
+                                const double* t_scale, const double* t_shift,
+                                const double* ridge, int n_ridge,
+                                double* W_out, double* score, int* choice, int* status,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_groups, int T,
+                                    int transient, int cols, int n_out,
+                                    const double* t_scale, const double* t_shift,
+                                    const double* ridge, int n_ridge,
+                                    double* W_out, double* score, int* choice, int* status,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused detector tail: Y [B][N][2 N_t] time-domain ESN outputs
  * -> (1/N) FFT_N / sqrt(Pi[group]) -> nearest unit-power square-QAM point ->
  * natural-binary LSB-first bits -> compare with tx_bits [B][N*m][N_t] (uint8) ->

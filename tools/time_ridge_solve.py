@@ -7,6 +7,8 @@ median (and minimum) of the repeats; the candidates alternate inside every repea
     pinv           esn_readout_solve_chol_batch_f32 of this tree
     ridge L = 1    esn_readout_solve_chol_ridge_batch_f32, one lambda per system
     ridge L = 8    ... eight lambdas per system in one launch (one workgroup per (system, lambda))
+    loo L = 1      esn_readout_ridge_loo_batch_f32 (csrc/esn_loo.hip): one candidate, its score, W_out
+    loo L = 8      ... eight candidates per system: one Gram pass, eight factorisations and scores, one W_out
 
     python tools/time_ridge_solve.py [--parent-lib path/to/libesn_hip.so] [--groups 2048] [--repeats 15]
 """
@@ -58,11 +60,29 @@ def main():
         return lambda: check(lib.esn_readout_solve_chol_ridge_batch_f32(
             ptr(E), ptr(D), G, T, tr, cols, n_out, None, None, ptr(r), nl, ptr(W), ptr(s), None, 0, st), name)
 
+    def loo_call(nl, name, lam):
+        W = torch.empty((G, n_out, cols), dtype=torch.float64, device="cuda")
+        sc = torch.empty((G, nl), dtype=torch.float64, device="cuda")
+        ch = torch.empty(G, dtype=torch.int32, device="cuda")
+        s = torch.empty((G, nl), dtype=torch.int32, device="cuda")
+        # distinct candidates around lam, half a decade apart
+        r = (lam * 10.0 ** (0.5 * torch.arange(nl, dtype=torch.float64, device="cuda"))).expand(G, nl).contiguous()
+        wb = lib.esn_readout_ridge_loo_workspace_bytes(G, nl, rows, cols)
+        ws = torch.empty(wb, dtype=torch.uint8, device="cuda")
+        outs[name] = (W, s)
+        keep[name] = (r, sc, ch, ws)
+        return lambda: check(lib.esn_readout_ridge_loo_batch_f32(
+            ptr(E), ptr(D), G, T, tr, cols, n_out, None, None, ptr(r), nl, ptr(W), ptr(sc), ptr(ch), ptr(s), ptr(ws), wb,
+            st), name)
+
+    keep = {}
     if a.parent_lib:
         fns["parent pinv"] = pinv_call(C.CDLL(os.path.abspath(a.parent_lib)), "parent pinv")
     fns["pinv"] = pinv_call(lib, "pinv")
     fns["ridge L = 1"] = ridge_call(1, "ridge L = 1", a.lam)
     fns["ridge L = 8"] = ridge_call(8, "ridge L = 8", a.lam)
+    fns["loo L = 1"] = loo_call(1, "loo L = 1", a.lam)
+    fns["loo L = 8"] = loo_call(8, "loo L = 8", a.lam)
     print(f"device {_lib.device_info()['arch']}  {G} systems of {rows} x {cols}, float32 E, n_out {n_out}, "
           f"lambda {a.lam:g}  repeats {a.repeats} (median [min .. max])")
     ms = timed(fns, warmup=3, repeats=a.repeats)
@@ -79,6 +99,9 @@ def main():
     W0()
     torch.cuda.synchronize()
     print("  ridge(lambda = 0) == pinv bitwise:", bool(torch.equal(outs["ridge 0"][0][:, 0], outs["pinv"][0])))
+    w_r, w_l = outs["ridge L = 1"][0][:, 0], outs["loo L = 1"][0]
+    print(f"  loo L = 1 against ridge L = 1: max |dW| / max |W| = {float((w_l - w_r).abs().max() / w_r.abs().max()):.2e}")
+    print("  loo L = 8 choices:", torch.bincount(keep["loo L = 8"][2].clamp(min=0).long(), minlength=8).tolist())
 
 
 if __name__ == "__main__":
