@@ -67,6 +67,49 @@ class ReservoirBank:
         self.in_scale = self.in_shift = self.t_scale = self.t_shift = None
         self.W_out = None
 
+    def set_weights(self, W, W_in, W_feedb):
+        """Swap the weight sets: [n_res, n_res] / [n_res, n_in] / [n_res, n_out], or each with a leading [n_wsets]
+        axis.  Device tensors are taken as they are (float64, this device: no host round trip), anything else is
+        copied.  The number of sets may change; the packed weights of every precision are dropped and packed again
+        at the next call that needs them.  The read-out and the scalings stay."""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            W, W_in, W_feedb = (_as_dev(x, torch, self.device) for x in (W, W_in, W_feedb))
+        if W.ndim == 2:
+            W, W_in, W_feedb = W[None], W_in[None], W_feedb[None]
+        n_wsets, n = W.shape[0], self.n_reservoir
+        if tuple(W.shape[1:]) != (n, n) or tuple(W_in.shape) != (n_wsets, n, self.n_inputs) \
+                or tuple(W_feedb.shape) != (n_wsets, n, self.n_outputs):
+            raise ValueError("weight shapes do not match (n_wsets, n_reservoir, ...)")
+        self.n_wsets = n_wsets
+        self.shape = Shape(n, self.n_inputs, self.n_outputs, self.shape.teacher_forcing, n_wsets, self.leak_rate)
+        self._W, self._W_in, self._W_fb = W.contiguous(), W_in.contiguous(), W_feedb.contiguous()
+        self._packed = {}
+
+    @property
+    def weights(self):
+        """(W [n_wsets, n_res, n_res], W_in [n_wsets, n_res, n_in], W_fb [n_wsets, n_res, n_out]): float64, device."""
+        return self._W, self._W_in, self._W_fb
+
+    @classmethod
+    def generate(cls, n_inputs, n_outputs, n_reservoir, spectral_radius=0.9, sparsity=0.1, seed=0, first_set=0,
+                 n_sets=1, uniforms=None, teacher_forcing=True, noise=0.001, device=None, leak_rate=1.0):
+        """A bank whose weight sets are drawn, measured and scaled on the device (reservoirs.generate): the sets with
+        global index first_set .. first_set + n_sets - 1, set s in slot s % n_sets, which is the set the kernels pick
+        for global group s."""
+        from . import reservoirs
+        torch = _lib.require_gpu()
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        W, W_in, W_fb, radius, _ = reservoirs.generate(n_inputs, n_outputs, n_reservoir, spectral_radius, sparsity, seed,
+                                                       first_set=first_set, n_sets=n_sets, uniforms=uniforms, device=dev)
+        n = int(n_reservoir)
+        # (placeholders of one set for __init__, which keeps its signature; the device tensors replace them at once)
+        bank = cls(n_inputs, n_outputs, n, np.zeros((n, n)), np.zeros((n, int(n_inputs))), np.zeros((n, int(n_outputs))),
+                   teacher_forcing=teacher_forcing, noise=noise, device=dev, leak_rate=leak_rate)
+        bank.set_weights(W, W_in, W_fb)
+        bank.generated_radius = radius          # of the unscaled W, float64 [n_sets] on the device
+        return bank
+
     # ------------------------------------------------------------------ packing
     def tile_frames(self, precision):
         rc = self.lib.esn_tile_frames(PRECISIONS[precision], C.byref(self.shape))

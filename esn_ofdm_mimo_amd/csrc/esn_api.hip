@@ -639,6 +639,57 @@ int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_group
                             stream);
 }
 
+// ---- reservoirs drawn on the device (esn_reservoir.hip) ------------------------------------------------------------
+static const int kResMaxN = 4096;           // n_res: element counters of the draw and the tile grid stay far inside int
+
+int esn_gen_reservoirs(int n_res, int n_in, int n_out, double sparsity, uint64_t seed, uint64_t first_set, int n_sets,
+                       const double* uniforms, double* W, double* W_in, double* W_fb, void* stream) {
+    const char* who = "esn_gen_reservoirs";
+    if (!W || !W_in || !W_fb) return fail(-1, "%s: null pointer", who);
+    if (n_res <= 0 || n_in <= 0 || n_out <= 0 || n_sets <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_res > kResMaxN || n_in > kResMaxN || n_out > kResMaxN)
+        return fail(-1, "%s: n_res, n_in and n_out are served up to %d", who, kResMaxN);
+    if (!(sparsity >= 0.0 && sparsity <= 1.0)) return fail(-1, "%s: sparsity = %g is outside [0, 1]", who, sparsity);
+    return hip_fail(launch_gen_reservoirs(n_res, n_in, n_out, sparsity, seed, first_set, n_sets, uniforms, W, W_in,
+                                          W_fb, (hipStream_t)stream), who);
+}
+
+size_t esn_spectral_radius_workspace_bytes(int n_sets, int n_res) {
+    if (n_sets <= 0 || n_res <= 0) return 0;
+    if (n_res > kResMaxN) {
+        fail(-1, "esn_spectral_radius_workspace_bytes: n_res = %d, served up to %d", n_res, kResMaxN);
+        return 0;
+    }
+    return sizeof(double) * specrad_work_doubles(n_res) * (size_t)n_sets;
+}
+
+int esn_spectral_radius_batch(const double* W, int n_sets, int n_res, int n_squarings, double* radius, int* status,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "esn_spectral_radius_batch";
+    if (!W || !radius || !status) return fail(-1, "%s: null pointer", who);
+    if (n_sets <= 0 || n_res <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_res > kResMaxN) return fail(-1, "%s: n_res = %d, served up to %d", who, n_res, kResMaxN);
+    if (n_squarings < 4 || n_squarings > 32)
+        return fail(-1, "%s: n_squarings = %d, 4 to 32 are served", who, n_squarings);
+    const size_t need = esn_spectral_radius_workspace_bytes(n_sets, n_res);
+    if (!workspace || workspace_bytes < need)
+        return fail(-1, "%s: workspace holds %zu bytes, esn_spectral_radius_workspace_bytes says %zu", who,
+                    workspace ? workspace_bytes : (size_t)0, need);
+    if ((uintptr_t)workspace & 7) return fail(-1, "%s: the workspace must be 8-byte aligned", who);
+    return hip_fail(launch_spectral_radius(W, n_sets, n_res, n_squarings, radius, status, workspace,
+                                           (hipStream_t)stream), who);
+}
+
+int esn_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const double* radius, const int* status,
+                         void* stream) {
+    const char* who = "esn_scale_reservoirs";
+    if (!W || !radius || !status) return fail(-1, "%s: null pointer", who);
+    if (n_sets <= 0 || n_res <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_res > kResMaxN) return fail(-1, "%s: n_res = %d, served up to %d", who, n_res, kResMaxN);
+    if (!(rho > 0.0 && rho <= 1.7976931348623157e308)) return fail(-1, "%s: rho = %g must be positive and finite", who, rho);
+    return hip_fail(launch_scale_reservoirs(W, n_sets, n_res, rho, radius, status, (hipStream_t)stream), who);
+}
+
 static int detect_common(const char* who, bool io32, const void* Y, int n_frames, int frames_per_group, int n_sub,
                          int n_t, int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
                          long long* bit_count, double* X_hat, void* stream) {

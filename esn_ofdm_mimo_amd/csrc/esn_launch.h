@@ -83,6 +83,16 @@ size_t ridge_loo_work_doubles();
 int launch_ridge_loo(const double* E, const float* E32, const double* D, int n_groups, int T, int transient, int cols,
                      int n_out, const double* t_scale, const double* t_shift, const double* ridge, int n_ridge,
                      double* W_out, double* score, int* choice, int* status, void* workspace, hipStream_t stream);
+// esn_reservoir.hip: reservoirs drawn, measured (spectral radius by repeated squaring) and rescaled on the device; the
+// workspace holds specrad_work_doubles(n_res) doubles per matrix (two padded images, the per-tile norms, the log)
+size_t specrad_work_doubles(int n_res);
+int launch_gen_reservoirs(int n_res, int n_in, int n_out, double sparsity, uint64_t seed, uint64_t first_set,
+                          int n_sets, const double* uniforms, double* W, double* W_in, double* W_fb,
+                          hipStream_t stream);
+int launch_spectral_radius(const double* W, int n_sets, int n_res, int n_squarings, double* radius, int* status,
+                           void* workspace, hipStream_t stream);
+int launch_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const double* radius, const int* status,
+                            hipStream_t stream);
 // esn_gen.hip
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);

@@ -25,6 +25,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from . import reservoirs as _reservoirs
 from .batched import ReservoirBank
 from ._lib import check, ptr
 
@@ -331,8 +332,22 @@ class DetectorSweep:
 
     def __init__(self, params: LinkParams, n_reservoir=512, spectral_radius=0.9, sparsity=0.1, noise=0.001,
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
-                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None):
-        """ridge (extension; None = the reference's pinv fit): lambda of the ridge read-out (ReservoirBank.solve), a
+                 rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None,
+                 radius="host"):
+        """reservoirs: "shared" (one reservoir for every block), "per_block" (block b uses set b % pool of a pool
+        drawn here) or "fresh" (the reference's own rule, SURVEY F5: every coherence block gets a reservoir of its
+        own, drawn on the device by reservoirs.generate and keyed by (seed, global block index) -- the same at every
+        Eb/No point, as the pool is, and the same for any chunking and world size; each chunk draws its blocks'
+        reservoirs and swaps them into the bank before it trains).  With "fresh" the default chunk of run() is also
+        bounded by memory: 2 GiB for the float64 W, the two squaring images and the packed weights of a chunk, counted
+        as 40 n_reservoir^2 bytes per block (about 200 blocks at n_reservoir = 512); see default_chunk_blocks.
+
+        radius: "host" (default: draw_reservoir, np.linalg.eigvals per set, bit for bit what it always was) or
+        "device" for the "shared" and "per_block" modes: the same RandomState uniforms, drawn on the host in the same
+        order, are scaled by the device's spectral radius (reservoirs.generate(uniforms=...)) -- W within 1e-6 of the
+        host's, without pool x eigvals in this constructor (8.8 s per set at n_reservoir = 2048).
+
+        ridge (extension; None = the reference's pinv fit): lambda of the ridge read-out (ReservoirBank.solve), a
         float or a callable ebno_db -> float (the best lambda moves with Eb/No and n_reservoir).
 
         ridge_grid (extension): a sequence of L candidates; every block takes the one with the smallest
@@ -363,13 +378,60 @@ class DetectorSweep:
         self.seed = seed
         self.src = FrameSource(params, device, seed)
         self.device = self.src.device
+        if radius not in ("host", "device"):
+            raise ValueError(f"radius must be 'host' or 'device', not {radius!r}")
+        self.reservoirs = reservoirs
+        self._res_args = (self.n_in, self.n_out, int(n_reservoir), float(spectral_radius), float(sparsity))
+        self.reservoir_seed = seed * 7919 + 17
+        if reservoirs == "fresh":
+            # block 0's reservoir until the first chunk swaps its own in
+            self.bank = ReservoirBank.generate(*self._res_args, seed=self.reservoir_seed, first_set=0, n_sets=1,
+                                               teacher_forcing=True, noise=noise, device=self.device)
+            self.n_sets = 1
+            return
         n_sets = 1 if reservoirs == "shared" else int(pool)
+        if radius == "device":
+            sets = [self._device_scaled(self.reservoir_seed + i) for i in range(n_sets)]
+            self.bank = ReservoirBank(self.n_in, self.n_out, n_reservoir, np.zeros((n_reservoir, n_reservoir)),
+                                      np.zeros((n_reservoir, self.n_in)), np.zeros((n_reservoir, self.n_out)),
+                                      teacher_forcing=True, noise=noise, device=self.device)
+            self.bank.set_weights(*(torch.cat([w[k] for w in sets]) for k in range(3)))
+            self.n_sets = n_sets
+            return
         ws = [draw_reservoir(self.n_in, self.n_out, n_reservoir, spectral_radius, sparsity, seed * 7919 + 17 + i)
               for i in range(n_sets)]
         self.bank = ReservoirBank(self.n_in, self.n_out, n_reservoir, np.stack([w[0] for w in ws]),
                                   np.stack([w[1] for w in ws]), np.stack([w[2] for w in ws]),
                                   teacher_forcing=True, noise=noise, device=self.device)
         self.n_sets = n_sets
+
+    def _device_scaled(self, seed):
+        """radius="device": the uniforms draw_reservoir(seed) consumes, in its order, scaled on the device."""
+        n_in, n_out, n, rho, sparsity = self._res_args
+        rs = np.random.RandomState(seed)
+        u = np.concatenate([rs.rand(n, n).ravel(), rs.rand(n, n).ravel(), rs.rand(n, n_in).ravel(),
+                            rs.rand(n, n_out).ravel()])
+        return _reservoirs.generate(n_in, n_out, n, rho, sparsity, 0, uniforms=u[None], device=self.device)[:3]
+
+    # "fresh": bytes per block of a chunk -- float64 W (8 n^2), two squaring images (16 n^2, padded to 64) and the packed
+    # weights of the fit and the detect precision (at most 8 n^2 each) -- and the budget they are held to
+    FRESH_BYTES_PER_BLOCK_N2, FRESH_BUDGET_BYTES = 40, 2 << 30
+
+    def _swap_in_fresh(self, first_block, n_blocks, check):
+        """The reservoirs of global blocks [first_block, first_block + n_blocks) into the bank: block b in slot
+        b % n_blocks, which is the set the kernels pick for it under group_offset = first_block.  Returns the int32
+        status [n_blocks] on the device; `check` reads it on the host and raises for a set that could not be scaled."""
+        W, W_in, W_fb, _, status = _reservoirs.generate(*self._res_args, seed=self.reservoir_seed,
+                                                        first_set=first_block, n_sets=n_blocks, device=self.device,
+                                                        check_status=check)
+        self.bank.set_weights(W, W_in, W_fb)
+        self.n_sets = n_blocks
+        return status
+
+    def _require_block_independent_bank(self, who):
+        if self.reservoirs == "fresh":
+            raise ValueError(f"{who} trains through the bank as it stands, which under reservoirs='fresh' holds one "
+                             "block's reservoir only: build the sweep with reservoirs='shared' or 'per_block'")
 
     def set_snr(self, ebno_db, n_groups):
         torch, p = self.torch, self.p
@@ -466,7 +528,10 @@ class DetectorSweep:
         info = _lib.device_info()
         tile = self.bank.tile_frames(self.precision)
         fpad = ((frames_per_block + 15) // 16) * 16
-        return max(1, (5 * info["cu_count"] * tile) // fpad)
+        chunk = max(1, (5 * info["cu_count"] * tile) // fpad)
+        if self.reservoirs == "fresh":      # one reservoir per block lives on the device for the length of a chunk
+            chunk = min(chunk, max(1, self.FRESH_BUDGET_BYTES // (self.FRESH_BYTES_PER_BLOCK_N2 * self.n_res ** 2)))
+        return chunk
 
     def _chunk(self, ebno, si, ids, F, repair):
         """One launch group: generate, train, detect the contiguous global blocks `ids`; returns the device
@@ -476,6 +541,9 @@ class DetectorSweep:
         g = len(ids)
         data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128")
         self.set_snr(ebno, g)
+        unscaled = None
+        if self.reservoirs == "fresh":      # (no host read unless `repair`: an unscalable set counts as a flagged fit)
+            unscaled = self._swap_in_fresh(ids[0], g, check=repair).ne(0).sum().to(torch.int64)
         if self.train_ebno is not None:
             # the "train@fixed Eb/No" ESN of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:181-183,347-367):
             # pilot generated at the training Eb/No over the SAME taps, input scaling of that Eb/No at train AND
@@ -505,14 +573,18 @@ class DetectorSweep:
                 self.bank.raise_if_harvest_timed_out()
             else:
                 flagged = flagged + ht.ne(0).sum().to(torch.int64)
+        if unscaled is not None and not repair:
+            flagged = flagged + unscaled
         head = torch.stack([err.sum(), nb.sum(), flagged])
         return head if picks is None else torch.cat([head, picks])
 
     def run(self, ebno_list, blocks_per_snr, frames_per_block=None, chunk_blocks=None, dist=None):
         """Returns (BER[n_snr], counters [n_snr, 2]) -- identical on every rank and for every world size and
         chunking (contiguous block ranges per rank; every stream keyed by global indices).  No host
-        synchronisation inside an Eb/No point: the Cholesky status flags are summed on the device and read once
-        per point; a chunk with a flagged fit (none on any run so far) is redone with the QR repair."""
+        synchronisation inside an Eb/No point: the Cholesky status flags (and, with reservoirs="fresh", the flags of
+        reservoirs whose radius could not be measured) are summed on the device and read once per point; a chunk with
+        a flagged fit (none on any run so far) is redone with the QR repair, and that pass raises EsnHipError for an
+        unscalable fresh reservoir."""
         torch = self.torch
         F = frames_per_block or self.p.coherence_symbols
         chunk = int(chunk_blocks or self.default_chunk_blocks(F))
@@ -544,6 +616,7 @@ def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=No
     blocks (the reference: the first 30 % of the symbols, :266,:476-482,:513-523) and sum-product
     decoding of the rest.  Returns dict(ESN_uncoded, MMSE_uncoded, ESN_coded, MMSE_coded, a_esn, ...).
     Frames and the ESN leg stay float64 / complex128 whatever sweep.io says: the MMSE leg reads complex128."""
+    sweep._require_block_independent_bank("coded_ber_point")
     torch, p, src = sweep.torch, sweep.p, sweep.src
     F = frames_per_block or p.coherence_symbols
     G = n_blocks
@@ -592,6 +665,9 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     capacity_bits_per_sc, frac_rank_ge_full, cond_p50, cond_p90 (FrameSource.channel_metrics on H_true).
     Frames and the ESN legs stay float64 / complex128 whatever the sweeps' io says: the LS / MMSE / ZF legs read
     complex128."""
+    sweep._require_block_independent_bank("block_fading_point")
+    if fixed_sweep is not None:
+        fixed_sweep._require_block_independent_bank("block_fading_point")
     torch, p, src = sweep.torch, sweep.p, sweep.src
     L = p.coherence_symbols
     F, G = L - 1, n_blocks

@@ -379,6 +379,41 @@ int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_group
                                     double* W_out, double* score, int* choice, int* status,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Reservoirs drawn on the device (an extension: the reference draws them on the host, pyESN.py:93-109, once per
+ * coherence block).  All float64, device pointers, explicit stream, no allocation; every check returns -1 before any
+ * HIP call and esn_last_error() names the function and the limit.  These are additions: the ABI version is unchanged.
+ *
+ * esn_gen_reservoirs  the sets with global index first_set .. first_set + n_sets - 1, UNSCALED:
+ *     W [n_sets][n_res][n_res] = u - 0.5, zero where a second uniform < sparsity;
+ *     W_in [n_sets][n_res][n_in] = 2u - 1;  W_fb [n_sets][n_res][n_out] = 2u - 1.
+ *   The set with global index s is written to slot s % n_sets: the recurrence kernels pick weight set
+ *   (group_offset + g) % n_wsets, so a chunk of blocks [b0, b0 + n) generated with first_set = b0, n_sets = n is
+ *   aligned with group_offset = b0.
+ *   uniforms == NULL: Philox4x32-10 keyed by (seed, global set, purpose, element) -- set s is the same bits in any
+ *   batch, chunk or rank.  uniforms != NULL: [n_sets][2 n_res^2 + n_res n_in + n_res n_out] values in [0, 1), the i-th
+ *   row for set first_set + i, in the reference's draw order rand(n,n), mask rand(n,n), rand(n,n_in), rand(n,n_out);
+ *   the results are then bitwise the NumPy expressions on those values.
+ *   0 <= sparsity <= 1; n_res, n_in, n_out <= 4096.
+ *
+ * esn_spectral_radius_batch  radius[s] of W [n_sets][n_res][n_res] by repeated squaring, |.| the Frobenius norm:
+ *     f_0 = |W|, A_0 = W / f_0, l_0 = ln f_0
+ *     k = 1..K:  B = A_{k-1} A_{k-1};  f_k = |B|;  l_k = 2 l_{k-1} + ln f_k;  A_k = B / f_k
+ *     radius = exp((l_{K-1} + ln f_K) / 2^(K-1))
+ *   K = n_squarings in 4..32 (24: within 1e-7 relative of max|eig| on the reference's matrices).  status[s] = 1 and
+ *   radius[s] = 0 when some f_k is zero or not finite (a zero or nilpotent W); the other matrices are unaffected.  The
+ *   sums run in an order fixed by n_res alone: a matrix's radius is bitwise the same alone and inside any batch.
+ *   The workspace (esn_spectral_radius_workspace_bytes, 8-byte aligned) holds two zero-padded images per matrix; the
+ *   query answers 0 for n_sets <= 0, n_res <= 0 or n_res > 4096 (the last with the limit in esn_last_error()).
+ *
+ * esn_scale_reservoirs  W[s] *= rho / radius[s] where status[s] == 0; a flagged set is left as it is. */
+int esn_gen_reservoirs(int n_res, int n_in, int n_out, double sparsity, uint64_t seed, uint64_t first_set, int n_sets,
+                       const double* uniforms, double* W, double* W_in, double* W_fb, void* stream);
+size_t esn_spectral_radius_workspace_bytes(int n_sets, int n_res);
+int esn_spectral_radius_batch(const double* W, int n_sets, int n_res, int n_squarings, double* radius, int* status,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int esn_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const double* radius, const int* status,
+                         void* stream);
+
 /* Fused detector tail: Y [B][N][2 N_t] time-domain ESN outputs
  * -> (1/N) FFT_N / sqrt(Pi[group]) -> nearest unit-power square-QAM point ->
  * natural-binary LSB-first bits -> compare with tx_bits [B][N*m][N_t] (uint8) ->

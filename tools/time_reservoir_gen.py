@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""What a reservoir costs on the device and on the host, and what `reservoirs="fresh"` costs a sweep.
+
+For every N_res (default 100 300 512 2048):
+    device   generate + spectral radius (24 squarings) + scale through reservoirs.generate, per reservoir, for a batch
+             of 1 and for a full chunk (the memory-bounded default of DetectorSweep(reservoirs="fresh"), at most
+             --max-chunk); device events, warmed, median of the repeats
+    host     montecarlo.draw_reservoir (np.linalg.eigvals) on the CPUs this process is given, median
+    error    |device radius - max|eigvals|| / max|eigvals| on the matrix the device drew (copied to the host)
+Then DetectorSweep.run symbols/s and BER at 6, 12 and 21 dB for "shared", "per_block" (pool of 8) and "fresh" at the
+headline configuration (4x8 link, N_res = 512, fp16 fit and predict).
+
+    python tools/time_reservoir_gen.py [--out profiles/reservoir_gen_time.txt] [--skip-sweep] [--host-2048]
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from esn_ofdm_mimo_amd import _lib, reservoirs  # noqa: E402
+from esn_ofdm_mimo_amd.montecarlo import DetectorSweep, LinkParams, draw_reservoir  # noqa: E402
+
+
+def device_ms(n_res, n_sets, repeats, warmup=2):
+    """sorted ms of generate(n_sets) (draw + radius + scale; check_status=False: no host read inside the events)"""
+    def call():
+        return reservoirs.generate(16, 8, n_res, 0.9, 0.1, 5, first_set=0, n_sets=n_sets, check_status=False)
+    for _ in range(warmup):
+        call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        call()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return sorted(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n-res", type=int, nargs="+", default=[100, 300, 512, 2048])
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--max-chunk", type=int, default=256)
+    ap.add_argument("--host-repeats", type=int, default=3)
+    ap.add_argument("--host-2048", action="store_true", help="time the host draw at N_res >= 2048 too (8.8 s each)")
+    ap.add_argument("--skip-sweep", action="store_true")
+    ap.add_argument("--blocks", type=int, default=0, help="blocks per Eb/No point of the sweeps (0: two default chunks)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"device {_lib.device_info()['arch']}  CPUs {len(os.sched_getaffinity(0))} (BLAS threads: OMP_NUM_THREADS={os.environ.get('OMP_NUM_THREADS', 'unset')})  repeats {a.repeats} (median [min .. max])")
+    say("N_res  batch   device ms/reservoir                host draw_reservoir s   radius rel. error vs eigvals")
+    for n in a.n_res:
+        budget = DetectorSweep.FRESH_BUDGET_BYTES // (DetectorSweep.FRESH_BYTES_PER_BLOCK_N2 * n * n)
+        full = max(1, min(a.max_chunk, budget))
+        host = None
+        if n < 2048 or a.host_2048:
+            ts = []
+            for r in range(a.host_repeats):
+                t0 = time.perf_counter()
+                draw_reservoir(16, 8, n, 0.9, 0.1, 100 + r)
+                ts.append(time.perf_counter() - t0)
+            host = sorted(ts)[len(ts) // 2]
+        err = None
+        if n < 2048 or a.host_2048:
+            W, _, _, radius, status = reservoirs.generate(16, 8, n, 0.9, 0.1, 5, first_set=0, n_sets=1)
+            w = W[0].cpu().numpy() * (float(radius[0].cpu()) / 0.9)              # the unscaled draw
+            eig = float(np.max(np.abs(np.linalg.eigvals(w))))
+            err = abs(float(radius[0].cpu()) - eig) / eig
+        for s in sorted({1, full}):
+            ms = device_ms(n, s, a.repeats)
+            med = ms[len(ms) // 2]
+            say(f"{n:5d}  {s:5d}   {med / s:9.4f} [{ms[0] / s:9.4f} .. {ms[-1] / s:9.4f}]   "
+                f"{'-' if host is None else f'{host:8.3f}':>12s}            {'-' if err is None else f'{err:.2e}'}")
+    if not a.skip_sweep:
+        ebno = [6, 12, 21]
+        prm = LinkParams()
+        F = prm.coherence_symbols
+        say(f"DetectorSweep.run at the headline configuration: N_res 512, fp16 fit and predict, {F} frames per block, "
+            f"Eb/No {ebno} dB")
+        for name, kw in (("shared", dict(reservoirs="shared")), ("per_block", dict(reservoirs="per_block", pool=8)),
+                         ("fresh", dict(reservoirs="fresh"))):
+            t0 = time.perf_counter()
+            sw = DetectorSweep(prm, n_reservoir=512, noise=0.001, seed=1234, precision="f16", fit_precision="f16", **kw)
+            t_init = time.perf_counter() - t0
+            chunk = sw.default_chunk_blocks(F)
+            blocks = a.blocks or 2 * chunk
+            sw.run(ebno[:1], min(blocks, chunk))                                  # warm-up: allocations, first launches
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ber, cnt = sw.run(ebno, blocks)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            sym = len(ebno) * blocks * F
+            say(f"  {name:10s} constructor {t_init:7.2f} s   chunk {chunk:5d}   blocks/point {blocks:6d}   "
+                f"{sym / dt / 1e6:8.3f} M symbols/s   BER " + "  ".join(f"{e} dB {b:.4e}" for e, b in zip(ebno, ber)))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
