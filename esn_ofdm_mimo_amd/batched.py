@@ -36,6 +36,30 @@ def _as_dev(x, torch, device, dtype=None):
     return t.contiguous()
 
 
+_HARVEST_TIMED_OUT = ("harvest cluster kernel: a workgroup timed out waiting for the others "
+                      "(the device is oversubscribed); the extended states are invalid")
+
+
+def _lambdas(torch, device, lam, g, grid=False):
+    """The lambdas of G groups -- `ridge` (a scalar, [G] or [G, L]) or, with `grid`, `ridge_grid` (L candidates or
+    [G, L]), as an array, a sequence or a tensor -> (device float64 [G, L], whether the caller gave no L axis)."""
+    flat = not grid and (lam.ndim if isinstance(lam, torch.Tensor) else np.ndim(lam)) < 2
+    if isinstance(lam, torch.Tensor):
+        r = lam.to(device=device, dtype=torch.float64)
+    elif flat and np.ndim(lam) == 0:
+        r = torch.full((g, 1), float(lam), dtype=torch.float64, device=device)   # (no host copy)
+    else:
+        r = torch.as_tensor(np.array(lam, dtype=np.float64), device=device)
+    if r.ndim == 1:
+        r = r[None, :].expand(g, r.shape[0]) if grid else r[:, None]
+    elif r.ndim == 0 and not grid:
+        r = r.reshape(1, 1).expand(g, 1)
+    if r.ndim != 2 or r.shape[0] != g or (r.shape[1] < 1 and not grid):
+        raise ValueError(f"ridge_grid must hold L candidates or be [G, L] with G = {g}, not {tuple(r.shape)}" if grid else
+                         f"ridge must be a scalar, [G] or [G, L] with G = {g}, not {tuple(r.shape)}")
+    return r.contiguous(), flat
+
+
 class ReservoirBank:
     def __init__(self, n_inputs, n_outputs, n_reservoir, W, W_in, W_feedb,
                  teacher_forcing=True, noise=0.001, device=None, leak_rate=1.0):
@@ -66,6 +90,10 @@ class ReservoirBank:
         self._packed_wout = {}
         self.in_scale = self.in_shift = self.t_scale = self.t_shift = None
         self.W_out = None
+        # what the last harvest / solve / fit left (device tensors; None until then, see those methods)
+        self.harvest_timeout = self._cluster_err = self.last_solve_status = None
+        self.last_ridge_choice = self.last_ridge_scores = self.last_ridge_status = None
+        self.last_ridge_grid = self.last_ridge_lambda = self.fit_ridge = self.fit_status = None
 
     def set_weights(self, W, W_in, W_feedb):
         """Swap the weight sets: [n_res, n_res] / [n_res, n_in] / [n_res, n_out], or each with a leading [n_wsets]
@@ -196,58 +224,68 @@ class ReservoirBank:
             # the two cluster kernels wait for their peers with bounded spins and raise an error word instead of hanging
             path = _lib.recur_path(True, precision, self.shape, g, have_workspace=wbytes > 0)
             if path == "cluster_f64":
-                self._cluster_err = ws[wbytes - 64:wbytes - 60]
-            self.harvest_timeout = ws[wbytes - 64:wbytes - 60].view(torch.int32) if path == "harvest_cluster" else None
+                self._cluster_err = self._error_word(ws, wbytes)
+            self.harvest_timeout = self._error_word(ws, wbytes) if path == "harvest_cluster" else None
         return E
 
     def raise_if_harvest_timed_out(self):
         """Host-synchronising check of the last fp16/bf16 harvest on the cluster kernel (see harvest)."""
-        w = getattr(self, "harvest_timeout", None)
-        if w is not None and int(w.item()) != 0:
-            raise _lib.EsnHipError("harvest cluster kernel: a workgroup timed out waiting for the others "
-                                   "(the device is oversubscribed); the extended states are invalid")
+        if self.harvest_timeout is not None and int(self.harvest_timeout.item()) != 0:
+            raise _lib.EsnHipError(_HARVEST_TIMED_OUT)
 
     def chol_fits(self, rows, cols):
         """Shapes the Cholesky solve covers (esn_readout_solve_chol_batch): Gram dimension up to 128 in LDS,
         up to 512 out of a workspace."""
         return min(rows, cols) <= 512 and self.n_outputs <= 8
 
-    def _ridge_arg(self, ridge, g):
-        """ridge (float, [G] or [G, L] array / tensor) -> (device float64 [G, L], whether the caller gave no L axis)."""
-        torch = self.torch
-        flat = (ridge.ndim if isinstance(ridge, torch.Tensor) else np.ndim(ridge)) < 2
-        if isinstance(ridge, torch.Tensor):
-            r = ridge.to(device=self.device, dtype=torch.float64)
-        elif np.ndim(ridge) == 0:
-            r = torch.full((g, 1), float(ridge), dtype=torch.float64, device=self.device)   # (no host copy)
-        else:
-            r = torch.as_tensor(np.array(ridge, dtype=np.float64), device=self.device)
-        if r.ndim == 0:
-            r = r.reshape(1, 1).expand(g, 1)
-        elif r.ndim == 1:
-            r = r[:, None]
-        if r.ndim != 2 or r.shape[0] != g or r.shape[1] < 1:
-            raise ValueError(f"ridge must be a scalar, [G] or [G, L] with G = {g}, not {tuple(r.shape)}")
-        return r.contiguous(), flat
-
     LOO_MAX_GRAM, LOO_MAX_GRID = 128, 16      # esn_readout_ridge_loo_batch: Gram dimension, candidates per group
+
+    # (kind, lambdas given, float32 E) -> (entry point, workspace query, the bank's scratch buffer; None: one per call)
+    _READOUT = {
+        ("qr", False, False): ("esn_readout_solve_batch", "esn_readout_solve_workspace_bytes", None),
+        ("qr", True, False): ("esn_readout_solve_ridge_batch", "esn_readout_solve_ridge_workspace_bytes", None),
+        ("chol", False, False): ("esn_readout_solve_chol_batch", "esn_readout_chol_workspace_bytes", "_chol_ws"),
+        ("chol", False, True): ("esn_readout_solve_chol_batch_f32", "esn_readout_chol_workspace_bytes", "_chol_ws"),
+        ("chol", True, False): ("esn_readout_solve_chol_ridge_batch", "esn_readout_chol_ridge_workspace_bytes", "_chol_ws"),
+        ("chol", True, True): ("esn_readout_solve_chol_ridge_batch_f32", "esn_readout_chol_ridge_workspace_bytes", "_chol_ws"),
+        ("loo", True, False): ("esn_readout_ridge_loo_batch", "esn_readout_ridge_loo_workspace_bytes", "_loo_ws"),
+        ("loo", True, True): ("esn_readout_ridge_loo_batch_f32", "esn_readout_ridge_loo_workspace_bytes", "_loo_ws"),
+    }
+
+    def _readout(self, E, D, transient, kind, lam, t_scale, t_shift):
+        """The one way into the read-out kernels.  kind "qr", "chol" or "loo" (leave-one-out among the lambdas); lam
+        None (pinv) or device float64 [G, L]; t_scale / t_shift the teacher scalings of these G groups.  Returns
+        (W_out, status) with an L axis after G where lam is given, for "loo" (W_out [G, n_out, cols], status [G, L],
+        scores [G, L], choice [G])."""
+        torch, lib, n_out = self.torch, self.lib, self.n_outputs
+        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32       # as written by harvest(e_dtype="f32")
+        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
+        if e32 and kind == "qr":
+            E, e32 = E.double(), False                                      # the QR kernel works in place on float64
+        D = _as_dev(D, torch, self.device)
+        g, t, cols = E.shape
+        nl = () if lam is None else (lam.shape[1],)
+        entry, query, scratch = self._READOUT[kind, lam is not None, e32]
+        with torch.cuda.device(self.device):
+            def new(dtype, *shape):
+                return torch.empty(shape, dtype=dtype, device=self.device)
+            W_out = new(torch.float64, g, *(nl if kind != "loo" else ()), n_out, cols)
+            status = new(torch.int32, g, *nl)
+            loo = (new(torch.float64, g, *nl), new(torch.int32, g)) if kind == "loo" else ()      # scores, choice
+            wbytes = getattr(lib, query)(g, *nl, t - transient, cols, *((n_out,) if kind == "qr" else ()))
+            ws = self._scratch(scratch, wbytes) if scratch else new(torch.uint8, wbytes)
+            check(getattr(lib, entry)(ptr(E), ptr(D), g, t, int(transient), cols, n_out, ptr(t_scale), ptr(t_shift),
+                                      *((ptr(lam), *nl) if nl else ()), ptr(W_out), *map(ptr, loo), ptr(status), ptr(ws),
+                                      *((wbytes,) if kind != "qr" else ()), _lib.stream_handle()),
+                  "esn_readout_solve_chol_batch" if (kind, nl) == ("chol", ()) else entry)
+        return (W_out, status, *loo)
 
     def _solve_ridge_grid(self, E, D, transient, ridge_grid):
         """solve(ridge_grid=...): leave-one-out choice among the candidates, one Gram pass per group."""
         torch = self.torch
-        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32
-        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
-        D = _as_dev(D, torch, self.device)
-        g, t, cols = E.shape
+        g, t, cols = np.shape(E)
         rows = t - transient
-        if isinstance(ridge_grid, torch.Tensor):
-            lam = ridge_grid.to(device=self.device, dtype=torch.float64)
-        else:
-            lam = torch.as_tensor(np.array(ridge_grid, dtype=np.float64), device=self.device)
-        if lam.ndim == 1:
-            lam = lam[None, :].expand(g, lam.shape[0])
-        if lam.ndim != 2 or lam.shape[0] != g:
-            raise ValueError(f"ridge_grid must hold L candidates or be [G, L] with G = {g}, not {tuple(lam.shape)}")
+        lam, _ = _lambdas(torch, self.device, ridge_grid, g, grid=True)
         nl = lam.shape[1]
         if not 1 <= nl <= self.LOO_MAX_GRID:
             raise ValueError(f"ridge_grid holds {nl} candidates per group, the kernel takes 1 to {self.LOO_MAX_GRID}")
@@ -255,19 +293,8 @@ class ReservoirBank:
             raise ValueError(f"ridge_grid needs min(rows, cols) <= {self.LOO_MAX_GRAM}, not {min(rows, cols)}")
         if self.n_outputs > 8:
             raise ValueError(f"ridge_grid needs n_outputs <= 8, not {self.n_outputs}")
-        lam = lam.contiguous()
+        W_out, status_l, scores, choice = self._readout(E, D, transient, "loo", lam, self.t_scale, self.t_shift)
         with torch.cuda.device(self.device):
-            W_out = torch.empty((g, self.n_outputs, cols), dtype=torch.float64, device=self.device)
-            scores = torch.empty((g, nl), dtype=torch.float64, device=self.device)
-            choice = torch.empty(g, dtype=torch.int32, device=self.device)
-            status_l = torch.empty((g, nl), dtype=torch.int32, device=self.device)
-            fn, name = (self.lib.esn_readout_ridge_loo_batch_f32, "esn_readout_ridge_loo_batch_f32") if e32 \
-                else (self.lib.esn_readout_ridge_loo_batch, "esn_readout_ridge_loo_batch")
-            wbytes = self.lib.esn_readout_ridge_loo_workspace_bytes(g, nl, rows, cols)
-            ws = self._scratch("_loo_ws", wbytes)
-            check(fn(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale), ptr(self.t_shift),
-                     ptr(lam), nl, ptr(W_out), ptr(scores), ptr(choice), ptr(status_l), ptr(ws), wbytes,
-                     _lib.stream_handle()), name)
             self.last_ridge_choice = choice
             self.last_ridge_scores = scores
             self.last_ridge_status = status_l
@@ -303,66 +330,19 @@ class ReservoirBank:
             if ridge is not None:
                 raise ValueError("give ridge or ridge_grid, not both")
             return self._solve_ridge_grid(E, D, transient, ridge_grid)
-        torch = self.torch
-        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32       # as written by harvest(e_dtype="f32")
-        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
-        D = _as_dev(D, torch, self.device)
-        g, t, cols = E.shape
-        rows = t - transient
-        fits = self.chol_fits(rows, cols)
+        g, t, cols = np.shape(E)
+        fits = self.chol_fits(t - transient, cols)
         if method == "auto":
             method = "chol" if fits else "qr"
-        if e32 and method != "chol":
-            E = E.double()                                                  # the QR kernel works in place on float64
         if method == "chol" and not fits:
             raise ValueError("method='chol' needs min(rows, cols) <= 512 and n_outputs <= 8")
-        if ridge is not None:
-            lam, flat = self._ridge_arg(ridge, g)
-            nl = lam.shape[1]
-            with torch.cuda.device(self.device):
-                W_out = torch.empty((g, nl, self.n_outputs, cols), dtype=torch.float64, device=self.device)
-                status = torch.empty((g, nl), dtype=torch.int32, device=self.device)
-                if method == "chol":
-                    fn, name = (self.lib.esn_readout_solve_chol_ridge_batch_f32, "esn_readout_solve_chol_ridge_batch_f32") \
-                        if e32 else (self.lib.esn_readout_solve_chol_ridge_batch, "esn_readout_solve_chol_ridge_batch")
-                    wbytes = self.lib.esn_readout_chol_ridge_workspace_bytes(g, nl, rows, cols)
-                    ws = self._scratch("_chol_ws", wbytes)
-                    check(fn(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale),
-                             ptr(self.t_shift), ptr(lam), nl, ptr(W_out), ptr(status), ptr(ws), wbytes,
-                             _lib.stream_handle()), name)
-                else:
-                    wbytes = self.lib.esn_readout_solve_ridge_workspace_bytes(g, nl, rows, cols, self.n_outputs)
-                    work = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
-                    check(self.lib.esn_readout_solve_ridge_batch(
-                        ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale),
-                        ptr(self.t_shift), ptr(lam), nl, ptr(W_out), ptr(status), ptr(work), _lib.stream_handle()),
-                        "esn_readout_solve_ridge_batch")
-            if flat:
-                W_out, status = W_out[:, 0], status[:, 0]       # (L = 1: contiguous views)
-            if method == "chol":
-                self.last_solve_status = status
-            return W_out, status
+        lam, flat = (None, False) if ridge is None else _lambdas(self.torch, self.device, ridge, g)
+        W_out, status = self._readout(E, D, transient, "chol" if method == "chol" else "qr", lam,
+                                      self.t_scale, self.t_shift)
+        if flat:
+            W_out, status = W_out[:, 0], status[:, 0]       # (L = 1: contiguous views)
         if method == "chol":
-            with torch.cuda.device(self.device):
-                W_out = torch.empty((g, self.n_outputs, cols), dtype=torch.float64, device=self.device)
-                status = torch.empty(g, dtype=torch.int32, device=self.device)
-                fn = self.lib.esn_readout_solve_chol_batch_f32 if e32 else self.lib.esn_readout_solve_chol_batch
-                wbytes = self.lib.esn_readout_chol_workspace_bytes(g, rows, cols)
-                ws = self._scratch("_chol_ws", wbytes)
-                check(fn(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs, ptr(self.t_scale),
-                         ptr(self.t_shift), ptr(W_out), ptr(status), ptr(ws), wbytes, _lib.stream_handle()),
-                      "esn_readout_solve_chol_batch")
             self.last_solve_status = status        # checked lazily: no host sync on the fast path
-            return W_out, status
-        with torch.cuda.device(self.device):
-            wbytes = self.lib.esn_readout_solve_workspace_bytes(g, rows, cols, self.n_outputs)
-            work = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
-            W_out = torch.empty((g, self.n_outputs, cols), dtype=torch.float64, device=self.device)
-            status = torch.empty(g, dtype=torch.int32, device=self.device)
-            check(self.lib.esn_readout_solve_batch(ptr(E), ptr(D), g, t, int(transient), cols, self.n_outputs,
-                                                   ptr(self.t_scale), ptr(self.t_shift), ptr(W_out),
-                                                   ptr(status), ptr(work), _lib.stream_handle()),
-                  "esn_readout_solve_batch")
         return W_out, status
 
     def resolve_failed(self, E, D, transient, W_out, status, ridge=None, ridge_grid=None):
@@ -370,76 +350,38 @@ class ReservoirBank:
         that solve: each flagged entry is re-solved with its own lambda, so a repaired group is a ridge solution too.
         `ridge_grid` as given to a solve(ridge_grid=...): a group left without a choice (choice == -1, status 1) is
         re-solved by QR at its largest finite candidate -- the most regularised fit the caller was willing to accept --
-        and last_ridge_lambda takes that value; the choice stays -1."""
+        and last_ridge_lambda takes that value; the choice stays -1.  A status of -9 (fit: the harvest cluster kernel
+        timed out, the states were never written) is not repaired: EsnHipError, W_out and status untouched."""
         torch = self.torch
+        if ridge is not None and ridge_grid is not None:
+            raise ValueError("give ridge or ridge_grid, not both")
+        at = torch.nonzero(status).unbind(1)        # (groups,) of a status [G], (groups, lambdas) of a [G, L] one
+        bad, nbad = at[0], int(at[0].numel())
+        if not nbad:
+            return 0
+        if bool(status.eq(-9).any()):
+            raise _lib.EsnHipError(_HARVEST_TIMED_OUT)
+        lam = None
         if ridge_grid is not None:
-            if ridge is not None:
-                raise ValueError("give ridge or ridge_grid, not both")
-            bad = torch.nonzero(status).flatten()
-            nbad = int(bad.numel())
-            if nbad:
-                if isinstance(ridge_grid, torch.Tensor):
-                    lam = ridge_grid.to(device=self.device, dtype=torch.float64)
-                else:
-                    lam = torch.as_tensor(np.array(ridge_grid, dtype=np.float64), device=self.device)
-                if lam.ndim == 1:
-                    lam = lam[None, :].expand(status.shape[0], lam.shape[0])
-                lam = lam[bad]
-                lam = torch.where(torch.isfinite(lam), lam, torch.full_like(lam, -1.0)).max(dim=1).values
-                # (no finite candidate at all: lambda stays negative, the QR solve answers status 2 and a zero W_out)
-                w2 = self.resolve_failed_at(E, D, transient, bad, lam.contiguous())
-                W_out[bad] = w2[0]
-                status[bad] = w2[1]
-                if getattr(self, "last_ridge_lambda", None) is not None and self.last_ridge_lambda.shape[0] == status.shape[0]:
-                    self.last_ridge_lambda[bad] = lam
-            return nbad
-        if ridge is not None and status.ndim == 2:
-            idx = torch.nonzero(status)
-            bad, bad_l = idx[:, 0], idx[:, 1]
-        else:
-            bad, bad_l = torch.nonzero(status).flatten(), None
-        nbad = int(bad.numel())
-        if nbad and ridge is not None:
-            lam, _ = self._ridge_arg(ridge, status.shape[0])
-            lam = lam[bad, bad_l if bad_l is not None else 0].contiguous()
-            keep = (self.t_scale, self.t_shift)
-            self.t_scale = None if keep[0] is None else keep[0][bad].contiguous()
-            self.t_shift = None if keep[1] is None else keep[1][bad].contiguous()
-            try:
-                w2, st2 = self.solve(E[bad].contiguous(), _as_dev(D, torch, self.device)[bad].contiguous(),
-                                     transient, method="qr", ridge=lam)
-            finally:
-                self.t_scale, self.t_shift = keep
-            if bad_l is None:
-                W_out[bad] = w2
-                status[bad] = st2
-            else:
-                W_out[bad, bad_l] = w2
-                status[bad, bad_l] = st2
-        elif nbad:
-            keep = (self.t_scale, self.t_shift)
-            self.t_scale = None if keep[0] is None else keep[0][bad].contiguous()
-            self.t_shift = None if keep[1] is None else keep[1][bad].contiguous()
-            try:
-                w2, st2 = self.solve(E[bad].contiguous(), _as_dev(D, torch, self.device)[bad].contiguous(),
-                                     transient, method="qr")
-            finally:
-                self.t_scale, self.t_shift = keep
-            W_out[bad] = w2
-            status[bad] = st2
+            lam = _lambdas(torch, self.device, ridge_grid, status.shape[0], grid=True)[0][bad]
+            # (no finite candidate at all: lambda stays negative, the QR solve answers status 2 and a zero W_out)
+            lam = torch.where(torch.isfinite(lam), lam, torch.full_like(lam, -1.0)).max(dim=1).values
+        elif ridge is not None:
+            lam = _lambdas(torch, self.device, ridge, status.shape[0])[0][bad, at[1] if len(at) > 1 else 0]
+        W_out[at], status[at] = self.resolve_failed_at(E, D, transient, bad, lam)
+        if ridge_grid is not None and self.last_ridge_lambda is not None \
+                and self.last_ridge_lambda.shape[0] == status.shape[0]:
+            self.last_ridge_lambda[bad] = lam
         return nbad
 
     def resolve_failed_at(self, E, D, transient, bad, lam):
-        """QR ridge solve of the groups `bad` (device index tensor) at lam [len(bad)]; returns (W_out, status)."""
-        torch = self.torch
-        keep = (self.t_scale, self.t_shift)
-        self.t_scale = None if keep[0] is None else keep[0][bad].contiguous()
-        self.t_shift = None if keep[1] is None else keep[1][bad].contiguous()
-        try:
-            return self.solve(E[bad].contiguous(), _as_dev(D, torch, self.device)[bad].contiguous(), transient,
-                              method="qr", ridge=lam)
-        finally:
-            self.t_scale, self.t_shift = keep
+        """QR solve of the groups `bad` (device index tensor) at lam [len(bad)], or pinv for lam None, under those
+        groups' own teacher scalings; returns (W_out, status) of len(bad) groups."""
+        def sub(x):
+            return None if x is None else x[bad].contiguous()
+        out = self._readout(sub(E), sub(_as_dev(D, self.torch, self.device)), transient, "qr",
+                            None if lam is None else lam.reshape(-1, 1).contiguous(), sub(self.t_scale), sub(self.t_shift))
+        return out if lam is None else (out[0][:, 0], out[1][:, 0])
 
     def fit(self, U, D, transient=0, precision="f64", noise_mode="counter", noise_u=None, seed=0,
             method="qr", e_dtype="f64", group_offset=0, ridge=None, ridge_grid=None):
@@ -454,7 +396,7 @@ class ReservoirBank:
         W_out, status = self.solve(E, D, transient, method=method, ridge=ridge, ridge_grid=ridge_grid)
         self.fit_ridge = ridge if ridge_grid is None else self.last_ridge_lambda
         self.set_readout(W_out)
-        ht = getattr(self, "harvest_timeout", None)
+        ht = self.harvest_timeout
         if ht is not None:
             # a harvest cluster that timed out waiting for its peer left invalid states: every group's status says so
             # (-9; device-side, no host sync here -- whoever reads fit_status sees it)
@@ -510,17 +452,16 @@ class ReservoirBank:
                 int(group_offset), ptr(out), ptr(ws), wbytes, _lib.stream_handle()),
                 "esn_predict_batch_f32" if io32 else "esn_predict_batch")
             if _lib.recur_path(False, precision, self.shape, b, frames_per_group, wbytes > 0) == "cluster_f64":
-                self._cluster_err = ws[wbytes - 64:wbytes - 60]      # error word of the single-sequence cluster kernel
+                self._cluster_err = self._error_word(ws, wbytes)     # of the single-sequence cluster kernel
         return out
 
     def raise_if_cluster_timed_out(self):
         """Host-synchronising check after a single-sequence float64 call (the 2-D drop-in makes it when it copies the
         result to the host): the cluster kernel's workgroups wait for each other with bounded spins and raise an
         error word instead of hanging (include/esn_hip.h, esn_predict_batch: workspace)."""
-        w = getattr(self, "_cluster_err", None)
+        w, self._cluster_err = self._cluster_err, None
         if w is not None:
-            self._cluster_err = None
-            if int(w.view(self.torch.int32).item()) != 0:
+            if int(w.item()) != 0:
                 raise _lib.EsnHipError("single-sequence cluster kernel: a workgroup timed out waiting for the others "
                                        "(the device is oversubscribed); outputs are invalid")
 
@@ -559,13 +500,16 @@ class ReservoirBank:
             setattr(self, name, ws)
         return ws
 
+    def _error_word(self, ws, wbytes):
+        """int32 view [1] of the error word that the two cluster kernels (paths "cluster_f64", "harvest_cluster")
+        keep 64 bytes before the end of their workspace: non-zero after a workgroup gave up waiting for its peers."""
+        return ws[wbytes - 64:wbytes - 60].view(self.torch.int32)
+
     def _check_groups(self, g):
         for name in ("in_scale", "in_shift", "t_scale", "t_shift"):
             t = getattr(self, name)
             if t is not None and t.shape[0] < g:
                 raise ValueError(f"{name} holds {t.shape[0]} groups, batch has {g}")
-        if self.n_wsets > 1 and g % self.n_wsets and g > self.n_wsets:
-            pass  # weight set = group % n_wsets by contract
 
     def _noise_args(self, noise_mode, noise_u, shape):
         if self.noise == 0.0 or noise_mode in (None, "none"):

@@ -474,20 +474,15 @@ int esn_harvest_batch_f32(int precision, const esn_shape_t* shape, const void* p
                           noise_mode, noise_u, seed, group_offset, nullptr, E, workspace, workspace_bytes, stream);
 }
 
+// ---- read-out solves: QR, Cholesky and leave-one-out; pinv and ridge (an extension: the reference fits with pinv only)
 size_t esn_readout_solve_workspace_bytes(int n_groups, int rows, int cols, int n_out) {
     if (n_groups <= 0 || rows <= 0 || cols <= 0 || n_out <= 0) return 0;
     return sizeof(double) * solve_work_doubles(rows, cols, n_out) * (size_t)n_groups;
 }
 
-int esn_readout_solve_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
-                            int n_out, const double* t_scale, const double* t_shift, double* W_out,
-                            int* status, void* workspace, void* stream) {
-    if (!E || !D || !W_out || !status || !workspace) return fail(-1, "esn_readout_solve_batch: null pointer");
-    if (n_groups <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
-        return fail(-1, "esn_readout_solve_batch: invalid sizes");
-    return hip_fail(launch_readout_solve(E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
-                                         status, workspace, (hipStream_t)stream),
-                    "esn_readout_solve_batch");
+size_t esn_readout_solve_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols, int n_out) {
+    if (n_groups <= 0 || n_ridge <= 0 || rows <= 0 || cols <= 0 || n_out <= 0) return 0;
+    return sizeof(double) * solve_ridge_work_doubles(rows, cols, n_out) * (size_t)n_groups * (size_t)n_ridge;
 }
 
 size_t esn_readout_chol_workspace_bytes(int n_groups, int rows, int cols) {
@@ -497,146 +492,148 @@ size_t esn_readout_chol_workspace_bytes(int n_groups, int rows, int cols) {
     return sizeof(double) * chol_big_work_doubles(n) * (size_t)n_groups;
 }
 
-static int chol_common(const char* who, const double* E, const float* E32, const double* D, int n_groups, int T,
-                       int transient, int cols, int n_out, const double* t_scale, const double* t_shift, double* W_out,
-                       int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if ((!E && !E32) || !D || !W_out || !status) return fail(-1, "%s: null pointer", who);
-    if (n_groups <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
-        return fail(-1, "%s: invalid sizes", who);
-    const int rows = T - transient, n = rows < cols ? rows : cols;
-    if (n > 128) {            // Gram matrix and factor in the caller's workspace (esn_solve.hip, readout_chol_big_kernel)
-        const size_t need = esn_readout_chol_workspace_bytes(n_groups, rows, cols);
-        if (need == 0 || n_out > 8) return fail(-2, "%s: no kernel instance for this shape", who);
-        if (!workspace || workspace_bytes < need)
-            return fail(-1, "%s: workspace holds %zu bytes, esn_readout_chol_workspace_bytes says %zu", who,
-                        workspace ? workspace_bytes : (size_t)0, need);
-        if (((uintptr_t)(E ? (const void*)E : (const void*)E32) & 15) || ((uintptr_t)workspace & 15))
-            return fail(-1, "%s: E and the workspace must be 16-byte aligned", who);
-        return hip_fail(launch_readout_chol_big(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
-                                                status, workspace, (hipStream_t)stream), who);
-    }
-    return hip_fail(launch_readout_chol(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
-                                        status, (hipStream_t)stream), who);
-}
-
-int esn_readout_solve_chol_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
-                                 int n_out, const double* t_scale, const double* t_shift, double* W_out,
-                                 int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    return chol_common("esn_readout_solve_chol_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
-                       t_shift, W_out, status, workspace, workspace_bytes, stream);
-}
-
-int esn_readout_solve_chol_batch_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols,
-                                     int n_out, const double* t_scale, const double* t_shift, double* W_out,
-                                     int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    return chol_common("esn_readout_solve_chol_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale,
-                       t_shift, W_out, status, workspace, workspace_bytes, stream);
-}
-
-// ---- ridge read-out (an extension: the reference fits with pinv only) --------------------------------------------
-size_t esn_readout_solve_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols, int n_out) {
-    if (n_groups <= 0 || n_ridge <= 0 || rows <= 0 || cols <= 0 || n_out <= 0) return 0;
-    return sizeof(double) * solve_ridge_work_doubles(rows, cols, n_out) * (size_t)n_groups * (size_t)n_ridge;
-}
-
-int esn_readout_solve_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
-                                  int n_out, const double* t_scale, const double* t_shift, const double* ridge,
-                                  int n_ridge, double* W_out, int* status, void* workspace, void* stream) {
-    if (!E || !D || !ridge || !W_out || !status || !workspace)
-        return fail(-1, "esn_readout_solve_ridge_batch: null pointer");
-    if (n_groups <= 0 || n_ridge <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
-        return fail(-1, "esn_readout_solve_ridge_batch: invalid sizes");
-    return hip_fail(launch_readout_solve(E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out, status,
-                                         workspace, (hipStream_t)stream, ridge, n_ridge),
-                    "esn_readout_solve_ridge_batch");
-}
-
 size_t esn_readout_chol_ridge_workspace_bytes(int n_groups, int n_ridge, int rows, int cols) {
     if (n_ridge <= 0) return 0;
     return esn_readout_chol_workspace_bytes(n_groups, rows, cols) * (size_t)n_ridge;
 }
 
-static int chol_ridge_common(const char* who, const double* E, const float* E32, const double* D, int n_groups, int T,
-                             int transient, int cols, int n_out, const double* t_scale, const double* t_shift,
-                             const double* ridge, int n_ridge, double* W_out, int* status, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    if ((!E && !E32) || !D || !ridge || !W_out || !status) return fail(-1, "%s: null pointer", who);
-    if (n_groups <= 0 || n_ridge <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
+size_t esn_readout_ridge_loo_workspace_bytes(int n_groups, int n_ridge, int rows, int cols) {
+    if (n_groups <= 0 || n_ridge <= 0 || rows <= 0 || cols <= 0) return 0;
+    return sizeof(double) * ridge_loo_work_doubles() * (size_t)n_groups;
+}
+
+// The arguments of one read-out entry point; what an entry point does not take stays nullptr (and n_ridge 1).
+struct ReadoutCall {
+    const char* who;
+    const double* E; const float* E32; const double* D;
+    int n_groups, T, transient, cols, n_out;
+    const double *t_scale, *t_shift, *ridge; int n_ridge;
+    double *W_out, *score; int *choice, *status;
+    void* workspace; size_t workspace_bytes; void* stream;
+};
+
+// What an entry point requires of them.
+enum ReadoutKernel { kQr, kChol, kLoo };
+struct ReadoutRule {
+    ReadoutKernel kernel;
+    bool ridge;                                 // lambdas: mandatory, or absent (the pinv solve)
+    int max_gram;                               // largest min(rows, cols) served; 0: any
+    int max_ridge;                              // 1 .. max_ridge lambdas per group; 0: any number
+    size_t (*need)(int, int, int, int);         // workspace query (n_groups, n_ridge, rows, cols); nullptr: QR, which
+    const char* query;                          //   takes no size (its pointer is mandatory); the query's own name
+    int align;                                  // 16: E and the workspace; 8: the workspace
+};
+static const int kCholLds = 128;                // the Cholesky kernel keeps Gram matrices up to this in LDS (no workspace)
+static const ReadoutRule
+    kQrPinv = {kQr, false, 0, 0, nullptr, nullptr, 0}, kQrRidge = {kQr, true, 0, 0, nullptr, nullptr, 0},
+    kCholPinv = {kChol, false, 512, 0, esn_readout_chol_ridge_workspace_bytes, "esn_readout_chol_workspace_bytes", 16},
+    kCholRidge = {kChol, true, 512, 0, esn_readout_chol_ridge_workspace_bytes, "esn_readout_chol_ridge_workspace_bytes", 16},
+    kLooRidge = {kLoo, true, 128, 16, esn_readout_ridge_loo_workspace_bytes, "esn_readout_ridge_loo_workspace_bytes", 8};
+
+// Null pointers, sizes, "not served", workspace size, alignment -- in that order for every entry point -- then the launch.
+static int readout_call(const ReadoutCall& c, const ReadoutRule& r) {
+    const char* who = c.who;
+    const bool loo = r.kernel == kLoo;
+    if ((!c.E && !c.E32) || !c.D || !c.W_out || !c.status || (r.ridge && !c.ridge) || (loo && (!c.score || !c.choice))
+        || (!r.need && !c.workspace))
+        return fail(-1, "%s: null pointer", who);
+    if (c.n_groups <= 0 || (!r.max_ridge && c.n_ridge <= 0) || c.T <= 0 || c.transient < 0 || c.transient >= c.T
+        || c.cols <= 0 || c.n_out <= 0)
         return fail(-1, "%s: invalid sizes", who);
-    const int rows = T - transient, n = rows < cols ? rows : cols;
-    if (n > 512 || n_out > 8) return fail(-2, "%s: no kernel instance for this shape", who);
-    if (n > 128) {            // one Gram matrix / factor per (group, lambda) in the caller's workspace
-        const size_t need = esn_readout_chol_ridge_workspace_bytes(n_groups, n_ridge, rows, cols);
-        if (!workspace || workspace_bytes < need)
-            return fail(-1, "%s: workspace holds %zu bytes, esn_readout_chol_ridge_workspace_bytes says %zu", who,
-                        workspace ? workspace_bytes : (size_t)0, need);
-        if (((uintptr_t)(E ? (const void*)E : (const void*)E32) & 15) || ((uintptr_t)workspace & 15))
-            return fail(-1, "%s: E and the workspace must be 16-byte aligned", who);
-        return hip_fail(launch_readout_chol_big(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
-                                                status, workspace, (hipStream_t)stream, ridge, n_ridge), who);
+    const int rows = c.T - c.transient, n = rows < c.cols ? rows : c.cols;
+    const bool big = r.kernel == kChol && n > kCholLds;     // Gram matrix and factor in the caller's workspace
+    if (r.max_ridge && (c.n_ridge < 1 || c.n_ridge > r.max_ridge))
+        return fail(-1, "%s: n_ridge = %d, 1 to %d candidates are served", who, c.n_ridge, r.max_ridge);
+    if (loo && c.n_out > 8) return fail(-1, "%s: n_out = %d, at most 8 outputs are served", who, c.n_out);
+    if (loo && n > r.max_gram)
+        return fail(-2, "%s: min(rows, cols) = %d, the limit is %d (the factor stays in LDS)", who, n, r.max_gram);
+    // (the pinv Cholesky entry points leave n_out > 8 at an LDS shape to the launcher, which has no instance for it)
+    if (r.kernel == kChol && (n > r.max_gram || (c.n_out > 8 && (r.ridge || big))))
+        return fail(-2, "%s: no kernel instance for this shape", who);
+    if (loo || big) {
+        const size_t need = r.need(c.n_groups, c.n_ridge, rows, c.cols);
+        if (!c.workspace || c.workspace_bytes < need)
+            return fail(-1, "%s: workspace holds %zu bytes, %s says %zu", who, c.workspace ? c.workspace_bytes : (size_t)0,
+                        r.query, need);
+        const uintptr_t e = (uintptr_t)(c.E ? (const void*)c.E : (const void*)c.E32), w = (uintptr_t)c.workspace;
+        if (r.align == 16 && ((e | w) & 15)) return fail(-1, "%s: E and the workspace must be 16-byte aligned", who);
+        if (r.align == 8 && (w & 7)) return fail(-1, "%s: the workspace must be 8-byte aligned", who);
     }
-    return hip_fail(launch_readout_chol(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, W_out,
-                                        status, (hipStream_t)stream, ridge, n_ridge), who);
+    hipStream_t s = (hipStream_t)c.stream;
+    if (loo)
+        return hip_fail(launch_ridge_loo(c.E, c.E32, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
+                                         c.t_shift, c.ridge, c.n_ridge, c.W_out, c.score, c.choice, c.status,
+                                         c.workspace, s), who);
+    if (r.kernel == kQr)
+        return hip_fail(launch_readout_solve(c.E, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
+                                             c.t_shift, c.W_out, c.status, c.workspace, s, c.ridge, c.n_ridge), who);
+    if (big)
+        return hip_fail(launch_readout_chol_big(c.E, c.E32, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
+                                                c.t_shift, c.W_out, c.status, c.workspace, s, c.ridge, c.n_ridge), who);
+    return hip_fail(launch_readout_chol(c.E, c.E32, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
+                                        c.t_shift, c.W_out, c.status, s, c.ridge, c.n_ridge), who);
+}
+
+int esn_readout_solve_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
+                            int n_out, const double* t_scale, const double* t_shift, double* W_out,
+                            int* status, void* workspace, void* stream) {
+    return readout_call({"esn_readout_solve_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift,
+                         nullptr, 1, W_out, nullptr, nullptr, status, workspace, 0, stream}, kQrPinv);
+}
+
+int esn_readout_solve_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
+                                  int n_out, const double* t_scale, const double* t_shift, const double* ridge,
+                                  int n_ridge, double* W_out, int* status, void* workspace, void* stream) {
+    return readout_call({"esn_readout_solve_ridge_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
+                         t_shift, ridge, n_ridge, W_out, nullptr, nullptr, status, workspace, 0, stream}, kQrRidge);
+}
+
+int esn_readout_solve_chol_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
+                                 int n_out, const double* t_scale, const double* t_shift, double* W_out,
+                                 int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return readout_call({"esn_readout_solve_chol_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
+                         t_shift, nullptr, 1, W_out, nullptr, nullptr, status, workspace, workspace_bytes, stream}, kCholPinv);
+}
+
+int esn_readout_solve_chol_batch_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols,
+                                     int n_out, const double* t_scale, const double* t_shift, double* W_out,
+                                     int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return readout_call({"esn_readout_solve_chol_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale,
+                         t_shift, nullptr, 1, W_out, nullptr, nullptr, status, workspace, workspace_bytes, stream}, kCholPinv);
 }
 
 int esn_readout_solve_chol_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                                        int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                        int n_ridge, double* W_out, int* status, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    return chol_ridge_common("esn_readout_solve_chol_ridge_batch", E, nullptr, D, n_groups, T, transient, cols, n_out,
-                             t_scale, t_shift, ridge, n_ridge, W_out, status, workspace, workspace_bytes, stream);
+    return readout_call({"esn_readout_solve_chol_ridge_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
+                         t_shift, ridge, n_ridge, W_out, nullptr, nullptr, status, workspace, workspace_bytes, stream},
+                        kCholRidge);
 }
 
 int esn_readout_solve_chol_ridge_batch_f32(const float* E, const double* D, int n_groups, int T, int transient,
                                            int cols, int n_out, const double* t_scale, const double* t_shift,
                                            const double* ridge, int n_ridge, double* W_out, int* status,
                                            void* workspace, size_t workspace_bytes, void* stream) {
-    return chol_ridge_common("esn_readout_solve_chol_ridge_batch_f32", nullptr, E, D, n_groups, T, transient, cols,
-                             n_out, t_scale, t_shift, ridge, n_ridge, W_out, status, workspace, workspace_bytes, stream);
-}
-
-// ---- leave-one-out choice of the ridge parameter (esn_loo.hip) -----------------------------------------------------
-size_t esn_readout_ridge_loo_workspace_bytes(int n_groups, int n_ridge, int rows, int cols) {
-    if (n_groups <= 0 || n_ridge <= 0 || rows <= 0 || cols <= 0) return 0;
-    return sizeof(double) * ridge_loo_work_doubles() * (size_t)n_groups;
-}
-
-static int ridge_loo_common(const char* who, const double* E, const float* E32, const double* D, int n_groups, int T,
-                            int transient, int cols, int n_out, const double* t_scale, const double* t_shift,
-                            const double* ridge, int n_ridge, double* W_out, double* score, int* choice, int* status,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-    if ((!E && !E32) || !D || !ridge || !W_out || !score || !choice || !status) return fail(-1, "%s: null pointer", who);
-    if (n_groups <= 0 || T <= 0 || transient < 0 || transient >= T || cols <= 0 || n_out <= 0)
-        return fail(-1, "%s: invalid sizes", who);
-    if (n_ridge < 1 || n_ridge > 16) return fail(-1, "%s: n_ridge = %d, 1 to 16 candidates are served", who, n_ridge);
-    if (n_out > 8) return fail(-1, "%s: n_out = %d, at most 8 outputs are served", who, n_out);
-    const int rows = T - transient, n = rows < cols ? rows : cols;
-    if (n > 128)
-        return fail(-2, "%s: min(rows, cols) = %d, the limit is 128 (the factor stays in LDS)", who, n);
-    const size_t need = esn_readout_ridge_loo_workspace_bytes(n_groups, n_ridge, rows, cols);
-    if (!workspace || workspace_bytes < need)
-        return fail(-1, "%s: workspace holds %zu bytes, esn_readout_ridge_loo_workspace_bytes says %zu", who,
-                    workspace ? workspace_bytes : (size_t)0, need);
-    if ((uintptr_t)workspace & 7) return fail(-1, "%s: the workspace must be 8-byte aligned", who);
-    return hip_fail(launch_ridge_loo(E, E32, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge,
-                                     W_out, score, choice, status, workspace, (hipStream_t)stream), who);
+    return readout_call({"esn_readout_solve_chol_ridge_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out,
+                         t_scale, t_shift, ridge, n_ridge, W_out, nullptr, nullptr, status, workspace, workspace_bytes,
+                         stream}, kCholRidge);
 }
 
 int esn_readout_ridge_loo_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                                 int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                 int n_ridge, double* W_out, double* score, int* choice, int* status, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    return ridge_loo_common("esn_readout_ridge_loo_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
-                            t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes, stream);
+    return readout_call({"esn_readout_ridge_loo_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
+                         t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes, stream}, kLooRidge);
 }
 
 int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols,
                                     int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                     int n_ridge, double* W_out, double* score, int* choice, int* status,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    return ridge_loo_common("esn_readout_ridge_loo_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out,
-                            t_scale, t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes,
-                            stream);
+    return readout_call({"esn_readout_ridge_loo_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale,
+                         t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes, stream}, kLooRidge);
 }
 
 // ---- reservoirs drawn on the device (esn_reservoir.hip) ------------------------------------------------------------

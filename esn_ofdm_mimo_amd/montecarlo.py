@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from . import reservoirs as _reservoirs
-from .batched import ReservoirBank
+from .batched import ReservoirBank, _lambdas
 from ._lib import check, ptr
 
 @dataclass
@@ -378,6 +378,9 @@ class DetectorSweep:
         self.seed = seed
         self.src = FrameSource(params, device, seed)
         self.device = self.src.device
+        # the candidates on the device, copied once: [L]
+        self._grid_t = None if ridge_grid is None else _lambdas(torch, self.device, self.ridge_grid, 1, grid=True)[0][0]
+        self._ebno = self._train_bufs = self._fit_io = self._cont = None     # set_snr / train leave these
         if radius not in ("host", "device"):
             raise ValueError(f"radius must be 'host' or 'device', not {radius!r}")
         self.reservoirs = reservoirs
@@ -447,14 +450,6 @@ class DetectorSweep:
             return None
         return float(self.ridge(ebno_db)) if callable(self.ridge) else float(self.ridge)
 
-    def _grid_dev(self):
-        """ridge_grid on the device, copied once (None without one)."""
-        if self.ridge_grid is None:
-            return None
-        if getattr(self, "_grid_t", None) is None:
-            self._grid_t = self.torch.as_tensor(self.ridge_grid, device=self.device)
-        return self._grid_t
-
     def stream_seed(self, snr_idx, leg):
         """64-bit seed of the state-noise stream of one Eb/No point; leg 0 = training (harvest), 1 = detection.
         With the kernels' global frame index this makes the noise a function of (seed, snr, leg, global frame,
@@ -471,7 +466,7 @@ class DetectorSweep:
         d = p.delay
         g, t = pilot_y.shape[0], pilot_y.shape[1]
         # zero-padded pilot buffers are kept between calls of the same shape (the padding rows are never written)
-        io = getattr(self, "_train_bufs", None)
+        io = self._train_bufs
         if io is None or io[0].shape != (g, t + d, self.n_in):
             io = self._train_bufs = (torch.zeros((g, t + d, self.n_in), dtype=torch.float64, device=self.device),
                                      torch.zeros((g, t + d, self.n_out), dtype=torch.float64, device=self.device))
@@ -486,7 +481,7 @@ class DetectorSweep:
         e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
         E = self.bank.fit(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
                           seed=seed, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
-                          ridge=self.ridge_at(getattr(self, "_ebno", None)), ridge_grid=self._grid_dev())
+                          ridge=self.ridge_at(self._ebno), ridge_grid=self._grid_t)
         self._cont = None
         if p.continuation:      # laststate / lastoutput of pyESN.py:195-197: training-final state, scaled teacher
             y_last = D[:, -1, :]
@@ -501,11 +496,8 @@ class DetectorSweep:
         """Host-synchronising check of the last fit: groups the Cholesky path flagged are re-solved
         with the QR kernel (GPU).  Returns how many were."""
         U, D, tr = self._fit_io
-        if self.ridge_grid is not None:
-            n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status, ridge_grid=self._grid_dev())
-        else:
-            n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status,
-                                         ridge=getattr(self.bank, "fit_ridge", None))
+        n = self.bank.resolve_failed(E, D, tr, self.bank.W_out, self.bank.fit_status, ridge_grid=self._grid_t,
+                                     ridge=None if self._grid_t is not None else self.bank.fit_ridge)
         if n:
             self.bank.set_readout(self.bank.W_out)
         return n
@@ -515,7 +507,7 @@ class DetectorSweep:
         in-kernel) -> fused FFT/slicer/count."""
         p = self.p
         U = _view_real(data_y)
-        x0, y0 = self._cont if (p.continuation and getattr(self, "_cont", None)) else (None, None)
+        x0, y0 = self._cont if (p.continuation and self._cont) else (None, None)
         y = self.bank.predict(U, frames_per_block, T=p.t_frame + p.delay, transient=p.forget, x0=x0, y0=y0,
                               precision=self.precision, noise_mode="counter", seed=seed, out=out,
                               group_offset=group_offset, io=self.io)
@@ -567,7 +559,7 @@ class DetectorSweep:
             (), dtype=torch.int64, device=self.device)
         # (a timed-out harvest cluster counts as a flagged fit: the chunk is then redone with `repair`, whose host
         #  read raises)
-        ht = getattr(self.bank, "harvest_timeout", None)
+        ht = self.bank.harvest_timeout
         if ht is not None:
             if repair:
                 self.bank.raise_if_harvest_timed_out()
