@@ -80,6 +80,8 @@ SIGNATURES = {
                                      _dp, _dp, _dp, _dp, _vp]),
     "esn_spectral_radius_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "esn_spectral_radius_batch": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
+    "esn_spectral_radius_split_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "esn_spectral_radius_split_batch": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
     "esn_scale_reservoirs": (C.c_int, [_dp, C.c_int, C.c_int, C.c_double, _dp, _ip, _vp]),
     "esn_gen_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp,
                                C.c_uint64, C.c_uint64, _dp, _vp]),

@@ -121,15 +121,20 @@ class ReservoirBank:
 
     @classmethod
     def generate(cls, n_inputs, n_outputs, n_reservoir, spectral_radius=0.9, sparsity=0.1, seed=0, first_set=0,
-                 n_sets=1, uniforms=None, teacher_forcing=True, noise=0.001, device=None, leak_rate=1.0):
+                 n_sets=1, uniforms=None, teacher_forcing=True, noise=0.001, device=None, leak_rate=1.0,
+                 radius_precision="f64", n_squarings=None):
         """A bank whose weight sets are drawn, measured and scaled on the device (reservoirs.generate): the sets with
         global index first_set .. first_set + n_sets - 1, set s in slot s % n_sets, which is the set the kernels pick
-        for global group s."""
+        for global group s.  radius_precision and n_squarings (None: reservoirs.N_SQUARINGS) go to
+        reservoirs.generate."""
         from . import reservoirs
         torch = _lib.require_gpu()
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         W, W_in, W_fb, radius, _ = reservoirs.generate(n_inputs, n_outputs, n_reservoir, spectral_radius, sparsity, seed,
-                                                       first_set=first_set, n_sets=n_sets, uniforms=uniforms, device=dev)
+                                                       first_set=first_set, n_sets=n_sets, uniforms=uniforms, device=dev,
+                                                       radius_precision=radius_precision,
+                                                       n_squarings=reservoirs.N_SQUARINGS if n_squarings is None
+                                                       else n_squarings)
         n = int(n_reservoir)
         # (placeholders of one set for __init__, which keeps its signature; the device tensors replace them at once)
         bank = cls(n_inputs, n_outputs, n, np.zeros((n, n)), np.zeros((n, int(n_inputs))), np.zeros((n, int(n_outputs))),

@@ -677,6 +677,35 @@ int esn_spectral_radius_batch(const double* W, int n_sets, int n_res, int n_squa
                                            (hipStream_t)stream), who);
 }
 
+// (16 bytes more than the images take: the 8-byte aligned workspace of the caller is rounded up to the 16 bytes the
+//  kernel's loads want)
+size_t esn_spectral_radius_split_workspace_bytes(int n_sets, int n_res) {
+    if (n_sets <= 0 || n_res <= 0) return 0;
+    if (n_res > kResMaxN) {
+        fail(-1, "esn_spectral_radius_split_workspace_bytes: n_res = %d, served up to %d", n_res, kResMaxN);
+        return 0;
+    }
+    return specrad_split_work_bytes(n_res) * (size_t)n_sets + 16;
+}
+
+int esn_spectral_radius_split_batch(const double* W, int n_sets, int n_res, int n_squarings, double* radius,
+                                    int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "esn_spectral_radius_split_batch";
+    if (!W || !radius || !status) return fail(-1, "%s: null pointer", who);
+    if (n_sets <= 0 || n_res <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_res > kResMaxN) return fail(-1, "%s: n_res = %d, served up to %d", who, n_res, kResMaxN);
+    if (n_squarings < 4 || n_squarings > 32)
+        return fail(-1, "%s: n_squarings = %d, 4 to 32 are served", who, n_squarings);
+    const size_t need = specrad_split_work_bytes(n_res) * (size_t)n_sets + 16;
+    if (!workspace || workspace_bytes < need)
+        return fail(-1, "%s: workspace holds %zu bytes, esn_spectral_radius_split_workspace_bytes says %zu", who,
+                    workspace ? workspace_bytes : (size_t)0, need);
+    if ((uintptr_t)workspace & 7) return fail(-1, "%s: the workspace must be 8-byte aligned", who);
+    void* aligned = reinterpret_cast<void*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+    return hip_fail(launch_spectral_radius_split(W, n_sets, n_res, n_squarings, radius, status, aligned,
+                                                 (hipStream_t)stream), who);
+}
+
 int esn_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const double* radius, const int* status,
                          void* stream) {
     const char* who = "esn_scale_reservoirs";

@@ -93,6 +93,11 @@ int launch_spectral_radius(const double* W, int n_sets, int n_res, int n_squarin
                            void* workspace, hipStream_t stream);
 int launch_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const double* radius, const int* status,
                             hipStream_t stream);
+// esn_specrad_split.hip: the same radius with every squaring as three fp16 MFMA products of split operands; the
+// workspace (16-byte aligned) holds specrad_split_work_bytes(n_res) bytes per matrix
+size_t specrad_split_work_bytes(int n_res);
+int launch_spectral_radius_split(const double* W, int n_sets, int n_res, int n_squarings, double* radius, int* status,
+                                 void* workspace, hipStream_t stream);
 // esn_gen.hip
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);

@@ -333,7 +333,7 @@ class DetectorSweep:
     def __init__(self, params: LinkParams, n_reservoir=512, spectral_radius=0.9, sparsity=0.1, noise=0.001,
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
                  rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None,
-                 radius="host"):
+                 radius="host", radius_precision="f64", radius_squarings=24, fresh_radius_cache=True):
         """reservoirs: "shared" (one reservoir for every block), "per_block" (block b uses set b % pool of a pool
         drawn here) or "fresh" (the reference's own rule, SURVEY F5: every coherence block gets a reservoir of its
         own, drawn on the device by reservoirs.generate and keyed by (seed, global block index) -- the same at every
@@ -346,6 +346,15 @@ class DetectorSweep:
         "device" for the "shared" and "per_block" modes: the same RandomState uniforms, drawn on the host in the same
         order, are scaled by the device's spectral radius (reservoirs.generate(uniforms=...)) -- W within 1e-6 of the
         host's, without pool x eigvals in this constructor (8.8 s per set at n_reservoir = 2048).
+
+        radius_precision, radius_squarings: how the device measures a radius, for reservoirs="fresh" and for
+        radius="device" -- "f64" (default) or "f16x2" (reservoirs.RADIUS_PRECISIONS: split fp16 operands, within 1e-6
+        of "f64"), and the number of squarings.
+
+        fresh_radius_cache ("fresh" only): a block's reservoir is keyed by (seed, global block), so its radius is the
+        same at every Eb/No point of a run(); the first point's radius and status stay on the device (12 bytes per
+        block of this rank) and the later points scale with them instead of measuring again -- the same bits, so the
+        same counters.  fresh_radius_hits counts the blocks of the last run() that were served this way.
 
         ridge (extension; None = the reference's pinv fit): lambda of the ridge read-out (ReservoirBank.solve), a
         float or a callable ebno_db -> float (the best lambda moves with Eb/No and n_reservoir).
@@ -383,13 +392,19 @@ class DetectorSweep:
         self._ebno = self._train_bufs = self._fit_io = self._cont = None     # set_snr / train leave these
         if radius not in ("host", "device"):
             raise ValueError(f"radius must be 'host' or 'device', not {radius!r}")
+        if radius_precision not in _reservoirs.RADIUS_PRECISIONS:
+            raise ValueError(f"radius_precision must be one of {sorted(_reservoirs.RADIUS_PRECISIONS)}, "
+                             f"not {radius_precision!r}")
+        self.radius_precision, self.radius_squarings = radius_precision, int(radius_squarings)
+        self.fresh_radius_cache, self.fresh_radius_hits, self._radius_cache = bool(fresh_radius_cache), 0, None
         self.reservoirs = reservoirs
         self._res_args = (self.n_in, self.n_out, int(n_reservoir), float(spectral_radius), float(sparsity))
         self.reservoir_seed = seed * 7919 + 17
         if reservoirs == "fresh":
             # block 0's reservoir until the first chunk swaps its own in
             self.bank = ReservoirBank.generate(*self._res_args, seed=self.reservoir_seed, first_set=0, n_sets=1,
-                                               teacher_forcing=True, noise=noise, device=self.device)
+                                               teacher_forcing=True, noise=noise, device=self.device,
+                                               radius_precision=radius_precision, n_squarings=self.radius_squarings)
             self.n_sets = 1
             return
         n_sets = 1 if reservoirs == "shared" else int(pool)
@@ -414,7 +429,8 @@ class DetectorSweep:
         rs = np.random.RandomState(seed)
         u = np.concatenate([rs.rand(n, n).ravel(), rs.rand(n, n).ravel(), rs.rand(n, n_in).ravel(),
                             rs.rand(n, n_out).ravel()])
-        return _reservoirs.generate(n_in, n_out, n, rho, sparsity, 0, uniforms=u[None], device=self.device)[:3]
+        return _reservoirs.generate(n_in, n_out, n, rho, sparsity, 0, uniforms=u[None], device=self.device,
+                                    radius_precision=self.radius_precision, n_squarings=self.radius_squarings)[:3]
 
     # "fresh": bytes per block of a chunk -- float64 W (8 n^2), two squaring images (16 n^2, padded to 64) and the packed
     # weights of the fit and the detect precision (at most 8 n^2 each) -- and the budget they are held to
@@ -424,12 +440,52 @@ class DetectorSweep:
         """The reservoirs of global blocks [first_block, first_block + n_blocks) into the bank: block b in slot
         b % n_blocks, which is the set the kernels pick for it under group_offset = first_block.  Returns the int32
         status [n_blocks] on the device; `check` reads it on the host and raises for a set that could not be scaled."""
-        W, W_in, W_fb, _, status = _reservoirs.generate(*self._res_args, seed=self.reservoir_seed,
-                                                        first_set=first_block, n_sets=n_blocks, device=self.device,
-                                                        check_status=check)
+        known = self._cached_radius(first_block, n_blocks)
+        W, W_in, W_fb, radius, status = _reservoirs.generate(*self._res_args, seed=self.reservoir_seed,
+                                                             first_set=first_block, n_sets=n_blocks, device=self.device,
+                                                             check_status=check, n_squarings=self.radius_squarings,
+                                                             radius_precision=self.radius_precision,
+                                                             radius=None if known is None else known[0],
+                                                             radius_status=None if known is None else known[1])
+        if known is not None:
+            self.fresh_radius_hits += n_blocks
+        else:
+            self._keep_radius(first_block, n_blocks, radius, status)
         self.bank.set_weights(W, W_in, W_fb)
         self.n_sets = n_blocks
         return status
+
+    # the radius cache of one run(): radius float64 [n] and status int32 [n] on the device for this rank's n contiguous
+    # blocks, and on the host which of them are filled (so no decision here reads the device)
+    def _reset_radius_cache(self, mine):
+        self.fresh_radius_hits, self._radius_cache = 0, None
+        if self.reservoirs == "fresh" and self.fresh_radius_cache and len(mine):
+            torch, n = self.torch, len(mine)
+            self._radius_cache = (mine[0], torch.zeros(n, dtype=torch.float64, device=self.device),
+                                  torch.ones(n, dtype=torch.int32, device=self.device), np.zeros(n, dtype=bool))
+
+    def _slot_blocks(self, first_block, n_blocks, base):
+        """Cache index of the block in slot 0 .. n_blocks - 1 (block b sits in slot b % n_blocks)."""
+        slots = np.arange(n_blocks)
+        idx = first_block + (slots - first_block) % n_blocks - base
+        return self.torch.as_tensor(idx, dtype=self.torch.int64, device=self.device), idx
+
+    def _cached_radius(self, first_block, n_blocks):
+        """(radius, status) of a chunk, slot by slot, when the cache holds every one of its blocks; else None."""
+        c = self._radius_cache
+        if c is None or first_block < c[0] or first_block + n_blocks - c[0] > len(c[3]):
+            return None
+        idx_t, idx = self._slot_blocks(first_block, n_blocks, c[0])
+        return (c[1][idx_t], c[2][idx_t]) if c[3][idx].all() else None
+
+    def _keep_radius(self, first_block, n_blocks, radius, status):
+        c = self._radius_cache
+        if c is None or first_block < c[0] or first_block + n_blocks - c[0] > len(c[3]):
+            return
+        idx_t, idx = self._slot_blocks(first_block, n_blocks, c[0])
+        c[1][idx_t] = radius
+        c[2][idx_t] = status
+        c[3][idx] = True
 
     def _require_block_independent_bank(self, who):
         if self.reservoirs == "fresh":
@@ -584,6 +640,7 @@ class DetectorSweep:
         counters = torch.zeros((n_snr, 2), dtype=torch.int64, device=self.device)
         mine = blocks_for_rank(self.rank, self.world, blocks_per_snr)
         self.fits_repaired = 0
+        self._reset_radius_cache(mine)
         for si, ebno in enumerate(ebno_list):
             chunks = [mine[c0:c0 + chunk] for c0 in range(0, len(mine), chunk)]
             if not chunks:
@@ -596,6 +653,7 @@ class DetectorSweep:
             counters[si] += res[:, :2].sum(dim=0)
             if self.ridge_grid is not None:
                 self.ridge_choice_counts[ebno] = res[:, 3:].sum(dim=0).cpu().numpy()
+        self._radius_cache = None           # (a run()'s own: nothing outside it is served from the cache)
         reduce_counters(counters, dist, self.world)
         c = counters.cpu().numpy()
         return c[:, 0] / np.maximum(c[:, 1], 1), c

@@ -405,12 +405,24 @@ int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_group
  *   The workspace (esn_spectral_radius_workspace_bytes, 8-byte aligned) holds two zero-padded images per matrix; the
  *   query answers 0 for n_sets <= 0, n_res <= 0 or n_res > 4096 (the last with the limit in esn_last_error()).
  *
+ * esn_spectral_radius_split_batch  the same recurrence, ratio form, arguments, checks, status and batch invariance, with
+ *   every squaring on the fp16 matrix pipe: X = s B (s a power of two fixed by n_res alone, |B| <= 1) is split into
+ *   hi = fp16(X) and lo = fp16((X - hi) 2^11), and X X ~ hi hi + 2^-11 (hi lo + lo hi) is three products accumulated
+ *   in float32; the norms f_k stay float64.  Within 1e-6 relative of esn_spectral_radius_batch at the same K on the
+ *   reference's matrices (the two pieces carry 22 bits).  A matrix whose powers fall below the fp16 range may be
+ *   flagged (status 1) where esn_spectral_radius_batch would still measure it.  Its workspace
+ *   (esn_spectral_radius_split_workspace_bytes, 8-byte aligned) holds two images per matrix in both orientations as
+ *   fp16 hi / lo planes: the bytes of the float64 path's two images.
+ *
  * esn_scale_reservoirs  W[s] *= rho / radius[s] where status[s] == 0; a flagged set is left as it is. */
 int esn_gen_reservoirs(int n_res, int n_in, int n_out, double sparsity, uint64_t seed, uint64_t first_set, int n_sets,
                        const double* uniforms, double* W, double* W_in, double* W_fb, void* stream);
 size_t esn_spectral_radius_workspace_bytes(int n_sets, int n_res);
 int esn_spectral_radius_batch(const double* W, int n_sets, int n_res, int n_squarings, double* radius, int* status,
                               void* workspace, size_t workspace_bytes, void* stream);
+size_t esn_spectral_radius_split_workspace_bytes(int n_sets, int n_res);
+int esn_spectral_radius_split_batch(const double* W, int n_sets, int n_res, int n_squarings, double* radius,
+                                    int* status, void* workspace, size_t workspace_bytes, void* stream);
 int esn_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const double* radius, const int* status,
                          void* stream);
 
