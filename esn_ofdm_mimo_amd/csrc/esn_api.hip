@@ -57,6 +57,7 @@ static const KnobRow kKnobTable[] = {
     {"gen_ko", nullptr, offsetof(Knobs, gen_ko), KNOB_INT, 0},
     {"s16", "ESN_S16", offsetof(Knobs, s16), KNOB_FLAG, 1},
     {"hcluster", "ESN_HCLUSTER", offsetof(Knobs, hcluster), KNOB_HCLUSTER, 1},
+    {"detect_fixed", "ESN_DETECT_FIXED", offsetof(Knobs, detect_fixed), KNOB_FLAG, 1},
 };
 
 static void knob_parse(const KnobRow& r, const char* v, Knobs& k) {

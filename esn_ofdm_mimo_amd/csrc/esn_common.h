@@ -247,6 +247,8 @@ struct Knobs {
     int s16;               // 1 (default): fp16/bf16 predict at 257..512 units on the 16x16x32 kernel; 0: the 32x32x16 one (A/B)
     int hcluster;          // 1 (default): fp16/bf16 harvest at 257..512 units on the cluster kernel (two members per cluster)
                            // when a workspace is given; 4 / 8: that many members (A/B); 0: the persistent kernel
+    int detect_fixed;      // 1 (default): the detector tail at (N 128, n_t 4, 16-QAM) runs its fixed-shape instance; 0: every
+                           // call runs the generic kernel (A/B and bitwise tests)
 };
 Knobs& knobs();
 

@@ -83,7 +83,8 @@ int esn_abi_version(void);
 /* Tuning / diagnostic knobs for benchmarks and A/B tests (no counterpart in the reference).  The
  * library reads the initial value of every key but "gen_ko" from the environment ONCE, at its first call -- the
  * variable is ESN_ + the key in capitals: ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP, ESN_CHOL_DMA,
- * ESN_F64_MFMA, ESN_RS, ESN_S16, ESN_BIG_GEMM, ESN_CLUSTER, ESN_BIG_PIPE, ESN_BIG_NT, ESN_HARVEST_GEMM, ESN_HCLUSTER
+ * ESN_F64_MFMA, ESN_RS, ESN_S16, ESN_BIG_GEMM, ESN_CLUSTER, ESN_BIG_PIPE, ESN_BIG_NT, ESN_HARVEST_GEMM, ESN_HCLUSTER,
+ * ESN_DETECT_FIXED
  * (one table in csrc/esn_api.hip serves both) -- and afterwards only this call changes them:
  *   "skew"          "0" = in-step schedule for the fp16/bf16 predict kernel, else skewed (default)
  *   "mfma_geom"     "NW,MT,NT" re-cuts the fp16/bf16 predict tiling; ignored unless 32*NW*MT equals
@@ -108,6 +109,10 @@ int esn_abi_version(void);
  *                   "4" / "8" = clusters of that many workgroups instead of pairs (esn_harvest_cluster.hip; A/B runs).
  *                   esn_harvest_workspace_bytes follows the knob: ask for the size after setting it
  *   "gen_ko"        frame-generator knock-out mask for tools/time_gen.py (timing only, wrong frames)
+ *   "detect_fixed"  "0" = esn_detect_count / esn_detect_count_f32 always on the generic kernel.  By default a call
+ *                   at N = 128, N_t = 4, 16-QAM with 16-byte aligned tx_bits and Y (8-byte for float Y) runs the
+ *                   fixed-shape instance (esn_detect.hip: one wave per frame, eight frames per workgroup); counts
+ *                   and X_hat are bitwise the same (tx_bits bytes are 0 or 1); A/B runs (ESN_DETECT_FIXED)
  * Returns 0, or -1 for an unknown key. */
 int esn_debug_set(const char* key, const char* value);
 
