@@ -7,6 +7,7 @@
 #include <math.h>
 #include <string.h>
 #include "esn_launch.h"
+#include "esn_solve.h"      // the workspace sizes of the read-out solves
 
 using namespace esn;
 
@@ -503,17 +504,7 @@ size_t esn_readout_ridge_loo_workspace_bytes(int n_groups, int n_ridge, int rows
     return sizeof(double) * ridge_loo_work_doubles() * (size_t)n_groups;
 }
 
-// The arguments of one read-out entry point; what an entry point does not take stays nullptr (and n_ridge 1).
-struct ReadoutCall {
-    const char* who;
-    const double* E; const float* E32; const double* D;
-    int n_groups, T, transient, cols, n_out;
-    const double *t_scale, *t_shift, *ridge; int n_ridge;
-    double *W_out, *score; int *choice, *status;
-    void* workspace; size_t workspace_bytes; void* stream;
-};
-
-// What an entry point requires of them.
+// What an entry point requires of its arguments (esn_launch.h: ReadoutArgs).
 enum ReadoutKernel { kQr, kChol, kLoo };
 struct ReadoutRule {
     ReadoutKernel kernel;
@@ -532,8 +523,7 @@ static const ReadoutRule
     kLooRidge = {kLoo, true, 128, 16, esn_readout_ridge_loo_workspace_bytes, "esn_readout_ridge_loo_workspace_bytes", 8};
 
 // Null pointers, sizes, "not served", workspace size, alignment -- in that order for every entry point -- then the launch.
-static int readout_call(const ReadoutCall& c, const ReadoutRule& r) {
-    const char* who = c.who;
+static int readout_call(const char* who, const ReadoutArgs& c, const ReadoutRule& r) {
     const bool loo = r.kernel == kLoo;
     if ((!c.E && !c.E32) || !c.D || !c.W_out || !c.status || (r.ridge && !c.ridge) || (loo && (!c.score || !c.choice))
         || (!r.need && !c.workspace))
@@ -560,81 +550,77 @@ static int readout_call(const ReadoutCall& c, const ReadoutRule& r) {
         if (r.align == 16 && ((e | w) & 15)) return fail(-1, "%s: E and the workspace must be 16-byte aligned", who);
         if (r.align == 8 && (w & 7)) return fail(-1, "%s: the workspace must be 8-byte aligned", who);
     }
-    hipStream_t s = (hipStream_t)c.stream;
-    if (loo)
-        return hip_fail(launch_ridge_loo(c.E, c.E32, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
-                                         c.t_shift, c.ridge, c.n_ridge, c.W_out, c.score, c.choice, c.status,
-                                         c.workspace, s), who);
-    if (r.kernel == kQr)
-        return hip_fail(launch_readout_solve(c.E, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
-                                             c.t_shift, c.W_out, c.status, c.workspace, s, c.ridge, c.n_ridge), who);
-    if (big)
-        return hip_fail(launch_readout_chol_big(c.E, c.E32, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
-                                                c.t_shift, c.W_out, c.status, c.workspace, s, c.ridge, c.n_ridge), who);
-    return hip_fail(launch_readout_chol(c.E, c.E32, c.D, c.n_groups, c.T, c.transient, c.cols, c.n_out, c.t_scale,
-                                        c.t_shift, c.W_out, c.status, s, c.ridge, c.n_ridge), who);
+    if (loo) return hip_fail(launch_ridge_loo(c), who);
+    if (r.kernel == kQr) return hip_fail(launch_readout_solve(c), who);
+    return hip_fail(big ? launch_readout_chol_big(c) : launch_readout_chol(c), who);
 }
 
 int esn_readout_solve_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                             int n_out, const double* t_scale, const double* t_shift, double* W_out,
                             int* status, void* workspace, void* stream) {
-    return readout_call({"esn_readout_solve_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift,
-                         nullptr, 1, W_out, nullptr, nullptr, status, workspace, 0, stream}, kQrPinv);
+    return readout_call("esn_readout_solve_batch",
+                        {E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, nullptr, 1, W_out,
+                         nullptr, nullptr, status, workspace, 0, (hipStream_t)stream}, kQrPinv);
 }
 
 int esn_readout_solve_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                                   int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                   int n_ridge, double* W_out, int* status, void* workspace, void* stream) {
-    return readout_call({"esn_readout_solve_ridge_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
-                         t_shift, ridge, n_ridge, W_out, nullptr, nullptr, status, workspace, 0, stream}, kQrRidge);
+    return readout_call("esn_readout_solve_ridge_batch",
+                        {E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge, W_out,
+                         nullptr, nullptr, status, workspace, 0, (hipStream_t)stream}, kQrRidge);
 }
 
 int esn_readout_solve_chol_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                                  int n_out, const double* t_scale, const double* t_shift, double* W_out,
                                  int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    return readout_call({"esn_readout_solve_chol_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
-                         t_shift, nullptr, 1, W_out, nullptr, nullptr, status, workspace, workspace_bytes, stream}, kCholPinv);
+    return readout_call("esn_readout_solve_chol_batch",
+                        {E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, nullptr, 1, W_out,
+                         nullptr, nullptr, status, workspace, workspace_bytes, (hipStream_t)stream}, kCholPinv);
 }
 
 int esn_readout_solve_chol_batch_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols,
                                      int n_out, const double* t_scale, const double* t_shift, double* W_out,
                                      int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    return readout_call({"esn_readout_solve_chol_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale,
-                         t_shift, nullptr, 1, W_out, nullptr, nullptr, status, workspace, workspace_bytes, stream}, kCholPinv);
+    return readout_call("esn_readout_solve_chol_batch_f32",
+                        {nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, nullptr, 1, W_out,
+                         nullptr, nullptr, status, workspace, workspace_bytes, (hipStream_t)stream}, kCholPinv);
 }
 
 int esn_readout_solve_chol_ridge_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                                        int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                        int n_ridge, double* W_out, int* status, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    return readout_call({"esn_readout_solve_chol_ridge_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
-                         t_shift, ridge, n_ridge, W_out, nullptr, nullptr, status, workspace, workspace_bytes, stream},
-                        kCholRidge);
+    return readout_call("esn_readout_solve_chol_ridge_batch",
+                        {E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge, W_out,
+                         nullptr, nullptr, status, workspace, workspace_bytes, (hipStream_t)stream}, kCholRidge);
 }
 
 int esn_readout_solve_chol_ridge_batch_f32(const float* E, const double* D, int n_groups, int T, int transient,
                                            int cols, int n_out, const double* t_scale, const double* t_shift,
                                            const double* ridge, int n_ridge, double* W_out, int* status,
                                            void* workspace, size_t workspace_bytes, void* stream) {
-    return readout_call({"esn_readout_solve_chol_ridge_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out,
-                         t_scale, t_shift, ridge, n_ridge, W_out, nullptr, nullptr, status, workspace, workspace_bytes,
-                         stream}, kCholRidge);
+    return readout_call("esn_readout_solve_chol_ridge_batch_f32",
+                        {nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge, W_out,
+                         nullptr, nullptr, status, workspace, workspace_bytes, (hipStream_t)stream}, kCholRidge);
 }
 
 int esn_readout_ridge_loo_batch(const double* E, const double* D, int n_groups, int T, int transient, int cols,
                                 int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                 int n_ridge, double* W_out, double* score, int* choice, int* status, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    return readout_call({"esn_readout_ridge_loo_batch", E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
-                         t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes, stream}, kLooRidge);
+    return readout_call("esn_readout_ridge_loo_batch",
+                        {E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge, W_out,
+                         score, choice, status, workspace, workspace_bytes, (hipStream_t)stream}, kLooRidge);
 }
 
 int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols,
                                     int n_out, const double* t_scale, const double* t_shift, const double* ridge,
                                     int n_ridge, double* W_out, double* score, int* choice, int* status,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    return readout_call({"esn_readout_ridge_loo_batch_f32", nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale,
-                         t_shift, ridge, n_ridge, W_out, score, choice, status, workspace, workspace_bytes, stream}, kLooRidge);
+    return readout_call("esn_readout_ridge_loo_batch_f32",
+                        {nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, ridge, n_ridge, W_out,
+                         score, choice, status, workspace, workspace_bytes, (hipStream_t)stream}, kLooRidge);
 }
 
 // ---- reservoirs drawn on the device (esn_reservoir.hip) ------------------------------------------------------------

@@ -354,9 +354,11 @@ __device__ __forceinline__ float tanh_prescaled(float z) {
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
 #define ESN_STAMP_SET(var) { __builtin_amdgcn_sched_barrier(0); \
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
+#define ESN_STAMPS_ONLY(...) __VA_ARGS__      // what only the diagnostic build holds: accumulators, sums, the write-out
 #else
 #define ESN_STAMP(var)
 #define ESN_STAMP_SET(var)
+#define ESN_STAMPS_ONLY(...)
 #endif
 
 }  // namespace esn

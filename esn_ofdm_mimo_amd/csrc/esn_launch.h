@@ -59,30 +59,24 @@ int launch_pack_weights(int precision, const esn_shape_t* sh, const Geometry& g,
                         const double* Win, const double* Wfb, void* packed, hipStream_t stream);
 int launch_pack_readout(int precision, const esn_shape_t* sh, const Geometry& g, int n_groups,
                         const double* Wout, void* packed, hipStream_t stream);
-// esn_solve.hip
-// ridge != nullptr (device, [n_groups][n_ridge]): the ridge instances, one workgroup per (group, lambda);
-// W_out, status and the workspace then hold n_groups * n_ridge entries
-size_t solve_work_doubles(int rows, int cols, int n_out);
-size_t solve_ridge_work_doubles(int rows, int cols, int n_out);
-int launch_readout_solve(const double* E, const double* D, int n_groups, int T, int transient,
-                         int cols, int n_out, const double* t_scale, const double* t_shift,
-                         double* W_out, int* status, void* workspace, hipStream_t stream,
-                         const double* ridge = nullptr, int n_ridge = 1);
-int launch_readout_chol(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
-                        int cols, int n_out, const double* t_scale, const double* t_shift,
-                        double* W_out, int* status, hipStream_t stream,
-                        const double* ridge = nullptr, int n_ridge = 1);
-size_t chol_big_work_doubles(int n);
-int launch_readout_chol_big(const double* E, const float* E32, const double* D, int n_groups, int T, int transient,
-                            int cols, int n_out, const double* t_scale, const double* t_shift,
-                            double* W_out, int* status, void* workspace, hipStream_t stream,
-                            const double* ridge = nullptr, int n_ridge = 1);
+// The arguments of one read-out entry point, from the ABI to the launch; what an entry point does not take stays
+// nullptr (and n_ridge 1).  ridge != nullptr (device, [n_groups][n_ridge]): the ridge instances, one workgroup per
+// (group, lambda); W_out, status and the workspace then hold n_groups * n_ridge entries.
+struct ReadoutArgs {
+    const double* E; const float* E32; const double* D;
+    int n_groups, T, transient, cols, n_out;
+    const double *t_scale, *t_shift, *ridge; int n_ridge;
+    double *W_out, *score; int *choice, *status;
+    void* workspace; size_t workspace_bytes; hipStream_t stream;
+};
+// esn_solve_qr.hip, esn_solve_chol.hip, esn_solve_chol_big.hip (esn_solve.h: the parameter block, the workspace sizes)
+int launch_readout_solve(const ReadoutArgs& a);
+int launch_readout_chol(const ReadoutArgs& a);
+int launch_readout_chol_big(const ReadoutArgs& a);
 // esn_loo.hip: leave-one-out choice among n_ridge candidates per group; the workspace holds ridge_loo_work_doubles()
 // doubles per group (the un-factored Gram matrix, the right-hand side and the best solution so far)
 size_t ridge_loo_work_doubles();
-int launch_ridge_loo(const double* E, const float* E32, const double* D, int n_groups, int T, int transient, int cols,
-                     int n_out, const double* t_scale, const double* t_shift, const double* ridge, int n_ridge,
-                     double* W_out, double* score, int* choice, int* status, void* workspace, hipStream_t stream);
+int launch_ridge_loo(const ReadoutArgs& a);
 // esn_reservoir.hip: reservoirs drawn, measured (spectral radius by repeated squaring) and rescaled on the device; the
 // workspace holds specrad_work_doubles(n_res) doubles per matrix (two padded images, the per-tile norms, the log)
 size_t specrad_work_doubles(int n_res);

@@ -11,8 +11,9 @@
 // K^-1 D_s = X^T (X D_s) and diag(K^-1)[i] = sum_k X[k][i]^2 are plain products.  Every sum runs in an order fixed by
 // the shape alone, so a group's score, choice and W_out do not depend on the batch it is solved in.
 //
-// Self-contained on purpose: the Gram staging and the MFMA operand layout repeat what readout_chol_kernel does, but
-// sharing them through a header would change how the eight instances of that kernel compile.
+// Self-contained on purpose: the Gram staging and the MFMA operand layout repeat what readout_chol_kernel
+// (esn_solve_chol.hip) does, but sharing them through a header would change how the eight instances of that kernel
+// compile.  Only the host-side argument struct (esn_launch.h: ReadoutArgs) is common.
 #include <stdlib.h>
 #include "esn_common.h"
 #include "esn_launch.h"
@@ -371,24 +372,20 @@ __global__ __launch_bounds__(LO_NT) void ridge_loo_kernel(LooParams sp) {
 
 size_t ridge_loo_work_doubles() { return (size_t)LO_TRI + 2 * LO_NP * LO_RHS; }
 
-int launch_ridge_loo(const double* E, const float* E32, const double* D, int n_groups, int T, int transient, int cols,
-                     int n_out, const double* t_scale, const double* t_shift, const double* ridge, int n_ridge,
-                     double* W_out, double* score, int* choice, int* status, void* workspace, hipStream_t stream) {
-    const int rows = T - transient;
+int launch_ridge_loo(const ReadoutArgs& a) {
+    const int rows = a.T - a.transient, cols = a.cols;
     const int n = rows <= cols ? rows : cols;
-    if (n > LO_NP || n_out > LO_RHS) return -1;
-    LooParams sp;
-    sp.E = E; sp.E32 = E32; sp.D = D; sp.T = T; sp.transient = transient; sp.cols = cols; sp.n_out = n_out;
-    sp.t_scale = t_scale; sp.t_shift = t_shift; sp.ridge = ridge; sp.n_ridge = n_ridge;
-    sp.W_out = W_out; sp.score = score; sp.choice = choice; sp.status = status;
-    sp.work = reinterpret_cast<double*>(workspace); sp.work_stride = ridge_loo_work_doubles();
+    if (n > LO_NP || a.n_out > LO_RHS) return -1;
+    const LooParams sp = {a.E, a.E32, a.D, a.T, a.transient, cols, a.n_out, a.t_scale, a.t_shift, a.ridge, a.n_ridge,
+                          a.W_out, a.score, a.choice, a.status,
+                          reinterpret_cast<double*>(a.workspace), ridge_loo_work_doubles()};
     const bool wide = rows <= cols;
-    void (*fn)(LooParams) = E32 ? (wide ? ridge_loo_kernel<float, true> : ridge_loo_kernel<float, false>)
-                                : (wide ? ridge_loo_kernel<double, true> : ridge_loo_kernel<double, false>);
+    void (*fn)(LooParams) = a.E32 ? (wide ? ridge_loo_kernel<float, true> : ridge_loo_kernel<float, false>)
+                                  : (wide ? ridge_loo_kernel<double, true> : ridge_loo_kernel<double, false>);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)LO_LDS);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fn, dim3(n_groups), dim3(LO_NT), LO_LDS, stream, sp);
+    hipLaunchKernelGGL(fn, dim3(a.n_groups), dim3(LO_NT), LO_LDS, a.stream, sp);
     return (int)hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 """(no GPU) What the residency and the diagonal-block factorisation of the LDS Cholesky read-out kernel
-(readout_chol_kernel in esn_solve.hip) rest on, read off the gfx950 assembly of all eight instances, compiled with the
+(readout_chol_kernel in esn_solve_chol.hip) rest on, read off the gfx950 assembly of all eight instances, compiled with the
 product flags the way tools/chol_isa.py does:
 
   * no scratch and at most 128 VGPRs in any instance: two workgroups of 512 threads per CU (four waves per SIMD);
@@ -36,7 +36,7 @@ def _name(key):
 def instances(tmp_path_factory):
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not found")
-    out = str(tmp_path_factory.mktemp("chol_isa") / "esn_solve.s")
+    out = str(tmp_path_factory.mktemp("chol_isa") / "esn_solve_chol.s")
     isa.compile_asm(out)
     with open(out) as f:
         return isa.functions(f.read().splitlines())

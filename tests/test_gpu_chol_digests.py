@@ -3,7 +3,8 @@ which its diagonal-block factorisation can go wrong, exactly the W_out and statu
 tests/golden/chol_parent_digests.json wrote: the DPP form of the factorisation -- and any later rewrite that is meant
 to keep the results -- changes no output bit.  The sample and the inputs are those of tools/record_chol_digests.py
 (one tile and ragged tiles, wide and tall, the residency tail, a rejected pivot by a duplicated row, a zero row and a
-duplicated column, the ridge instances, the workspace kernel; float64 and float32 E).  Every status is 0 except the
+duplicated column, the ridge instances, the workspace kernel, the W_out passes that cols 528 and 60 never take; float64
+and float32 E).  Every status is 0 except the
 singular group of the rejected-pivot cases, which is 1."""
 import importlib.util
 import json
@@ -45,6 +46,8 @@ def test_sample_covers_what_the_factorisation_can_get_wrong():
                 assert ("ridge", r, c, 8, 3, e32, None, lam) in key
         for r, c in ((144, 528), (130, 200), (600, 144)):
             assert ("big", r, c, 8, 2, e32, None, None) in key
+        for r, c, o in ((40, 61, 3), (20, 600, 8), (20, 800, 8)):
+            assert ("wide", r, c, o, 3, e32, None, None) in key
     assert ("tail", 128, 528, 8, 513, True, None, None) in key
 
 

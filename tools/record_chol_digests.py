@@ -16,6 +16,10 @@ The sample (rows x cols is the system after the transient; E is seeded randn wit
          tall 300 x 100 with a duplicated column -- status 1 for group 2 only, its W_out is part of the digest
   ridge  lambda 0.0 and 1e-3 on one wide and one tall shape (the ridge instances of the kernel)
   big    readout_chol_big_kernel: wide 144 x 528 and 130 x 200, tall 600 x 144, G 2, n_out 8
+  w_out  the W_out passes of the LDS kernel that cols 528 and 60 never take, wide, G 3: 40 x 61, n_out 3 (no 16-byte
+         runs: scalar Gram fetch and scalar W_out loop); 20 x 600 (float32: DMA Gram, then the scalar loop, three parts
+         do not fit the tile area; float64: the vector pass with one part); 20 x 800 (float32: two parts through the
+         W_out ring, two rows per chunk)
 each with float64 and float32 E, except G 513.  Inputs come from seeded NumPy generators, so this tool and the test
 build the same arrays."""
 import argparse
@@ -51,6 +55,9 @@ def cases():
                 for lam in (0.0, 1e-3) for e32 in (False, True)]
     for r, c in ((144, 528), (130, 200), (600, 144)):
         out += [dict(kind="big", rows=r, cols=c, n_out=8, G=2, e32=e32, drop=None, ridge=None) for e32 in (False, True)]
+    # the W_out paths no shape above takes (appended: inputs are seeded by case index)
+    for r, c, o in ((40, 61, 3), (20, 600, 8), (20, 800, 8)):
+        out += [dict(kind="wide", rows=r, cols=c, n_out=o, G=3, e32=e32, drop=None, ridge=None) for e32 in (False, True)]
     for c in out:
         c["id"] = (f"{c['kind']}-{c['rows']}x{c['cols']}-o{c['n_out']}-G{c['G']}-{'f32' if c['e32'] else 'f64'}"
                    + (f"-drop_{c['drop']}" if c["drop"] else "") + (f"-ridge{c['ridge']:g}" if c["ridge"] is not None else ""))

@@ -1,4 +1,4 @@
-"""Time budget of the LDS-resident Cholesky read-out solve (csrc/esn_solve.hip readout_chol_kernel) on the
+"""Time budget of the LDS-resident Cholesky read-out solve (csrc/esn_solve_chol.hip readout_chol_kernel) on the
 headline shape: the whole kernel, then with phases switched off through the `chol_skip` debug knob
 (1: Gram over one k-chunk only, 2: one 16-column block of the factorisation, 4: no triangular solves,
 8: no W_out = A^T alpha).  Differences of the totals are the phases' shares.  Results with a knob set are
