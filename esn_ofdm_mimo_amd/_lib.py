@@ -85,6 +85,9 @@ SIGNATURES = {
     "esn_scale_reservoirs": (C.c_int, [_dp, C.c_int, C.c_int, C.c_double, _dp, _ip, _vp]),
     "esn_gen_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp,
                                C.c_uint64, C.c_uint64, _dp, _vp]),
+    # Jakes taps inside a coherence block: taps [n_blocks][n_sym][n_r][n_t][isi]; angles_in [links][paths][16][2]
+    "esn_gen_taps_doppler": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                       C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, _vp]),
     "esn_gen_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  _dp, _dp, C.c_double, _dp, _vp, _dp, C.c_uint64, C.c_uint64, _vp, _dp, _dp, _vp]),
     "esn_gen_frames_c64": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

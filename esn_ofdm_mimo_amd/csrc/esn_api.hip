@@ -743,14 +743,9 @@ static const double kTdlbDelay[23] = {0.0000, 0.1072, 0.2155, 0.2095, 0.2870, 0.
 static const double kTdlbPowDb[23] = {0.0, -2.2, -4.0, -3.2, -9.8, -1.2, -3.4, -5.2, -7.6, -3.0, -8.9, -9.0,
                                       -4.8, -5.7, -7.5, -1.9, -7.6, -12.2, -9.8, -11.4, -14.9, -9.2, -11.3};
 
-int esn_gen_taps(int kind, int n_blocks, int n_r, int n_t, int isi, double fs_hz, double ds_ns,
-                 const double* gains_in, uint64_t seed, uint64_t link_offset, double* taps, void* stream) {
-    if (!taps) return fail(-1, "esn_gen_taps: null pointer");
-    if (kind < 0 || kind > 2 || n_blocks <= 0 || n_r <= 0 || n_t <= 0 || isi <= 0 || isi > 16)
-        return fail(-1, "esn_gen_taps: invalid arguments (kind=%d isi=%d)", kind, isi);
-    TapParams tp;
-    memset(&tp, 0, sizeof(tp));
-    tp.kind = kind; tp.n_links = n_blocks * n_r * n_t; tp.isi = isi;
+// kind, isi, paths, powers and delays of a TapParams (kinds 0 and 1 shared with esn_gen_taps_doppler)
+static void tap_tables(TapParams& tp, int kind, int isi, double fs_hz, double ds_ns) {
+    tp.kind = kind; tp.isi = isi;
     if (kind == 0) {
         tp.n_paths = 23;
         double sum = 0.0;
@@ -770,8 +765,40 @@ int esn_gen_taps(int kind, int n_blocks, int n_r, int n_t, int isi, double fs_hz
         tp.n_paths = 1;
         tp.path_sqrt_pow[0] = 1.0;
     }
+}
+
+int esn_gen_taps(int kind, int n_blocks, int n_r, int n_t, int isi, double fs_hz, double ds_ns,
+                 const double* gains_in, uint64_t seed, uint64_t link_offset, double* taps, void* stream) {
+    if (!taps) return fail(-1, "esn_gen_taps: null pointer");
+    if (kind < 0 || kind > 2 || n_blocks <= 0 || n_r <= 0 || n_t <= 0 || isi <= 0 || isi > 16)
+        return fail(-1, "esn_gen_taps: invalid arguments (kind=%d isi=%d)", kind, isi);
+    TapParams tp;
+    memset(&tp, 0, sizeof(tp));
+    tap_tables(tp, kind, isi, fs_hz, ds_ns);
+    tp.n_links = n_blocks * n_r * n_t;
     tp.gains_in = gains_in; tp.seed = seed; tp.link_offset = link_offset; tp.taps = taps;
     return hip_fail(launch_gen_taps(tp, (hipStream_t)stream), "esn_gen_taps");
+}
+
+int esn_gen_taps_doppler(int kind, int n_blocks, int n_sym, int n_r, int n_t, int isi, double fs_hz, double ds_ns,
+                         double fd_tsym, const double* angles_in, uint64_t seed, uint64_t link_offset, double* taps,
+                         void* stream) {
+    const char* who = "esn_gen_taps_doppler";
+    if (!taps) return fail(-1, "%s: null pointer", who);
+    if (kind < 0 || kind > 1) return fail(-1, "%s: kind=%d must be 0 (TDL-B) or 1 (exponential PDP)", who, kind);
+    if (n_blocks <= 0 || n_r <= 0 || n_t <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_sym < 1 || n_sym > 4096) return fail(-1, "%s: n_sym=%d must be in [1, 4096]", who, n_sym);
+    if (isi < 1 || isi > 16) return fail(-1, "%s: isi=%d must be in [1, 16]", who, isi);
+    if (!(fd_tsym >= 0.0 && fd_tsym <= 0.5))
+        return fail(-1, "%s: fd_tsym=%g must be in [0, 0.5] cycles per symbol", who, fd_tsym);
+    if ((long long)n_blocks * n_r * n_t > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 links", who);
+    DopplerParams dp;
+    memset(&dp, 0, sizeof(dp));
+    tap_tables(dp.tp, kind, isi, fs_hz, ds_ns);
+    dp.tp.n_links = n_blocks * n_r * n_t;
+    dp.tp.seed = seed; dp.tp.link_offset = link_offset; dp.tp.taps = taps;
+    dp.n_sym = n_sym; dp.links_per_block = n_r * n_t; dp.fd_tsym = fd_tsym; dp.angles_in = angles_in;
+    return hip_fail(launch_gen_taps_doppler(dp, (hipStream_t)stream), who);
 }
 
 static int gen_common(const char* who, bool c64, int n_frames, int frames_per_block, int n_sub, int cp, int n_t,

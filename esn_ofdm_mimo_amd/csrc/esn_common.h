@@ -97,6 +97,16 @@ struct TapParams {
     double* taps;        // complex [n_links][isi]
 };
 
+// Doppler taps (gen_taps_doppler_kernel): the paths, powers and delays of TapParams, one tap set per OFDM symbol
+struct DopplerParams {
+    TapParams tp;        // kind 0 / 1 tables; n_links = n_blocks * links_per_block; gains_in unused;
+                         // taps = complex [n_blocks][n_sym][links_per_block][isi]
+    int n_sym;           // symbols stored per block: s = 0 .. n_sym - 1
+    int links_per_block; // n_r * n_t
+    double fd_tsym;      // Doppler frequency * symbol time, cycles per symbol
+    const double* angles_in;   // optional [n_links][n_paths][ESN_DOPPLER_SINUSOIDS][2] = (a, phi) in half-turns (parity)
+};
+
 struct FrameGenParams {
     int n_frames, frames_per_block, n_sub, log2n, cp, n_t, n_r, isi, m;
     const double* p_i;        // [n_blocks]  Pi = 10^(EbNo/10) No

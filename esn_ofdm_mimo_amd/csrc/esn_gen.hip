@@ -57,7 +57,7 @@ __device__ __forceinline__ void box_muller_fast(uint32_t a, uint32_t b, double& 
     z1 = (double)(rr * __builtin_amdgcn_sinf(u2));
 }
 
-enum { PURPOSE_BITS = 1, PURPOSE_NOISE = 2, PURPOSE_TAPS = 3 };
+enum { PURPOSE_BITS = 1, PURPOSE_NOISE = 2, PURPOSE_TAPS = 3, PURPOSE_DOPPLER = 4 };
 
 __global__ void gen_taps_kernel(TapParams tp) {
     const int link = blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,6 +101,106 @@ __global__ void gen_taps_kernel(TapParams tp) {
     for (int k = 0; k < tp.isi; ++k) {
         tp.taps[((size_t)link * tp.isi + k) * 2] = hr[k];
         tp.taps[((size_t)link * tp.isi + k) * 2 + 1] = hi[k];
+    }
+}
+
+// Clarke / Jakes fading inside a coherence block: path p of a link is a sum of M = ESN_DOPPLER_SINUSOIDS unit phasors,
+//     g_p(s) = sqrt(P_p / M) sum_m exp(j pi (2 fd_tsym s cos(pi a_m) + phi_m)),       a, phi uniform on [0, 2) half-turns
+// (counter (global link, PURPOSE_DOPPLER, p M + m), words 0 and 1), placed on the taps exactly as gen_taps_kernel places
+// its Gaussian gains; TDL-B's unit-energy factor is the one of symbol 0 for the whole block.
+//
+// One wave per workgroup, two links per wave, one lane per (link, path).  A lane keeps its path's M phasors and their
+// per-symbol rotators in registers (4 M doubles), seeds both exactly with sincospi at s = 0 and advances a phasor by
+// ONE complex multiplication per symbol (a sincospi per (symbol, sinusoid) would be 368 pairs per link and symbol);
+// the loop always starts at s = 0, so symbol s is a function of (seed, global link, s) alone.  Every sum has a fixed
+// order: a lane adds its phasors in index order; TDL-B's taps are gathered through LDS by lane k < isi over the paths
+// in path order (the order of gen_taps_kernel's loop); the energy is summed over k in tap order.  No atomics.
+// KIND 1 has one path per tap: lane k's path IS tap k, nothing is exchanged.
+constexpr int DOP_M = ESN_DOPPLER_SINUSOIDS;
+constexpr int DOP_LANES = 32;       // lanes per link: >= 23 paths, >= 16 taps
+constexpr int DOP_TDLB_PATHS = 23;
+
+template <int KIND>
+__global__ __launch_bounds__(64) void gen_taps_doppler_kernel(DopplerParams dp) {
+    __shared__ double2 gsh[2][2][DOP_LANES];       // [buffer][link of the wave][path]  path gains of one symbol
+    __shared__ double2 tsh[2][16];                 // [link of the wave][tap]           symbol 0's taps, for the energy
+    const TapParams& tp = dp.tp;
+    const int sub = threadIdx.x >> 5, p = threadIdx.x & (DOP_LANES - 1);
+    const int link = blockIdx.x * 2 + sub;
+    const bool live = link < tp.n_links;
+    const bool path = live && p < tp.n_paths;      // this lane owns a path
+    const bool tap = live && p < tp.isi;           // this lane stores a tap
+    const uint64_t gl = tp.link_offset + (uint64_t)(live ? link : 0);
+    const Philox ph{(uint32_t)tp.seed, (uint32_t)(tp.seed >> 32)};
+
+    double zr[DOP_M], zi[DOP_M], rr[DOP_M], ri[DOP_M];
+#pragma unroll
+    for (int m = 0; m < DOP_M; ++m) {
+        double a = 0.5, phi = 0.0;
+        if (path) {
+            if (dp.angles_in) {
+                const double* ap = dp.angles_in + (((size_t)link * tp.n_paths + p) * DOP_M + m) * 2;
+                a = ap[0]; phi = ap[1];
+            } else {
+                uint32_t w[4];
+                ph((uint32_t)gl, (uint32_t)(gl >> 32), PURPOSE_DOPPLER, (uint32_t)(p * DOP_M + m), w);
+                a = ((double)w[0] + 0.5) * (1.0 / 2147483648.0);
+                phi = ((double)w[1] + 0.5) * (1.0 / 2147483648.0);
+            }
+        }
+        sincospi(phi, &zi[m], &zr[m]);
+        sincospi(2.0 * dp.fd_tsym * cospi(a), &ri[m], &rr[m]);     // fd_tsym = 0: exactly 1 + 0j
+    }
+    const double scale = path ? tp.path_sqrt_pow[p] * 0.25 : 0.0;   // sqrt(P_p / M), M = 16
+    static_assert(DOP_M == 16, "scale assumes sqrt(1 / M) = 0.25");
+
+    // TDL-B: weight of path q on this lane's tap (1 - frac on floor(delay), frac on the next tap)
+    [[maybe_unused]] double w[KIND == 0 ? DOP_TDLB_PATHS : 1];
+    if constexpr (KIND == 0) {
+#pragma unroll
+        for (int q = 0; q < DOP_TDLB_PATHS; ++q) {
+            const double d = tp.path_delay_samples[q];
+            const int i0 = (int)floor(d);
+            const double frac = d - (double)i0;
+            w[q] = (i0 == p) ? 1.0 - frac : ((i0 + 1 == p) ? frac : 0.0);
+        }
+    }
+    const int lpb = dp.links_per_block;
+    const int blk = (live ? link : 0) / lpb, lib = (live ? link : 0) % lpb;
+    double2* out = reinterpret_cast<double2*>(tp.taps) + (((size_t)blk * dp.n_sym) * lpb + lib) * tp.isi + p;
+    const size_t sym_stride = (size_t)lpb * tp.isi;
+    double nrm = 1.0;
+
+    for (int s = 0; s < dp.n_sym; ++s) {
+        double sr = 0.0, si = 0.0;
+#pragma unroll
+        for (int m = 0; m < DOP_M; ++m) { sr += zr[m]; si += zi[m]; }
+        double hr = sr * scale, hi = si * scale;
+        if constexpr (KIND == 0) {
+            gsh[s & 1][sub][p] = make_double2(hr, hi);
+            __syncthreads();                        // (one wave: the other buffer is free again by the next symbol)
+            hr = 0.0; hi = 0.0;
+#pragma unroll
+            for (int q = 0; q < DOP_TDLB_PATHS; ++q) {
+                const double2 g = gsh[s & 1][sub][q];
+                hr = fma(g.x, w[q], hr); hi = fma(g.y, w[q], hi);
+            }
+            if (s == 0) {                           // unit energy at the pilot instant (driver :162-164)
+                if (p < 16) tsh[sub][p] = make_double2(hr, hi);
+                __syncthreads();
+                double e = 0.0;
+                for (int k = 0; k < tp.isi; ++k) { const double2 t = tsh[sub][k]; e += t.x * t.x + t.y * t.y; }
+                if (e > 0.0) nrm = 1.0 / sqrt(e);
+            }
+            hr *= nrm; hi *= nrm;
+        }
+        if (tap) out[(size_t)s * sym_stride] = make_double2(hr, hi);
+#pragma unroll
+        for (int m = 0; m < DOP_M; ++m) {
+            const double nr_ = fma(-zi[m], ri[m], zr[m] * rr[m]);
+            const double ni_ = fma(zi[m], rr[m], zr[m] * ri[m]);
+            zr[m] = nr_; zi[m] = ni_;
+        }
     }
 }
 
@@ -337,6 +437,13 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
 int launch_gen_taps(const TapParams& tp, hipStream_t stream) {
     const int threads = 128;
     hipLaunchKernelGGL(gen_taps_kernel, dim3((tp.n_links + threads - 1) / threads), dim3(threads), 0, stream, tp);
+    return (int)hipGetLastError();
+}
+
+int launch_gen_taps_doppler(const DopplerParams& dp, hipStream_t stream) {
+    const dim3 grid((dp.tp.n_links + 1) / 2), block(64);
+    if (dp.tp.kind == 0) hipLaunchKernelGGL(gen_taps_doppler_kernel<0>, grid, block, 0, stream, dp);
+    else hipLaunchKernelGGL(gen_taps_doppler_kernel<1>, grid, block, 0, stream, dp);
     return (int)hipGetLastError();
 }
 

@@ -94,6 +94,7 @@ int launch_spectral_radius_split(const double* W, int n_sets, int n_res, int n_s
                                  void* workspace, hipStream_t stream);
 // esn_gen.hip
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
+int launch_gen_taps_doppler(const DopplerParams& dp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);
 // esn_baseline.hip
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);

@@ -50,6 +50,16 @@ class LinkParams:
     forget_fixed: int = -1        # >= 0: rows dropped from the fit and from every prediction
     continuation: bool = False    # True: every predict starts from the training-final state / teacher output
     coherence_fixed: int = 0      # > 0: data symbols per pilot instead of the Doppler formula
+    # "block": one tap set per coherence block (the reference).  "jakes" (extension): the taps move from OFDM symbol to
+    # OFDM symbol with Doppler f_d (esn_gen_taps_doppler): the pilot sees symbol 0, data frame k symbol k + 1
+    fading: str = "block"
+
+    def __post_init__(self):
+        if self.fading not in ("block", "jakes"):
+            raise ValueError(f"fading must be 'block' or 'jakes', not {self.fading!r}")
+        if self.fading == "jakes" and self.channel == "awgn":
+            raise ValueError("fading='jakes' needs a multipath channel ('tdlb' or 'exp'): the flat 'awgn' channel of "
+                             "the SISO driver has no Doppler mode")
 
     @classmethod
     def siso_awgn(cls, n_sub=512, symbols_per_pilot=400):
@@ -93,6 +103,11 @@ class LinkParams:
         t_sym = (self.n_sub + self.isi - 1) / self.fs
         return max(1, math.floor((0.5 / max(self.f_d, 1e-9)) / t_sym))
 
+    @property
+    def fd_tsym(self):
+        """Doppler frequency x OFDM symbol time, in cycles per symbol."""
+        return self.f_d * (self.n_sub + self.cp) / self.fs
+
     def p_i(self, ebno_db):
         return (10 ** (ebno_db / 10)) * self.no
 
@@ -135,6 +150,19 @@ class FrameSource:
                                         ptr(out), _lib.stream_handle()), "esn_gen_taps")
         return out
 
+    def taps_doppler(self, n_blocks, n_sym, snr_idx, first_block, angles=None):
+        """[G, n_sym, n_r, n_t, isi] complex128: the taps of symbols 0 .. n_sym - 1 of every block under Jakes fading
+        with params.fd_tsym cycles per symbol (esn_gen_taps_doppler; key and link counters of taps()).  angles:
+        optional float64 [G n_r n_t, n_paths, 16, 2] = (a, phi) in half-turns instead of the device's draws."""
+        torch, p = self.torch, self.p
+        with torch.cuda.device(self.device):
+            out = torch.empty((n_blocks, n_sym, p.n_r, p.n_t, p.isi), dtype=torch.complex128, device=self.device)
+            check(self.lib.esn_gen_taps_doppler(self.CHANNEL_KIND[p.channel], n_blocks, n_sym, p.n_r, p.n_t, p.isi,
+                                                p.fs, p.ds_ns, p.fd_tsym, ptr(angles), self._key(snr_idx, 1),
+                                                int(first_block) * p.n_r * p.n_t, ptr(out), _lib.stream_handle()),
+                  "esn_gen_taps_doppler")
+        return out
+
     def frames(self, taps, frames_per_block, ebno_db, snr_idx, first_frame, stream_id, want_x=False,
                bits_in=None, noise_in=None, ls_pattern=False, io="c128"):
         """frames_per_block frames per block of `taps` -> (bits uint8 [B,N*m,n_t], x_cp or None, y_cp).
@@ -175,11 +203,24 @@ class FrameSource:
 
     def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False, io="c128"):
         """Blocks first_block .. first_block + n_blocks - 1 in three launches (taps, pilots, data).
-        io="c64": the DATA frames are complex64; pilots stay complex128 (training is unchanged)."""
-        taps = self.taps(n_blocks, snr_idx, first_block)
+        io="c64": the DATA frames are complex64; pilots stay complex128 (training is unchanged).
+        params.fading == "jakes": the taps move inside the block (taps_doppler, 1 + F symbols): the pilots pass
+        through symbol 0, data frame k through symbol k + 1 -- one frames() call over the per-frame taps with one frame
+        per "block"; frame counters and streams are those of block fading, so bits and noise are the same for the same
+        seed.  `taps` stays the pilot-instant taps [G, n_r, n_t, isi]; `taps_sym` [G, 1 + F, n_r, n_t, isi] is added."""
+        p, F = self.p, frames_per_block
+        if p.fading == "jakes":
+            taps_sym = self.taps_doppler(n_blocks, 1 + F, snr_idx, first_block)
+            taps = taps_sym[:, 0].contiguous()
+            data_taps, per_taps = taps_sym[:, 1:].reshape(n_blocks * F, p.n_r, p.n_t, p.isi), 1
+        else:
+            taps_sym, taps = None, self.taps(n_blocks, snr_idx, first_block)
+            data_taps, per_taps = taps, F
         pbits, px, py = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, want_x=True)
-        bits, _, dy = self.frames(taps, frames_per_block, ebno_db, snr_idx, first_block * frames_per_block, 1, io=io)
+        bits, _, dy = self.frames(data_taps, per_taps, ebno_db, snr_idx, first_block * F, 1, io=io)
         out = dict(pilot_y=py, pilot_x=px, pilot_bits=pbits, data_y=dy, data_bits=bits, taps=taps)
+        if taps_sym is not None:
+            out["taps_sym"] = taps_sym
         if with_ls_pilot:     # same bits, same noise, sparse pattern (driver:330-356)
             _, _, out["pilot_y_ls"] = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, ls_pattern=True)
         return out
@@ -333,7 +374,8 @@ class DetectorSweep:
     def __init__(self, params: LinkParams, n_reservoir=512, spectral_radius=0.9, sparsity=0.1, noise=0.001,
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
                  rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None,
-                 radius="host", radius_precision="f64", radius_squarings=24, fresh_radius_cache=True):
+                 radius="host", radius_precision="f64", radius_squarings=24, fresh_radius_cache=True,
+                 symbol_counts=False):
         """reservoirs: "shared" (one reservoir for every block), "per_block" (block b uses set b % pool of a pool
         drawn here) or "fresh" (the reference's own rule, SURVEY F5: every coherence block gets a reservoir of its
         own, drawn on the device by reservoirs.generate and keyed by (seed, global block index) -- the same at every
@@ -364,6 +406,12 @@ class DetectorSweep:
         ridge_choice_counts is {ebno: int64 [L]}: how many of this rank's blocks took each candidate (summed on the
         device, read once per Eb/No point).
 
+        symbol_counts (extension): the detector tail counts every data frame on its own (one frame per group, Pi
+        expanded) and the counts are summed on the device by position in the block; after run(),
+        symbol_error_counts is {ebno: int64 [F, 2]} = (errors, bits) of data symbol 0 .. F - 1 over this rank's blocks,
+        read once per Eb/No point.  The block totals, so the returned BER and counters, are the same integers either
+        way.  With params.fading == "jakes" (FrameSource.blocks_fast) this is BER against the age of the pilot.
+
         io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
         predict kernels see the same float inputs and write the same float outputs).  Pilots and training stay
         float64.  Needs precision f32 / f16 / bf16."""
@@ -382,6 +430,7 @@ class DetectorSweep:
             raise ValueError("give ridge or ridge_grid, not both")
         self.ridge_grid = None if ridge_grid is None else np.array(ridge_grid, dtype=np.float64).reshape(-1)
         self.ridge_choice_counts = {}
+        self.symbol_counts, self.symbol_error_counts = bool(symbol_counts), {}
         self.train_ebno = train_ebno      # not None: every ESN is trained at this fixed Eb/No
         self.n_in, self.n_out, self.n_res = 2 * params.n_r, 2 * params.n_t, n_reservoir
         self.seed = seed
@@ -487,6 +536,11 @@ class DetectorSweep:
         c[2][idx_t] = status
         c[3][idx] = True
 
+    def _require_block_fading(self, who):
+        if self.p.fading != "block":
+            raise ValueError(f"{who} generates block-fading frames only (one tap set per block): params.fading is "
+                             f"{self.p.fading!r}; BER against the symbol index is DetectorSweep(symbol_counts=True).run")
+
     def _require_block_independent_bank(self, who):
         if self.reservoirs == "fresh":
             raise ValueError(f"{who} trains through the bank as it stands, which under reservoirs='fresh' holds one "
@@ -558,16 +612,22 @@ class DetectorSweep:
             self.bank.set_readout(self.bank.W_out)
         return n
 
-    def detect(self, data_y, data_bits, frames_per_block, err, bits, seed=0, out=None, group_offset=0):
+    def detect(self, data_y, data_bits, frames_per_block, err, bits, seed=0, out=None, group_offset=0,
+               per_frame=False):
         """driver:433-456 for all data frames of G blocks: predict (d trailing zero rows synthesised
-        in-kernel) -> fused FFT/slicer/count."""
+        in-kernel) -> fused FFT/slicer/count.  per_frame: err / bits are [G F], one counter per data frame (the tail
+        runs with one frame per group and Pi expanded) instead of [G]."""
         p = self.p
         U = _view_real(data_y)
         x0, y0 = self._cont if (p.continuation and self._cont) else (None, None)
         y = self.bank.predict(U, frames_per_block, T=p.t_frame + p.delay, transient=p.forget, x0=x0, y0=y0,
                               precision=self.precision, noise_mode="counter", seed=seed, out=out,
                               group_offset=group_offset, io=self.io)
-        self.bank.detect_count(y, data_bits, self.p_i, frames_per_block, p.n_sub, p.n_t, p.m, err=err, bits=bits)
+        if per_frame:
+            self.bank.detect_count(y, data_bits, self.p_i.repeat_interleave(frames_per_block), 1, p.n_sub, p.n_t, p.m,
+                                   err=err, bits=bits)
+        else:
+            self.bank.detect_count(y, data_bits, self.p_i, frames_per_block, p.n_sub, p.n_t, p.m, err=err, bits=bits)
         return y
 
     def default_chunk_blocks(self, frames_per_block):
@@ -584,7 +644,8 @@ class DetectorSweep:
     def _chunk(self, ebno, si, ids, F, repair):
         """One launch group: generate, train, detect the contiguous global blocks `ids`; returns the device
         tensor [errors, bits, flagged fits] (int64) without synchronising the host unless `repair`; with a ridge_grid,
-        L more entries: how many blocks took each candidate."""
+        L more entries: how many blocks took each candidate; with symbol_counts, 2 F more: (errors, bits) of every
+        data symbol of the block."""
         torch = self.torch
         g = len(ids)
         data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128")
@@ -608,9 +669,11 @@ class DetectorSweep:
                                    minlength=len(self.ridge_grid)).to(torch.int64)
         if repair:
             self.repair_fit(E)
-        err = torch.zeros(g, dtype=torch.int64, device=self.device)
-        nb = torch.zeros(g, dtype=torch.int64, device=self.device)
-        self.detect(data["data_y"], data["data_bits"], F, err, nb, seed=self.stream_seed(si, 1), group_offset=ids[0])
+        n_cnt = g * F if self.symbol_counts else g
+        err = torch.zeros(n_cnt, dtype=torch.int64, device=self.device)
+        nb = torch.zeros(n_cnt, dtype=torch.int64, device=self.device)
+        self.detect(data["data_y"], data["data_bits"], F, err, nb, seed=self.stream_seed(si, 1), group_offset=ids[0],
+                    per_frame=self.symbol_counts)
         flagged = self.bank.fit_status.ne(0).sum().to(torch.int64) if not repair else torch.zeros(
             (), dtype=torch.int64, device=self.device)
         # (a timed-out harvest cluster counts as a flagged fit: the chunk is then redone with `repair`, whose host
@@ -623,8 +686,12 @@ class DetectorSweep:
                 flagged = flagged + ht.ne(0).sum().to(torch.int64)
         if unscaled is not None and not repair:
             flagged = flagged + unscaled
-        head = torch.stack([err.sum(), nb.sum(), flagged])
-        return head if picks is None else torch.cat([head, picks])
+        parts = [torch.stack([err.sum(), nb.sum(), flagged])]
+        if picks is not None:
+            parts.append(picks)
+        if self.symbol_counts:
+            parts.append(torch.stack([err.view(g, F).sum(dim=0), nb.view(g, F).sum(dim=0)], dim=1).reshape(-1))
+        return torch.cat(parts)
 
     def run(self, ebno_list, blocks_per_snr, frames_per_block=None, chunk_blocks=None, dist=None):
         """Returns (BER[n_snr], counters [n_snr, 2]) -- identical on every rank and for every world size and
@@ -651,8 +718,11 @@ class DetectorSweep:
                     self.fits_repaired += int(res[ci, 2].item())
                     res[ci] = self._chunk(ebno, si, chunks[ci], F, repair=True)
             counters[si] += res[:, :2].sum(dim=0)
-            if self.ridge_grid is not None:
-                self.ridge_choice_counts[ebno] = res[:, 3:].sum(dim=0).cpu().numpy()
+            n_pick = 0 if self.ridge_grid is None else len(self.ridge_grid)
+            if n_pick:
+                self.ridge_choice_counts[ebno] = res[:, 3:3 + n_pick].sum(dim=0).cpu().numpy()
+            if self.symbol_counts:
+                self.symbol_error_counts[ebno] = res[:, 3 + n_pick:].sum(dim=0).view(F, 2).cpu().numpy()
         self._radius_cache = None           # (a run()'s own: nothing outside it is served from the cache)
         reduce_counters(counters, dist, self.world)
         c = counters.cpu().numpy()
@@ -667,6 +737,7 @@ def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=No
     decoding of the rest.  Returns dict(ESN_uncoded, MMSE_uncoded, ESN_coded, MMSE_coded, a_esn, ...).
     Frames and the ESN leg stay float64 / complex128 whatever sweep.io says: the MMSE leg reads complex128."""
     sweep._require_block_independent_bank("coded_ber_point")
+    sweep._require_block_fading("coded_ber_point")
     torch, p, src = sweep.torch, sweep.p, sweep.src
     F = frames_per_block or p.coherence_symbols
     G = n_blocks
@@ -716,6 +787,7 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     Frames and the ESN legs stay float64 / complex128 whatever the sweeps' io says: the LS / MMSE / ZF legs read
     complex128."""
     sweep._require_block_independent_bank("block_fading_point")
+    sweep._require_block_fading("block_fading_point")
     if fixed_sweep is not None:
         fixed_sweep._require_block_independent_bank("block_fading_point")
     torch, p, src = sweep.torch, sweep.p, sweep.src

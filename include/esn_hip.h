@@ -519,7 +519,29 @@ int esn_detect_count_mem(int mem_kind, const double* Y, int n_frames, int frames
  *                p_i / a_clip are per block [n_blocks]; x_cp (pre-PA teacher) may be NULL.
  *                ls_pattern = 1 keeps only tx = sc % n_t on subcarrier sc (the sparse LS pilot of
  *                :330-333); with the pilot's seed / frame index it shares the pilot's bits AND noise
- *                (:354-356), as the reference does. */
+ *                (:354-356), as the reference does.
+ * esn_gen_taps_doppler  (extension) the taps of esn_gen_taps kinds 0 and 1 moving INSIDE a coherence block: complex128
+ *                [n_blocks][n_sym][n_r][n_t][isi], one tap set per OFDM symbol s = 0 .. n_sym - 1.  Clarke / Jakes
+ *                sum of sinusoids: path p of link l = (block, rx, tx) is
+ *                    g(s) = sqrt(P_p / M) sum_{m<M} exp(j pi (2 fd_tsym s cos(pi a_m) + phi_m)),  M = ESN_DOPPLER_SINUSOIDS,
+ *                a and phi uniform on [0, 2) half-turns from Philox (key = seed, counter = (global link lo, hi, 4,
+ *                p M + m), words 0 and 1, (w + 0.5) / 2^31), or supplied as angles_in [n_links][n_paths][M][2]
+ *                = (a, phi) (n_paths = 23 for kind 0, isi for kind 1).  Paths, powers and delays are those of
+ *                esn_gen_taps; kind 0's unit-energy factor is computed at s = 0 and applied to the whole block.
+ *                fd_tsym = f_d T_sym in cycles per symbol, 0 .. 0.5; the ensemble autocorrelation of a path is
+ *                P_p J0(2 pi fd_tsym s).  The phasors are seeded exactly at s = 0 and advanced by one complex
+ *                multiplication per symbol, always from s = 0: symbol s is a function of (seed, global link, s), and
+ *                with fd_tsym = 0 all symbols are bitwise equal.  The marginal is Gaussian up to a kurtosis of 2 - 1/M,
+ *                so fd_tsym = 0 is the block channel of esn_gen_taps statistically, not bitwise.  Viewed as
+ *                [n_blocks * n_sym][n_r][n_t][isi] the output is the `taps` of esn_gen_frames / esn_taps_to_freq
+ *                with frames_per_block = 1.  Device pointers only.  -1: null taps, kind outside {0, 1}, n_blocks,
+ *                n_r or n_t <= 0, n_sym outside 1 .. 4096, isi outside 1 .. 16, fd_tsym negative, not finite or above 0.5
+ *                (more than half a cycle per symbol aliases). */
+#define ESN_DOPPLER_SINUSOIDS 16
+int esn_gen_taps_doppler(int kind, int n_blocks, int n_sym, int n_r, int n_t, int isi,
+                         double fs_hz, double ds_ns, double fd_tsym,
+                         const double* angles_in, uint64_t seed, uint64_t link_offset,
+                         double* taps, void* stream);
 int esn_gen_taps(int kind, int n_blocks, int n_r, int n_t, int isi, double fs_hz, double ds_ns,
                  const double* gains_in, uint64_t seed, uint64_t link_offset,
                  double* taps, void* stream);
