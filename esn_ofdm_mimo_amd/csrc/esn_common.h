@@ -34,6 +34,16 @@ struct Geometry {
                      //          stays the tile of the vector-ALU kernel (esn_recur_f64.hip)
 };
 
+// Dynamic LDS of the persistent MFMA kernel (esn_recur_mfma_impl.h carves it in this order): the Zt image, the frame
+// table, the {scale, shift} tables of inputs and outputs per 16-frame column tile, the raw-input staging area (the skewed
+// schedule: one 1 KB slot per DMA instruction, two per column tile) and the input offsets of the frames.  mfma_geometry
+// and the launch both ask here.
+inline size_t mfma_lds_bytes(const Geometry& g, int es, int n_in, bool skew) {
+    const size_t nown = g.Bt / 16;
+    return (size_t)g.Bt * g.Ks * es + 4 * (size_t)g.Bt + 8 * nown * ((g.kfb - g.kin) + 16)
+           + (skew ? nown * 2048 : 8 * (size_t)g.Bt * n_in) + 4 * (size_t)g.Bt;
+}
+
 struct RecurParams {
     int n_res, n_in, n_out, teacher_forcing;
     Geometry g;

@@ -20,7 +20,7 @@
 // blocks of one XCD (block id mod 8).
 // Arithmetic, noise stream (counter noise keyed by (seed, global pilot, step, row)) and the rounding of the states to
 // the operand type are those of the persistent harvest kernel; only the summation order inside a dot product differs.
-#include "esn_recur_mfma_impl.h"
+#include "esn_mfma_traits.h"
 #include "esn_launch.h"
 
 namespace esn {

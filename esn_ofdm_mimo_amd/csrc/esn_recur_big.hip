@@ -23,7 +23,7 @@
 // The launch boundaries are the per-step dependencies (X_{s+1} needs every row of X_s, Y_s every row
 // tile's partial): two boundaries of ~1.5 us per step against ~0.3-0.5 ms of GEMM at the benchmark size.  Arithmetic and noise stream are those of the
 // persistent fp16/bf16 kernels (same packed weights incl. the 2 log2 e pre-scale, same counter noise).
-#include "esn_recur_mfma_impl.h"
+#include "esn_mfma_traits.h"
 #include "esn_launch.h"
 
 namespace esn {

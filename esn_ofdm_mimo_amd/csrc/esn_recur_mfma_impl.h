@@ -25,138 +25,26 @@
 // 1 x v_mfma_f32_32x32x16_{f16,bf16}.  (The k order inside a group is a fixed
 // permutation applied to both operands, which a dot product does not see.)
 #pragma once
-#include <type_traits>
-#include "esn_common.h"
+#include "esn_mfma_traits.h"
 
 namespace esn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b16x4 __attribute__((ext_vector_type(4)));
-
-struct TraitsF32 {
-    typedef float elem;
-    static constexpr int ES = 4;
-    static constexpr int PARTS = 1;   // readout images (1 = W_out as is)
-    static __device__ __forceinline__ void mma32(f32x16& c, u32x4 a, u32x4 b) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-        {
-            const uint32_t ai = a[i], bi = b[i];   // copy out: bit_cast of a vector element lvalue reads lane 0
-            c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(ai), __uint_as_float(bi), c, 0, 0, 0);
-        }
-    }
-    // 64-byte row group, lane quarter q takes 16 B: 4 x (16x16x4)
-    static __device__ __forceinline__ void mma16(f32x4& c, u32x4 a, u32x4 b) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-        {
-            const uint32_t ai = a[i], bi = b[i];
-            c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ai), __uint_as_float(bi), c, 0, 0, 0);
-        }
-    }
-    static __device__ __forceinline__ void store4(char* dst, float v0, float v1, float v2, float v3) {
-        f32x4 v = {v0, v1, v2, v3};
-        *reinterpret_cast<f32x4*>(dst) = v;
-    }
-    static __device__ __forceinline__ void store1(char* dst, float v) { *reinterpret_cast<float*>(dst) = v; }
-    static __device__ __forceinline__ void store2(char* dst, float v0, float v1) {
-        *reinterpret_cast<float2*>(dst) = make_float2(v0, v1);
-    }
-    static __device__ __forceinline__ float load1(const char* src) { return *reinterpret_cast<const float*>(src); }
-    static __device__ __forceinline__ void load4(const char* src, float (&v)[4]) {     // 16-byte aligned
-        const f32x4 t = *reinterpret_cast<const f32x4*>(src);
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    }
-    static __device__ __forceinline__ float act(float x) { return tanh_f32(x); }
-    // when every pre-activation of a wave is below TANH32_SERIES_MAX the select in tanh_f32 always takes the
-    // series: evaluate only that (bit-identical result, half the instructions)
-    static constexpr bool HAS_SMALL = true;
-    static __device__ __forceinline__ float act_small(float x) { return tanh_f32_series(x); }
-};
-
-struct TraitsF16 {
-    typedef _Float16 elem;
-    static constexpr int ES = 2;
-    static constexpr int PARTS = 2;   // W_out = hi + lo (two fp16 images)
-    static __device__ __forceinline__ void mma32(f32x16& c, u32x4 a, u32x4 b) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a),
-                                                   __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void mma16(f32x4& c, u32x4 a, u32x4 b) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a),
-                                                   __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void store4(char* dst, float v0, float v1, float v2, float v3) {
-        h16x4 v = {(_Float16)v0, (_Float16)v1, (_Float16)v2, (_Float16)v3};
-        *reinterpret_cast<h16x4*>(dst) = v;
-    }
-    static __device__ __forceinline__ void store1(char* dst, float v) { *reinterpret_cast<_Float16*>(dst) = (_Float16)v; }
-    static __device__ __forceinline__ void store2(char* dst, float v0, float v1) {      // 4-byte aligned
-        typedef _Float16 h16x2v __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<h16x2v*>(dst) = h16x2v{(_Float16)v0, (_Float16)v1};
-    }
-    static __device__ __forceinline__ uint32_t pack2(float v0, float v1) {
-        typedef _Float16 h16x2v __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, h16x2v{(_Float16)v0, (_Float16)v1});
-    }
-    static __device__ __forceinline__ void unpack2(uint32_t w, float& v0, float& v1) {
-        typedef _Float16 h16x2v __attribute__((ext_vector_type(2)));
-        const h16x2v h = __builtin_bit_cast(h16x2v, w);
-        v0 = (float)h[0]; v1 = (float)h[1];
-    }
-    static __device__ __forceinline__ float load1(const char* src) { return (float)*reinterpret_cast<const _Float16*>(src); }
-    static __device__ __forceinline__ void load4(const char* src, float (&v)[4]) {     // 8-byte aligned
-        const h16x4 t = *reinterpret_cast<const h16x4*>(src);
-        v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
-    }
-    static __device__ __forceinline__ float act(float z) { return tanh_prescaled(z); }   // weights carry 2 log2 e
-    static constexpr bool HAS_SMALL = false;
-    static __device__ __forceinline__ float act_small(float z) { return tanh_prescaled(z); }
-};
-
-struct TraitsBF16 {
-    typedef __bf16 elem;
-    static constexpr int ES = 2;
-    static constexpr int PARTS = 2;
-    static __device__ __forceinline__ void mma32(f32x16& c, u32x4 a, u32x4 b) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b16x8, a),
-                                                    __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void mma16(f32x4& c, u32x4 a, u32x4 b) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b16x8, a),
-                                                    __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void store4(char* dst, float v0, float v1, float v2, float v3) {
-        b16x4 v = {(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
-        *reinterpret_cast<b16x4*>(dst) = v;
-    }
-    static __device__ __forceinline__ void store1(char* dst, float v) { *reinterpret_cast<__bf16*>(dst) = (__bf16)v; }
-    static __device__ __forceinline__ void store2(char* dst, float v0, float v1) {      // 4-byte aligned
-        typedef __bf16 b16x2v __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<b16x2v*>(dst) = b16x2v{(__bf16)v0, (__bf16)v1};
-    }
-    static __device__ __forceinline__ uint32_t pack2(float v0, float v1) {
-        typedef __bf16 b16x2v __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, b16x2v{(__bf16)v0, (__bf16)v1});
-    }
-    static __device__ __forceinline__ void unpack2(uint32_t w, float& v0, float& v1) {
-        v0 = __uint_as_float(w << 16); v1 = __uint_as_float(w & 0xffff0000u);
-    }
-    static __device__ __forceinline__ float load1(const char* src) { return (float)*reinterpret_cast<const __bf16*>(src); }
-    static __device__ __forceinline__ void load4(const char* src, float (&v)[4]) {     // 8-byte aligned
-        const b16x4 t = *reinterpret_cast<const b16x4*>(src);
-        v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
-    }
-    static __device__ __forceinline__ float act(float z) { return tanh_prescaled(z); }   // weights carry 2 log2 e
-    static constexpr bool HAS_SMALL = false;
-    static __device__ __forceinline__ float act_small(float z) { return tanh_prescaled(z); }
-};
+// knock-out builds (timing only, wrong results; README, tools/phase_stamps.py)
+#ifdef ESN_KO_A
+constexpr bool KO_A = true;         // no weight traffic, MFMAs on zeros
+#else
+constexpr bool KO_A = false;
+#endif
+#ifdef ESN_KO_E
+constexpr bool KO_E = true;         // no transcendental work in phase E
+#else
+constexpr bool KO_E = false;
+#endif
+#ifdef ESN_KO_PURE
+constexpr bool KO_PURE = true;      // the k-group is its MFMAs and nothing else
+#else
+constexpr bool KO_PURE = false;
+#endif
 
 // IO32: predict with float32 U / Y (esn_predict_batch_f32); the float64-I/O instances are unchanged by it
 template <typename TR, int NW, int MT, int NT, bool HARVEST, int NOISE, bool SKEW, bool IO32 = false>
@@ -497,6 +385,13 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
     bool any_ro = false;
 #pragma unroll
     for (int i = 0; i < OC; ++i) any_ro = any_ro || (wop[i] != nullptr);
+    // after the last step: Y_S = yU_{S-1} + Wout_x X_S
+    auto final_readout = [&]() __attribute__((always_inline)) {
+        if (any_ro) {
+            readout_groups(0, nk64S);
+            finish_readout(p.S - 1 - p.transient, false);
+        }
+    };
 
     if constexpr (SKEW) {
         // ================= skewed schedule (predict) ==================================
@@ -543,11 +438,6 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             const_cast<char*>(reinterpret_cast<const char*>(p.packed_w) + (size_t)wset * p.wset_stride), 0,
             (int)p.wset_stride, 0x00020000);
         const int w_row0 = wave * MT * nkg;
-#ifdef ESN_KO_A      // knock-out build (timing only, wrong results): no weight traffic, MFMAs on zeros
-        constexpr bool KO_A = true;
-#else
-        constexpr bool KO_A = false;
-#endif
         auto loadA = [&](u32x4 (&a)[MT], int kg) {       // kg >= nkg: no load, zeros
             const bool live = !KO_A && kg < nkg;
             const int voff = live ? lane16 : OOB;
@@ -565,12 +455,6 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
                 b[nt] = *reinterpret_cast<const u32x4*>(bbase + (size_t)nt * 32 * row_bytes + kg * 32);
-        };
-        auto mma_all = [&](const u32x4 (&a)[MT], const u32x4 (&b)[NT]) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) TR::mma32(acc[mt][nt], a[mt], b[nt]);
         };
         // W_out fragments of the owned column tile, two trips ahead: ra[2i], ra[2i+1] = 64-byte
         // groups t and t + nk64H of the trips t = i (mod 2); `on` false: zeros, no traffic
@@ -601,28 +485,6 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
         auto gemm_half = [&](int kg0, bool ro_on) {
             loadB(bA, kg0);
             u32x4 rb0, rb1;
-#ifdef ESN_GEMM_BLOCKED
-            // (round-1 placement, kept for A/B runs: all MFMAs of the k-group, then all of its loads)
-            for (int i = 0; i < nkgH; i += 4) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int kg = kg0 + i + j;
-                    const int t = (i + j) >> 1;
-                    mma_all(abuf[j], bA);
-                    if (j % 2 == 1) { TR::mma16(yacc[0], ra[j - 1], rb0); TR::mma16(yacc[0], ra[j], rb1); }
-                    __builtin_amdgcn_sched_barrier(0);
-                    loadA(abuf[j], kg + 4);
-                    loadB(bA, kg + 1);
-                    if (j % 2 == 0) {
-                        rb0 = *reinterpret_cast<const u32x4*>(zrow0 + t * 64);
-                        rb1 = *reinterpret_cast<const u32x4*>(zrow0 + (t + nk64H) * 64);
-                    } else {
-                        load_ra(j >> 1, t + 2, ro_on);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#else
             // Hand-placed k-groups.  A wave issues in order and the SIMD issues about one instruction per four
             // cycles for BOTH of its waves, so every instruction of this loop is paid twice: as matrix-pipe idle
             // time when it sits between two MFMA bursts, and as an issue slot the partner wave's phase E does not
@@ -664,27 +526,27 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                         for (int mt = 0; mt < MT; ++mt) {
                             TR::mma32(acc[mt][nt], abuf[j][mt], bA[nt]);
                             const int m = nt * MT + mt;
-#ifndef ESN_KO_PURE  // knock-out build (timing only, wrong results): the k-group is its MFMAs and nothing else
-                            if (j % 2 == 0) {
-                                if (m == 0) rb0 = *reinterpret_cast<const u32x4*>(zrow0 + t * 64);
-                                if (m == 1) rb1 = *reinterpret_cast<const u32x4*>(zrow0 + (t + nk64H) * 64);
-                            } else if (TAIL) {
-                                if (m == 0) load_ra1(ra[j - 1], t + 2, 0, ro_on);
-                                if (m == 1) load_ra1(ra[j], t + 2, nk64H, ro_on);
-                            } else {
-                                if (m == 0) ra[j - 1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                wo_rsrc, voff_ro, sR0 + (j >> 1) * 1024, 0));
-                                if (m == 1) ra[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                wo_rsrc, voff_ro, sR1 + (j >> 1) * 1024, 0));
+                            if constexpr (!KO_PURE) {
+                                if (j % 2 == 0) {
+                                    if (m == 0) rb0 = *reinterpret_cast<const u32x4*>(zrow0 + t * 64);
+                                    if (m == 1) rb1 = *reinterpret_cast<const u32x4*>(zrow0 + (t + nk64H) * 64);
+                                } else if (TAIL) {
+                                    if (m == 0) load_ra1(ra[j - 1], t + 2, 0, ro_on);
+                                    if (m == 1) load_ra1(ra[j], t + 2, nk64H, ro_on);
+                                } else {
+                                    if (m == 0) ra[j - 1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                    wo_rsrc, voff_ro, sR0 + (j >> 1) * 1024, 0));
+                                    if (m == 1) ra[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                    wo_rsrc, voff_ro, sR1 + (j >> 1) * 1024, 0));
+                                }
+                                if (nt == NT - 1) {
+                                    if (TAIL) loadA1(abuf[j][mt], mt, kg + 4);
+                                    else abuf[j][mt] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                             w_rsrc, KO_A ? OOB : lane16, sA[mt] + j * 1024, 0));
+                                }
+                                if (mt == MT - 1) bA[nt] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(
+                                                      (uintptr_t)(bp[nt] + j * 32));
                             }
-                            if (nt == NT - 1) {
-                                if (TAIL) loadA1(abuf[j][mt], mt, kg + 4);
-                                else abuf[j][mt] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                         w_rsrc, KO_A ? OOB : lane16, sA[mt] + j * 1024, 0));
-                            }
-                            if (mt == MT - 1) bA[nt] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(
-                                                  (uintptr_t)(bp[nt] + j * 32));
-#endif
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
@@ -699,7 +561,6 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             };
             for (int i = 0; i < nkgH - 4; i += 4) trip(i, std::false_type{});
             trip(nkgH - 4, std::true_type{});
-#endif
         };
         auto uf_groups = [&]() {
             loadB(bA, nkgS);
@@ -763,12 +624,12 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                             float t[4];
 #pragma unroll
                             for (int j = 0; j < 4; ++j) {
-#ifdef ESN_KO_E      // knock-out build (timing only, wrong results): no transcendental work in phase E
-                                t[j] = acc[mt][nt][4 * q + j] + t_bias;
-#else
-                                const float e = __builtin_amdgcn_exp2f(acc[mt][nt][4 * q + j]);
-                                t[j] = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), t_bias);
-#endif
+                                if constexpr (KO_E) {
+                                    t[j] = acc[mt][nt][4 * q + j] + t_bias;
+                                } else {
+                                    const float e = __builtin_amdgcn_exp2f(acc[mt][nt][4 * q + j]);
+                                    t[j] = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), t_bias);
+                                }
                             }
                             const uint32_t sq = noise_mix(key + (uint32_t)(mt * 8 + 2 * q) * 0x9E3779B9U);
                             const h16x2 w01 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x3C3C3C3Cu, sq, 0x04010400u));
@@ -915,12 +776,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                 }
             }
         };
-#ifdef ESN_STAMPS
-        unsigned long long sk_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define ESN_SK_ADD(i, a, b) sk_acc[i] += (b) - (a);
-#else
-#define ESN_SK_ADD(i, a, b)
-#endif
+        ESN_STAMPS_ONLY(unsigned long long sk_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};)
         // One program for both sets.  The readout runs in slot 3s+1 (P1 of set A, P0 of set B) and
         // yU_s in slot 3s+2 (P2 of set A, P1 of set B).
         const bool has_ro = __builtin_amdgcn_readfirstlane(wop[0] != nullptr ? 1 : 0) != 0;   // provably wave-uniform
@@ -983,30 +839,21 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             ESN_STAMP(t5)
             __syncthreads();
             ESN_STAMP(t6)
-            ESN_SK_ADD(0, t0, t1) ESN_SK_ADD(1, t1, t2) ESN_SK_ADD(2, t2, t3)
-            ESN_SK_ADD(3, t3, t4) ESN_SK_ADD(4, t4, t5) ESN_SK_ADD(5, t5, t6)
-            ESN_SK_ADD(6, t4, u1) ESN_SK_ADD(7, u1, u2) ESN_SK_ADD(8, u2, u3) ESN_SK_ADD(9, u3, u4)
-            ESN_SK_ADD(10, u4, u5) ESN_SK_ADD(11, u5, t5)
+            ESN_STAMPS_ONLY(sk_acc[0] += t1 - t0; sk_acc[1] += t2 - t1; sk_acc[2] += t3 - t2; sk_acc[3] += t4 - t3;
+                            sk_acc[4] += t5 - t4; sk_acc[5] += t6 - t5; sk_acc[6] += u1 - t4; sk_acc[7] += u2 - u1;
+                            sk_acc[8] += u3 - u2; sk_acc[9] += u4 - u3; sk_acc[10] += u5 - u4; sk_acc[11] += t5 - u5;)
         }
         if (!lag) __syncthreads();                                     // slot 3S: set B finishes X_B(S)
-#undef ESN_SK_ADD
-        if (any_ro) {                                                  // Y_S = yU_{S-1} + Wout_x X_S
-            readout_groups(0, nk64S);
-            finish_readout(p.S - 1 - p.transient, false);
-        }
-#ifdef ESN_STAMPS
-        if (p.stamps && blockIdx.x == 0 && lane == 0) {
+        final_readout();
+        ESN_STAMPS_ONLY(if (p.stamps && blockIdx.x == 0 && lane == 0) {
             for (int i = 0; i < 6; ++i) p.stamps[wave * 8 + i] = sk_acc[i];
             for (int i = 0; i < 6; ++i) p.stamps[(8 + wave) * 8 + i] = sk_acc[6 + i];    // inside P2
             p.stamps[wave * 8 + 6] = (unsigned long long)__builtin_amdgcn_s_getreg(63492);   // HW_ID
-        }
-#endif
+        })
         return;
     }
 
-#ifdef ESN_STAMPS
-    unsigned long long st_acc[7] = {0, 0, 0, 0, 0, 0, 0};
-#endif
+    ESN_STAMPS_ONLY(unsigned long long st_acc[7] = {0, 0, 0, 0, 0, 0, 0};)
     // Harvest: few sequences (one pilot per trained ESN), so a launch is a handful of workgroups
     // whose critical path is the weight stream of every step.  Same recipe as the skewed
     // schedule: HD k-groups in flight per wave in fixed buffers, refilled by buffer loads right
@@ -1118,9 +965,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
-#ifdef ESN_STAMPS
-        unsigned long long t1 = 0, t2 = 0;
-#endif
+        ESN_STAMPS_ONLY(unsigned long long t1 = 0, t2 = 0;)
         if constexpr (HARVEST) {
             // B fragments double-buffered: with two MFMAs per k-group the LDS latency of a
             // single-buffered B operand was the critical path (285 cycles per k-group)
@@ -1164,11 +1009,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
             const int kg = kg_of(pos);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
-#ifdef ESN_NT_WEIGHTS   // measured: non-temporal weight loads are 1.5x SLOWER in G1 (every CU re-reads W from L2)
-                a[mt] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp + ((size_t)mt * nkg + kg) * 1024));
-#else
                 a[mt] = *reinterpret_cast<const u32x4*>(wp + ((size_t)mt * nkg + kg) * 1024);
-#endif
         };
         auto loadB = [&](u32x4 (&b)[NT], int pos) {
             const int kg = kg_of(pos);
@@ -1343,29 +1184,19 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
         ESN_STAMP(t6)
         if (HARVEST) copy_row(s + 1);
         ESN_STAMP(t7)
-#ifdef ESN_STAMPS
-        st_acc[0] += t1 - t0; st_acc[1] += t2 - t1; st_acc[2] += t3 - t2;
-        st_acc[3] += t4 - t3; st_acc[4] += t5 - t4; st_acc[5] += t6 - t5; st_acc[6] += t7 - t6;
-#endif
+        ESN_STAMPS_ONLY(st_acc[0] += t1 - t0; st_acc[1] += t2 - t1; st_acc[2] += t3 - t2; st_acc[3] += t4 - t3;
+                        st_acc[4] += t5 - t4; st_acc[5] += t6 - t5; st_acc[6] += t7 - t6;)
     }
-    // final readout Y_S = yU_{S-1} + Wout_x X_S
-    if (any_ro) {
-        readout_groups(0, nk64S);
-        finish_readout(p.S - 1 - p.transient, false);
-    }
-#ifdef ESN_STAMPS
-    if (p.stamps && blockIdx.x == 0 && lane == 0)
-        for (int i = 0; i < 7; ++i) p.stamps[wave * 8 + i] = st_acc[i];
-#endif
+    final_readout();
+    ESN_STAMPS_ONLY(if (p.stamps && blockIdx.x == 0 && lane == 0)
+                        for (int i = 0; i < 7; ++i) p.stamps[wave * 8 + i] = st_acc[i];)
 }
 
 // ---- host side: geometry choice and launch -------------------------------------
 
 template <typename TR, int NW, int MT, int NT, bool HARVEST, int NOISE, bool SKEW = false, bool IO32 = false>
 static int launch_k(const RecurParams& p, hipStream_t stream) {
-    const int kin_p = p.g.kfb - p.g.kin, nown = p.g.Bt / 16;
-    size_t lds = (size_t)p.g.Bt * p.g.Ks * TR::ES + 4 * (size_t)p.g.Bt + 8 * (size_t)nown * (kin_p + 16)
-                 + (SKEW ? (size_t)nown * 2048 : 8 * (size_t)p.g.Bt * p.n_in) + 4 * (size_t)p.g.Bt;
+    const size_t lds = mfma_lds_bytes(p.g, TR::ES, p.n_in, SKEW);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(recur_mfma_kernel<TR, NW, MT, NT, HARVEST, NOISE, SKEW, IO32>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;

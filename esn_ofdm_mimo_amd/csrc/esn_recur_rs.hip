@@ -21,7 +21,7 @@
 //
 // Arithmetic, weight image and noise stream are those of the other fp16 / bf16 kernels.
 #include <utility>
-#include "esn_recur_mfma_impl.h"
+#include "esn_mfma_traits.h"
 #include "esn_launch.h"
 
 namespace esn {

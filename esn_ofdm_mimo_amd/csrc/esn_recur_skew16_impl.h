@@ -20,7 +20,7 @@
 // LDS-DMA input staging, packed-half noise tail, the counter noise as a function of (seed, frame, step, row) --
 // is the 32x32x16 kernel's, and the two are compared bit-for-bit-tolerance in tests/test_gpu_parity.py.
 #pragma once
-#include "esn_recur_mfma_impl.h"
+#include "esn_mfma_traits.h"
 
 namespace esn {
 

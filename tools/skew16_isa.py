@@ -33,11 +33,12 @@ def compile_asm(out):
     subprocess.check_call([hipcc, *build.FLAGS, *extra, "--cuda-device-only", "-S", src, "-o", out])
 
 
-def functions(lines):
-    """{name: (body lines, {metadata key: value})}"""
+def functions(lines, kernel="_ZN3esn19recur_skew16_kernel"):
+    """{name: (body lines, {metadata key: value})} of the instances of `kernel` (the head of the mangled name)"""
     out, name, body = {}, None, []
+    head = re.compile(r"^(" + re.escape(kernel) + r"\w+):")
     for ln in lines:
-        m = re.match(r"^(_ZN3esn19recur_skew16_kernel\w+):", ln)
+        m = head.match(ln)
         if m:
             name, body = m.group(1), []
             out[name] = (body, {})
