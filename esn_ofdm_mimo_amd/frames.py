@@ -1,0 +1,229 @@
+"""The frame side of the Monte-Carlo harness (montecarlo.py tells the whole chain): FrameSource, the HIP frame generator
+with the baseline equalisers and channel metrics that read its taps and frames; percentiles_linear and
+summarize_channel_metrics, the per-Eb/No channel record reduced on the device; _view_real / complex_as_io, complex
+frames as the interleaved real rows the ESN reads.  torch is imported where it is used: no GPU is needed to import."""
+from __future__ import annotations
+
+from . import _lib
+from ._lib import check, ptr
+from .link import LinkParams
+
+
+class FrameSource:
+    """HIP frame generator (esn_gen_taps / esn_gen_frames of include/esn_hip.h).  Counter-based
+    random streams: frame f of block b at SNR index s is a pure function of (seed, s, b, f)."""
+
+    CHANNEL_KIND = {"tdlb": 0, "exp": 1, "awgn": 2}
+
+    def __init__(self, params: LinkParams, device=None, seed=0):
+        torch = _lib.require_gpu()
+        self.torch, self.p = torch, params
+        self.lib = _lib.load()
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.seed = int(seed)
+
+    def _key(self, *parts):
+        h = self.seed & (2 ** 64 - 1)
+        for k in parts:
+            h = (h * 6364136223846793005 + int(k) + 0x9E3779B97F4A7C15) % (2 ** 64)
+        return h
+
+    def _per_group(self, value, g):
+        """float64 [g] on the device, every entry `value`: the kernels take Pi and the clip level per group."""
+        return self.torch.full((g,), value, dtype=self.torch.float64, device=self.device)
+
+    def taps(self, n_blocks, snr_idx, first_block, gains=None):
+        """[G, n_r, n_t, isi] complex128.  Link l of block b draws from counter (first_block + b)."""
+        torch, p = self.torch, self.p
+        with torch.cuda.device(self.device):
+            out = torch.empty((n_blocks, p.n_r, p.n_t, p.isi), dtype=torch.complex128, device=self.device)
+            check(self.lib.esn_gen_taps(self.CHANNEL_KIND[p.channel], n_blocks, p.n_r, p.n_t, p.isi, p.fs, p.ds_ns,
+                                        ptr(gains), self._key(snr_idx, 1), int(first_block) * p.n_r * p.n_t,
+                                        ptr(out), _lib.stream_handle()), "esn_gen_taps")
+        return out
+
+    def taps_doppler(self, n_blocks, n_sym, snr_idx, first_block, angles=None):
+        """[G, n_sym, n_r, n_t, isi] complex128: the taps of symbols 0 .. n_sym - 1 of every block under Jakes fading
+        with params.fd_tsym cycles per symbol (esn_gen_taps_doppler; key and link counters of taps()).  angles:
+        optional float64 [G n_r n_t, n_paths, 16, 2] = (a, phi) in half-turns instead of the device's draws."""
+        torch, p = self.torch, self.p
+        with torch.cuda.device(self.device):
+            out = torch.empty((n_blocks, n_sym, p.n_r, p.n_t, p.isi), dtype=torch.complex128, device=self.device)
+            check(self.lib.esn_gen_taps_doppler(self.CHANNEL_KIND[p.channel], n_blocks, n_sym, p.n_r, p.n_t, p.isi,
+                                                p.fs, p.ds_ns, p.fd_tsym, ptr(angles), self._key(snr_idx, 1),
+                                                int(first_block) * p.n_r * p.n_t, ptr(out), _lib.stream_handle()),
+                  "esn_gen_taps_doppler")
+        return out
+
+    def frames(self, taps, frames_per_block, ebno_db, snr_idx, first_frame, stream_id, want_x=False,
+               bits_in=None, noise_in=None, ls_pattern=False, io="c128"):
+        """frames_per_block frames per block of `taps` -> (bits uint8 [B,N*m,n_t], x_cp or None, y_cp).
+        stream_id separates pilots (0) from data (1); first_frame is the global frame counter.
+        io="c64": x_cp / y_cp complex64 (esn_gen_frames_c64), bitwise the complex128 frames rounded."""
+        torch, p = self.torch, self.p
+        if io not in ("c128", "c64"):
+            raise ValueError(f"io must be 'c128' or 'c64', not {io!r}")
+        cdt = torch.complex64 if io == "c64" else torch.complex128
+        g = taps.shape[0]
+        b = g * frames_per_block
+        with torch.cuda.device(self.device):
+            p_i = self._per_group(p.p_i(ebno_db), g)
+            a_clip = self._per_group(p.a_clip(ebno_db), g)
+            bits = torch.empty((b, p.n_sub * p.m, p.n_t), dtype=torch.uint8, device=self.device)
+            x_cp = torch.empty((b, p.t_frame, p.n_t), dtype=cdt, device=self.device) if want_x else None
+            y_cp = torch.empty((b, p.t_frame, p.n_r), dtype=cdt, device=self.device)
+            name = "esn_gen_frames_c64" if io == "c64" else "esn_gen_frames"
+            check(getattr(self.lib, name)(b, frames_per_block, p.n_sub, p.cp, p.n_t, p.n_r, p.isi, p.m,
+                                          1 if ls_pattern else 0, ptr(p_i),
+                                          ptr(a_clip), p.no, ptr(taps), ptr(bits_in), ptr(noise_in),
+                                          self._key(snr_idx, 2 + stream_id), int(first_frame), ptr(bits), ptr(x_cp),
+                                          ptr(y_cp), _lib.stream_handle()), name)
+        return bits, x_cp, y_cp
+
+    def blocks(self, ebno_db, snr_idx, block_ids, frames_per_block, with_ls_pilot=False, io="c128"):
+        """Pilot + data frames of the given coherence blocks (any subset, any order: every block is
+        generated from its own global index, so the result does not depend on the rank that asks).
+        Returns pilot_y [G,T,n_r], pilot_x [G,T,n_t] (pre-PA teacher), data_y [G*F,T,n_r], data_bits."""
+        torch = self.torch
+        ids = list(block_ids)
+        runs, start = [], 0                          # contiguous runs of block ids -> one launch each
+        for i in range(1, len(ids) + 1):
+            if i == len(ids) or ids[i] != ids[i - 1] + 1:
+                runs.append((ids[start], i - start)); start = i
+        outs = [self.blocks_fast(ebno_db, snr_idx, b0, n, frames_per_block, with_ls_pilot, io) for b0, n in runs]
+        return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+
+    def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False, io="c128"):
+        """Blocks first_block .. first_block + n_blocks - 1 in three launches (taps, pilots, data).
+        io="c64": the DATA frames are complex64; pilots stay complex128 (training is unchanged).
+        params.fading == "jakes": the taps move inside the block (taps_doppler, 1 + F symbols): the pilots pass
+        through symbol 0, data frame k through symbol k + 1 -- one frames() call over the per-frame taps with one frame
+        per "block"; frame counters and streams are those of block fading, so bits and noise are the same for the same
+        seed.  `taps` stays the pilot-instant taps [G, n_r, n_t, isi]; `taps_sym` [G, 1 + F, n_r, n_t, isi] is added."""
+        p, F = self.p, frames_per_block
+        if p.fading == "jakes":
+            taps_sym = self.taps_doppler(n_blocks, 1 + F, snr_idx, first_block)
+            taps = taps_sym[:, 0].contiguous()
+            data_taps, per_taps = taps_sym[:, 1:].reshape(n_blocks * F, p.n_r, p.n_t, p.isi), 1
+        else:
+            taps_sym, taps = None, self.taps(n_blocks, snr_idx, first_block)
+            data_taps, per_taps = taps, F
+        pbits, px, py = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, want_x=True)
+        bits, _, dy = self.frames(data_taps, per_taps, ebno_db, snr_idx, first_block * F, 1, io=io)
+        out = dict(pilot_y=py, pilot_x=px, pilot_bits=pbits, data_y=dy, data_bits=bits, taps=taps)
+        if taps_sym is not None:
+            out["taps_sym"] = taps_sym
+        if with_ls_pilot:     # same bits, same noise, sparse pattern (driver:330-356)
+            _, _, out["pilot_y_ls"] = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, ls_pattern=True)
+        return out
+
+    # ---- baseline equaliser ------------------------------------------------------
+    def estimate_channel(self, pilot_bits, pilot_y_ls, ebno_db, ls_only=False):
+        """LS + time-domain MMSE channel estimate H [G, N, n_r, n_t] (driver:358-382); ls_only: the interpolated
+        LS estimate H_LS of the block-fading drivers' LS-ZF detector (OFDM_MIMO_2-2_NBF_LDPC.py:321-333)."""
+        torch, p = self.torch, self.p
+        g = pilot_bits.shape[0]
+        with torch.cuda.device(self.device):
+            p_i = self._per_group(p.p_i(ebno_db), g)
+            H = torch.empty((g, p.n_sub, p.n_r, p.n_t), dtype=torch.complex128, device=self.device)
+            check(self.lib.esn_channel_estimate(g, p.n_sub, p.cp, p.n_t, p.n_r, p.isi, p.m, ptr(p_i), p.no,
+                                                ptr(pilot_bits.contiguous()), ptr(pilot_y_ls.contiguous()),
+                                                1 if ls_only else 0, ptr(H), _lib.stream_handle()),
+                  "esn_channel_estimate")
+        return H
+
+    def true_channel(self, taps):
+        """H_true [G, N, n_r, n_t] = FFT_N of the zero-padded taps (OFDM_MIMO_2-2_NBF_LDPC.py:273-279)."""
+        torch, p = self.torch, self.p
+        g = taps.shape[0]
+        with torch.cuda.device(self.device):
+            H = torch.empty((g, p.n_sub, p.n_r, p.n_t), dtype=torch.complex128, device=self.device)
+            check(self.lib.esn_taps_to_freq(g, p.n_sub, p.n_t, p.n_r, p.isi, ptr(taps.contiguous()), ptr(H),
+                                            _lib.stream_handle()), "esn_taps_to_freq")
+        return H
+
+    def mmse_detect_count(self, H, data_y, data_bits, frames_per_block, ebno_db, err=None, bits=None,
+                          want_xhat=False, zf=False):
+        """Per-subcarrier MMSE detector + error counters (driver:444-456); zf=True: equalize_zf (driver:34-39),
+        LS-ZF with an estimated H, Perfect-ZF with `true_channel` (OFDM_MIMO_2-2_NBF_LDPC.py:450-460)."""
+        torch, p = self.torch, self.p
+        g, b = H.shape[0], data_y.shape[0]
+        with torch.cuda.device(self.device):
+            p_i = self._per_group(p.p_i(ebno_db), g)
+            if err is None:
+                err = torch.zeros(g, dtype=torch.int64, device=self.device)
+            if bits is None:
+                bits = torch.zeros(g, dtype=torch.int64, device=self.device)
+            xh = torch.empty((b, p.n_sub, p.n_t), dtype=torch.complex128, device=self.device) if want_xhat else None
+            if zf:
+                check(self.lib.esn_zf_detect_count(b, int(frames_per_block), p.n_sub, p.cp, p.n_t, p.n_r, p.m,
+                                                   ptr(p_i), ptr(H), ptr(data_y.contiguous()),
+                                                   ptr(data_bits.contiguous()), ptr(err), ptr(bits), ptr(xh),
+                                                   _lib.stream_handle()), "esn_zf_detect_count")
+            else:
+                check(self.lib.esn_mmse_detect_count(b, int(frames_per_block), p.n_sub, p.cp, p.n_t, p.n_r, p.m,
+                                                     ptr(p_i), p.no, ptr(H), ptr(data_y.contiguous()),
+                                                     ptr(data_bits.contiguous()), ptr(err), ptr(bits), ptr(xh),
+                                                     _lib.stream_handle()), "esn_mmse_detect_count")
+        return (err, bits, xh) if want_xhat else (err, bits)
+
+    def channel_metrics(self, H, ebno_db, want_s=False):
+        """Per-subcarrier SVD metrics of H [G, N, n_r, n_t] (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; esn_channel_metrics):
+        cond [G, N] float64, rank [G, N] uint8, cap [G] float64 (the block's mean capacity per subcarrier), and with
+        want_s the singular values S [G, N, min(n_t, n_r)], descending.  Device tensors; nothing is read back."""
+        torch, p = self.torch, self.p
+        g, n = H.shape[0], H.shape[1]
+        if H.dtype != torch.complex128 or tuple(H.shape[2:]) != (p.n_r, p.n_t):
+            raise ValueError(f"H must be complex128 [G, N, {p.n_r}, {p.n_t}], not {H.dtype} {tuple(H.shape)}")
+        with torch.cuda.device(self.device):
+            p_i = self._per_group(p.p_i(ebno_db), g)
+            cond = torch.empty((g, n), dtype=torch.float64, device=self.device)
+            rank = torch.empty((g, n), dtype=torch.uint8, device=self.device)
+            cap = torch.empty((g,), dtype=torch.float64, device=self.device)
+            S = torch.empty((g, n, min(p.n_t, p.n_r)), dtype=torch.float64, device=self.device) if want_s else None
+            check(self.lib.esn_channel_metrics(g, n, p.n_t, p.n_r, ptr(H.contiguous()), ptr(p_i), p.no, ptr(S),
+                                               ptr(cond), ptr(rank), ptr(cap), _lib.stream_handle()),
+                  "esn_channel_metrics")
+        return (cond, rank, cap, S) if want_s else (cond, rank, cap)
+
+
+def percentiles_linear(x, qs):
+    """np.percentile(x, qs) with its default linear rule, on the tensor's own device: sorted value at the virtual index
+    (n - 1) q / 100, interpolated between its two neighbours as NumPy does (a + (b - a) t below the midpoint,
+    b - (b - a)(1 - t) from it on).  One torch.sort, no torch.quantile (which refuses large inputs).  Returns a float64
+    tensor [len(qs)]."""
+    import torch
+    v = torch.sort(x.reshape(-1).to(torch.float64)).values
+    n = v.numel()
+    if n == 0:
+        raise ValueError("percentiles of an empty tensor")
+    q = torch.tensor([float(a) for a in qs], dtype=torch.float64) / 100.0
+    vi = q * (n - 1)                                  # host arithmetic, as NumPy's: the index must not depend on the device
+    lo = torch.floor(vi).clamp(0, n - 1)
+    t = (vi - lo).to(v.device)
+    lo = lo.to(torch.int64).to(v.device)
+    hi = (lo + 1).clamp(max=n - 1)
+    a, b = v[lo], v[hi]
+    d = b - a
+    return torch.where(t >= 0.5, b - d * (1 - t), a + d * t)
+
+
+def summarize_channel_metrics(cond, rank, cap, n_t, n_r):
+    """The per-Eb/No channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:515-521) from the outputs
+    of FrameSource.channel_metrics, reduced on the device; only these four floats are read back."""
+    import torch
+    pct = percentiles_linear(cond, (50, 90))
+    full = rank.reshape(-1).ge(min(n_t, n_r)).to(torch.float64).mean()
+    vals = torch.stack([cap.to(torch.float64).mean(), full, pct[0], pct[1]]).cpu().tolist()
+    return dict(zip(("capacity_bits_per_sc", "frac_rank_ge_full", "cond_p50", "cond_p90"), vals))
+
+
+def _view_real(z):
+    """complex128 [..., T, n] -> float64 view [..., T, 2n] (Re/Im interleaved; driver:433-436); complex64 ->
+    float32."""
+    import torch
+    z = z.contiguous()
+    return torch.view_as_real(z).reshape(*z.shape[:-1], 2 * z.shape[-1])
+
+
+complex_as_io = _view_real

@@ -1,0 +1,117 @@
+"""The two coded comparison points of the Monte-Carlo harness, one Eb/No point each, batched on the device: the 4x8
+driver's coded + uncoded ESN against LS/MMSE (coded_ber_point) and the block-fading drivers' five detectors
+(block_fading_point).  Both send LDPC-coded payloads through the frames of a DetectorSweep's FrameSource and train
+through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says."""
+from __future__ import annotations
+
+from .frames import _view_real, summarize_channel_metrics
+
+
+def _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, salt):
+    """The coded data of G blocks with F data frames each: info bits u [G F, n_t, k] from a generator keyed by
+    (seed, snr_idx, salt), their code words tx_bits [G F, N m, n_t], the blocks' taps, the pilot (bits, x, y), the
+    LS-pattern pilot and the data frames that carry tx_bits."""
+    torch, p, src = sweep.torch, sweep.p, sweep.src
+    gen = torch.Generator(device=sweep.device)
+    gen.manual_seed((seed * 1000003 + snr_idx * 7919 + salt) % (2 ** 63 - 1))
+    u = torch.randint(0, 2, (G * F, p.n_t, code.k), generator=gen, device=sweep.device, dtype=torch.uint8)
+    tx_bits = code.encode(u, p.n_t)
+    taps = src.taps(G, snr_idx, 0)
+    pilot = src.frames(taps, 1, ebno_db, snr_idx, 0, 0, want_x=True)
+    _, _, py_ls = src.frames(taps, 1, ebno_db, snr_idx, 0, 0, ls_pattern=True)
+    _, _, dy = src.frames(taps, F, ebno_db, snr_idx, 0, 1, bits_in=tx_bits)
+    return u, tx_bits, taps, pilot, py_ls, dy
+
+
+def _esn_leg(sweep, ebno_db, pilot_y, pilot_x, data_y, tx_bits, F, snr_idx, seed, scale_ebno=None):
+    """The ESN of `sweep` on one point's blocks: train on the pilots (input scaling of scale_ebno, if given), repair,
+    predict and detect the data frames.  Returns (errors [G], bits [G]) and X_hat complex [G F, N, n_t]."""
+    torch, p, G = sweep.torch, sweep.p, pilot_y.shape[0]
+    sweep.set_snr(ebno_db, G, scale_ebno=scale_ebno)
+    E = sweep.train(pilot_y, pilot_x, seed=sweep.stream_seed(snr_idx, 0) + seed)
+    sweep.repair_fit(E)
+    y = sweep.bank.predict(_view_real(data_y), F, T=p.t_frame + p.delay, transient=p.forget,
+                           precision=sweep.precision, noise_mode="counter", seed=sweep.stream_seed(snr_idx, 1) + seed)
+    e, nb, xh = sweep.bank.detect_count(y, tx_bits, sweep.p_i, F, p.n_sub, p.n_t, p.m, want_xhat=True)
+    return (e, nb), torch.view_as_complex(xh.view(G * F, p.n_sub, p.n_t, 2).contiguous())
+
+
+def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=None, cal_frac=0.3, seed=0):
+    """One Eb/No point of the reference's coded + uncoded comparison, batched on the device
+    (Demo_MIMO_4x8_Sionna_CDL_ESN_v2.py:283-530): LDPC-coded payloads on every data symbol, ESN and
+    LS/MMSE detection, max-log LLRs, logistic LLR calibration fitted on the first `cal_frac` of the
+    blocks (the reference: the first 30 % of the symbols, :266,:476-482,:513-523) and sum-product
+    decoding of the rest.  Returns dict(ESN_uncoded, MMSE_uncoded, ESN_coded, MMSE_coded, a_esn, ...).
+    Frames and the ESN leg stay float64 / complex128 whatever sweep.io says: the MMSE leg reads complex128."""
+    sweep._require_block_independent_bank("coded_ber_point")
+    sweep._require_block_fading("coded_ber_point")
+    p, src = sweep.p, sweep.src
+    F, G = frames_per_block or p.coherence_symbols, n_blocks
+    u, tx_bits, _, (pbits, px, py), py_ls, dy = _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, 12345)
+    (e_esn, n_esn), x_esn = _esn_leg(sweep, ebno_db, py, px, dy, tx_bits, F, snr_idx, seed)
+    # LS/MMSE baseline
+    H = src.estimate_channel(pbits, py_ls, ebno_db)
+    e_mm, n_mm, x_mm = src.mmse_detect_count(H, dy, tx_bits, F, ebno_db, want_xhat=True)
+    out = dict(ESN_uncoded=float(e_esn.sum()) / float(n_esn.sum()), MMSE_uncoded=float(e_mm.sum()) / float(n_mm.sum()))
+    n_cal = max(1, int(round(cal_frac * G))) * F                             # frames used for calibration
+    for name, xhat in (("ESN", x_esn), ("MMSE", x_mm)):
+        llr, _ = code.llrs(xhat, p.m)
+        a, b = code.fit_calibration(llr[:n_cal], tx_bits[:n_cal], p.m)
+        err, nb = code.decode_count(llr[n_cal:].contiguous(), a, b, u[n_cal:], p.n_t * F, p.m)
+        out[name + "_coded"] = float(err.sum()) / max(float(nb.sum()), 1.0)
+        out["a_" + name.lower()] = a.cpu().numpy()
+        out["b_" + name.lower()] = b.cpu().numpy()
+    return out
+
+
+def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None, decode_every=4, llr_scale=1.5,
+                       seed=0, channel_metrics=False):
+    """One Eb/No point of the block-fading drivers' comparison (OFDM_{SISO,SIMO_1-2,MIMO_2-2}_NBF_LDPC.py /
+    Demo_MIMO_4x8_ChannelRank_..._fast.py :266-521), batched on the device: per coherence block one pilot and
+    L - 1 LDPC-coded data symbols (the pilot symbol carries no data here, :387); detectors ESN (SNR-matched),
+    ESN trained at a fixed Eb/No (`fixed_sweep`: a DetectorSweep built with train_ebno=12), LS-ZF,
+    MMSE and Perfect-ZF (:450-460); uncoded BER over every data symbol, coded BER on every `decode_every`-th
+    symbol of the run (kk % 4 == 1, :202,389) with the drivers' uncalibrated LLRs: per-stream decision-directed
+    sigma^2, x LLR_SCALE 1.5, clip +-20 (:478-485).  Returns the reference's holder names (BER_* / BERC_*).
+    channel_metrics=True adds the drivers' channel record of this Eb/No point (:369-385,515-521) as plain floats:
+    capacity_bits_per_sc, frac_rank_ge_full, cond_p50, cond_p90 (FrameSource.channel_metrics on H_true).
+    Frames and the ESN legs stay float64 / complex128 whatever the sweeps' io says: the LS / MMSE / ZF legs read
+    complex128."""
+    sweep._require_block_independent_bank("block_fading_point")
+    sweep._require_block_fading("block_fading_point")
+    if fixed_sweep is not None:
+        fixed_sweep._require_block_independent_bank("block_fading_point")
+    torch, p, src = sweep.torch, sweep.p, sweep.src
+    L = p.coherence_symbols
+    F, G = L - 1, n_blocks
+    u, tx_bits, taps, (pbits, px, py), py_ls, dy = _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, 4242)
+    xhat = {}
+    err = {}
+    err["ESN_matched"], xhat["ESN_matched"] = _esn_leg(sweep, ebno_db, py, px, dy, tx_bits, F, snr_idx, seed)
+    if fixed_sweep is not None:
+        t_eb = fixed_sweep.train_ebno
+        _, px_f, py_f = src.frames(taps, 1, t_eb, snr_idx, 0, 0, want_x=True)     # same pilot bits at the fixed power
+        err["ESN_trainFixed"], xhat["ESN_trainFixed"] = _esn_leg(fixed_sweep, ebno_db, py_f, px_f, dy, tx_bits, F,
+                                                                 snr_idx, seed, scale_ebno=t_eb)
+    H_ls = src.estimate_channel(pbits, py_ls, ebno_db, ls_only=True)
+    H_mmse = src.estimate_channel(pbits, py_ls, ebno_db)
+    H_true = src.true_channel(taps)
+    for name, H, zf in (("LS_ZF", H_ls, True), ("MMSE", H_mmse, False), ("PerfectZF", H_true, True)):
+        e, nb, xh = src.mmse_detect_count(H, dy, tx_bits, F, ebno_db, want_xhat=True, zf=zf)
+        xhat[name], err[name] = xh, (e, nb)
+    out = {"BER_" + k: float(v[0].sum()) / float(v[1].sum()) for k, v in err.items()}
+    # coded leg: symbol kk (1-based over the run; block b holds kk = L b + 1 (pilot) .. L b + L) decodes iff kk % every == 1
+    kk = (torch.arange(G, device=sweep.device)[:, None] * L + 2 + torch.arange(F, device=sweep.device)[None, :]).reshape(-1)
+    sel = torch.nonzero((kk % decode_every) == 1).flatten()
+    a = torch.full((p.m,), -float(llr_scale), dtype=torch.float64, device=sweep.device)   # -(a llr + b) = scale * llr
+    b = torch.zeros(p.m, dtype=torch.float64, device=sweep.device)
+    for name, xh in xhat.items():
+        xs = xh[sel]                                                           # [S, N, n_t]
+        per_stream = xs.permute(0, 2, 1).reshape(-1, p.n_sub, 1).contiguous()  # sigma^2 per (frame, tx) column (:479)
+        llr, _ = code.llrs(per_stream, p.m)                                    # [S n_t, 1, N m]
+        e, nb = code.decode_count(llr.view(xs.shape[0], p.n_t, -1), a, b, u[sel], max(1, xs.shape[0] * p.n_t), p.m)
+        out["BERC_" + name] = float(e.sum()) / max(float(nb.sum()), 1.0)
+    out["decoded_symbols"] = int(sel.numel())
+    if channel_metrics:
+        out.update(summarize_channel_metrics(*src.channel_metrics(H_true, ebno_db), p.n_t, p.n_r))
+    return out

@@ -57,6 +57,15 @@ def sweep_ab(torch, rounds, log):
         f"counters identical: {same}")
 
 
+def one_step(torch, sw, G, F):
+    """What DetectorSweep.run launches for blocks 0 .. G - 1 at 12 dB, without the counter sums."""
+    data = sw.src.blocks_fast(12.0, 0, 0, G, F, io="c64" if sw.io == "f32" else "c128")
+    sw.set_snr(12.0, G)
+    sw.train(data["pilot_y"], data["pilot_x"], seed=sw.stream_seed(0, 0))
+    err, bits = (torch.zeros(G, dtype=torch.int64, device=sw.device) for _ in range(2))
+    sw.detect(data["data_y"], data["data_bits"], F, err, bits, seed=sw.stream_seed(0, 1))
+
+
 def step_times(torch, steps, log, tag="[step]"):
     """gen + train + predict + detect of one default chunk of blocks, per width, interleaved step by step."""
     sw = {io: make_sweep(io) for io in ("f64", "f32")}
@@ -67,7 +76,7 @@ def step_times(torch, steps, log, tag="[step]"):
         for io in ("f64", "f32"):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            sw[io]._chunk(12.0, 0, list(range(G)), F, repair=False)
+            one_step(torch, sw[io], G, F)
             b.record()
             torch.cuda.synchronize()
             if i >= 2:

@@ -73,7 +73,7 @@ def main():
             E = sw.train(data["pilot_y"], data["pilot_x"], seed=sw.stream_seed(si, 0), group_offset=b0)   # pinv fit
             repaired += sw.repair_fit(E)
             readouts = [bank.W_out]
-            U, D, tr = sw._fit_io
+            U, D, tr = sw.fit_io
             ridge = torch.tensor(lams, dtype=torch.float64, device=dev).expand(g, len(lams)).contiguous()
             W, st = bank.solve(E, D, tr, method=sw.solve_method, ridge=ridge)    # every lambda, one launch
             repaired += bank.resolve_failed(E, D, tr, W, st, ridge=ridge)
