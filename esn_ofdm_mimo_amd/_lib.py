@@ -109,6 +109,9 @@ SIGNATURES = {
                                    _vp, _vp, _dp, _vp]),
     "esn_detect_count_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
                                        _vp, _vp, _dp, _vp]),
+    # decide and re-modulate: Y, B, F, N, cp, delay, n_t, m, p_i, tx_bits, err, bits, X_hat, dec_bits, D_hat, stream
+    "esn_detect_remod": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
+                                   _vp, _vp, _dp, _vp, _dp, _vp]),
 }
 # host-memory front ends: the arguments of esn_X behind a leading esn_mem_kind (include/esn_hip.h)
 for _name in ("esn_pack_weights", "esn_pack_readout", "esn_predict_batch", "esn_harvest_batch",

@@ -494,6 +494,36 @@ class ReservoirBank:
                      ptr(xh), _lib.stream_handle()), "esn_detect_count_f32" if y32 else "esn_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
+    def detect_remod(self, Y, tx_bits, p_i, frames_per_group, n_sub, cp, delay, n_t, bits_per_sym,
+                     err=None, bits=None, want_xhat=False, want_bits=False):
+        """detect_count and, in the same launch, the decisions re-modulated (esn_detect_remod): Y [B, N, 2 n_t] float64
+        -> D_hat [B, delay + cp + N, 2 n_t], the time-domain teacher rows of the decided symbols in the layout harvest
+        takes (delay zero rows, cyclic prefix, body).  tx_bits None: nothing is counted.  Returns
+        (D_hat, err, bits[, X_hat][, dec_bits]) -- err / bits are None without tx_bits, dec_bits uint8 [B, N m, n_t]."""
+        torch = self.torch
+        if getattr(Y, "dtype", None) in (torch.float32, np.float32):
+            raise ValueError("detect_remod reads float64 Y (predict with io='f64'): the tracked path has no float32 I/O")
+        Y = _as_dev(Y, torch, self.device)
+        b = Y.shape[0]
+        g = (b + frames_per_group - 1) // frames_per_group
+        p_i = _as_dev(p_i, torch, self.device)
+        tx_bits = _as_dev(tx_bits, torch, self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            if tx_bits is not None:
+                if err is None:
+                    err = torch.zeros(g, dtype=torch.int64, device=self.device)
+                if bits is None:
+                    bits = torch.zeros(g, dtype=torch.int64, device=self.device)
+            else:
+                err = bits = None
+            xh = torch.empty((b, n_sub, 2 * n_t), dtype=torch.float64, device=self.device) if want_xhat else None
+            db = torch.empty((b, n_sub * bits_per_sym, n_t), dtype=torch.uint8, device=self.device) if want_bits else None
+            D_hat = torch.empty((b, int(delay) + int(cp) + int(n_sub), 2 * n_t), dtype=torch.float64, device=self.device)
+            check(self.lib.esn_detect_remod(ptr(Y), b, int(frames_per_group), int(n_sub), int(cp), int(delay), int(n_t),
+                                            int(bits_per_sym), ptr(p_i), ptr(tx_bits), ptr(err), ptr(bits), ptr(xh),
+                                            ptr(db), ptr(D_hat), _lib.stream_handle()), "esn_detect_remod")
+        return (D_hat, err, bits) + ((xh,) if want_xhat else ()) + ((db,) if want_bits else ())
+
     # ------------------------------------------------------------------ helpers
     def _scratch(self, name, nbytes):
         """The bank's device scratch `name`, grown on demand to nbytes (None for 0).  Called under the device guard."""

@@ -737,6 +737,32 @@ int esn_detect_count_f32(const float* Y, int n_frames, int frames_per_group, int
                          tx_bits, err_count, bit_count, X_hat, stream);
 }
 
+int esn_detect_remod(const double* Y, int n_frames, int frames_per_group, int n_sub, int cp, int delay, int n_t,
+                     int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
+                     long long* bit_count, double* X_hat, uint8_t* dec_bits, double* D_hat, void* stream) {
+    const char* who = "esn_detect_remod";
+    if (!Y || !p_i || !D_hat) return fail(-1, "%s: null pointer", who);
+    if (tx_bits && (!err_count || !bit_count)) return fail(-1, "%s: tx_bits given without err_count / bit_count", who);
+    if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_t > 16) return fail(-1, "%s: n_t=%d, served up to 16", who, n_t);
+    int log2n = 0;
+    while ((1 << log2n) < n_sub) ++log2n;
+    if ((1 << log2n) != n_sub || n_sub < 2 || n_sub > 2048)
+        return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
+    if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
+        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
+    if (cp < 0 || cp >= n_sub) return fail(-1, "%s: cp=%d must be in [0, N) with N=%d", who, cp, n_sub);
+    if (delay < 0 || delay > (1 << 20)) return fail(-1, "%s: delay=%d must be in [0, %d]", who, delay, 1 << 20);
+    RemodParams rp;
+    rp.d.Y = Y;
+    rp.d.n_frames = n_frames; rp.d.frames_per_group = frames_per_group; rp.d.n_sub = n_sub;
+    rp.d.log2n = log2n; rp.d.n_t = n_t; rp.d.m = bits_per_sym; rp.d.p_i = p_i; rp.d.tx_bits = tx_bits;
+    rp.d.err = tx_bits ? err_count : nullptr; rp.d.bits = tx_bits ? bit_count : nullptr; rp.d.X_hat = X_hat;
+    rp.d.na_wg = 0;
+    rp.cp = cp; rp.delay = delay; rp.dec_bits = dec_bits; rp.D_hat = D_hat;
+    return hip_fail(launch_detect_remod(rp, (hipStream_t)stream), who);
+}
+
 static const double kTdlbDelay[23] = {0.0000, 0.1072, 0.2155, 0.2095, 0.2870, 0.2986, 0.3752, 0.5055, 0.3681,
                                       0.3697, 0.5700, 0.5283, 1.1021, 1.2756, 1.5474, 1.7842, 2.0169, 2.8294,
                                       3.0219, 3.6187, 4.1067, 4.2790, 4.7834};

@@ -93,6 +93,13 @@ struct DetectParams {
     long long* err; long long* bits; double* X_hat;
     int na_wg;             // antennas per workgroup (set by the launcher: all of them unless LDS is short)
 };
+// decide and re-modulate (esn_remod.hip): the tail above, then the decisions back in the time domain
+struct RemodParams {
+    DetectParams d;        // tx_bits may be nullptr (nothing is counted; err and bits are then not touched)
+    int cp, delay;
+    uint8_t* dec_bits;     // [B][N m][n_t] decided bits, or nullptr
+    double* D_hat;         // [B][delay + cp + N][2 n_t] teacher rows of the decisions
+};
 
 // frame generator (esn_gen.hip)
 struct TapParams {

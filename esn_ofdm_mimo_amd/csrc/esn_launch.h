@@ -108,4 +108,6 @@ int launch_qam_llr(const LlrParams& lp, hipStream_t stream);
 int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
 // esn_detect.hip
 int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
+// esn_remod.hip
+int launch_detect_remod(const RemodParams& rp, hipStream_t stream);
 }  // namespace esn

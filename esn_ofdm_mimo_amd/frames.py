@@ -93,13 +93,16 @@ class FrameSource:
         outs = [self.blocks_fast(ebno_db, snr_idx, b0, n, frames_per_block, with_ls_pilot, io) for b0, n in runs]
         return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
 
-    def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False, io="c128"):
+    def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False, io="c128",
+                    want_data_x=False):
         """Blocks first_block .. first_block + n_blocks - 1 in three launches (taps, pilots, data).
         io="c64": the DATA frames are complex64; pilots stay complex128 (training is unchanged).
         params.fading == "jakes": the taps move inside the block (taps_doppler, 1 + F symbols): the pilots pass
         through symbol 0, data frame k through symbol k + 1 -- one frames() call over the per-frame taps with one frame
         per "block"; frame counters and streams are those of block fading, so bits and noise are the same for the same
-        seed.  `taps` stays the pilot-instant taps [G, n_r, n_t, isi]; `taps_sym` [G, 1 + F, n_r, n_t, isi] is added."""
+        seed.  `taps` stays the pilot-instant taps [G, n_r, n_t, isi]; `taps_sym` [G, 1 + F, n_r, n_t, isi] is added.
+        want_data_x: `data_x` [G F, T, n_t] is added, the pre-PA transmit signal of every data frame (what pilot_x is to
+        the pilot: the teacher a genie-aided re-fit would use)."""
         p, F = self.p, frames_per_block
         if p.fading == "jakes":
             taps_sym = self.taps_doppler(n_blocks, 1 + F, snr_idx, first_block)
@@ -109,8 +112,11 @@ class FrameSource:
             taps_sym, taps = None, self.taps(n_blocks, snr_idx, first_block)
             data_taps, per_taps = taps, F
         pbits, px, py = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, want_x=True)
-        bits, _, dy = self.frames(data_taps, per_taps, ebno_db, snr_idx, first_block * F, 1, io=io)
+        bits, dx, dy = self.frames(data_taps, per_taps, ebno_db, snr_idx, first_block * F, 1, io=io,
+                                   want_x=want_data_x)
         out = dict(pilot_y=py, pilot_x=px, pilot_bits=pbits, data_y=dy, data_bits=bits, taps=taps)
+        if want_data_x:
+            out["data_x"] = dx
         if taps_sym is not None:
             out["taps_sym"] = taps_sym
         if with_ls_pilot:     # same bits, same noise, sparse pattern (driver:330-356)

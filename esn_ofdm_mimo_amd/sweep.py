@@ -109,7 +109,7 @@ class DetectorSweep:
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
                  rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None,
                  radius="host", radius_precision="f64", radius_squarings=24, fresh_radius_cache=True,
-                 symbol_counts=False):
+                 symbol_counts=False, track=None, track_window=2):
         """reservoirs: "shared" (one reservoir for every block), "per_block" (block b uses set b % pool of a pool
         drawn here) or "fresh" (the reference's own rule, SURVEY F5: every coherence block gets a reservoir of its
         own, drawn on the device by reservoirs.generate and keyed by (seed, global block index) -- the same at every
@@ -146,6 +146,18 @@ class DetectorSweep:
         read once per Eb/No point.  The block totals, so the returned BER and counters, are the same integers either
         way.  With params.fading == "jakes" (FrameSource.blocks_fast) this is BER against the age of the pilot.
 
+        track (extension; None = every read-out is fitted once, on the pilot): "decisions" or "genie" re-fits the
+        read-out after every data symbol of a block (_chunk_tracked).  Data symbol k of all blocks of a chunk is predicted
+        with the current read-outs and detected; "decisions" turns the detector's own decisions back into the teacher
+        signal on the device (ReservoirBank.detect_remod), "genie" takes the generator's transmit signal of that frame
+        (the bound: what a receiver that decided without error would have); the frame is harvested against that teacher
+        and the read-out solved again over the most recent track_window training sets (the pilot is one, and drops out
+        once track_window data symbols have been seen), with the sweep's solve_method and ridge.  Symbol k detects under
+        stream_seed(si, 2 + 2 k) and re-trains under stream_seed(si, 3 + 2 k), keyed by the global block, so the
+        counters do not depend on chunking or world size.  Read it with symbol_counts=True.  Not with ridge_grid,
+        train_ebno, params.continuation or io="f32".  keep_track_xhat = True (an attribute, for tests and tools) makes
+        every chunk leave its X_hat [F, G, N, 2 n_t] in track_xhat.
+
         io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
         predict kernels see the same float inputs and write the same float outputs).  Pilots and training stay
         float64.  Needs precision f32 / f16 / bf16."""
@@ -154,6 +166,18 @@ class DetectorSweep:
         if io == "f32" and precision == "f64":
             raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
         self.io = io
+        if track not in (None, "decisions", "genie"):
+            raise ValueError(f"track must be None, 'decisions' or 'genie', not {track!r}")
+        if track is not None:
+            if int(track_window) < 1:
+                raise ValueError(f"track_window must be at least 1 (the training sets a re-fit sees), not {track_window}")
+            for name, given in (("ridge_grid", ridge_grid is not None), ("train_ebno", train_ebno is not None),
+                                ("params.continuation", params.continuation), ("io='f32'", io == "f32")):
+                if given:
+                    raise ValueError(f"track={track!r} does not go with {name}: the re-fits are plain pinv / ridge solves "
+                                     "on float64 frames of the actual Eb/No, every frame from a fresh state")
+        self.track, self.track_window = track, int(track_window)
+        self.keep_track_xhat, self.track_xhat = False, None
         torch = _lib.require_gpu()
         self.torch, self.p = torch, params
         self.rank, self.world = rank, world_size
@@ -304,7 +328,7 @@ class DetectorSweep:
         # columns are exactly representable, the fit is unchanged to ~1e-7
         rows, cols = t + d - p.forget, self.bank.n_reservoir + self.n_in
         chol = self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
-        e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
+        e_dtype = self._fit_e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
         E = self.bank.fit(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
                           seed=seed, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
                           ridge=self.ridge_at(self._ebno), ridge_grid=self._grid_t)
@@ -378,7 +402,8 @@ class DetectorSweep:
         device vector (ChunkLayout) without synchronising the host unless `repair`."""
         torch = self.torch
         g = len(ids)
-        data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128")
+        data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128",
+                                    want_data_x=self.track == "genie")
         self.set_snr(ebno, g, scale_ebno=self.train_ebno)
         unscaled = None
         if self.reservoirs == "fresh":      # (no host read unless `repair`: an unscalable set counts as a flagged fit)
@@ -397,6 +422,10 @@ class DetectorSweep:
                                    minlength=len(self.ridge_grid)).to(torch.int64)
         if repair:
             self.repair_fit(E)
+        if self.track is not None:
+            err, nb, flagged = self._chunk_tracked(ebno, si, ids, F, data, E, self._flagged_fits(unscaled, repair), repair)
+            per_symbol = torch.stack([err.sum(dim=1), nb.sum(dim=1)], dim=1) if self.symbol_counts else None
+            return ChunkLayout.pack(torch, err.sum(), nb.sum(), flagged, picks, per_symbol)
         n_cnt = g * F if self.symbol_counts else g
         err = torch.zeros(n_cnt, dtype=torch.int64, device=self.device)
         nb = torch.zeros(n_cnt, dtype=torch.int64, device=self.device)
@@ -406,6 +435,55 @@ class DetectorSweep:
         if self.symbol_counts:
             per_symbol = torch.stack([err.view(g, F).sum(dim=0), nb.view(g, F).sum(dim=0)], dim=1)
         return ChunkLayout.pack(torch, err.sum(), nb.sum(), self._flagged_fits(unscaled, repair), picks, per_symbol)
+
+    def _chunk_tracked(self, ebno, si, ids, F, data, E, flagged, repair):
+        """The data symbols of a chunk under `track`, after the pilot fit (E: its extended states; `flagged`: its
+        flagged-fit count): for k = 0 .. F - 1 predict and detect symbol k of every block with the current read-outs,
+        harvest it against the teacher, solve over the window, swap the read-outs in.  Returns (err [F, G], bits [F, G],
+        flagged + the flagged re-fits); `repair` re-solves flagged re-fits by QR on the spot (host reads)."""
+        torch, p, bank = self.torch, self.p, self.bank
+        g, d, T = len(ids), p.delay, p.t_frame
+        U0, D0, forget = self._fit_io
+        y_sym = _view_real(data["data_y"]).view(g, F, T, self.n_in)
+        bits_sym = data["data_bits"].view(g, F, p.n_sub * p.m, p.n_t)
+        x_sym = _view_real(data["data_x"]).view(g, F, T, self.n_out) if self.track == "genie" else None
+        err = torch.zeros((F, g), dtype=torch.int64, device=self.device)
+        nb = torch.zeros((F, g), dtype=torch.int64, device=self.device)
+        U = torch.zeros((g, T + d, self.n_in), dtype=torch.float64, device=self.device)       # d trailing zero rows
+        D_true = torch.zeros((g, T + d, self.n_out), dtype=torch.float64, device=self.device) if x_sym is not None else None
+        window = [(E[:, forget:], D0[:, forget:].clone())]        # (the pilot buffers are reused by the next chunk)
+        ridge, xhats = self.ridge_at(ebno), []
+        for k in range(F):
+            y = bank.predict(y_sym[:, k], 1, T=T + d, transient=forget, precision=self.precision, noise_mode="counter",
+                             seed=self.stream_seed(si, 2 + 2 * k), group_offset=ids[0])
+            out = bank.detect_remod(y, bits_sym[:, k].contiguous(), self.p_i, 1, p.n_sub, p.cp, d, p.n_t, p.m,
+                                    err=err[k], bits=nb[k], want_xhat=self.keep_track_xhat)
+            D_hat = out[0]
+            if self.keep_track_xhat:
+                xhats.append(out[3])
+            if k == F - 1:
+                break
+            U[:, :T] = y_sym[:, k]
+            if x_sym is not None:
+                D_true[:, d:d + T] = x_sym[:, k]
+                D_hat = D_true.clone()
+            Ek = bank.harvest(U, D_hat, precision=self.fit_precision, noise_mode="counter",
+                              seed=self.stream_seed(si, 3 + 2 * k), e_dtype=self._fit_e_dtype, group_offset=ids[0])
+            if repair:
+                bank.raise_if_harvest_timed_out()
+            elif bank.harvest_timeout is not None:
+                flagged = flagged + bank.harvest_timeout.ne(0).sum().to(torch.int64)
+            window = (window + [(Ek[:, forget:], D_hat[:, forget:])])[-self.track_window:]
+            E_w, D_w = (torch.cat([w[i] for w in window], dim=1) for i in (0, 1))
+            W_out, status = bank.solve(E_w, D_w, 0, method=self.solve_method, ridge=ridge)
+            if repair:
+                bank.resolve_failed(E_w, D_w, 0, W_out, status, ridge=ridge)
+            else:
+                flagged = flagged + status.ne(0).sum().to(torch.int64)
+            bank.set_readout(W_out)
+        if self.keep_track_xhat:
+            self.track_xhat = torch.stack(xhats)
+        return err, nb, flagged
 
     def run(self, ebno_list, blocks_per_snr, frames_per_block=None, chunk_blocks=None, dist=None):
         """Returns (BER[n_snr], counters [n_snr, 2]) -- identical on every rank and for every world size and

@@ -450,6 +450,23 @@ int esn_detect_count_f32(const float* Y, int n_frames, int frames_per_group,
                          long long* err_count, long long* bit_count,
                          double* X_hat, void* stream);
 
+/* Decide and re-modulate (extension: decision-directed tracking of the read-out).  The tail of esn_detect_count --
+ * err_count, bit_count and X_hat are bitwise those of esn_detect_count on the same Y -- and then, in the same launch
+ * (the spectrum never leaves the chip), the decisions back in the time domain as the teacher of a re-fit:
+ *   X_dec = the constellation point of the decided index;  x_t = N IFFT_N(X_dec) sqrt(Pi[group]);
+ *   D_hat [B][delay + cp + N][2 N_t]: rows [0, delay) zero, rows [delay, delay + cp) the last cp samples of x_t, rows
+ *   [delay + cp, delay + cp + N) x_t; Re/Im interleaved per antenna -- the teacher layout of esn_harvest_batch
+ *   (helper_mimo_esn_generic.py:26-38).  Every element is written.
+ * tx_bits may be NULL: nothing is counted and err_count / bit_count (may be NULL too) are not touched.  dec_bits
+ * (uint8 [B][N*m][N_t], the decided bits in the layout of tx_bits) and X_hat are optional.  A frame's outputs do not
+ * depend on what else is in the launch.  Served: N a power of two in [2, 2048], N_t <= 16, m even in [2, 10],
+ * 0 <= cp < N, 0 <= delay <= 2^20; anything else returns -1 before any HIP call, the limit in esn_last_error(). */
+int esn_detect_remod(const double* Y, int n_frames, int frames_per_group,
+                     int n_sub, int cp, int delay, int n_t, int bits_per_sym,
+                     const double* p_i, const uint8_t* tx_bits,
+                     long long* err_count, long long* bit_count,
+                     double* X_hat, uint8_t* dec_bits, double* D_hat, void* stream);
+
 /* ---- Host-memory front ends ("caller-owned device or host pointers flagged by an enum").
  * The reference's callers hold C-contiguous float64 NumPy arrays on the host (pyESN.py:154,218); a binding that
  * lives there passes them as they are with ESN_MEM_HOST.  Each `esn_X_mem(mem_kind, ...)` takes the arguments
