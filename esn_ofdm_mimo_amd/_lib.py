@@ -101,6 +101,10 @@ SIGNATURES = {
                                       _dp, _dp, _vp, _vp, _vp, _dp, _vp]),
     "esn_taps_to_freq": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp]),
     "esn_channel_metrics": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp, _dp, _vp, _dp, _vp]),
+    # decision-directed channel estimate: y_cp, X_hat | bits, n_est, window, est_per_group, N, cp, n_t, n_r, isi, m, p_i,
+    # reg, taps, H, status, stream
+    "esn_channel_track": (C.c_int, [_dp, _dp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _vp]),
     "esn_ldpc_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "esn_qam_llr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _vp]),
     "esn_ldpc_decode_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp,

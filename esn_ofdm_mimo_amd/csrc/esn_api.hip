@@ -925,6 +925,38 @@ int esn_zf_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, i
                          0.0, H, y_cp, tx_bits, err_count, bit_count, X_hat, stream);
 }
 
+int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bits, int n_est, int window,
+                      int est_per_group, int n_sub, int cp, int n_t, int n_r, int isi, int bits_per_sym,
+                      const double* p_i, const double* reg, double* taps, double* H, int* status, void* stream) {
+    const char* who = "esn_channel_track";
+    if (!y_cp || !p_i || !reg || !H || !status) return fail(-1, "%s: null pointer", who);
+    if ((X_hat != nullptr) == (bits != nullptr)) return fail(-1, "%s: exactly one of X_hat and bits must be given", who);
+    if (n_est <= 0 || est_per_group <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (window < 1 || window > 8) return fail(-1, "%s: window=%d must be in [1, 8]", who, window);
+    if ((long long)n_est * window > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 frames", who);
+    const int l2 = pow2_log(n_sub);
+    if (l2 < 1 || n_sub > 2048) return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
+    if (n_t < 1 || n_t > 4) return fail(-1, "%s: n_t=%d must be in [1, 4]", who, n_t);
+    if (n_r < 1 || n_r > 8) return fail(-1, "%s: n_r=%d must be in [1, 8]", who, n_r);
+    if (isi < 1 || isi > 16) return fail(-1, "%s: isi=%d must be in [1, 16]", who, isi);
+    if (n_t * isi > 64 || n_t * isi > n_sub)
+        return fail(-1, "%s: n_t * isi = %d unknowns, served up to min(64, N) with N=%d", who, n_t * isi, n_sub);
+    if (cp < 0 || cp >= n_sub) return fail(-1, "%s: cp=%d must be in [0, N) with N=%d", who, cp, n_sub);
+    if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
+        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM) in [2, 10]", who, bits_per_sym);
+    const size_t lds = chantrack_lds_bytes(n_sub, n_t, n_r, isi);
+    if (lds > 150 * 1024)
+        return fail(-1, "%s: N=%d n_t=%d n_r=%d isi=%d needs %zu bytes of LDS, served up to %d", who, n_sub, n_t, n_r,
+                    isi, lds, 150 * 1024);
+    if ((((uintptr_t)y_cp) | ((uintptr_t)X_hat) | ((uintptr_t)taps) | ((uintptr_t)H)) & 15)
+        return fail(-1, "%s: y_cp, X_hat, taps and H must be 16-byte aligned", who);
+    ChanTrackParams c;
+    c.n_est = n_est; c.window = window; c.est_per_group = est_per_group; c.n_sub = n_sub; c.log2n = l2; c.cp = cp;
+    c.n_t = n_t; c.n_r = n_r; c.isi = isi; c.m = bits_per_sym; c.y_cp = y_cp; c.X_hat = X_hat; c.bits = bits;
+    c.p_i = p_i; c.reg = reg; c.taps = taps; c.H = H; c.status = status; c.n_seg = 0; c.log2m2 = 0;
+    return hip_fail(launch_channel_track(c, (hipStream_t)stream), who);
+}
+
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream) {
     if (!taps || !H) return fail(-1, "esn_taps_to_freq: null pointer");
     if (n_blocks <= 0 || n_sub <= 0 || n_t <= 0 || n_r <= 0 || isi <= 0 || isi > n_sub)

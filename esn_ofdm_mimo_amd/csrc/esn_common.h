@@ -173,6 +173,19 @@ struct MmseParams {
     const uint8_t* tx_bits;      // [B][N*m][n_t]
     long long* err; long long* bits; double* X_hat;
 };
+// decision-directed channel estimate (esn_chantrack.hip): estimate e reads frames e window .. e window + window - 1
+struct ChanTrackParams {
+    int n_est, window, est_per_group, n_sub, log2n, cp, n_t, n_r, isi, m;
+    const double* y_cp;          // complex [n_est window][T][n_r]
+    const double* X_hat;         // complex [n_est window][N][n_t], or nullptr: then bits
+    const uint8_t* bits;         // [n_est window][N*m][n_t]
+    const double* p_i;           // [groups]
+    const double* reg;           // [groups][isi]
+    double* taps;                // complex [n_est][n_r][n_t][isi], or nullptr
+    double* H;                   // complex [n_est][N][n_r][n_t]
+    int* status;                 // [n_est]
+    int n_seg, log2m2;           // set by the launcher: k ranges per sum; log2 of n_t isi rounded up to a power of two
+};
 
 // coded leg (esn_coded.hip)
 struct LdpcEncodeParams {

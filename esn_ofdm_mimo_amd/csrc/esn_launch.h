@@ -110,4 +110,8 @@ int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
 int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
 // esn_remod.hip
 int launch_detect_remod(const RemodParams& rp, hipStream_t stream);
+// esn_chantrack.hip: the k ranges a sum is split into and the LDS of one workgroup, functions of the shape alone
+int chantrack_segments(int n_sub, int n_t, int n_r);
+size_t chantrack_lds_bytes(int n_sub, int n_t, int n_r, int isi);
+int launch_channel_track(const ChanTrackParams& cp, hipStream_t stream);
 }  // namespace esn

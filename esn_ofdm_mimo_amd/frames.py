@@ -21,6 +21,7 @@ class FrameSource:
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.seed = int(seed)
+        self._track_reg = {}                 # Eb/No -> reg [isi] on the device (track_channel)
 
     def _key(self, *parts):
         h = self.seed & (2 ** 64 - 1)
@@ -172,6 +173,49 @@ class FrameSource:
                                                      ptr(data_bits.contiguous()), ptr(err), ptr(bits), ptr(xh),
                                                      _lib.stream_handle()), "esn_mmse_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
+
+    def track_prior(self, ebno_db):
+        """reg [isi] of track_channel: the MAP weight T No / (N Pi r_h[l]) of the exponential prior r_h that
+        esn_channel_estimate shrinks with (exp(-l / (cp / 9)) normalised over cp + 1 taps), T = N + cp."""
+        import math
+        p = self.p
+        tc = max(p.cp / 9.0, 1e-12)
+        rsum = sum(math.exp(-j / tc) for j in range(p.cp + 1))
+        return [p.t_frame * p.no / (p.n_sub * p.p_i(ebno_db) * (math.exp(-l / tc) / rsum)) for l in range(p.isi)]
+
+    def track_channel(self, y_cp, ebno_db, X_hat=None, bits=None, window=1, est_per_group=1, want_taps=False):
+        """Decision-directed channel estimate (esn_channel_track): estimate e from the `window` consecutive frames
+        e window .. e window + window - 1 of y_cp [n_est window, T, n_r] and the points decided on them -- X_hat complex
+        [n_est window, N, n_t] (sliced as the detectors slice) or bits uint8 [n_est window, N m, n_t], exactly one.
+        Returns (H [n_est, N, n_r, n_t], status int32 [n_est][, taps [n_est, n_r, n_t, isi]]); a flagged estimate
+        (status 1: singular normal equations) is NaN."""
+        torch, p = self.torch, self.p
+        if (X_hat is None) == (bits is None):
+            raise ValueError("track_channel takes exactly one of X_hat and bits")
+        if not 1 <= int(window) <= 8:
+            raise ValueError(f"window must be in 1..8, not {window}")
+        if y_cp.shape[0] % int(window):
+            raise ValueError(f"{y_cp.shape[0]} frames are no multiple of window = {window}")
+        n_est = y_cp.shape[0] // int(window)
+        g = (n_est + int(est_per_group) - 1) // int(est_per_group)
+        with torch.cuda.device(self.device):
+            p_i = self._per_group(p.p_i(ebno_db), g)
+            row = self._track_reg.get(float(ebno_db))      # one upload per Eb/No: the tracking loop calls per data symbol
+            if row is None:
+                row = self._track_reg[float(ebno_db)] = torch.tensor(self.track_prior(ebno_db), dtype=torch.float64,
+                                                                     device=self.device)
+            reg = row.repeat(g, 1)
+            H = torch.empty((n_est, p.n_sub, p.n_r, p.n_t), dtype=torch.complex128, device=self.device)
+            status = torch.empty((n_est,), dtype=torch.int32, device=self.device)
+            taps = torch.empty((n_est, p.n_r, p.n_t, p.isi), dtype=torch.complex128, device=self.device) if want_taps \
+                else None
+            xh = None if X_hat is None else X_hat.contiguous()
+            bt = None if bits is None else bits.contiguous()
+            check(self.lib.esn_channel_track(ptr(y_cp.contiguous()), ptr(xh), ptr(bt), n_est, int(window),
+                                             int(est_per_group), p.n_sub, p.cp, p.n_t, p.n_r, p.isi, p.m, ptr(p_i),
+                                             ptr(reg), ptr(taps), ptr(H), ptr(status), _lib.stream_handle()),
+                  "esn_channel_track")
+        return (H, status, taps) if want_taps else (H, status)
 
     def channel_metrics(self, H, ebno_db, want_s=False):
         """Per-subcarrier SVD metrics of H [G, N, n_r, n_t] (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; esn_channel_metrics):

@@ -16,6 +16,9 @@
                     reduced over ranks with a single all_reduce (RCCL) at the end.
     coded_ber_point, block_fading_point
                     one Eb/No point of the coded comparisons of the drivers                      points.py
+    baseline_tracking_point
+                    the LS-MMSE baseline of one Eb/No point with its channel estimate re-made after    points.py
+                    every data symbol (FrameSource.track_channel, esn_channel_track)
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -25,5 +28,5 @@ This module is the import path of all of them; the code lives in the four module
 """
 from .frames import FrameSource, _view_real, complex_as_io, percentiles_linear, summarize_channel_metrics  # noqa: F401
 from .link import LinkParams  # noqa: F401
-from .points import block_fading_point, coded_ber_point  # noqa: F401
+from .points import baseline_tracking_point, block_fading_point, coded_ber_point  # noqa: F401
 from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters  # noqa: F401

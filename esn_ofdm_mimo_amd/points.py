@@ -1,7 +1,10 @@
 """The two coded comparison points of the Monte-Carlo harness, one Eb/No point each, batched on the device: the 4x8
 driver's coded + uncoded ESN against LS/MMSE (coded_ber_point) and the block-fading drivers' five detectors
 (block_fading_point).  Both send LDPC-coded payloads through the frames of a DetectorSweep's FrameSource and train
-through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says."""
+through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says.
+Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, uncoded, detected symbol by symbol with its
+channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
+only."""
 from __future__ import annotations
 
 from .frames import _view_real, summarize_channel_metrics
@@ -34,6 +37,78 @@ def _esn_leg(sweep, ebno_db, pilot_y, pilot_x, data_y, tx_bits, F, snr_idx, seed
                            precision=sweep.precision, noise_mode="counter", seed=sweep.stream_seed(snr_idx, 1) + seed)
     e, nb, xh = sweep.bank.detect_count(y, tx_bits, sweep.p_i, F, p.n_sub, p.n_t, p.m, want_xhat=True)
     return (e, nb), torch.view_as_complex(xh.view(G * F, p.n_sub, p.n_t, 2).contiguous())
+
+
+def baseline_tracking_point(src, ebno_db, snr_idx, n_blocks, frames_per_block=None, track=None, window=1, first_block=0,
+                            chunk_blocks=None, zf=False, want_xhat=False):
+    """One Eb/No point of the LS-MMSE baseline with its channel estimate tracked through the block, on the frames a
+    DetectorSweep over the same FrameSource seed detects (blocks_fast with the sweep's keys): per chunk the pilot
+    estimate H (esn_channel_estimate on the sparse LS pilot), then data symbol k of all blocks at once through
+    mmse_detect_count with one H per frame and, unless k is the last, a new H from FrameSource.track_channel over the
+    most recent `window` data symbols -- track="decisions": the detector's own X_hat, sliced; "genie": the transmitted
+    bits, the bound.  The pilot is not part of the window.  An estimate the kernel flags keeps the block's previous H.
+    track=None: every symbol against the pilot estimate, what tools/doppler_sweep.py counts.  zf=True: the zero-forcing
+    detector in place of MMSE.  Returns dict(errors int64 [F], bits int64 [F] per data symbol, ber, failed = flagged
+    estimates); counters stay on the device until the end.  want_xhat is test support, not part of a sweep: on a tracked
+    run it adds `x_hat` complex [F, n_blocks, N, n_t], the detector's output on every data symbol, and keeps all of those
+    tensors alive until the end -- tests/test_gpu_baseline_tracking.py holds it against the NumPy loop; leave it False
+    at any size that matters."""
+    if track not in (None, "decisions", "genie"):
+        raise ValueError(f"track must be None, 'decisions' or 'genie', not {track!r}")
+    if not isinstance(window, int) or not 1 <= window <= 8:
+        raise ValueError(f"window must be an integer in 1..8, not {window!r}")
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    torch, p = src.torch, src.p
+    F = int(frames_per_block or p.coherence_symbols)
+    chunk = int(chunk_blocks or n_blocks)
+    errors = torch.zeros(F, dtype=torch.int64, device=src.device)
+    nbits = torch.zeros(F, dtype=torch.int64, device=src.device)
+    failed = torch.zeros((), dtype=torch.int64, device=src.device)
+    kept = []
+    for b0 in range(int(first_block), int(first_block) + int(n_blocks), chunk):
+        g = min(chunk, int(first_block) + int(n_blocks) - b0)
+        d = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
+        H = src.estimate_channel(d["pilot_bits"], d["pilot_y_ls"], ebno_db)
+        if track is None:
+            e, nb = src.mmse_detect_count(H.repeat_interleave(F, dim=0), d["data_y"], d["data_bits"], 1, ebno_db, zf=zf)
+            errors += e.view(g, F).sum(dim=0)
+            nbits += nb.view(g, F).sum(dim=0)
+            continue
+        dy = d["data_y"].view(g, F, p.t_frame, p.n_r)
+        db = d["data_bits"].view(g, F, p.n_sub * p.m, p.n_t)
+        decided = []                                                  # X_hat of the most recent `window` symbols
+        kept.append([])
+        for k in range(F):
+            e, nb, xh = src.mmse_detect_count(H, dy[:, k].contiguous(), db[:, k].contiguous(), 1, ebno_db,
+                                              want_xhat=True, zf=zf)
+            errors[k] += e.sum()
+            nbits[k] += nb.sum()
+            if want_xhat:
+                kept[-1].append(xh)
+            if k == F - 1:
+                break
+            decided = (decided + [xh])[-window:]
+            ws = min(window, k + 1)
+            y_win = dy[:, k + 1 - ws:k + 1].reshape(g * ws, p.t_frame, p.n_r)
+            if track == "decisions":
+                Hn, st = src.track_channel(y_win, ebno_db, X_hat=torch.stack(decided, dim=1).reshape(g * ws, p.n_sub, p.n_t),
+                                           window=ws)
+            else:
+                Hn, st = src.track_channel(y_win, ebno_db, bits=db[:, k + 1 - ws:k + 1].reshape(g * ws, -1, p.n_t),
+                                           window=ws)
+            bad = st != 0
+            failed += bad.sum()
+            H = torch.where(bad[:, None, None, None], H, Hn)
+    errors, nbits = errors.cpu().numpy(), nbits.cpu().numpy()
+    out = dict(errors=errors, bits=nbits, ber=float(errors.sum()) / float(nbits.sum()), failed=int(failed))
+    if want_xhat and kept:
+        out["x_hat"] = torch.cat([torch.stack(c) for c in kept], dim=1)
+    return out
 
 
 def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=None, cal_frac=0.3, seed=0):

@@ -604,6 +604,34 @@ int esn_zf_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, i
                         long long* err_count, long long* bit_count, double* X_hat, void* stream);
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream);
 
+/* ---- Decision-directed channel estimate (extension: the MMSE baseline tracked through a block under Doppler), float64.
+ * Estimate e is made from `window` frames stored consecutively, frames e window .. e window + window - 1, and belongs to
+ * group e / est_per_group (p_i [groups], reg [groups][isi]).  With w = exp(-2 pi i / N), L = isi, Pi = p_i[group]:
+ *   Y_f[k, r] = (1/N) FFT_N(y_f[cp:, r])[k] / sqrt(Pi)               y_cp complex [n_est window][cp + N][n_r]
+ *   X_f[k, t] = the unit-power square QAM point decided for (k, t): the nearest point to X_hat complex
+ *               [n_est window][N][n_t] (slicer and index rule of esn_detect_count), or the point of `bits`
+ *               [n_est window][N*m][n_t] (layout of tx_bits: natural binary, LSB first) -- exactly one of the two.
+ *   model       Y_f[k, r] ~ sum_t X_f[k, t] sum_{l<L} c[r, t, l] w^{kl}
+ *   G[(t,l),(t',l')] = sum_f sum_k conj(X_f[k,t]) X_f[k,t'] w^{k(l'-l)} + delta reg[l]   (block-Toeplitz: computed as
+ *                      n_t^2 L lag sums), b[(t,l), r] = sum_f sum_k conj(X_f[k,t]) w^{-kl} Y_f[k,r]
+ *   c[r] = G^-1 b[:, r] by root-free Cholesky (G = L D L^H);   H[k, r, t] = sum_l c[r,t,l] w^{kl}
+ * reg[l] >= 0 is the caller's prior weight: the MAP weight of a tap of variance r_h[l] under noise of variance
+ * T No / (N Pi) on Y is reg[l] = T No / (N Pi r_h[l]), T = N + cp.  Outputs: H complex [n_est][N][n_r][n_t], taps
+ * complex [n_est][n_r][n_t][isi] (optional), status [n_est].  A pivot D_j that is not finite or not above 64 2^-52 times
+ * its original diagonal entry sets status[e] = 1 and that estimate's taps and H to NaN; otherwise status[e] = 0.  Every
+ * output element is written in every case.  Sums run in a fixed order (frame after frame, k ascending inside one of S
+ * contiguous ranges of k, the ranges joined pairwise, S a function of the shape), so an estimate is bitwise the same
+ * alone or inside any launch.  Served: N a power of two in [2, 2048], n_t <= 4, n_r <= 8, isi <= 16, n_t isi <=
+ * min(64, N), 1 <= window <= 8, 0 <= cp < N, m even in [2, 10], 16-byte aligned y_cp / X_hat / taps / H, and a workgroup
+ * image of at most 150 KB of LDS (16 (N (1 + n_r + n_t) + n_r) bytes plus the solver's: up to N = 512 at 4x8 with
+ * isi = 8, up to N = 2048 at 2x2 -- wider than the N the detector's other limits suggest, since LDS allows it); anything
+ * else returns -1 before any HIP call, the limit in esn_last_error(). */
+int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bits,
+                      int n_est, int window, int est_per_group,
+                      int n_sub, int cp, int n_t, int n_r, int isi, int bits_per_sym,
+                      const double* p_i, const double* reg,
+                      double* taps, double* H, int* status, void* stream);
+
 /* ---- Channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; the 4x8 ChannelRank driver is
  * named after it), float64.  H complex [G][N][n_r][n_t] in the layout of the function above, 16-byte aligned; p_i [G]
  * on the device as in the detectors; per subcarrier k the singular values s_1 >= ... of H_k by one-sided complex

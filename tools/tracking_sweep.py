@@ -6,10 +6,13 @@ bit error rate of data symbol 1 .. F of a block (LinkParams.fading = "jakes") fo
     decisions   re-fitted after every data symbol on the detector's own re-modulated decisions (track="decisions")
     genie       re-fitted on the true transmit signal (track="genie"): the bound, not a receiver
 
-with the window (training sets per re-fit) given.  Beside the curves: the wall time of a chunk of each mode (one warm-up
+with the window (training sets per re-fit) given, and beside each the LS-MMSE baseline on the same frames treated the same
+way (baseline_tracking_point: "mmse static" counts every symbol against the pilot estimate, "mmse decisions" / "mmse genie"
+re-estimate the channel after every data symbol from the last --mmse-window symbols, esn_channel_track) -- six curves, so
+a tracked ESN is never set against an untracked baseline.  Beside the curves: the wall time of a chunk of each mode (one warm-up
 chunk, then the whole run timed with a device synchronisation at the end), so the price of tracking is on record.
 
-    python tools/tracking_sweep.py [--preset 4x8|2x2] [--ebno 21] [--fd HZ] [--frames F] [--blocks 64] [--window 2]
+    python tools/tracking_sweep.py [--preset 4x8|2x2] [--ebno 21] [--fd HZ] [--frames F] [--blocks 64] [--window 2] [--mmse-window 1]
                                    [--n-res N] [--precision P] [--fit-precision P] [--noise X] [--ridge LAMBDA]
                                    [--chunk 64] [--out file.json]
 
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--frames", type=int, default=None, help="data symbols per block (0: the coherence rule at 100 Hz)")
     ap.add_argument("--blocks", type=int, default=64)
     ap.add_argument("--window", type=int, default=2, help="training sets per re-fit (track_window)")
+    ap.add_argument("--mmse-window", type=int, default=1, help="data symbols per channel re-estimate of the MMSE baseline")
     ap.add_argument("--n-res", type=int, default=None)
     ap.add_argument("--precision", default=None)
     ap.add_argument("--fit-precision", default=None)
@@ -51,7 +55,7 @@ def main():
     a = ap.parse_args()
     import torch
     from esn_ofdm_mimo_amd import _lib
-    from esn_ofdm_mimo_amd.montecarlo import DetectorSweep, LinkParams
+    from esn_ofdm_mimo_amd.montecarlo import DetectorSweep, LinkParams, baseline_tracking_point
     o = dict(PRESETS[a.preset])
     for k in o:
         if getattr(a, k) is not None:
@@ -90,6 +94,21 @@ def main():
         pick = sorted({0, F // 4, F // 2, F - 1})
         print(f"{label:10s} BER {curve['ber']:.4e}  {curve['ms_per_chunk']:9.2f} ms per chunk of {min(a.chunk, a.blocks)} "
               f"blocks   per symbol " + "  ".join(f"s={s + 1}: {curve['ber_per_symbol'][s]:.3e}" for s in pick))
+        # the LS-MMSE baseline over the same frames (the sweep's FrameSource, Eb/No index 0, blocks 0 ..), tracked the
+        # same way: its channel estimate re-made after every data symbol from the last --mmse-window symbols
+        kw = dict(track=track, window=a.mmse_window, chunk_blocks=a.chunk)
+        baseline_tracking_point(sw.src, a.ebno, 0, min(a.chunk, a.blocks), F, **kw)              # warm-up: one chunk
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mm = baseline_tracking_point(sw.src, a.ebno, 0, a.blocks, F, **kw)
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        curve = dict(label="mmse " + label, track=track, detector="mmse", window=a.mmse_window, ber=mm["ber"],
+                     errors=int(mm["errors"].sum()), bits=int(mm["bits"].sum()), estimates_flagged=mm["failed"],
+                     ms_per_chunk=1e3 * seconds / n_chunks, ber_per_symbol=(mm["errors"] / mm["bits"]).tolist())
+        result["curves"].append(curve)
+        print(f"{curve['label']:15s} BER {curve['ber']:.4e}  {curve['ms_per_chunk']:9.2f} ms per chunk   per symbol "
+              + "  ".join(f"s={s + 1}: {curve['ber_per_symbol'][s]:.3e}" for s in pick))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
