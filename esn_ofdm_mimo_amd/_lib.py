@@ -105,6 +105,15 @@ SIGNATURES = {
     # reg, taps, H, status, stream
     "esn_channel_track": (C.c_int, [_dp, _dp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _vp]),
+    # windowed ELM: precision, n_in, n_hidden, window, bias_col, n_wsets, W_in, b, in_scale, in_shift, U, n_groups, T_in,
+    # T, group_offset, E, e_f32, e_cols, stream
+    "esn_elm_features": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp,
+                                   C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, C.c_int, C.c_int, _vp]),
+    # precision, n_in, n_hidden, window, bias_col, n_wsets, n_out, W_in, b, W_out, e_cols, in_scale, in_shift, t_scale,
+    # t_shift, U, n_frames, frames_per_group, T_in, T, transient, group_offset, Y, stream
+    "esn_elm_predict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                  _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _dp,
+                                  _vp]),
     "esn_ldpc_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "esn_qam_llr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _vp]),
     "esn_ldpc_decode_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp,

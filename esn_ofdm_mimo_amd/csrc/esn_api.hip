@@ -957,6 +957,72 @@ int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bi
     return hip_fail(launch_channel_track(c, (hipStream_t)stream), who);
 }
 
+// the checks esn_elm_features and esn_elm_predict share; n_out = 0: features
+static int elm_check(const char* who, int precision, int n_in, int n_hidden, int window, int bias_col, int n_wsets,
+                     int n_out, int e_cols, int n_seq, int seq_per_group, int T_in, int T, int transient) {
+    if (precision == ESN_F32 || precision == ESN_BF16)
+        return fail(-2, "%s: precision %d is not built: ESN_F64 and (predict) ESN_F16 are", who, precision);
+    if (precision != ESN_F64 && precision != ESN_F16) return fail(-1, "%s: unknown precision %d", who, precision);
+    if (n_in < 1) return fail(-1, "%s: n_in=%d must be positive", who, n_in);
+    if (window < 1 || window > 16) return fail(-1, "%s: window=%d must be in [1, 16]", who, window);
+    if ((long long)window * n_in > 256)
+        return fail(-1, "%s: window * n_in = %lld, served up to K = 256", who, (long long)window * n_in);
+    if (n_hidden < 1 || n_hidden > 1024) return fail(-1, "%s: n_hidden=%d must be in [1, 1024]", who, n_hidden);
+    if (bias_col != 0 && bias_col != 1) return fail(-1, "%s: bias_col=%d must be 0 or 1", who, bias_col);
+    if (n_wsets < 1) return fail(-1, "%s: n_wsets=%d must be positive", who, n_wsets);
+    if (n_out && (n_out < 1 || n_out > 8)) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
+    if (e_cols < n_hidden + bias_col || e_cols > n_hidden + 4)
+        return fail(-1, "%s: e_cols=%d must be in [n_hidden + bias_col, n_hidden + 4] = [%d, %d]", who, e_cols,
+                    n_hidden + bias_col, n_hidden + 4);
+    if (n_seq < 1 || seq_per_group < 1) return fail(-1, "%s: invalid sizes (sequences, frames per group)", who);
+    if (T_in < 1 || T_in > T || T > (1 << 20))
+        return fail(-1, "%s: need 1 <= T_in <= T <= 2^20 (T_in=%d, T=%d)", who, T_in, T);
+    if (window > T) return fail(-1, "%s: window=%d exceeds T=%d", who, window, T);
+    if (transient < 0 || transient >= T) return fail(-1, "%s: transient=%d must be in [0, T) with T=%d", who, transient, T);
+    if ((long long)n_seq * ((T + 15) / 16) > 0x7fffffffLL)
+        return fail(-1, "%s: more than 2^31 - 1 tiles of 16 rows", who);
+    return 0;
+}
+
+int esn_elm_features(int precision, int n_in, int n_hidden, int window, int bias_col, int n_wsets, const double* W_in,
+                     const double* b, const double* in_scale, const double* in_shift, const double* U, int n_groups,
+                     int T_in, int T, uint64_t group_offset, void* E, int e_f32, int e_cols, void* stream) {
+    const char* who = "esn_elm_features";
+    if (!W_in || !b || !U || !E) return fail(-1, "%s: null pointer", who);
+    const int rc = elm_check(who, precision, n_in, n_hidden, window, bias_col, n_wsets, 0, e_cols, n_groups, 1, T_in, T, 0);
+    if (rc) return rc;
+    if (precision != ESN_F64)
+        return fail(-2, "%s: features are float64 arithmetic (ESN_F64); ESN_F16 is served by esn_elm_predict", who);
+    if ((uintptr_t)E & 15) return fail(-1, "%s: E must be 16-byte aligned", who);
+    ElmParams p;
+    memset(&p, 0, sizeof(p));
+    p.n_in = n_in; p.n_hidden = n_hidden; p.window = window; p.bias_col = bias_col; p.n_wsets = n_wsets; p.n_out = 1;
+    p.e_cols = e_cols; p.n_seq = n_groups; p.seq_per_group = 1; p.T_in = T_in; p.T = T; p.transient = 0;
+    p.group_offset = group_offset; p.W_in = W_in; p.b = b; p.in_scale = in_scale; p.in_shift = in_shift; p.U = U;
+    p.E = E; p.e_f32 = e_f32 ? 1 : 0;
+    return hip_fail(launch_elm_features(p, (hipStream_t)stream), who);
+}
+
+int esn_elm_predict(int precision, int n_in, int n_hidden, int window, int bias_col, int n_wsets, int n_out,
+                    const double* W_in, const double* b, const double* W_out, int e_cols, const double* in_scale,
+                    const double* in_shift, const double* t_scale, const double* t_shift, const double* U, int n_frames,
+                    int frames_per_group, int T_in, int T, int transient, uint64_t group_offset, double* Y, void* stream) {
+    const char* who = "esn_elm_predict";
+    if (!W_in || !b || !W_out || !U || !Y) return fail(-1, "%s: null pointer", who);
+    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
+    const int rc = elm_check(who, precision, n_in, n_hidden, window, bias_col, n_wsets, n_out, e_cols, n_frames,
+                             frames_per_group, T_in, T, transient);
+    if (rc) return rc;
+    if ((uintptr_t)Y & 15) return fail(-1, "%s: Y must be 16-byte aligned", who);
+    ElmParams p;
+    memset(&p, 0, sizeof(p));
+    p.n_in = n_in; p.n_hidden = n_hidden; p.window = window; p.bias_col = bias_col; p.n_wsets = n_wsets; p.n_out = n_out;
+    p.e_cols = e_cols; p.n_seq = n_frames; p.seq_per_group = frames_per_group; p.T_in = T_in; p.T = T;
+    p.transient = transient; p.group_offset = group_offset; p.W_in = W_in; p.b = b; p.W_out = W_out;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
+    return hip_fail(launch_elm_predict(precision, p, (hipStream_t)stream), who);
+}
+
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream) {
     if (!taps || !H) return fail(-1, "esn_taps_to_freq: null pointer");
     if (n_blocks <= 0 || n_sub <= 0 || n_t <= 0 || n_r <= 0 || isi <= 0 || isi > n_sub)

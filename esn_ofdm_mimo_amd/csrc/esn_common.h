@@ -186,6 +186,21 @@ struct ChanTrackParams {
     int* status;                 // [n_est]
     int n_seg, log2m2;           // set by the launcher: k ranges per sum; log2 of n_t isi rounded up to a power of two
 };
+// windowed ELM (esn_elm.hip): a random tanh layer over the last `window` input rows, a bias column, a linear read-out.
+// Sequence q belongs to group q / seq_per_group and reads weight set (group_offset + group) % n_wsets.
+struct ElmParams {
+    int n_in, n_hidden, window, bias_col, n_wsets, n_out, e_cols;
+    int n_seq, seq_per_group, T_in, T, transient;      // features: one sequence per group, transient 0
+    unsigned long long group_offset;
+    const double* W_in;          // [n_wsets][n_hidden][window n_in], window sample 0 the oldest
+    const double* b;             // [n_wsets][n_hidden]
+    const double* W_out;         // [groups][n_out][e_cols]                       (predict)
+    const double *in_scale, *in_shift;   // [groups][n_in] or nullptr
+    const double *t_scale, *t_shift;     // [groups][n_out] or nullptr             (predict)
+    const double* U;             // [n_seq][T_in][n_in]
+    double* Y;                   // [n_seq][T - transient][n_out]                 (predict)
+    void* E; int e_f32;          // [groups][T][e_cols] float64 or float32         (features)
+};
 
 // coded leg (esn_coded.hip)
 struct LdpcEncodeParams {

@@ -114,4 +114,7 @@ int launch_detect_remod(const RemodParams& rp, hipStream_t stream);
 int chantrack_segments(int n_sub, int n_t, int n_r);
 size_t chantrack_lds_bytes(int n_sub, int n_t, int n_r, int isi);
 int launch_channel_track(const ChanTrackParams& cp, hipStream_t stream);
+// esn_elm.hip: float64 features (p.E) or fused float64 / fp16 prediction (p.Y) of the windowed ELM
+int launch_elm_features(const ElmParams& p, hipStream_t stream);
+int launch_elm_predict(int precision, const ElmParams& p, hipStream_t stream);
 }  // namespace esn

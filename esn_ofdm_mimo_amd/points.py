@@ -4,7 +4,7 @@ driver's coded + uncoded ESN against LS/MMSE (coded_ber_point) and the block-fad
 through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says.
 Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, uncoded, detected symbol by symbol with its
 channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
-only."""
+only.  And elm_point: the windowed ELM (elm.py), the reference's pinv-trained comparator, on the same frames."""
 from __future__ import annotations
 
 from .frames import _view_real, summarize_channel_metrics
@@ -190,3 +190,97 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     if channel_metrics:
         out.update(summarize_channel_metrics(*src.channel_metrics(H_true, ebno_db), p.n_t, p.n_r))
     return out
+
+
+def elm_weights(n_hidden, k, gain, seed, block=None):
+    """W_in = gain U(-1, 1) [n_hidden, k], then b = U(-1, 1) [n_hidden], from RandomState(seed) -- or, for the set of
+    one global block, RandomState([seed, block])."""
+    import numpy as np
+    rs = np.random.RandomState(seed if block is None else [seed, block])
+    return gain * rs.uniform(-1, 1, (n_hidden, k)), rs.uniform(-1, 1, n_hidden)
+
+
+def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0.05, ridge=None, method="auto",
+              precision="f64", slice="aligned", weights="shared", first_block=0, seed=0, frames_per_block=None,
+              chunk_blocks=None):
+    """One Eb/No point of the windowed ELM (elm.ElmBank), the reference's pinv-trained comparator, on the frames a
+    DetectorSweep over the same FrameSource seed detects (blocks_fast with the sweep's keys, as baseline_tracking_point):
+    per chunk the pilot of every block gives one fit (inputs and teacher scaled by 1 / sqrt(var_x), transient
+    max(delay + cp, window - 1), pinv or `ridge`), then all data frames are predicted in one launch and counted by the
+    detector tail.  slice "aligned": the tail reads rows [delay + cp, + N) of the output; "reference": rows [0, N) of
+    the un-cut output, the slice the reference's ELM / FNN branches take (system_model_2_all_comparision.py:151-152,
+    :570-571), delay + cp rows early.  weights "shared": one (W_in, b) = elm_weights(seed); "per_block": one per global
+    block.  Returns (errors, bits): int64 [n_blocks] on the device; nothing is read back inside the chunk loop (a fit
+    the Cholesky solve flags has the whole point redone with method="qr" after it)."""
+    if slice not in ("aligned", "reference"):
+        raise ValueError(f"slice must be 'aligned' or 'reference', not {slice!r}")
+    if weights not in ("shared", "per_block"):
+        raise ValueError(f"weights must be 'shared' or 'per_block', not {weights!r}")
+    if precision not in ("f64", "f16"):
+        raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
+    if method not in ("auto", "qr", "chol"):
+        raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
+    if not isinstance(window, int) or not 1 <= window <= 16:
+        raise ValueError(f"window must be an integer in 1..16, not {window!r}")
+    if not isinstance(n_hidden, int) or not 1 <= n_hidden <= 1024:
+        raise ValueError(f"n_hidden must be an integer in 1..1024, not {n_hidden!r}")
+    if not gain > 0:
+        raise ValueError(f"gain = {gain} must be positive")
+    if ridge is not None and not float(ridge) >= 0:
+        raise ValueError(f"ridge = {ridge} must be None or non-negative")
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    import numpy as np
+    from .elm import ElmBank
+    torch, p = src.torch, src.p
+    n_in, n_out = 2 * p.n_r, 2 * p.n_t
+    if window * n_in > 256:
+        raise ValueError(f"window * 2 n_r = {window * n_in}: the ELM kernels serve up to 256")
+    F = int(frames_per_block or p.coherence_symbols)
+    first_block, n_blocks = int(first_block), int(n_blocks)
+    chunk = int(chunk_blocks or min(n_blocks, 4096))
+    d, T = p.delay, p.t_frame + p.delay
+    transient = max(p.forget, window - 1)
+    shared = elm_weights(n_hidden, window * n_in, gain, seed) if weights == "shared" else None
+    bank = None
+    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    flagged = torch.zeros((), dtype=torch.int64, device=src.device)
+    scale = 1.0 / np.sqrt(p.var_x(ebno_db))
+    for b0 in range(first_block, first_block + n_blocks, chunk):
+        g = min(chunk, first_block + n_blocks - b0)
+        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F)
+        if shared is None:
+            sets = [elm_weights(n_hidden, window * n_in, gain, seed, b0 + i) for i in range(g)]
+            W_in, b = np.stack([s[0] for s in sets]), np.stack([s[1] for s in sets])
+        else:
+            W_in, b = shared
+        if bank is None:
+            bank = ElmBank(n_in, n_out, n_hidden, window, W_in, b, n_groups=g, device=src.device)
+        elif shared is None:
+            bank.set_weights(W_in, b)
+        bank.set_scaling(torch.full((g, n_in), scale, dtype=torch.float64, device=src.device), None,
+                         torch.full((g, n_out), scale, dtype=torch.float64, device=src.device), None)
+        U = torch.zeros((g, T, n_in), dtype=torch.float64, device=src.device)
+        D = torch.zeros((g, T, n_out), dtype=torch.float64, device=src.device)
+        U[:, :p.t_frame] = _view_real(data["pilot_y"])
+        D[:, d:] = _view_real(data["pilot_x"])
+        bank.fit(U, D, transient=transient, method=method, ridge=ridge, repair=False)
+        flagged += bank.fit_status.ne(0).sum()
+        dy = _view_real(data["data_y"])
+        if slice == "aligned":
+            Y = bank.predict(dy, F, T=T, transient=p.forget, precision=precision)
+        else:
+            Y = bank.predict(dy, F, T=T, transient=0, precision=precision)[:, :p.n_sub].contiguous()
+        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
+        lo = b0 - first_block
+        bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g])
+    if method != "qr" and int(flagged) != 0:
+        return elm_point(src, ebno_db, snr_idx, n_blocks, n_hidden=n_hidden, window=window, gain=gain, ridge=ridge,
+                         method="qr", precision=precision, slice=slice, weights=weights, first_block=first_block,
+                         seed=seed, frames_per_block=frames_per_block, chunk_blocks=chunk_blocks)
+    return errors, nbits

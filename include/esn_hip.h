@@ -632,6 +632,47 @@ int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bi
                       const double* p_i, const double* reg,
                       double* taps, double* H, int* status, void* stream);
 
+/* ---- Windowed ELM (extension of the batched kind; the reference's pinv-trained comparator: class ELM,
+ * system_model_2_all_comparision.py:51-69, windowed as trainMIMOModel('ELM') does, :115-127, :147-149, :551-575): a random
+ * tanh layer over the last `window` input rows, a bias column, a linear read-out.  With w = window, K = w n_in, frame (or
+ * training sequence) b in group g = b / frames_per_group (features: g = b) and weight set s = (group_offset + g) % n_wsets:
+ *   us[t][i]  = U[b][t][i] in_scale[g][i] + in_shift[g][i]     0 <= t < T_in      (NULL scale / shift: 1 / 0)
+ *             = in_shift[g][i]                                 T_in <= t < T      (zero rows BEFORE scaling, as
+ *                                                                                  esn_predict_batch)
+ *   pre[t][h] = b[s][h] + sum_{k<w} sum_{i<n_in} W_in[s][h][k n_in + i] us[t-(w-1)+k][i]                     t >= w-1
+ *   row[t]    = [ tanh(pre[t][0..n_hidden)) | 1.0 if bias_col | 0.0 up to e_cols ]                           t >= w-1
+ *             = all zeros (the bias column too)                                                              t <  w-1
+ *   Ys[t][o]  = sum_c W_out[g][o][c] row[t][c]
+ *   Y[b][t-transient][o] = (Ys[t][o] - t_shift[g][o]) / t_scale[g][o]    t >= max(transient, w-1);
+ *                          exactly 0.0 for transient <= t < w-1
+ * The flat window index k n_in + i with k = 0 the oldest sample is ESN_input[j:j+w].flatten() (:118-120); only whole
+ * windows give a row (:117) and the rows before them are the reference's x_hat_temp[:window-1] = 0 (:147-148).
+ * W_in [n_wsets][n_hidden][K], b [n_wsets][n_hidden], W_out [groups][n_out][e_cols], scalings [groups][n], all float64
+ * on the device.  e_cols >= n_hidden + bias_col: the extra columns of E are written as zeros (a read-out solve takes its
+ * 16-byte path when cols % 4 == 0, float32 E, or cols % 2 == 0, float64 E; a zero column takes zero weight in the
+ * minimum-norm and ridge solutions) and the extra columns of W_out are not read.
+ * esn_elm_features  the fit side, one sequence per group: E [n_groups][T][e_cols], float64 or (e_f32) the float64 value
+ *                   rounded to float32 -- what the read-out solves take.  ESN_F64 only (ESN_F16: -2).
+ * esn_elm_predict   fused: the hidden rows never reach memory.  ESN_F64: plain FMA, every sum in an order that depends on
+ *                   the shape alone, so a frame is bitwise the same alone and inside any batch.  ESN_F16:
+ *                   v_mfma_f32_16x16x32_f16 with W_in, us, the hidden rows and W_out rounded to fp16 (from the float64
+ *                   arrays, at load: there is no packed image), float32 accumulators, bias add and tanh, and the
+ *                   un-scaling as a multiplication by 1 / t_scale in float64.
+ * ESN_F32 / ESN_BF16 return -2.  Served: 1 <= n_in, 1 <= window <= 16, K <= 256, 1 <= n_hidden <= 1024, n_out <= 8,
+ * bias_col 0 or 1, n_hidden + bias_col <= e_cols <= n_hidden + 4, 1 <= T_in <= T <= 2^20, window <= T,
+ * 0 <= transient < T, fewer than 2^31 tiles of 16 rows, E / Y 16-byte aligned; anything else returns -1 before any HIP
+ * call, the limit in esn_last_error().  There is no float32 I/O variant and no _mem front end.  These are additions: the
+ * ABI version is unchanged. */
+int esn_elm_features(int precision, int n_in, int n_hidden, int window, int bias_col, int n_wsets,
+                     const double* W_in, const double* b, const double* in_scale, const double* in_shift,
+                     const double* U, int n_groups, int T_in, int T, uint64_t group_offset,
+                     void* E, int e_f32, int e_cols, void* stream);
+int esn_elm_predict(int precision, int n_in, int n_hidden, int window, int bias_col, int n_wsets, int n_out,
+                    const double* W_in, const double* b, const double* W_out, int e_cols,
+                    const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                    const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
+                    uint64_t group_offset, double* Y, void* stream);
+
 /* ---- Channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; the 4x8 ChannelRank driver is
  * named after it), float64.  H complex [G][N][n_r][n_t] in the layout of the function above, 16-byte aligned; p_i [G]
  * on the device as in the detectors; per subcarrier k the singular values s_1 >= ... of H_k by one-sided complex
