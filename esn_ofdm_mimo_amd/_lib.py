@@ -75,6 +75,12 @@ SIGNATURES = {
                                               _dp, _dp, _dp, C.c_int, _dp, _dp, _ip, _ip, _vp, C.c_size_t, _vp]),
     "esn_readout_ridge_loo_batch_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   _dp, _dp, _dp, C.c_int, _dp, _dp, _ip, _ip, _vp, C.c_size_t, _vp]),
+    # hold-out score of the candidates W [G][L][n_out][cols] on a pilot the fit has not seen: E, D, W, n_groups, T,
+    # transient, cols, n_out, t_scale, t_shift, n_ridge, status_in, score [G][L], choice [G], stream
+    "esn_readout_holdout_score": (C.c_int, [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            _dp, _dp, C.c_int, _ip, _dp, _ip, _vp]),
+    "esn_readout_holdout_score_f32": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                _dp, _dp, C.c_int, _ip, _dp, _ip, _vp]),
     # reservoirs drawn on the device: W [S][n][n], W_in [S][n][n_in], W_fb [S][n][n_out], radius [S], status [S]
     "esn_gen_reservoirs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int,
                                      _dp, _dp, _dp, _dp, _vp]),

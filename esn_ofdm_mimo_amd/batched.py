@@ -93,7 +93,7 @@ class ReservoirBank:
         # what the last harvest / solve / fit left (device tensors; None until then, see those methods)
         self.harvest_timeout = self._cluster_err = self.last_solve_status = None
         self.last_ridge_choice = self.last_ridge_scores = self.last_ridge_status = None
-        self.last_ridge_grid = self.last_ridge_lambda = self.fit_ridge = self.fit_status = None
+        self.last_ridge_grid = self.last_ridge_lambda = self.fit_ridge = self.fit_status = self.fit_rows = None
 
     def set_weights(self, W, W_in, W_feedb):
         """Swap the weight sets: [n_res, n_res] / [n_res, n_in] / [n_res, n_out], or each with a leading [n_wsets]
@@ -408,6 +408,150 @@ class ReservoirBank:
             status = self.torch.where(ht.ne(0).expand_as(status), self.torch.full_like(status, -9), status)
         self.fit_status = status
         return E
+
+    # ------------------------------------------------------------------ several pilots per group
+    HOLDOUT_MAX_GRID = 16                     # esn_readout_holdout_score: candidates per group
+
+    def holdout_choose(self, E_val, D_val, transient, W_cand, status=None):
+        """Score the candidate read-outs W_cand [G, L, n_out, cols] (a multi-lambda solve's W_out) on rows
+        [transient, T) of a segment the fit has not seen -- E_val [G, T, cols] (float64, or float32 as
+        harvest(e_dtype="f32") writes it) and its unscaled teacher D_val [G, T, n_out] -- under this bank's teacher
+        scalings (esn_readout_holdout_score).  status: that solve's int32 [G, L], or None for all 0.  Returns
+        (scores float64 [G, L], +inf where the status is not 0 or the sum is not finite; choice int32 [G], the lowest
+        candidate with the smallest finite score, -1 if none).  Device tensors; nothing is read back."""
+        torch, n_out = self.torch, self.n_outputs
+        e32 = isinstance(E_val, torch.Tensor) and E_val.dtype == torch.float32
+        E = _as_dev(E_val, torch, self.device, torch.float32 if e32 else None)
+        D = _as_dev(D_val, torch, self.device)
+        W = _as_dev(W_cand, torch, self.device)
+        if E.ndim != 3 or W.ndim != 4:
+            raise ValueError("holdout_choose takes E_val [G, T, cols] and W_cand [G, L, n_out, cols]")
+        g, t, cols = E.shape
+        nl = W.shape[1]
+        if tuple(W.shape) != (g, nl, n_out, cols) or tuple(D.shape) != (g, t, n_out):
+            raise ValueError(f"W_cand must be [{g}, L, {n_out}, {cols}] and D_val [{g}, {t}, {n_out}], not "
+                             f"{tuple(W.shape)} and {tuple(D.shape)}")
+        if not 1 <= nl <= self.HOLDOUT_MAX_GRID:
+            raise ValueError(f"W_cand holds {nl} candidates per group, the kernel takes 1 to {self.HOLDOUT_MAX_GRID}")
+        status = _as_dev(status, torch, self.device, torch.int32)
+        if status is not None and tuple(status.shape) != (g, nl):
+            raise ValueError(f"status must be [{g}, {nl}], not {tuple(status.shape)}")
+        self._check_groups(g)
+        with torch.cuda.device(self.device):
+            if E.data_ptr() % 16:               # (a view into a larger buffer: the kernel loads 16-byte units)
+                E = E.clone()
+            if W.data_ptr() % 16:
+                W = W.clone()
+            scores = torch.empty((g, nl), dtype=torch.float64, device=self.device)
+            choice = torch.empty((g,), dtype=torch.int32, device=self.device)
+            name = "esn_readout_holdout_score_f32" if e32 else "esn_readout_holdout_score"
+            check(getattr(self.lib, name)(ptr(E), ptr(D), ptr(W), g, t, int(transient), cols, n_out, ptr(self.t_scale),
+                                          ptr(self.t_shift), nl, ptr(status), ptr(scores), ptr(choice),
+                                          _lib.stream_handle()), name)
+        return scores, choice
+
+    def _pilot_fit_method(self, u_shape, d_shape, transient, method, ridge, ridge_grid):
+        """The checks of fit_pilots that need no device, on the shapes alone; returns the solve kernel ("chol" or
+        "qr") of the stacked system."""
+        if len(u_shape) != 4 or len(d_shape) != 4 or tuple(u_shape[:3]) != tuple(d_shape[:3]):
+            raise ValueError(f"fit_pilots takes U [G, P, T, n_in] and D [G, P, T, n_out], not {tuple(u_shape)} and "
+                             f"{tuple(d_shape)}")
+        p, t = int(u_shape[1]), int(u_shape[2])
+        if p < 1 or not 0 <= int(transient) < t:
+            raise ValueError(f"need at least one pilot and 0 <= transient < T (P = {p}, transient = {transient}, T = {t})")
+        if ridge is not None and ridge_grid is not None:
+            raise ValueError("give ridge or ridge_grid, not both")
+        if ridge is not None and np.ndim(ridge) > 1:
+            raise ValueError("fit_pilots takes one lambda per group (a scalar or [G]); solve() takes [G, L]")
+        if ridge_grid is not None:
+            nl = np.shape(ridge_grid)[-1] if np.ndim(ridge_grid) else 0
+            if not 1 <= nl <= self.HOLDOUT_MAX_GRID:
+                raise ValueError(f"ridge_grid holds {nl} candidates per group, 1 to {self.HOLDOUT_MAX_GRID} are taken")
+        if method not in ("qr", "chol", "auto"):
+            raise ValueError(f"method must be 'qr', 'chol' or 'auto', not {method!r}")
+        rows, cols = p * (t - int(transient)), self.n_reservoir + self.n_inputs
+        fits = min(rows, cols) <= 512 and self.n_outputs <= 8
+        if method == "chol" and not fits:
+            raise ValueError(f"method='chol' needs min(rows, cols) <= 512 and n_outputs <= 8: {p} pilots stack to "
+                             f"{rows} rows against {cols} columns")
+        return "chol" if fits and method != "qr" else "qr"
+
+    def fit_pilots(self, U, D, transient=0, precision="f64", noise_mode="counter", noise_u=None, seed=0,
+                   method="qr", e_dtype="f64", group_offset=0, ridge=None, ridge_grid=None):
+        """fit on P pilots per group: U [G, P, T, n_in], D [G, P, T, n_out].  One harvest per pilot index p over all G
+        groups, every pilot from a zero state and under the same group_offset, so weight set, scalings and noise key
+        follow the global group as in fit; rows [transient, T) of the P results are stacked along the row axis
+        ([G, P (T - transient), cols]) and solved once.  seed: one value, or P of them (pilot p's state-noise stream;
+        with one value every pilot of a group sees the same noise).  noise_u (noise_mode="tensor"):
+        [G, P, T - 1, n_res].  Returns the stacked extended states; fit_rows keeps (them, the stacked teacher), which
+        is what resolve_failed takes with transient 0.
+
+        P = 1 is fit(), bit for bit (ridge_grid: leave-one-out).  With P >= 2, ridge_grid (at most 16 candidates, or
+        [G, L]) is chosen on a held-out pilot: the multi-lambda solve runs on pilots 0 .. P - 2, holdout_choose scores
+        every candidate on pilot P - 1 (candidates that solve flagged never win), and one solve on all P pilots at each
+        group's own winner gives W_out.  last_ridge_choice / _lambda / _scores / _grid, fit_ridge and fit_status mean
+        what they mean after the leave-one-out choice; a group without a choice gets status 1 and a zero W_out, which
+        resolve_failed(ridge_grid=...) repairs at the largest finite candidate (as it does a group whose last solve
+        was flagged).  A harvest that timed out marks every group -9, as in fit.
+
+        method: "chol" refuses a stacked shape outside min(rows, cols) <= 512; "auto" falls back to QR there.  At
+        T - transient = 128 and n_reservoir + n_inputs = 528 the Cholesky path therefore ends at P = 4 (512 rows);
+        five pilots and more are QR solves."""
+        kind = self._pilot_fit_method(np.shape(U), np.shape(D), transient, method, ridge, ridge_grid)
+        torch = self.torch
+        U = _as_dev(U, torch, self.device)
+        D = _as_dev(D, torch, self.device)
+        g, P = U.shape[0], U.shape[1]
+        seeds = [int(s) for s in seed] if np.ndim(seed) else [int(seed)] * P
+        if len(seeds) != P:
+            raise ValueError(f"seed must be one value or one per pilot ({P}), not {len(seeds)}")
+        if P == 1:
+            E = self.fit(U[:, 0], D[:, 0], transient, precision, noise_mode, None if noise_u is None else noise_u[:, 0],
+                         seeds[0], method=method, e_dtype=e_dtype, group_offset=group_offset, ridge=ridge,
+                         ridge_grid=ridge_grid)
+            self.fit_rows = (E[:, transient:], D[:, 0, transient:])
+            return self.fit_rows[0]
+        Es, timed_out = [], None
+        for p in range(P):
+            Es.append(self.harvest(U[:, p].contiguous(), D[:, p].contiguous(), precision, noise_mode,
+                                   None if noise_u is None else noise_u[:, p], seeds[p], e_dtype=e_dtype,
+                                   group_offset=group_offset))
+            ht = self.harvest_timeout
+            if ht is not None:
+                timed_out = ht.ne(0) if timed_out is None else timed_out | ht.ne(0)
+        with torch.cuda.device(self.device):
+            E_all = torch.cat([e[:, transient:] for e in Es], dim=1)
+            D_all = D[:, :, transient:].reshape(g, -1, D.shape[-1]).contiguous()
+            rows = E_all.shape[1] // P
+        if ridge_grid is None:
+            W_out, status = self.solve(E_all, D_all, 0, method=kind, ridge=ridge)
+            self.fit_ridge = ridge
+        else:
+            lam, _ = _lambdas(torch, self.device, ridge_grid, g, grid=True)
+            n_fit = (P - 1) * rows
+            W_cand, status_l = self._readout(E_all[:, :n_fit].contiguous(), D_all[:, :n_fit].contiguous(), 0, kind, lam,
+                                             self.t_scale, self.t_shift)
+            scores, choice = self.holdout_choose(Es[P - 1], D[:, P - 1].contiguous(), transient, W_cand, status_l)
+            del W_cand
+            with torch.cuda.device(self.device):
+                none = choice < 0
+                picked = lam.gather(1, choice.clamp(min=0).long()[:, None])[:, 0]
+                # (a group without a choice: solved at lambda 0 for the launch's sake, then zeroed and flagged)
+                W_out, status = self.solve(E_all, D_all, 0, method=kind, ridge=torch.where(none, torch.zeros_like(picked), picked))
+                W_out = torch.where(none[:, None, None], torch.zeros_like(W_out), W_out)
+                status = torch.where(none, torch.ones_like(status), status)
+                self.last_ridge_choice, self.last_ridge_scores, self.last_ridge_status = choice, scores, status_l
+                self.last_ridge_grid = lam
+                self.last_ridge_lambda = torch.where(none, torch.full_like(picked, float("nan")), picked)
+            self.last_solve_status = status
+            self.fit_ridge = self.last_ridge_lambda
+        self.set_readout(W_out)
+        self.harvest_timeout = None if timed_out is None else timed_out.to(torch.int32)
+        if timed_out is not None:
+            status = torch.where(timed_out.expand_as(status), torch.full_like(status, -9), status)
+        self.fit_status = status
+        self.fit_rows = (E_all, D_all)
+        return E_all
 
     # ------------------------------------------------------------------ predict
     def predict(self, U, frames_per_group, T=None, transient=0, precision="f32", x0=None, y0=None,

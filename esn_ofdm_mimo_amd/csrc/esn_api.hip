@@ -623,6 +623,36 @@ int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_group
                          score, choice, status, workspace, workspace_bytes, (hipStream_t)stream}, kLooRidge);
 }
 
+// ---- hold-out score of the candidates of a multi-lambda solve (esn_holdout.hip) -----------------------------------------
+// Null pointers, sizes, "not served", alignment -- the order of readout_call -- then the launch.
+static int holdout_call(const char* who, const HoldoutArgs& c) {
+    if ((!c.E && !c.E32) || !c.D || !c.W || !c.score || !c.choice) return fail(-1, "%s: null pointer", who);
+    if (c.n_groups <= 0 || c.T <= 0 || c.transient < 0 || c.transient >= c.T || c.cols <= 0 || c.n_out <= 0)
+        return fail(-1, "%s: invalid sizes (need n_groups, cols, n_out >= 1 and 0 <= transient < T)", who);
+    if (c.n_ridge < 1 || c.n_ridge > 16)
+        return fail(-1, "%s: n_ridge = %d, 1 to 16 candidates are served", who, c.n_ridge);
+    if (c.n_out > 8) return fail(-1, "%s: n_out = %d, at most 8 outputs are served", who, c.n_out);
+    const uintptr_t e = (uintptr_t)(c.E ? (const void*)c.E : (const void*)c.E32);
+    if ((e | (uintptr_t)c.W) & 15) return fail(-1, "%s: E and W must be 16-byte aligned", who);
+    return hip_fail(launch_holdout_score(c), who);
+}
+
+int esn_readout_holdout_score(const double* E, const double* D, const double* W, int n_groups, int T, int transient,
+                              int cols, int n_out, const double* t_scale, const double* t_shift, int n_ridge,
+                              const int* status_in, double* score, int* choice, void* stream) {
+    return holdout_call("esn_readout_holdout_score",
+                        {E, nullptr, D, W, n_groups, T, transient, cols, n_out, n_ridge, t_scale, t_shift, status_in,
+                         score, choice, (hipStream_t)stream});
+}
+
+int esn_readout_holdout_score_f32(const float* E, const double* D, const double* W, int n_groups, int T, int transient,
+                                  int cols, int n_out, const double* t_scale, const double* t_shift, int n_ridge,
+                                  const int* status_in, double* score, int* choice, void* stream) {
+    return holdout_call("esn_readout_holdout_score_f32",
+                        {nullptr, E, D, W, n_groups, T, transient, cols, n_out, n_ridge, t_scale, t_shift, status_in,
+                         score, choice, (hipStream_t)stream});
+}
+
 // ---- reservoirs drawn on the device (esn_reservoir.hip) ------------------------------------------------------------
 static const int kResMaxN = 4096;           // n_res: element counters of the draw and the tile grid stay far inside int
 

@@ -77,6 +77,15 @@ int launch_readout_chol_big(const ReadoutArgs& a);
 // doubles per group (the un-factored Gram matrix, the right-hand side and the best solution so far)
 size_t ridge_loo_work_doubles();
 int launch_ridge_loo(const ReadoutArgs& a);
+// esn_holdout.hip: the candidates W [n_groups][n_ridge][n_out][cols] of a multi-lambda solve scored on rows
+// [transient, T) of a held-out segment; exactly one of E / E32; t_scale, t_shift and status_in may be nullptr
+struct HoldoutArgs {
+    const double* E; const float* E32; const double* D; const double* W;
+    int n_groups, T, transient, cols, n_out, n_ridge;
+    const double *t_scale, *t_shift; const int* status_in;
+    double* score; int* choice; hipStream_t stream;
+};
+int launch_holdout_score(const HoldoutArgs& a);
 // esn_reservoir.hip: reservoirs drawn, measured (spectral radius by repeated squaring) and rescaled on the device; the
 // workspace holds specrad_work_doubles(n_res) doubles per matrix (two padded images, the per-tile norms, the log)
 size_t specrad_work_doubles(int n_res);

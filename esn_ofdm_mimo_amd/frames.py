@@ -81,7 +81,7 @@ class FrameSource:
                                           ptr(y_cp), _lib.stream_handle()), name)
         return bits, x_cp, y_cp
 
-    def blocks(self, ebno_db, snr_idx, block_ids, frames_per_block, with_ls_pilot=False, io="c128"):
+    def blocks(self, ebno_db, snr_idx, block_ids, frames_per_block, with_ls_pilot=False, io="c128", n_pilots=1):
         """Pilot + data frames of the given coherence blocks (any subset, any order: every block is
         generated from its own global index, so the result does not depend on the rank that asks).
         Returns pilot_y [G,T,n_r], pilot_x [G,T,n_t] (pre-PA teacher), data_y [G*F,T,n_r], data_bits."""
@@ -91,11 +91,14 @@ class FrameSource:
         for i in range(1, len(ids) + 1):
             if i == len(ids) or ids[i] != ids[i - 1] + 1:
                 runs.append((ids[start], i - start)); start = i
-        outs = [self.blocks_fast(ebno_db, snr_idx, b0, n, frames_per_block, with_ls_pilot, io) for b0, n in runs]
+        outs = [self.blocks_fast(ebno_db, snr_idx, b0, n, frames_per_block, with_ls_pilot, io, n_pilots=n_pilots)
+                for b0, n in runs]
         return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
 
+    PILOT_STREAM0 = 2                        # stream id of pilot 1 (0: pilot 0, 1: data); pilot p >= 1 has 1 + p
+
     def blocks_fast(self, ebno_db, snr_idx, first_block, n_blocks, frames_per_block, with_ls_pilot=False, io="c128",
-                    want_data_x=False):
+                    want_data_x=False, n_pilots=1):
         """Blocks first_block .. first_block + n_blocks - 1 in three launches (taps, pilots, data).
         io="c64": the DATA frames are complex64; pilots stay complex128 (training is unchanged).
         params.fading == "jakes": the taps move inside the block (taps_doppler, 1 + F symbols): the pilots pass
@@ -103,12 +106,20 @@ class FrameSource:
         per "block"; frame counters and streams are those of block fading, so bits and noise are the same for the same
         seed.  `taps` stays the pilot-instant taps [G, n_r, n_t, isi]; `taps_sym` [G, 1 + F, n_r, n_t, isi] is added.
         want_data_x: `data_x` [G F, T, n_t] is added, the pre-PA transmit signal of every data frame (what pilot_x is to
-        the pilot: the teacher a genie-aided re-fit would use)."""
-        p, F = self.p, frames_per_block
+        the pilot: the teacher a genie-aided re-fit would use).
+        n_pilots = P > 1 (an extension: the reference sends one pilot per block): pilot 0 is the pilot above, same key
+        and counter; pilot p >= 1 is one more frames() call over the block's taps under stream id 1 + p, a function of
+        (seed, Eb/No index, global block, p) alone.  The dict gains `pilots_y` [G, P, T, n_r], `pilots_x` [G, P, T, n_t],
+        `pilots_bits` [G, P, N m, n_t] and, with with_ls_pilot, `pilots_y_ls` [G, P, T, n_r]; the other keys are what
+        they are with one pilot.  Under "jakes" the block has P + F symbols: pilot p passes through symbol p and data
+        frame k through symbol P + k (`taps_sym` [G, P + F, ...])."""
+        p, F, P = self.p, frames_per_block, int(n_pilots)
+        if P < 1:
+            raise ValueError(f"n_pilots must be at least 1, not {n_pilots}")
         if p.fading == "jakes":
-            taps_sym = self.taps_doppler(n_blocks, 1 + F, snr_idx, first_block)
+            taps_sym = self.taps_doppler(n_blocks, P + F, snr_idx, first_block)
             taps = taps_sym[:, 0].contiguous()
-            data_taps, per_taps = taps_sym[:, 1:].reshape(n_blocks * F, p.n_r, p.n_t, p.isi), 1
+            data_taps, per_taps = taps_sym[:, P:].reshape(n_blocks * F, p.n_r, p.n_t, p.isi), 1
         else:
             taps_sym, taps = None, self.taps(n_blocks, snr_idx, first_block)
             data_taps, per_taps = taps, F
@@ -122,6 +133,19 @@ class FrameSource:
             out["taps_sym"] = taps_sym
         if with_ls_pilot:     # same bits, same noise, sparse pattern (driver:330-356)
             _, _, out["pilot_y_ls"] = self.frames(taps, 1, ebno_db, snr_idx, first_block, 0, ls_pattern=True)
+        if P > 1:
+            more = [(pbits, px, py, out.get("pilot_y_ls"))]
+            for q in range(1, P):
+                tq = taps if taps_sym is None else taps_sym[:, q].contiguous()
+                sid = self.PILOT_STREAM0 + q - 1
+                bq, xq, yq = self.frames(tq, 1, ebno_db, snr_idx, first_block, sid, want_x=True)
+                ls = self.frames(tq, 1, ebno_db, snr_idx, first_block, sid, ls_pattern=True)[2] if with_ls_pilot else None
+                more.append((bq, xq, yq, ls))
+            torch = self.torch
+            out["pilots_bits"], out["pilots_x"], out["pilots_y"] = (torch.stack([m[i] for m in more], dim=1)
+                                                                    for i in range(3))
+            if with_ls_pilot:
+                out["pilots_y_ls"] = torch.stack([m[3] for m in more], dim=1)
         return out
 
     # ---- baseline equaliser ------------------------------------------------------

@@ -109,7 +109,7 @@ class DetectorSweep:
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
                  rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None,
                  radius="host", radius_precision="f64", radius_squarings=24, fresh_radius_cache=True,
-                 symbol_counts=False, track=None, track_window=2):
+                 symbol_counts=False, track=None, track_window=2, n_pilots=1):
         """reservoirs: "shared" (one reservoir for every block), "per_block" (block b uses set b % pool of a pool
         drawn here) or "fresh" (the reference's own rule, SURVEY F5: every coherence block gets a reservoir of its
         own, drawn on the device by reservoirs.generate and keyed by (seed, global block index) -- the same at every
@@ -160,7 +160,17 @@ class DetectorSweep:
 
         io="f32": data frames complex64 and predict / detect with float32 I/O (same counters as "f64": the
         predict kernels see the same float inputs and write the same float outputs).  Pilots and training stay
-        float64.  Needs precision f32 / f16 / bf16."""
+        float64.  Needs precision f32 / f16 / bf16.
+
+        n_pilots (extension; 1 = the reference's one pilot per block, today's path bit for bit): every block sends P
+        pilot symbols (FrameSource.blocks_fast(n_pilots=P)) and its read-out is fitted on all of them, each harvested
+        from a zero state, rows stacked into one solve (ReservoirBank.fit_pilots).  Pilot 0 trains under
+        stream_seed(si, 0) as ever, pilot p >= 1 under stream_seed(si, PILOT_LEG0 + p).  ridge, ridge_grid,
+        solve_method, fit_precision, reservoirs and io work as with one pilot; with P >= 2 ridge_grid is chosen on the
+        held-out last pilot instead of by leave-one-out, for any stacked shape (pinv degrades as the stacked rows
+        approach the number of columns -- 4 pilots of 128 rows against 528 columns -- so give ridge or ridge_grid).
+        Not with track, train_ebno or params.continuation (ValueError): tracking and fixed-Eb/No training see one
+        pilot, and no pilot's final state is "the" training-final state."""
         if io not in ("f64", "f32"):
             raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
         if io == "f32" and precision == "f64":
@@ -178,6 +188,20 @@ class DetectorSweep:
                                      "on float64 frames of the actual Eb/No, every frame from a fresh state")
         self.track, self.track_window = track, int(track_window)
         self.keep_track_xhat, self.track_xhat = False, None
+        if int(n_pilots) != n_pilots or int(n_pilots) < 1:
+            raise ValueError(f"n_pilots must be a whole number of at least 1, not {n_pilots!r}")
+        if int(n_pilots) > 1:
+            for name, given in (("track", track is not None), ("train_ebno", train_ebno is not None),
+                                ("params.continuation", params.continuation)):
+                if given:
+                    raise ValueError(f"n_pilots={n_pilots} does not go with {name}: several pilots are fitted once, at "
+                                     "the actual Eb/No, each from a zero state")
+            if ridge is not None and ridge_grid is not None:
+                raise ValueError("give ridge or ridge_grid, not both")
+            if ridge_grid is not None and not 1 <= np.size(ridge_grid) <= ReservoirBank.HOLDOUT_MAX_GRID:
+                raise ValueError(f"ridge_grid holds {np.size(ridge_grid)} candidates, the hold-out choice takes 1 to "
+                                 f"{ReservoirBank.HOLDOUT_MAX_GRID}")
+        self.n_pilots = int(n_pilots)
         torch = _lib.require_gpu()
         self.torch, self.p = torch, params
         self.rank, self.world = rank, world_size
@@ -342,6 +366,30 @@ class DetectorSweep:
             self._cont = (E[:, -1, :self.bank.n_reservoir].double().contiguous(), y_last.contiguous())
         return E
 
+    PILOT_LEG0 = 1 << 20        # stream_seed leg of pilot p >= 1 is PILOT_LEG0 + p: beyond every leg of a tracked block
+
+    def train_pilots(self, pilots_y, pilots_x, snr_idx=0, group_offset=0):
+        """train for P pilots per block: pilots_y [G, P, T, n_r], pilots_x [G, P, T, n_t] (blocks_fast(n_pilots=P)),
+        through ReservoirBank.fit_pilots.  Returns the stacked extended states [G, P rows, cols]; fit_io becomes
+        (None, the stacked teacher, 0), which is what repair_fit needs."""
+        torch, p = self.torch, self.p
+        d = p.delay
+        g, P, t = pilots_y.shape[:3]
+        U = torch.zeros((g, P, t + d, self.n_in), dtype=torch.float64, device=self.device)
+        D = torch.zeros((g, P, t + d, self.n_out), dtype=torch.float64, device=self.device)
+        U[:, :, :t] = _view_real(pilots_y)
+        D[:, :, d:d + t] = _view_real(pilots_x)
+        rows, cols = P * (t + d - p.forget), self.bank.n_reservoir + self.n_in
+        chol = self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
+        e_dtype = self._fit_e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
+        seeds = [self.stream_seed(snr_idx, 0)] + [self.stream_seed(snr_idx, self.PILOT_LEG0 + q) for q in range(1, P)]
+        E = self.bank.fit_pilots(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
+                                 seed=seeds, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
+                                 ridge=self.ridge_at(self._ebno), ridge_grid=self._grid_t)
+        self._fit_io = (None, self.bank.fit_rows[1], 0)
+        self._cont = None
+        return E
+
     def repair_fit(self, E):
         """Host-synchronising check of the last fit: groups the Cholesky path flagged are re-solved
         with the QR kernel (GPU).  Returns how many were."""
@@ -403,7 +451,7 @@ class DetectorSweep:
         torch = self.torch
         g = len(ids)
         data = self.src.blocks_fast(ebno, si, ids[0], g, F, io="c64" if self.io == "f32" else "c128",
-                                    want_data_x=self.track == "genie")
+                                    want_data_x=self.track == "genie", n_pilots=self.n_pilots)
         self.set_snr(ebno, g, scale_ebno=self.train_ebno)
         unscaled = None
         if self.reservoirs == "fresh":      # (no host read unless `repair`: an unscalable set counts as a flagged fit)
@@ -414,7 +462,10 @@ class DetectorSweep:
             # Eb/No (:440-448)
             _, px, py = self.src.frames(data["taps"], 1, self.train_ebno, si, ids[0], 0, want_x=True)
             data["pilot_y"], data["pilot_x"] = py, px
-        E = self.train(data["pilot_y"], data["pilot_x"], seed=self.stream_seed(si, 0), group_offset=ids[0])
+        if self.n_pilots > 1:
+            E = self.train_pilots(data["pilots_y"], data["pilots_x"], snr_idx=si, group_offset=ids[0])
+        else:
+            E = self.train(data["pilot_y"], data["pilot_x"], seed=self.stream_seed(si, 0), group_offset=ids[0])
         picks = None
         if self.ridge_grid is not None:     # (before a repair: a block without a choice is in no bin)
             ch = self.bank.last_ridge_choice

@@ -384,6 +384,35 @@ int esn_readout_ridge_loo_batch_f32(const float* E, const double* D, int n_group
                                     double* W_out, double* score, int* choice, int* status,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Hold-out score of the candidates of a multi-lambda solve (an extension, like the ridge solves above: the ABI version
+ * is unchanged).  With several pilots per coherence block the read-outs W[g][l] fitted on all pilots but one are scored
+ * on the pilot left out.  For every trained ESN g and every candidate l < n_ridge, over rows [transient, T) of the
+ * held-out segment:
+ *     D_s         = D[g] * t_scale[g] + t_shift[g]                          (NULL scale / shift: 1 / 0)
+ *     r[i][o]     = sum_c E[g][i][c] * W[g][l][o][c] - D_s[i][o]
+ *     score[g][l] = sum_i sum_o r[i][o]^2                                   (scaled-teacher units, as the LOO score)
+ *     choice[g]   = the lowest l with the smallest finite score among the entries with status_in[g][l] == 0; -1 if none
+ *   E          [n_groups][T][cols], float64 (or float32 for the _f32 twin: what esn_harvest_batch_f32 writes)
+ *   D          [n_groups][T][n_out], unscaled
+ *   W          [n_groups][n_ridge][n_out][cols] float64: the W_out of esn_readout_solve_*_ridge_batch
+ *   status_in  [n_groups][n_ridge] (that solve's status), or NULL for all 0
+ *   score      [n_groups][n_ridge]: +inf where status_in is not 0 or the sum is not finite
+ *   choice     [n_groups] int32
+ * Every output element is written in every case.  A group's scores and choice are bitwise the same alone and inside
+ * any batch: the summation order is a function of the shape alone and there are no floating-point atomics.
+ * Served: n_out <= 8, 1 <= n_ridge <= 16, any cols >= 1, 0 <= transient < T, E and W 16-byte aligned; anything else
+ * returns -1 before any HIP call and esn_last_error() names the limit.  Explicit stream, no allocation, no workspace. */
+int esn_readout_holdout_score(const double* E, const double* D, const double* W, int n_groups, int T,
+                              int transient, int cols, int n_out,
+                              const double* t_scale, const double* t_shift,
+                              int n_ridge, const int* status_in,
+                              double* score, int* choice, void* stream);
+int esn_readout_holdout_score_f32(const float* E, const double* D, const double* W, int n_groups, int T,
+                                  int transient, int cols, int n_out,
+                                  const double* t_scale, const double* t_shift,
+                                  int n_ridge, const int* status_in,
+                                  double* score, int* choice, void* stream);
+
 /* Reservoirs drawn on the device (an extension: the reference draws them on the host, pyESN.py:93-109, once per
  * coherence block).  All float64, device pointers, explicit stream, no allocation; every check returns -1 before any
  * HIP call and esn_last_error() names the function and the limit.  These are additions: the ABI version is unchanged.
