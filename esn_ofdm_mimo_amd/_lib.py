@@ -81,6 +81,15 @@ SIGNATURES = {
                                             _dp, _dp, C.c_int, _ip, _dp, _ip, _vp]),
     "esn_readout_holdout_score_f32": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 _dp, _dp, C.c_int, _ip, _dp, _ip, _vp]),
+    # running normal equations: E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, decay, Gm [G][cols][cols],
+    # Cm [G][n_out][cols], stream; and Gm, Cm, n_groups, cols, n_out, ridge [G][L], n_ridge, W_out [G][L][n_out][cols],
+    # status [G][L], workspace, workspace_bytes, stream
+    "esn_gram_accumulate": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double,
+                                      _dp, _dp, _vp]),
+    "esn_gram_accumulate_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double,
+                                          _dp, _dp, _vp]),
+    "esn_gram_solve_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "esn_gram_solve": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
     # reservoirs drawn on the device: W [S][n][n], W_in [S][n][n_in], W_fb [S][n][n_out], radius [S], status [S]
     "esn_gen_reservoirs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int,
                                      _dp, _dp, _dp, _dp, _vp]),

@@ -60,6 +60,16 @@ def _lambdas(torch, device, lam, g, grid=False):
     return r.contiguous(), flat
 
 
+class GramState:
+    """A read-out kept as running normal equations (ReservoirBank.gram_accumulate): G [groups, cols, cols] and
+    C [groups, n_out, cols], float64 on the device, and the teacher scalings (t_scale, t_shift: [groups, n_out] or None)
+    every segment was accumulated under.  Its size does not depend on the number of segments it has seen."""
+    __slots__ = ("G", "C", "t_scale", "t_shift")
+
+    def __init__(self, G, C, t_scale, t_shift):
+        self.G, self.C, self.t_scale, self.t_shift = G, C, t_scale, t_shift
+
+
 class ReservoirBank:
     def __init__(self, n_inputs, n_outputs, n_reservoir, W, W_in, W_feedb,
                  teacher_forcing=True, noise=0.001, device=None, leak_rate=1.0):
@@ -94,6 +104,7 @@ class ReservoirBank:
         self.harvest_timeout = self._cluster_err = self.last_solve_status = None
         self.last_ridge_choice = self.last_ridge_scores = self.last_ridge_status = None
         self.last_ridge_grid = self.last_ridge_lambda = self.fit_ridge = self.fit_status = self.fit_rows = None
+        self.gram_state = None                  # fit_pilots(method="gram"): the GramState behind W_out
 
     def set_weights(self, W, W_in, W_feedb):
         """Swap the weight sets: [n_res, n_res] / [n_res, n_in] / [n_res, n_out], or each with a leading [n_wsets]
@@ -409,6 +420,126 @@ class ReservoirBank:
         self.fit_status = status
         return E
 
+    # ------------------------------------------------------------------ running normal equations
+    GRAM_MAX_COLS, GRAM_MAX_GRID, GRAM_MAX_OUT = 544, 16, 16      # esn_gram_accumulate / esn_gram_solve
+
+    def gram_accumulate(self, E, D, transient, state=None, decay=1.0):
+        """One training segment into a read-out kept as running normal equations (esn_gram_accumulate): over rows
+        [transient, T) of E [G, T, cols] (float64, or float32 as harvest(e_dtype="f32") writes it) and the unscaled
+        teacher D [G, T, n_out],  G <- decay G + E^T E,  C <- decay C + D_s^T E.  state None: a new GramState under
+        this bank's teacher scalings, started with decay 0 (`decay` is not read).  Otherwise `state` is updated in
+        place, under the scalings it was started with, and returned; decay in [0, 1] is the forgetting factor, and
+        decay 0 starts the sum again without reading what the state held.  Nothing is read back."""
+        torch, n_out = self.torch, self.n_outputs
+        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32
+        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
+        D = _as_dev(D, torch, self.device)
+        if E.ndim != 3 or tuple(D.shape) != (E.shape[0], E.shape[1], n_out):
+            raise ValueError(f"gram_accumulate takes E [G, T, cols] and D [G, T, {n_out}], not {tuple(E.shape)} and "
+                             f"{tuple(D.shape)}")
+        g, t, cols = E.shape
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"decay must lie in [0, 1], not {decay}")
+        with torch.cuda.device(self.device):
+            if state is None:
+                self._check_groups(g)
+                state = GramState(torch.empty((g, cols, cols), dtype=torch.float64, device=self.device),
+                                  torch.empty((g, n_out, cols), dtype=torch.float64, device=self.device),
+                                  None if self.t_scale is None else self.t_scale[:g],
+                                  None if self.t_shift is None else self.t_shift[:g])
+                decay = 0.0
+            elif tuple(state.G.shape) != (g, cols, cols) or tuple(state.C.shape) != (g, n_out, cols):
+                raise ValueError(f"the state holds G {tuple(state.G.shape)} and C {tuple(state.C.shape)}, the segment "
+                                 f"needs [{g}, {cols}, {cols}] and [{g}, {n_out}, {cols}]")
+            if E.data_ptr() % 16:               # (a view into a larger buffer: the kernel loads 16-byte units)
+                E = E.clone()
+            name = "esn_gram_accumulate_f32" if e32 else "esn_gram_accumulate"
+            check(getattr(self.lib, name)(ptr(E), ptr(D), g, t, int(transient), cols, n_out, ptr(state.t_scale),
+                                          ptr(state.t_shift), float(decay), ptr(state.G), ptr(state.C),
+                                          _lib.stream_handle()), name)
+        return state
+
+    def gram_solve(self, state, ridge):
+        """(G + lambda I) W^T = C^T for the groups of a GramState (esn_gram_solve): the ridge read-out of every row the
+        state has seen, weighted by its forgetting.  ridge as in solve: a scalar or [G] gives (W_out [G, n_out, cols],
+        status [G]); [G, L] (L <= 16) solves L lambdas per group from the one G and gives W_out [G, L, n_out, cols] and
+        status [G, L].  status 1: a pivot was rejected, that entry's W_out is zero (nothing is repaired: the state
+        keeps no rows); 2: a negative or non-finite lambda.  The state is only read."""
+        torch = self.torch
+        g, n_out, cols = state.C.shape
+        lam, flat = _lambdas(torch, self.device, ridge, g)
+        nl = lam.shape[1]
+        if not 1 <= nl <= self.GRAM_MAX_GRID:
+            raise ValueError(f"ridge holds {nl} candidates per group, the kernel takes 1 to {self.GRAM_MAX_GRID}")
+        with torch.cuda.device(self.device):
+            W_out = torch.empty((g, nl, n_out, cols), dtype=torch.float64, device=self.device)
+            status = torch.empty((g, nl), dtype=torch.int32, device=self.device)
+            wbytes = self.lib.esn_gram_solve_workspace_bytes(g, nl, cols)
+            ws = self._scratch("_gram_ws", max(wbytes, 16))
+            check(self.lib.esn_gram_solve(ptr(state.G), ptr(state.C), g, cols, n_out, ptr(lam), nl, ptr(W_out),
+                                          ptr(status), ptr(ws), wbytes, _lib.stream_handle()), "esn_gram_solve")
+        if flat:
+            W_out, status = W_out[:, 0], status[:, 0]
+        self.last_solve_status = status
+        return W_out, status
+
+    def _fit_pilots_gram(self, U, D, transient, precision, noise_mode, noise_u, seed, e_dtype, group_offset, ridge,
+                         ridge_grid):
+        """fit_pilots(method="gram"): one harvest and one gram_accumulate per pilot, no stacked rows."""
+        self._pilot_fit_method(np.shape(U), np.shape(D), transient, "qr", ridge, ridge_grid)      # (the shape checks)
+        if ridge is None and ridge_grid is None:
+            raise ValueError("method='gram' needs ridge or ridge_grid: with fewer rows than columns the normal "
+                             "equations have no pinv solution")
+        torch = self.torch
+        U = _as_dev(U, torch, self.device)
+        D = _as_dev(D, torch, self.device)
+        g, P = U.shape[0], U.shape[1]
+        if ridge_grid is not None and P < 2:
+            raise ValueError("method='gram' chooses among ridge_grid on a held-out pilot: it needs at least two pilots")
+        seeds = [int(s) for s in seed] if np.ndim(seed) else [int(seed)] * P
+        if len(seeds) != P:
+            raise ValueError(f"seed must be one value or one per pilot ({P}), not {len(seeds)}")
+        state, timed_out, E = None, None, None
+        for p in range(P):
+            D_p = D[:, p].contiguous()
+            E = self.harvest(U[:, p].contiguous(), D_p, precision, noise_mode,
+                             None if noise_u is None else noise_u[:, p], seeds[p], e_dtype=e_dtype,
+                             group_offset=group_offset)
+            ht = self.harvest_timeout
+            if ht is not None:
+                timed_out = ht.ne(0) if timed_out is None else timed_out | ht.ne(0)
+            if ridge_grid is not None and p == P - 1:
+                # the candidates from pilots 0 .. P - 2, all out of the one G, scored on pilot P - 1 before it goes in
+                lam, _ = _lambdas(torch, self.device, ridge_grid, g, grid=True)
+                W_cand, status_l = self.gram_solve(state, lam)
+                scores, choice = self.holdout_choose(E, D_p, transient, W_cand, status_l)
+                del W_cand
+            state = self.gram_accumulate(E, D_p, transient, state, 1.0)
+        with torch.cuda.device(self.device):
+            if ridge_grid is None:
+                W_out, status = self.gram_solve(state, ridge)
+                self.fit_ridge = ridge
+            else:
+                none = choice < 0
+                picked = lam.gather(1, choice.clamp(min=0).long()[:, None])[:, 0]
+                # (a group without a choice: solved at lambda 0 for the launch's sake, then zeroed and flagged)
+                W_out, status = self.gram_solve(state, torch.where(none, torch.zeros_like(picked), picked))
+                W_out = torch.where(none[:, None, None], torch.zeros_like(W_out), W_out)
+                status = torch.where(none, torch.ones_like(status), status)
+                self.last_ridge_choice, self.last_ridge_scores, self.last_ridge_status = choice, scores, status_l
+                self.last_ridge_grid = lam
+                self.last_ridge_lambda = torch.where(none, torch.full_like(picked, float("nan")), picked)
+                self.last_solve_status = status
+                self.fit_ridge = self.last_ridge_lambda
+        self.set_readout(W_out)
+        self.harvest_timeout = None if timed_out is None else timed_out.to(torch.int32)
+        if timed_out is not None:
+            status = torch.where(timed_out.expand_as(status), torch.full_like(status, -9), status)
+        self.fit_status = status
+        self.fit_rows = None
+        self.gram_state = state
+        return state
+
     # ------------------------------------------------------------------ several pilots per group
     HOLDOUT_MAX_GRID = 16                     # esn_readout_holdout_score: candidates per group
 
@@ -496,7 +627,17 @@ class ReservoirBank:
 
         method: "chol" refuses a stacked shape outside min(rows, cols) <= 512; "auto" falls back to QR there.  At
         T - transient = 128 and n_reservoir + n_inputs = 528 the Cholesky path therefore ends at P = 4 (512 rows);
-        five pilots and more are QR solves."""
+        five pilots and more are QR solves.
+
+        method "gram" (needs ridge or ridge_grid; any P >= 1, ridge_grid from P = 2): the primal form.  Every pilot is
+        harvested and accumulated into one GramState (gram_accumulate), so no rows are stacked and P is not bounded by
+        a kernel's shape.  With ridge_grid the L candidates are solved out of the one G of pilots 0 .. P - 2, scored by
+        holdout_choose on pilot P - 1, that pilot is accumulated into the same state and one solve at each group's
+        winner gives W_out.  Returns the GramState, which gram_state keeps; fit_rows is None (no rows exist, and a
+        flagged group cannot be repaired by resolve_failed)."""
+        if method == "gram":
+            return self._fit_pilots_gram(U, D, transient, precision, noise_mode, noise_u, seed, e_dtype, group_offset,
+                                         ridge, ridge_grid)
         kind = self._pilot_fit_method(np.shape(U), np.shape(D), transient, method, ridge, ridge_grid)
         torch = self.torch
         U = _as_dev(U, torch, self.device)

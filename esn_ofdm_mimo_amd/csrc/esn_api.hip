@@ -653,6 +653,57 @@ int esn_readout_holdout_score_f32(const float* E, const double* D, const double*
                          score, choice, (hipStream_t)stream});
 }
 
+// ---- running normal equations (esn_gram.hip) ----------------------------------------------------------------------------
+// Null pointers, sizes, "not served", workspace size, alignment -- the order of readout_call -- then the launch.
+static int gram_accumulate_call(const char* who, const GramAccArgs& c) {
+    if ((!c.E && !c.E32) || !c.D || !c.Gm || !c.Cm) return fail(-1, "%s: null pointer", who);
+    if (c.n_groups <= 0 || c.T <= 0 || c.transient < 0 || c.transient >= c.T || c.cols <= 0 || c.n_out <= 0)
+        return fail(-1, "%s: invalid sizes (need n_groups, cols, n_out >= 1 and 0 <= transient < T)", who);
+    if (!(c.decay >= 0.0 && c.decay <= 1.0)) return fail(-1, "%s: decay = %g, it must lie in [0, 1]", who, c.decay);
+    if (c.n_out > 16) return fail(-1, "%s: n_out = %d, at most 16 outputs are served", who, c.n_out);
+    if (c.cols > gram_max_cols()) return fail(-2, "%s: cols = %d, the limit is %d", who, c.cols, gram_max_cols());
+    const uintptr_t e = (uintptr_t)(c.E ? (const void*)c.E : (const void*)c.E32);
+    if (e & 15) return fail(-1, "%s: E must be 16-byte aligned", who);
+    return hip_fail(launch_gram_accumulate(c), who);
+}
+
+int esn_gram_accumulate(const double* E, const double* D, int n_groups, int T, int transient, int cols, int n_out,
+                        const double* t_scale, const double* t_shift, double decay, double* Gm, double* Cm,
+                        void* stream) {
+    return gram_accumulate_call("esn_gram_accumulate", {E, nullptr, D, n_groups, T, transient, cols, n_out, t_scale,
+                                                        t_shift, decay, Gm, Cm, (hipStream_t)stream});
+}
+
+int esn_gram_accumulate_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols, int n_out,
+                            const double* t_scale, const double* t_shift, double decay, double* Gm, double* Cm,
+                            void* stream) {
+    return gram_accumulate_call("esn_gram_accumulate_f32", {nullptr, E, D, n_groups, T, transient, cols, n_out, t_scale,
+                                                            t_shift, decay, Gm, Cm, (hipStream_t)stream});
+}
+
+size_t esn_gram_solve_workspace_bytes(int n_groups, int n_ridge, int cols) {
+    if (n_groups <= 0 || n_ridge <= 0 || cols <= 0 || cols > gram_max_cols()) return 0;
+    return sizeof(double) * gram_solve_work_doubles(cols) * (size_t)n_groups;      // one factor per group, any n_ridge
+}
+
+int esn_gram_solve(const double* Gm, const double* Cm, int n_groups, int cols, int n_out, const double* ridge,
+                   int n_ridge, double* W_out, int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "esn_gram_solve";
+    if (!Gm || !Cm || !ridge || !W_out || !status || !workspace) return fail(-1, "%s: null pointer", who);
+    if (n_groups <= 0 || cols <= 0 || n_out <= 0)
+        return fail(-1, "%s: invalid sizes (need n_groups, cols, n_out >= 1)", who);
+    if (n_ridge < 1 || n_ridge > 16) return fail(-1, "%s: n_ridge = %d, 1 to 16 candidates are served", who, n_ridge);
+    if (n_out > 16) return fail(-1, "%s: n_out = %d, at most 16 outputs are served", who, n_out);
+    if (cols > gram_max_cols()) return fail(-2, "%s: cols = %d, the limit is %d", who, cols, gram_max_cols());
+    const size_t need = esn_gram_solve_workspace_bytes(n_groups, n_ridge, cols);
+    if (workspace_bytes < need)
+        return fail(-1, "%s: workspace holds %zu bytes, esn_gram_solve_workspace_bytes says %zu", who, workspace_bytes,
+                    need);
+    if ((uintptr_t)workspace & 15) return fail(-1, "%s: the workspace must be 16-byte aligned", who);
+    return hip_fail(launch_gram_solve({Gm, Cm, n_groups, cols, n_out, ridge, n_ridge, W_out, status, workspace,
+                                       workspace_bytes, (hipStream_t)stream}), who);
+}
+
 // ---- reservoirs drawn on the device (esn_reservoir.hip) ------------------------------------------------------------
 static const int kResMaxN = 4096;           // n_res: element counters of the draw and the tile grid stay far inside int
 

@@ -86,6 +86,24 @@ struct HoldoutArgs {
     double* score; int* choice; hipStream_t stream;
 };
 int launch_holdout_score(const HoldoutArgs& a);
+// esn_gram.hip: running normal equations.  Gm [n_groups][cols][cols] <- decay Gm + E^T E and Cm [n_groups][n_out][cols]
+// <- decay Cm + D_s^T E over rows [transient, T), exactly one of E / E32; and (Gm + lambda I) W^T = Cm^T for n_ridge
+// lambdas per group out of one factor buffer of gram_solve_work_doubles(cols) doubles per group
+struct GramAccArgs {
+    const double* E; const float* E32; const double* D;
+    int n_groups, T, transient, cols, n_out;
+    const double *t_scale, *t_shift; double decay;
+    double *Gm, *Cm; hipStream_t stream;
+};
+struct GramSolveArgs {
+    const double *Gm, *Cm; int n_groups, cols, n_out;
+    const double* ridge; int n_ridge;
+    double* W_out; int* status; void* workspace; size_t workspace_bytes; hipStream_t stream;
+};
+int gram_max_cols();
+size_t gram_solve_work_doubles(int cols);
+int launch_gram_accumulate(const GramAccArgs& a);
+int launch_gram_solve(const GramSolveArgs& a);
 // esn_reservoir.hip: reservoirs drawn, measured (spectral radius by repeated squaring) and rescaled on the device; the
 // workspace holds specrad_work_doubles(n_res) doubles per matrix (two padded images, the per-tile norms, the log)
 size_t specrad_work_doubles(int n_res);

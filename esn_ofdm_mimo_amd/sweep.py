@@ -109,7 +109,7 @@ class DetectorSweep:
                  seed=0, precision="f32", fit_precision="f64", reservoirs="shared", pool=8, device=None,
                  rank=0, world_size=1, solve_method="auto", train_ebno=None, io="f64", ridge=None, ridge_grid=None,
                  radius="host", radius_precision="f64", radius_squarings=24, fresh_radius_cache=True,
-                 symbol_counts=False, track=None, track_window=2, n_pilots=1):
+                 symbol_counts=False, track=None, track_window=2, n_pilots=1, track_forget=1.0):
         """reservoirs: "shared" (one reservoir for every block), "per_block" (block b uses set b % pool of a pool
         drawn here) or "fresh" (the reference's own rule, SURVEY F5: every coherence block gets a reservoir of its
         own, drawn on the device by reservoirs.generate and keyed by (seed, global block index) -- the same at every
@@ -170,18 +170,37 @@ class DetectorSweep:
         held-out last pilot instead of by leave-one-out, for any stacked shape (pinv degrades as the stacked rows
         approach the number of columns -- 4 pilots of 128 rows against 528 columns -- so give ridge or ridge_grid).
         Not with track, train_ebno or params.continuation (ValueError): tracking and fixed-Eb/No training see one
-        pilot, and no pilot's final state is "the" training-final state."""
+        pilot, and no pilot's final state is "the" training-final state.
+
+        solve_method="gram" (extension; needs ridge or ridge_grid): the read-out is kept as running normal equations
+        (ReservoirBank.fit_pilots(method="gram"), gram_accumulate, gram_solve), whose size does not depend on the number
+        of pilots or symbols seen.  Without track: any n_pilots on the device path, ridge_grid (chosen on the held-out
+        last pilot) from n_pilots = 2.  With track: allowed together with n_pilots >= 1 and, from n_pilots = 2, with
+        ridge_grid -- the hold-out choice is made once, at the pilot fit, and each block keeps its lambda for every
+        re-fit.  After data symbol k the frame is harvested, accumulated into the block's state with decay
+        track_forget (in [0, 1], default 1.0: nothing is forgotten; 0: every re-fit sees the newest symbol alone) and the
+        read-out solved again at the block's lambda; track_window is not read in this mode.  A flagged re-fit keeps the
+        block's previous read-out (a device-side select, no host read) and adds to the chunk's flagged count; no rows
+        are kept, so nothing is repaired by QR and fits_repaired then counts fits that stayed flagged.  Stream seeds,
+        state-noise legs and keys are those of the other solve methods.  train_ebno, params.continuation and io="f32"
+        stay refused with track, and so does ridge_grid with one pilot; params.continuation is refused in this mode at
+        any n_pilots (every pilot is fitted from a zero state: no training-final state exists)."""
         if io not in ("f64", "f32"):
             raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
         if io == "f32" and precision == "f64":
             raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
         self.io = io
+        gram = solve_method == "gram"
+        if not 0.0 <= float(track_forget) <= 1.0:
+            raise ValueError(f"track_forget must lie in [0, 1], not {track_forget}")
+        self.track_forget = float(track_forget)
         if track not in (None, "decisions", "genie"):
             raise ValueError(f"track must be None, 'decisions' or 'genie', not {track!r}")
         if track is not None:
             if int(track_window) < 1:
                 raise ValueError(f"track_window must be at least 1 (the training sets a re-fit sees), not {track_window}")
-            for name, given in (("ridge_grid", ridge_grid is not None), ("train_ebno", train_ebno is not None),
+            grid_refused = ridge_grid is not None and not (gram and int(n_pilots) >= 2)
+            for name, given in (("ridge_grid", grid_refused), ("train_ebno", train_ebno is not None),
                                 ("params.continuation", params.continuation), ("io='f32'", io == "f32")):
                 if given:
                     raise ValueError(f"track={track!r} does not go with {name}: the re-fits are plain pinv / ridge solves "
@@ -190,8 +209,16 @@ class DetectorSweep:
         self.keep_track_xhat, self.track_xhat = False, None
         if int(n_pilots) != n_pilots or int(n_pilots) < 1:
             raise ValueError(f"n_pilots must be a whole number of at least 1, not {n_pilots!r}")
+        if gram and ridge is None and ridge_grid is None:
+            raise ValueError("solve_method='gram' needs ridge or ridge_grid: the normal equations of fewer rows than "
+                             "columns have no pinv solution")
+        if gram and ridge_grid is not None and int(n_pilots) == 1:
+            raise ValueError("solve_method='gram' chooses among ridge_grid on a held-out pilot: it needs n_pilots >= 2")
+        if gram and params.continuation:
+            raise ValueError("solve_method='gram' does not go with params.continuation: every pilot is fitted from a zero "
+                             "state and no training-final state is kept")
         if int(n_pilots) > 1:
-            for name, given in (("track", track is not None), ("train_ebno", train_ebno is not None),
+            for name, given in (("track", track is not None and not gram), ("train_ebno", train_ebno is not None),
                                 ("params.continuation", params.continuation)):
                 if given:
                     raise ValueError(f"n_pilots={n_pilots} does not go with {name}: several pilots are fitted once, at "
@@ -380,13 +407,14 @@ class DetectorSweep:
         U[:, :, :t] = _view_real(pilots_y)
         D[:, :, d:d + t] = _view_real(pilots_x)
         rows, cols = P * (t + d - p.forget), self.bank.n_reservoir + self.n_in
-        chol = self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
+        gram = self.solve_method == "gram"          # (the accumulate kernel reads float32 states as the Cholesky ones do)
+        chol = gram or self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
         e_dtype = self._fit_e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
         seeds = [self.stream_seed(snr_idx, 0)] + [self.stream_seed(snr_idx, self.PILOT_LEG0 + q) for q in range(1, P)]
         E = self.bank.fit_pilots(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
                                  seed=seeds, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
                                  ridge=self.ridge_at(self._ebno), ridge_grid=self._grid_t)
-        self._fit_io = (None, self.bank.fit_rows[1], 0)
+        self._fit_io = (None, None if gram else self.bank.fit_rows[1], 0)       # ("gram" keeps no rows)
         self._cont = None
         return E
 
@@ -427,7 +455,15 @@ class DetectorSweep:
         chunk = max(1, (5 * info["cu_count"] * tile) // fpad)
         if self.reservoirs == "fresh":      # one reservoir per block lives on the device for the length of a chunk
             chunk = min(chunk, max(1, self.FRESH_BUDGET_BYTES // (self.FRESH_BYTES_PER_BLOCK_N2 * self.n_res ** 2)))
+        if self.solve_method == "gram":     # a block's G, C and the factor of its solve live for the length of a chunk
+            cols = self.n_res + self.n_in
+            per_block = 8 * (cols * cols + self.n_out * cols + ((cols + 15) // 16 * 16) ** 2)
+            chunk = min(chunk, max(1, self.GRAM_BUDGET_BYTES // per_block))
         return chunk
+
+    # solve_method="gram": state (8 cols^2 + 8 n_out cols bytes) plus solve workspace (8 ceil16(cols)^2) per block of a
+    # chunk -- 4.5 MB at 528 columns -- are held to this budget (about 950 blocks there), whatever the candidates
+    GRAM_BUDGET_BYTES = 4 << 30
 
     def _flagged_fits(self, unscaled, repair):
         """How many fits of the chunk just trained cannot be trusted, an int64 scalar on the device: the groups the
@@ -462,7 +498,10 @@ class DetectorSweep:
             # Eb/No (:440-448)
             _, px, py = self.src.frames(data["taps"], 1, self.train_ebno, si, ids[0], 0, want_x=True)
             data["pilot_y"], data["pilot_x"] = py, px
-        if self.n_pilots > 1:
+        gram = self.solve_method == "gram"
+        if gram and self.n_pilots == 1:     # (one pilot goes the same way: fit_pilots(method="gram") takes any P)
+            E = self.train_pilots(data["pilot_y"][:, None], data["pilot_x"][:, None], snr_idx=si, group_offset=ids[0])
+        elif self.n_pilots > 1:
             E = self.train_pilots(data["pilots_y"], data["pilots_x"], snr_idx=si, group_offset=ids[0])
         else:
             E = self.train(data["pilot_y"], data["pilot_x"], seed=self.stream_seed(si, 0), group_offset=ids[0])
@@ -471,10 +510,11 @@ class DetectorSweep:
             ch = self.bank.last_ridge_choice
             picks = torch.bincount(ch.clamp(min=0).long(), weights=ch.ge(0).double(),
                                    minlength=len(self.ridge_grid)).to(torch.int64)
-        if repair:
+        if repair and not gram:             # ("gram" keeps no rows to solve again: a flagged fit stays flagged)
             self.repair_fit(E)
         if self.track is not None:
-            err, nb, flagged = self._chunk_tracked(ebno, si, ids, F, data, E, self._flagged_fits(unscaled, repair), repair)
+            tracked = self._chunk_tracked_gram if gram else self._chunk_tracked
+            err, nb, flagged = tracked(ebno, si, ids, F, data, E, self._flagged_fits(unscaled, repair), repair)
             per_symbol = torch.stack([err.sum(dim=1), nb.sum(dim=1)], dim=1) if self.symbol_counts else None
             return ChunkLayout.pack(torch, err.sum(), nb.sum(), flagged, picks, per_symbol)
         n_cnt = g * F if self.symbol_counts else g
@@ -487,14 +527,15 @@ class DetectorSweep:
             per_symbol = torch.stack([err.view(g, F).sum(dim=0), nb.view(g, F).sum(dim=0)], dim=1)
         return ChunkLayout.pack(torch, err.sum(), nb.sum(), self._flagged_fits(unscaled, repair), picks, per_symbol)
 
-    def _chunk_tracked(self, ebno, si, ids, F, data, E, flagged, repair):
-        """The data symbols of a chunk under `track`, after the pilot fit (E: its extended states; `flagged`: its
-        flagged-fit count): for k = 0 .. F - 1 predict and detect symbol k of every block with the current read-outs,
-        harvest it against the teacher, solve over the window, swap the read-outs in.  Returns (err [F, G], bits [F, G],
-        flagged + the flagged re-fits); `repair` re-solves flagged re-fits by QR on the spot (host reads)."""
+    def _track_symbols(self, ebno, si, ids, F, data, flagged, repair, refit):
+        """The per-symbol loop both tracked modes share: for k = 0 .. F - 1 predict and detect symbol k of every block
+        with the current read-outs and, unless it is the last, harvest it against the teacher (the re-modulated
+        decisions, or for "genie" the transmit signal) and hand the states to `refit(Ek, D_hat, flagged) -> flagged`,
+        which solves the read-outs again and swaps them in.  Symbol k detects under stream_seed(si, 2 + 2 k) and
+        re-trains under stream_seed(si, 3 + 2 k).  Returns (err [F, G], bits [F, G], flagged); `repair` raises for a
+        harvest that timed out instead of counting it."""
         torch, p, bank = self.torch, self.p, self.bank
-        g, d, T = len(ids), p.delay, p.t_frame
-        U0, D0, forget = self._fit_io
+        g, d, T, forget = len(ids), p.delay, p.t_frame, p.forget
         y_sym = _view_real(data["data_y"]).view(g, F, T, self.n_in)
         bits_sym = data["data_bits"].view(g, F, p.n_sub * p.m, p.n_t)
         x_sym = _view_real(data["data_x"]).view(g, F, T, self.n_out) if self.track == "genie" else None
@@ -502,8 +543,7 @@ class DetectorSweep:
         nb = torch.zeros((F, g), dtype=torch.int64, device=self.device)
         U = torch.zeros((g, T + d, self.n_in), dtype=torch.float64, device=self.device)       # d trailing zero rows
         D_true = torch.zeros((g, T + d, self.n_out), dtype=torch.float64, device=self.device) if x_sym is not None else None
-        window = [(E[:, forget:], D0[:, forget:].clone())]        # (the pilot buffers are reused by the next chunk)
-        ridge, xhats = self.ridge_at(ebno), []
+        xhats = []
         for k in range(F):
             y = bank.predict(y_sym[:, k], 1, T=T + d, transient=forget, precision=self.precision, noise_mode="counter",
                              seed=self.stream_seed(si, 2 + 2 * k), group_offset=ids[0])
@@ -517,14 +557,30 @@ class DetectorSweep:
             U[:, :T] = y_sym[:, k]
             if x_sym is not None:
                 D_true[:, d:d + T] = x_sym[:, k]
-                D_hat = D_true.clone()
+                D_hat = D_true.clone()              # (a window of training sets keeps it beyond this symbol)
             Ek = bank.harvest(U, D_hat, precision=self.fit_precision, noise_mode="counter",
                               seed=self.stream_seed(si, 3 + 2 * k), e_dtype=self._fit_e_dtype, group_offset=ids[0])
             if repair:
                 bank.raise_if_harvest_timed_out()
             elif bank.harvest_timeout is not None:
                 flagged = flagged + bank.harvest_timeout.ne(0).sum().to(torch.int64)
-            window = (window + [(Ek[:, forget:], D_hat[:, forget:])])[-self.track_window:]
+            flagged = refit(Ek, D_hat, flagged)
+        if self.keep_track_xhat:
+            self.track_xhat = torch.stack(xhats)
+        return err, nb, flagged
+
+    def _chunk_tracked(self, ebno, si, ids, F, data, E, flagged, repair):
+        """The data symbols of a chunk under `track`, after the pilot fit (E: its extended states; `flagged`: its
+        flagged-fit count), through _track_symbols: every re-fit solves over the window of the most recent training
+        sets.  Returns (err [F, G], bits [F, G], flagged + the flagged re-fits); `repair` re-solves flagged re-fits by QR
+        on the spot (host reads)."""
+        torch, bank = self.torch, self.bank
+        U0, D0, forget = self._fit_io
+        window = [(E[:, forget:], D0[:, forget:].clone())]        # (the pilot buffers are reused by the next chunk)
+        ridge = self.ridge_at(ebno)
+
+        def refit(Ek, D_hat, flagged):
+            window[:] = (window + [(Ek[:, forget:], D_hat[:, forget:])])[-self.track_window:]
             E_w, D_w = (torch.cat([w[i] for w in window], dim=1) for i in (0, 1))
             W_out, status = bank.solve(E_w, D_w, 0, method=self.solve_method, ridge=ridge)
             if repair:
@@ -532,9 +588,27 @@ class DetectorSweep:
             else:
                 flagged = flagged + status.ne(0).sum().to(torch.int64)
             bank.set_readout(W_out)
-        if self.keep_track_xhat:
-            self.track_xhat = torch.stack(xhats)
-        return err, nb, flagged
+            return flagged
+
+        return self._track_symbols(ebno, si, ids, F, data, flagged, repair, refit)
+
+    def _chunk_tracked_gram(self, ebno, si, ids, F, data, state, flagged, repair):
+        """_chunk_tracked for solve_method="gram": `state` is the GramState the pilot fit left.  Every re-fit accumulates
+        the symbol's states into it with decay track_forget and solves at the block's own lambda (the ridge of the
+        sweep, or the hold-out choice of the pilot fit); a flagged re-fit keeps the block's previous read-out and is
+        counted."""
+        torch, bank, forget = self.torch, self.bank, self.p.forget
+        # (a block without a hold-out choice carries NaN: its re-fits answer status 2 and its zero read-out stays)
+        lam = bank.fit_ridge if self.ridge_grid is not None else self.ridge_at(ebno)
+
+        def refit(Ek, D_hat, flagged):
+            bank.gram_accumulate(Ek, D_hat, forget, state, self.track_forget)
+            W_new, status = bank.gram_solve(state, lam)
+            bad = status.ne(0)
+            bank.set_readout(torch.where(bad[:, None, None], bank.W_out, W_new))
+            return flagged + bad.sum().to(torch.int64)
+
+        return self._track_symbols(ebno, si, ids, F, data, flagged, repair, refit)
 
     def run(self, ebno_list, blocks_per_snr, frames_per_block=None, chunk_blocks=None, dist=None):
         """Returns (BER[n_snr], counters [n_snr, 2]) -- identical on every rank and for every world size and

@@ -413,6 +413,43 @@ int esn_readout_holdout_score_f32(const float* E, const double* D, const double*
                                   int n_ridge, const int* status_in,
                                   double* score, int* choice, void* stream);
 
+/* Running normal equations: the primal form of the ridge fit (an extension, like the ridge solves above: the ABI version
+ * is unchanged).  A read-out is kept as
+ *     Gm[g] = sum_s gamma^age(s) E_s^T E_s        [cols][cols]   float64, symmetric, both triangles stored
+ *     Cm[g] = sum_s gamma^age(s) D_s^T E_s        [n_out][cols]  float64
+ * over the training segments s it has seen; its size does not depend on their number.  esn_gram_accumulate adds one
+ * segment, rows [transient, T) of E[g]:
+ *     D_s   = D[g] * t_scale[g] + t_shift[g]                                (NULL scale / shift: 1 / 0)
+ *     Gm[g] = decay * Gm[g] + E^T E,      Cm[g] = decay * Cm[g] + D_s^T E
+ *   E      [n_groups][T][cols], float64 (or float32 for the _f32 twin: what esn_harvest_batch_f32 writes)
+ *   D      [n_groups][T][n_out], unscaled
+ *   decay  in [0, 1]: the forgetting factor gamma.  decay == 0 starts a new sum and does not read Gm / Cm, which may
+ *          hold anything (NaN included).
+ * Gm is symmetric bit for bit, and a group's result is bitwise the same alone and inside any batch: the summation order
+ * is a function of the shape alone and there are no floating-point atomics.
+ * esn_gram_solve solves, for every group and each of its n_ridge lambdas (ridge [n_groups][n_ridge], absolute, >= 0),
+ *     (Gm[g] + lambda I) W^T = Cm[g]^T
+ * by blocked Cholesky -- the ridge solution of the stacked (weighted) rows.  Gm and Cm are only read.
+ *   W_out   [n_groups][n_ridge][n_out][cols], in the units esn_pack_readout takes
+ *   status  [n_groups][n_ridge]: 0; 1 where a pivot was <= 1e-14 * the largest diagonal entry of Gm + lambda I (that
+ *           entry's W_out is zero, the group's other candidates are unaffected); 2 for a negative or non-finite lambda
+ *           (W_out zero)
+ *   workspace: esn_gram_solve_workspace_bytes(n_groups, n_ridge, cols) bytes, 16-byte aligned: ONE factor per group --
+ *           the candidates of a group are factorised one after the other -- so the size does not grow with n_ridge.
+ * Served: 1 <= cols <= 544, 1 <= n_out <= 16, 1 <= n_ridge <= 16, 0 <= transient < T, E 16-byte aligned.  cols > 544
+ * returns -2 and esn_last_error() names the limit; anything else invalid returns -1; both before any HIP call.
+ * Explicit stream, no allocation. */
+int esn_gram_accumulate(const double* E, const double* D, int n_groups, int T, int transient, int cols, int n_out,
+                        const double* t_scale, const double* t_shift, double decay,
+                        double* Gm, double* Cm, void* stream);
+int esn_gram_accumulate_f32(const float* E, const double* D, int n_groups, int T, int transient, int cols, int n_out,
+                            const double* t_scale, const double* t_shift, double decay,
+                            double* Gm, double* Cm, void* stream);
+size_t esn_gram_solve_workspace_bytes(int n_groups, int n_ridge, int cols);
+int esn_gram_solve(const double* Gm, const double* Cm, int n_groups, int cols, int n_out,
+                   const double* ridge, int n_ridge, double* W_out, int* status,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* Reservoirs drawn on the device (an extension: the reference draws them on the host, pyESN.py:93-109, once per
  * coherence block).  All float64, device pointers, explicit stream, no allocation; every check returns -1 before any
  * HIP call and esn_last_error() names the function and the limit.  These are additions: the ABI version is unchanged.
