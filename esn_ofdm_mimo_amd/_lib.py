@@ -129,6 +129,18 @@ SIGNATURES = {
     "esn_elm_predict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
                                   _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _dp,
                                   _vp]),
+    # windowed FNN: n_in, n_hidden, window, n_out, n_groups, T -> bytes of esn_fnn_train's workspace
+    "esn_fnn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # precision, n_in, n_hidden, window, n_out, n_isets, W1_0, b1_0, W2_0, b2_0, in_scale, in_shift, t_scale, t_shift, U,
+    # D, n_groups, T_in, T, transient, group_offset, epochs, lr, beta1, beta2, eps, W1, b1, W2, b2, loss, workspace,
+    # workspace_bytes, stream
+    "esn_fnn_train": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double,
+                                C.c_double, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _vp, C.c_size_t, _vp]),
+    # precision, n_in, n_hidden, window, n_out, W1, b1, W2, b2, in_scale, in_shift, t_scale, t_shift, U, n_frames,
+    # frames_per_group, T_in, T, transient, Y, stream
+    "esn_fnn_predict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                  _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp]),
     "esn_ldpc_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "esn_qam_llr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _vp]),
     "esn_ldpc_decode_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp,

@@ -1104,6 +1104,75 @@ int esn_elm_predict(int precision, int n_in, int n_hidden, int window, int bias_
     return hip_fail(launch_elm_predict(precision, p, (hipStream_t)stream), who);
 }
 
+size_t esn_fnn_workspace_bytes(int n_in, int n_hidden, int window, int n_out, int n_groups, int T) {
+    (void)n_out; (void)T;
+    if (n_in < 1 || n_hidden < 1 || window < 1 || n_groups < 1) return 0;
+    return fnn_train_workspace_bytes(n_in, n_hidden, window, n_groups);      // Adam's moments of W1
+}
+
+int esn_fnn_train(int precision, int n_in, int n_hidden, int window, int n_out, int n_isets, const double* W1_0,
+                  const double* b1_0, const double* W2_0, const double* b2_0, const double* in_scale,
+                  const double* in_shift, const double* t_scale, const double* t_shift, const double* U, const double* D,
+                  int n_groups, int T_in, int T, int transient, uint64_t group_offset, int epochs, double lr, double beta1,
+                  double beta2, double eps, double* W1, double* b1, double* W2, double* b2, double* loss, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    const char* who = "esn_fnn_train";
+    if (!W1_0 || !b1_0 || !W2_0 || !b2_0 || !U || !D || !W1 || !b1 || !W2 || !b2) return fail(-1, "%s: null pointer", who);
+    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
+    const int rc = elm_check(who, precision == ESN_F16 ? ESN_F64 : precision, n_in, n_hidden, window, 1, n_isets, n_out,
+                             n_hidden + 1, n_groups, 1, T_in, T, transient);
+    if (rc) return rc;
+    if (precision != ESN_F64) return fail(-2, "%s: the training is float64 (ESN_F64); precision %d is not built", who, precision);
+    const int K = window * n_in;
+    if (n_hidden > 512 || n_out * n_hidden > 1024 || ((n_hidden + 3) / 4) * ((K + 7) / 8) > 512)
+        return fail(-1, "%s: n_hidden=%d K=%d n_out=%d: served up to n_hidden <= 512, n_out n_hidden <= 1024 and "
+                    "ceil(n_hidden / 4) ceil(K / 8) <= 512 (n_hidden K <= 16384)", who, n_hidden, K, n_out);
+    const size_t lds = fnn_train_lds_bytes(n_in, n_hidden, window, n_out, T);
+    if (lds > 160 * 1024)
+        return fail(-1, "%s: n_hidden=%d K=%d T=%d n_out=%d needs more than the served %d bytes of LDS "
+                    "(8 (n_hidden (K | 1) + T n_in + n_out n_hidden + n_hidden + n_out + 32 (n_hidden | 1) + 257))", who,
+                    n_hidden, K, T, n_out, 160 * 1024);
+    if (epochs < 1) return fail(-1, "%s: epochs=%d must be positive", who, epochs);
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
+        return fail(-1, "%s: need lr >= 0, 0 <= beta1, beta2 < 1 and eps > 0", who);
+    const size_t need = fnn_train_workspace_bytes(n_in, n_hidden, window, n_groups);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        return fail(-1, "%s: workspace of %zu bytes (8-byte aligned) needed, esn_fnn_workspace_bytes; got %zu", who, need,
+                    workspace ? workspace_bytes : (size_t)0);
+    FnnTrainParams p;
+    memset(&p, 0, sizeof(p));
+    p.n_in = n_in; p.n_hidden = n_hidden; p.window = window; p.n_out = n_out; p.n_isets = n_isets; p.n_groups = n_groups;
+    p.T_in = T_in; p.T = T; p.transient = transient; p.epochs = epochs; p.group_offset = group_offset;
+    p.lr = lr; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
+    p.W1_0 = W1_0; p.b1_0 = b1_0; p.W2_0 = W2_0; p.b2_0 = b2_0;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.D = D;
+    p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.loss = loss;
+    p.workspace = reinterpret_cast<double*>(workspace);
+    return hip_fail(launch_fnn_train(p, (hipStream_t)stream), who);
+}
+
+int esn_fnn_predict(int precision, int n_in, int n_hidden, int window, int n_out, const double* W1, const double* b1,
+                    const double* W2, const double* b2, const double* in_scale, const double* in_shift,
+                    const double* t_scale, const double* t_shift, const double* U, int n_frames, int frames_per_group,
+                    int T_in, int T, int transient, double* Y, void* stream) {
+    const char* who = "esn_fnn_predict";
+    if (!W1 || !b1 || !W2 || !b2 || !U || !Y) return fail(-1, "%s: null pointer", who);
+    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
+    const int rc = elm_check(who, precision, n_in, n_hidden, window, 1, 1, n_out, n_hidden + 1, n_frames, frames_per_group,
+                             T_in, T, transient);
+    if (rc) return rc;
+    if ((uintptr_t)Y & 15) return fail(-1, "%s: Y must be 16-byte aligned", who);
+    ElmParams p;
+    memset(&p, 0, sizeof(p));
+    // the ELM's parameter block: one weight set per group, the bias column's weights in b_out beside W_out = W2
+    p.n_in = n_in; p.n_hidden = n_hidden; p.window = window; p.bias_col = 1; p.n_out = n_out; p.e_cols = n_hidden;
+    p.n_wsets = (n_frames + frames_per_group - 1) / frames_per_group;
+    p.n_seq = n_frames; p.seq_per_group = frames_per_group; p.T_in = T_in; p.T = T; p.transient = transient;
+    p.group_offset = 0; p.W_in = W1; p.b = b1; p.W_out = W2; p.b_out = b2;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
+    return hip_fail(launch_fnn_predict(precision, p, (hipStream_t)stream), who);
+}
+
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream) {
     if (!taps || !H) return fail(-1, "esn_taps_to_freq: null pointer");
     if (n_blocks <= 0 || n_sub <= 0 || n_t <= 0 || n_r <= 0 || isi <= 0 || isi > n_sub)

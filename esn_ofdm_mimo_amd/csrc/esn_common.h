@@ -200,6 +200,21 @@ struct ElmParams {
     const double* U;             // [n_seq][T_in][n_in]
     double* Y;                   // [n_seq][T - transient][n_out]                 (predict)
     void* E; int e_f32;          // [groups][T][e_cols] float64 or float32         (features)
+    const double* b_out;         // [groups][n_out]: the ReLU instantiations (windowed FNN) read the weights of the bias
+                                 // column here, W_out = W2 has rows of e_cols = n_hidden; the tanh ones never look
+};
+// windowed FNN (esn_fnn.hip): Linear -> ReLU -> Linear over the ELM's window, trained per group by full-batch Adam
+struct FnnTrainParams {
+    int n_in, n_hidden, window, n_out, n_isets, n_groups, T_in, T, transient, epochs;
+    unsigned long long group_offset;
+    double lr, beta1, beta2, eps;
+    const double *W1_0, *b1_0, *W2_0, *b2_0;         // [n_isets][...]: group g starts from (group_offset + g) % n_isets
+    const double *in_scale, *in_shift, *t_scale, *t_shift;   // [groups][n] or nullptr
+    const double* U;             // [groups][T_in][n_in]
+    const double* D;             // [groups][T][n_out]
+    double *W1, *b1, *W2, *b2;   // [groups][...]
+    double* loss;                // [groups][epochs] or nullptr
+    double* workspace;           // the moments of W1: fnn_train_workspace_bytes
 };
 
 // coded leg (esn_coded.hip)

@@ -18,6 +18,9 @@
 //                    the read-out product Y^T += W_out[:, 32 units] hid^T (the sum runs over the accumulators' row index),
 //                    with the k order of that step permuted alike on the W_out side.  No barrier inside an item but the
 //                    one after staging; no atomics.
+// Both take the activation as a template parameter: RELU = true is the windowed FNN's prediction (esn_fnn_predict):
+// max(., 0) for tanh, and the bias column's weights come from p.b_out beside W_out = W2.  The fp16 kernel rounds the
+// ReLU outputs to fp16 like the tanh ones; they are unbounded, so inputs are expected at about unit variance.
 #include <atomic>
 #include "esn_common.h"
 #include "esn_launch.h"
@@ -55,7 +58,7 @@ static inline size_t elm_f64_lds_bytes(const ElmParams& p, bool predict) {
     return d * sizeof(double);
 }
 
-template <bool PREDICT>
+template <bool PREDICT, bool RELU = false>
 __global__ __launch_bounds__(ELM_THREADS) void elm_f64_kernel(ElmParams p, int n_seg) {
     extern __shared__ __attribute__((aligned(16))) char esm[];
     const int n_in = p.n_in, w = p.window, K = w * n_in, nh = p.n_hidden, T = p.T, n_out = p.n_out;
@@ -109,7 +112,10 @@ __global__ __launch_bounds__(ELM_THREADS) void elm_f64_kernel(ElmParams p, int n
             }
             const double bb = p.b[(size_t)s * nh + c];
 #pragma unroll
-            for (int r = 0; r < ELM_TR; ++r) v[r] = tanh(acc[r] + bb);
+            for (int r = 0; r < ELM_TR; ++r) {
+                if constexpr (RELU) v[r] = fmax(acc[r] + bb, 0.0);
+                else v[r] = tanh(acc[r] + bb);
+            }
         } else {
             const double one = (c == nh && p.bias_col) ? 1.0 : 0.0;
 #pragma unroll
@@ -133,7 +139,11 @@ __global__ __launch_bounds__(ELM_THREADS) void elm_f64_kernel(ElmParams p, int n
             for (int r = 0; r < ELM_TR; ++r) hid[r * ELM_HS + tid] = v[r];      // (zero beyond the last column)
             for (int e = tid; e < n_out * ELM_THREADS; e += ELM_THREADS) {
                 const int o = e / ELM_THREADS, cc = e - o * ELM_THREADS;
-                wo[o * ELM_HS + cc] = c0 + cc < ncol ? p.W_out[((size_t)g * n_out + o) * p.e_cols + c0 + cc] : 0.0;
+                if constexpr (RELU)                                     // W_out = W2 [n_out][nh], the bias column apart
+                    wo[o * ELM_HS + cc] = c0 + cc < nh ? p.W_out[((size_t)g * n_out + o) * p.e_cols + c0 + cc]
+                                                       : (c0 + cc == nh ? p.b_out[(size_t)g * n_out + o] : 0.0);
+                else
+                    wo[o * ELM_HS + cc] = c0 + cc < ncol ? p.W_out[((size_t)g * n_out + o) * p.e_cols + c0 + cc] : 0.0;
             }
             __syncthreads();
             if (owner) {
@@ -204,7 +214,7 @@ __device__ __forceinline__ u32x4 elm16_wout_frag(const double* wrow, bool valid,
     return __builtin_bit_cast(u32x4, r);
 }
 
-template <int NT, int KK, bool W_LDS>
+template <int NT, int KK, bool W_LDS, bool RELU = false>
 __global__ __launch_bounds__(64 * ELM16_WAVES) void elm_f16_kernel(ElmParams p, int n_batches, int ul) {
     extern __shared__ __attribute__((aligned(16))) char esm[];
     constexpr int ROWS = 16 * NT, KP = 32 * KK, WLD = KP + 8;      // (+ 8 halfs: rows 16 bytes apart in the banks)
@@ -214,7 +224,7 @@ __global__ __launch_bounds__(64 * ELM16_WAVES) void elm_f16_kernel(ElmParams p, 
     _Float16* Wl = reinterpret_cast<_Float16*>(esm);                                   // [nhp][WLD]
     float* bsc = reinterpret_cast<float*>(esm + (W_LDS ? (size_t)nhp * WLD * 2 : 0)); // [nhp]  b 2 log2 e
     _Float16* ust = reinterpret_cast<_Float16*>(bsc + nhp) + (size_t)wave * ul;        // this wave's rows
-    const float prescale = (float)ACT_PRESCALE;
+    const float prescale = RELU ? 1.0f : (float)ACT_PRESCALE;     // (ReLU: the plain pre-activation)
     for (int e = tile_elems + lane; e < ul; e += 64) ust[e] = (_Float16)0.0f;         // (never written again)
 
     const bool by_group = p.n_wsets > 1;              // then a workgroup walks whole groups: one weight set at a time
@@ -245,7 +255,7 @@ __global__ __launch_bounds__(64 * ELM16_WAVES) void elm_f16_kernel(ElmParams p, 
                 }
             }
             for (int h = tid; h < nhp; h += 64 * ELM16_WAVES)
-                bsc[h] = h < nh ? (float)(p.b[(size_t)s * nh + h] * ACT_PRESCALE) : 0.0f;
+                bsc[h] = h < nh ? (float)(p.b[(size_t)s * nh + h] * (RELU ? 1.0 : ACT_PRESCALE)) : 0.0f;
             loaded = s;
             __syncthreads();
         }
@@ -315,7 +325,8 @@ __global__ __launch_bounds__(64 * ELM16_WAVES) void elm_f16_kernel(ElmParams p, 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const size_t go = (size_t)g * n_out + (4 * qd + j < n_out ? 4 * qd + j : 0);
-                wb[j] = p.W_out[go * p.e_cols + (p.bias_col ? nh : nh - 1)];
+                if constexpr (RELU) wb[j] = p.b_out[go];
+                else wb[j] = p.W_out[go * p.e_cols + (p.bias_col ? nh : nh - 1)];
                 tsc[j] = 1.0; tsf[j] = 0.0;
             }
             if (p.t_scale) {
@@ -367,8 +378,13 @@ __global__ __launch_bounds__(64 * ELM16_WAVES) void elm_f16_kernel(ElmParams p, 
                     float x[8];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        x[j] = tanh_prescaled(fmaf(acc[0][nt][j], prescale, bz0[j]));
-                        x[4 + j] = tanh_prescaled(fmaf(acc[1][nt][j], prescale, bz1[j]));
+                        if constexpr (RELU) {
+                            x[j] = fmaxf(acc[0][nt][j] + bz0[j], 0.0f);
+                            x[4 + j] = fmaxf(acc[1][nt][j] + bz1[j], 0.0f);
+                        } else {
+                            x[j] = tanh_prescaled(fmaf(acc[0][nt][j], prescale, bz0[j]));
+                            x[4 + j] = tanh_prescaled(fmaf(acc[1][nt][j], prescale, bz1[j]));
+                        }
                     }
                     const u32x4 hf = {TraitsF16::pack2(x[0], x[1]), TraitsF16::pack2(x[2], x[3]),
                                       TraitsF16::pack2(x[4], x[5]), TraitsF16::pack2(x[6], x[7])};
@@ -438,11 +454,11 @@ int launch_elm_features(const ElmParams& p, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-template <int NT, int KK, bool W_LDS>
+template <int NT, int KK, bool W_LDS, bool RELU>
 static int launch_elm16(const ElmParams& p, hipStream_t stream) {
     static std::atomic<unsigned long long> raised{0};
     int cus = 0;
-    const int e = elm_raise_lds(reinterpret_cast<const void*>(elm_f16_kernel<NT, KK, W_LDS>), raised, &cus);
+    const int e = elm_raise_lds(reinterpret_cast<const void*>(elm_f16_kernel<NT, KK, W_LDS, RELU>), raised, &cus);
     if (e) return e;
     const size_t lds = elm16_lds_bytes<NT, KK>(p, W_LDS);
     const int n_batches = (p.T + 16 * NT - 1) / (16 * NT);
@@ -450,28 +466,36 @@ static int launch_elm16(const ElmParams& p, hipStream_t stream) {
     const int n_groups = (p.n_seq + p.seq_per_group - 1) / p.seq_per_group;
     const long long units = p.n_wsets > 1 ? n_groups : (n_items + ELM16_WAVES - 1) / ELM16_WAVES;
     const long long resident = (long long)cus * (lds <= ELM_MAX_LDS / 2 ? 2 : 1);
-    hipLaunchKernelGGL((elm_f16_kernel<NT, KK, W_LDS>), dim3((unsigned)(units < resident ? units : resident)),
+    hipLaunchKernelGGL((elm_f16_kernel<NT, KK, W_LDS, RELU>), dim3((unsigned)(units < resident ? units : resident)),
                        dim3(64 * ELM16_WAVES), lds, stream, p, n_batches, elm16_tile_halfs<NT, KK>(p));
     return (int)hipGetLastError();
 }
 
-int launch_elm_predict(int precision, const ElmParams& p, hipStream_t stream) {
+template <bool RELU>
+static int launch_predict(int precision, const ElmParams& p, hipStream_t stream) {
     if (precision == ESN_F64) {
         static std::atomic<unsigned long long> raised{0};
-        const int e = elm_raise_lds(reinterpret_cast<const void*>(elm_f64_kernel<true>), raised, nullptr);
+        const int e = elm_raise_lds(reinterpret_cast<const void*>((elm_f64_kernel<true, RELU>)), raised, nullptr);
         if (e) return e;
         const int n_tiles = (p.T + ELM_TR - 1) / ELM_TR;
-        hipLaunchKernelGGL(elm_f64_kernel<true>, dim3((unsigned)(p.n_seq * n_tiles)), dim3(ELM_THREADS),
+        hipLaunchKernelGGL((elm_f64_kernel<true, RELU>), dim3((unsigned)(p.n_seq * n_tiles)), dim3(ELM_THREADS),
                            elm_f64_lds_bytes(p, true), stream, p, elm_segments(p.n_out));
         return (int)hipGetLastError();
     }
     if (precision != ESN_F16) return -1;
     if (p.window * p.n_in <= 128) {
-        if (elm16_lds_bytes<9, 4>(p, true) <= ELM_MAX_LDS) return launch_elm16<9, 4, true>(p, stream);
-        return launch_elm16<9, 4, false>(p, stream);
+        if (elm16_lds_bytes<9, 4>(p, true) <= ELM_MAX_LDS) return launch_elm16<9, 4, true, RELU>(p, stream);
+        return launch_elm16<9, 4, false, RELU>(p, stream);
     }
-    if (elm16_lds_bytes<4, 8>(p, true) <= ELM_MAX_LDS) return launch_elm16<4, 8, true>(p, stream);
-    return launch_elm16<4, 8, false>(p, stream);
+    if (elm16_lds_bytes<4, 8>(p, true) <= ELM_MAX_LDS) return launch_elm16<4, 8, true, RELU>(p, stream);
+    return launch_elm16<4, 8, false, RELU>(p, stream);
+}
+
+int launch_elm_predict(int precision, const ElmParams& p, hipStream_t stream) {
+    return launch_predict<false>(precision, p, stream);
+}
+int launch_fnn_predict(int precision, const ElmParams& p, hipStream_t stream) {
+    return launch_predict<true>(precision, p, stream);
 }
 
 }  // namespace esn

@@ -144,4 +144,11 @@ int launch_channel_track(const ChanTrackParams& cp, hipStream_t stream);
 // esn_elm.hip: float64 features (p.E) or fused float64 / fp16 prediction (p.Y) of the windowed ELM
 int launch_elm_features(const ElmParams& p, hipStream_t stream);
 int launch_elm_predict(int precision, const ElmParams& p, hipStream_t stream);
+// the same kernels with max(., 0) for tanh and the bias column's weights in p.b_out: the windowed FNN's prediction
+int launch_fnn_predict(int precision, const ElmParams& p, hipStream_t stream);
+// esn_fnn.hip: per-group Adam training of the windowed FNN, one workgroup per group; the LDS image of one workgroup
+// (a function of the shape alone) and the workspace that holds Adam's moments of W1
+size_t fnn_train_lds_bytes(int n_in, int n_hidden, int window, int n_out, int T);
+size_t fnn_train_workspace_bytes(int n_in, int n_hidden, int window, int n_groups);
+int launch_fnn_train(const FnnTrainParams& p, hipStream_t stream);
 }  // namespace esn

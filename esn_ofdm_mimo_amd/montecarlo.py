@@ -21,6 +21,8 @@
                     every data symbol (FrameSource.track_channel, esn_channel_track)
     elm_point       one Eb/No point of the windowed ELM (elm.py, esn_elm_features / esn_elm_predict), the          points.py
                     reference's pinv-trained comparator, on the frames a DetectorSweep of the same seed detects
+    fnn_point       the same for the windowed FNN (fnn.py, esn_fnn_train / esn_fnn_predict), the reference's          points.py
+                    Adam-trained comparator: one training per block, all 50 epochs in one launch
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -31,4 +33,5 @@ This module is the import path of all of them; the code lives in the four module
 from .frames import FrameSource, _view_real, complex_as_io, percentiles_linear, summarize_channel_metrics  # noqa: F401
 from .link import LinkParams  # noqa: F401
 from .points import baseline_tracking_point, block_fading_point, coded_ber_point, elm_point  # noqa: F401
+from .points import fnn_point, fnn_weights  # noqa: F401
 from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters  # noqa: F401

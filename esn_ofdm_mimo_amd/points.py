@@ -4,7 +4,8 @@ driver's coded + uncoded ESN against LS/MMSE (coded_ber_point) and the block-fad
 through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says.
 Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, uncoded, detected symbol by symbol with its
 channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
-only.  And elm_point: the windowed ELM (elm.py), the reference's pinv-trained comparator, on the same frames."""
+only.  And elm_point / fnn_point: the windowed ELM (elm.py) and the windowed FNN (fnn.py), the reference's pinv-trained and
+Adam-trained comparators, on the same frames."""
 from __future__ import annotations
 
 from .frames import _view_real, summarize_channel_metrics
@@ -283,4 +284,88 @@ def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0
         return elm_point(src, ebno_db, snr_idx, n_blocks, n_hidden=n_hidden, window=window, gain=gain, ridge=ridge,
                          method="qr", precision=precision, slice=slice, weights=weights, first_block=first_block,
                          seed=seed, frames_per_block=frames_per_block, chunk_blocks=chunk_blocks)
+    return errors, nbits
+
+
+def fnn_weights(n_hidden, k, n_out, seed, block=None):
+    """(W1 [n_hidden, k], b1, W2 [n_out, n_hidden], b2), each U(+-1 / sqrt(fan_in)) -- the distribution of
+    torch.nn.Linear -- drawn in that order from RandomState(seed) or, for the set of one global block,
+    RandomState([seed, block])."""
+    import numpy as np
+    rs = np.random.RandomState(seed if block is None else [seed, block])
+    a1, a2 = 1.0 / np.sqrt(k), 1.0 / np.sqrt(n_hidden)
+    return (rs.uniform(-a1, a1, (n_hidden, k)), rs.uniform(-a1, a1, n_hidden),
+            rs.uniform(-a2, a2, (n_out, n_hidden)), rs.uniform(-a2, a2, n_out))
+
+
+def fnn_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, window=8, epochs=50, lr=0.01, precision="f64",
+              slice="aligned", weights="shared", first_block=0, seed=0, frames_per_block=None, chunk_blocks=None):
+    """One Eb/No point of the windowed FNN (fnn.FnnBank), the reference's Adam-trained comparator, on the frames
+    elm_point and a DetectorSweep over the same FrameSource seed detect: per chunk the pilot of every block gives one
+    training (inputs and teacher scaled by 1 / sqrt(var_x), transient max(delay + cp, window - 1), `epochs` Adam steps
+    from fnn_weights), then all data frames are predicted in one launch and counted by the detector tail.  slice and
+    weights as in elm_point ("reference": rows [0, N) of the un-cut output, the slice the reference's FNN branch
+    takes).  precision is the prediction's; the training is float64.  Returns (errors, bits): int64 [n_blocks] on the
+    device; nothing is read back inside the chunk loop."""
+    if slice not in ("aligned", "reference"):
+        raise ValueError(f"slice must be 'aligned' or 'reference', not {slice!r}")
+    if weights not in ("shared", "per_block"):
+        raise ValueError(f"weights must be 'shared' or 'per_block', not {weights!r}")
+    if precision not in ("f64", "f16"):
+        raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
+    if not isinstance(window, int) or not 1 <= window <= 16:
+        raise ValueError(f"window must be an integer in 1..16, not {window!r}")
+    if not isinstance(n_hidden, int) or n_hidden < 1:
+        raise ValueError(f"n_hidden must be a positive integer, not {n_hidden!r}")
+    if not isinstance(epochs, int) or epochs < 1:
+        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
+    if not lr >= 0:
+        raise ValueError(f"lr = {lr} must be non-negative")
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    import numpy as np
+    from .fnn import FnnBank, train_shape_error
+    torch, p = src.torch, src.p
+    n_in, n_out = 2 * p.n_r, 2 * p.n_t
+    d, T = p.delay, p.t_frame + p.delay
+    why = train_shape_error(n_in, n_hidden, window, n_out, T)
+    if why:
+        raise ValueError("the FNN training kernel does not serve this shape: " + why)
+    F = int(frames_per_block or p.coherence_symbols)
+    first_block, n_blocks = int(first_block), int(n_blocks)
+    chunk = int(chunk_blocks or min(n_blocks, 4096))
+    transient = max(p.forget, window - 1)
+    k = window * n_in
+    shared = fnn_weights(n_hidden, k, n_out, seed) if weights == "shared" else None
+    bank = FnnBank(n_in, n_out, n_hidden, window, n_groups=min(chunk, n_blocks), device=src.device)
+    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    scale = 1.0 / np.sqrt(p.var_x(ebno_db))
+    for b0 in range(first_block, first_block + n_blocks, chunk):
+        g = min(chunk, first_block + n_blocks - b0)
+        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F)
+        if shared is None:
+            sets = [fnn_weights(n_hidden, k, n_out, seed, b0 + i) for i in range(g)]
+            init = tuple(np.stack([s[j] for s in sets]) for j in range(4))
+        else:
+            init = shared
+        bank.set_scaling(torch.full((g, n_in), scale, dtype=torch.float64, device=src.device), None,
+                         torch.full((g, n_out), scale, dtype=torch.float64, device=src.device), None)
+        U = torch.zeros((g, T, n_in), dtype=torch.float64, device=src.device)
+        D = torch.zeros((g, T, n_out), dtype=torch.float64, device=src.device)
+        U[:, :p.t_frame] = _view_real(data["pilot_y"])
+        D[:, d:] = _view_real(data["pilot_x"])
+        bank.train(U, D, init, transient=transient, epochs=epochs, lr=lr)
+        dy = _view_real(data["data_y"])
+        if slice == "aligned":
+            Y = bank.predict(dy, F, T=T, transient=p.forget, precision=precision)
+        else:
+            Y = bank.predict(dy, F, T=T, transient=0, precision=precision)[:, :p.n_sub].contiguous()
+        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
+        lo = b0 - first_block
+        bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g])
     return errors, nbits

@@ -739,6 +739,59 @@ int esn_elm_predict(int precision, int n_in, int n_hidden, int window, int bias_
                     const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
                     uint64_t group_offset, double* Y, void* stream);
 
+/* ---- Windowed FNN (the reference's second learned comparator: class FNNModel, system_model_2_all_comparision.py:40-49,
+ * trained as trainMIMOModel('FNN') does, :115-122, :129-149): the ELM's window of scaled input rows feeding
+ * Linear -> ReLU -> Linear, trained per group by `epochs` full-batch Adam steps on the mean squared error.  Notation as in
+ * the ELM block: w = window, K = w n_in, group g, us[t][i] the scaled input with the zero rows before scaling for
+ * T_in <= t < T, and x[t][k n_in + i] = us[t-(w-1)+k][i] for t >= w-1.  With the trained rows
+ * R = { t : max(transient, w-1) <= t < T } and Ds[t][o] = D[g][t][o] t_scale[g][o] + t_shift[g][o]:
+ *   pre[t][h] = b1[h] + sum_k W1[h][k] x[t][k]         h[t] = max(pre[t], 0)
+ *   ys[t][o]  = b2[o] + sum_h W2[o][h] h[t][h]
+ *   loss      = sum_{t in R, o} (ys - Ds)^2 / (|R| n_out)                                      (nn.MSELoss, mean)
+ *   Adam, epoch e = 1..epochs, for every parameter p with gradient q = dloss/dp (the gradient of ReLU at 0 is 0):
+ *     m = beta1 m + (1-beta1) q;   v = beta2 v + (1-beta2) q^2
+ *     p -= (lr / (1-beta1^e)) m / ( sqrt(v)/sqrt(1-beta2^e) + eps )       (torch.optim.Adam, no weight decay, no amsgrad)
+ * The reference's values: epochs = 50, lr = 0.01, beta1 = 0.9, beta2 = 0.999, eps = 1e-8.  A parameter whose q is exactly 0
+ * in every epoch (a hidden unit inactive on every trained row) keeps m = v = 0 and comes out bitwise as it went in.
+ * esn_fnn_train   group g starts from the initial set (group_offset + g) % n_isets of W1_0 [n_isets][n_hidden][K],
+ *                 b1_0 [n_isets][n_hidden], W2_0 [n_isets][n_out][n_hidden], b2_0 [n_isets][n_out] and writes
+ *                 W1 [G][n_hidden][K], b1 [G][n_hidden], W2 [G][n_out][n_hidden], b2 [G][n_out]; loss [G][epochs], the
+ *                 loss BEFORE each step, may be NULL.  U [G][T_in][n_in], D [G][T][n_out], scalings [G][n] or NULL.  One
+ *                 workgroup per group and one launch for all epochs, the parameters resident in LDS, float64 plain FMA;
+ *                 every sum in an order that depends on the shape alone and no atomics, so a group is bitwise the same
+ *                 alone and inside any batch.  ESN_F64 only: every other precision returns -2.  workspace: device memory
+ *                 of esn_fnn_workspace_bytes(...) bytes (Adam's moments of W1, which do not fit the owning lanes'
+ *                 registers beside the gradient sums; 64 ceil(n_hidden / 4) ceil(K / 8) doubles per group), not
+ *                 initialised by the caller and of no meaning afterwards.
+ *                 Served: the ELM's 1 <= n_in, 1 <= window <= 16, K <= 256, n_out <= 8, T_in <= T, window <= T,
+ *                 0 <= transient < T, and what residency of the parameters allows: n_hidden <= 512,
+ *                 n_out n_hidden <= 1024, ceil(n_hidden / 4) ceil(K / 8) <= 512 (n_hidden K <= 16384 doubles of W1), and a
+ *                 workgroup image 8 (n_hidden (K | 1) + 2 ceil(T n_in / 2) + n_out n_hidden + n_hidden + n_out +
+ *                 32 (n_hidden | 1) + 256) bytes of at most 160 KB of LDS -- the reference's 100 units at K = 32 and at
+ *                 K = 128 (T = 138, n_out = 8: 156 KB) fit, 64 units at K = 256 too; epochs >= 1, lr >= 0,
+ *                 0 <= beta < 1, eps > 0.
+ * esn_fnn_predict the ELM's prediction (the same kernels, instantiated with another activation) with three changes:
+ *                 max(., 0) for tanh; bias_col = 1 with W_out[g] = [W2[g] | b2[g]]; one weight set per group, so W1, b1,
+ *                 W2, b2 are [groups][...] with groups = ceil(n_frames / frames_per_group).  ESN_F64 and ESN_F16 with the
+ *                 meaning they have for esn_elm_predict; the fp16 path rounds the ReLU outputs to fp16 -- unlike tanh
+ *                 they are unbounded, so inputs are expected scaled to about unit variance.  Served: esn_elm_predict's
+ *                 shapes (n_hidden <= 1024).
+ * Anything outside the served shapes returns -1 before any HIP call, the limit in esn_last_error().  There is no float32
+ * I/O variant and no _mem front end.  These are additions: the ABI version is unchanged. */
+size_t esn_fnn_workspace_bytes(int n_in, int n_hidden, int window, int n_out, int n_groups, int T);
+int esn_fnn_train(int precision, int n_in, int n_hidden, int window, int n_out, int n_isets,
+                  const double* W1_0, const double* b1_0, const double* W2_0, const double* b2_0,
+                  const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                  const double* U, const double* D, int n_groups, int T_in, int T, int transient,
+                  uint64_t group_offset, int epochs, double lr, double beta1, double beta2, double eps,
+                  double* W1, double* b1, double* W2, double* b2, double* loss,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int esn_fnn_predict(int precision, int n_in, int n_hidden, int window, int n_out,
+                    const double* W1, const double* b1, const double* W2, const double* b2,
+                    const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                    const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
+                    double* Y, void* stream);
+
 /* ---- Channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; the 4x8 ChannelRank driver is
  * named after it), float64.  H complex [G][N][n_r][n_t] in the layout of the function above, 16-byte aligned; p_i [G]
  * on the device as in the detectors; per subcarrier k the singular values s_1 >= ... of H_k by one-sided complex

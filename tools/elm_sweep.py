@@ -7,13 +7,17 @@ seed; the ELM and the baseline read the blocks the sweep detects):
     elm reference slice  the first --gain, pinv, rows [0, N) of the un-cut output: the slice the reference's ELM / FNN
                          branches take (system_model_2_all_comparision.py:151-152, :570-571)
     ls-mmse              baseline_tracking_point(track=None)
+    fnn, fnn reference slice   with --fnn: points.fnn_point (--fnn-hidden units, 50 Adam epochs per pilot), slices
+                         "aligned" and "reference"
 
     python tools/elm_sweep.py [--preset 4x8|2x2] [--blocks 256] [--ebno 0:30:3] [--hidden H] [--window 8]
                               [--gain 0.05,0.02] [--ridge 1e-3] [--n-res 512] [--precision f64|f16] [--out file.json]
+                              [--fnn [--fnn-hidden 100]]
 
 Presets: 4x8 = LinkParams() (TDL-B, N = 128, 16-QAM), 512 hidden units against N_res 512; 2x2 = the block-fading 2x2
 configuration at N = 512 (exponential PDP, 16-QAM), 100 hidden units as the reference's ELM(4 * window), N_res 100.
-Writes profiles/elm_sweep_<preset>.json unless --out is given.  Needs an MI355X."""
+Writes profiles/elm_sweep_<preset>.json (with --fnn: profiles/fnn_sweep_<preset>.json) unless --out is given.  Needs an
+MI355X."""
 import argparse
 import json
 import os
@@ -39,6 +43,8 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--commit", default=None, help="recorded in the JSON")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fnn", action="store_true", help="add the windowed FNN's curves")
+    ap.add_argument("--fnn-hidden", type=int, default=100)
     a = ap.parse_args()
     from esn_ofdm_mimo_amd import _lib
     from esn_ofdm_mimo_amd.montecarlo import DetectorSweep, LinkParams, baseline_tracking_point, elm_point
@@ -77,12 +83,22 @@ def main():
     add(f"elm g={gains[0]:g} reference slice", elm(gains[0], None, "reference"), gain=gains[0], ridge=None,
         slice="reference")
     add("ls-mmse", [baseline_tracking_point(src, eb, si, a.blocks, F)["ber"] for si, eb in enumerate(points)])
+    if a.fnn:
+        from esn_ofdm_mimo_amd.montecarlo import fnn_point
+        for sl in ("aligned", "reference"):
+            ber = []
+            for si, eb in enumerate(points):
+                e, n = fnn_point(src, eb, si, a.blocks, n_hidden=a.fnn_hidden, window=a.window, precision=a.precision,
+                                 slice=sl, seed=a.seed, frames_per_block=F)
+                ber.append(float(e.sum()) / float(n.sum()))
+            add("fnn" + ("" if sl == "aligned" else " reference slice"), ber, n_hidden=a.fnn_hidden, epochs=50, lr=0.01,
+                slice=sl)
     result = {"config": dict(preset=a.preset, n_t=params.n_t, n_r=params.n_r, n_sub=params.n_sub, bits_per_symbol=params.m,
                              channel=params.channel, blocks=a.blocks, frames_per_block=F, n_hidden=o["hidden"],
                              window=a.window, n_reservoir=o["n_res"], elm_precision=a.precision, seed=a.seed,
                              device=_lib.device_info()["arch"], commit=a.commit),
               "ebno_db": points, "curves": curves}
-    out = a.out or os.path.join(ROOT, "profiles", f"elm_sweep_{a.preset}.json")
+    out = a.out or os.path.join(ROOT, "profiles", f"{'fnn' if a.fnn else 'elm'}_sweep_{a.preset}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
