@@ -7,9 +7,13 @@ reservoir per coherence block) -- and runs the reference's three
 operations for all of them at once through the C ABI of ``include/esn_hip.h``:
 
     harvest  -> state-collection loop of ESN.fit      (libs/pyESN.py:176-189)
-    solve    -> pinv readout solve of ESN.fit         (libs/pyESN.py:191-192)
+    solve    -> pinv readout solve of ESN.fit         (libs/pyESN.py:191-192)         readout.ReadoutFit
     predict  -> ESN.predict                           (libs/pyESN.py:218-255)
-    detect   -> reconstruct/FFT/slicer/error count    (Demo_MIMO_4x8_..._v2.py:47-58,439-456)
+    detect   -> reconstruct/FFT/slicer/error count    (Demo_MIMO_4x8_..._v2.py:47-58,439-456)   bankbase.DetectorTail
+
+This module holds the recurrence: weights and their packing, harvest, predict, and fit / fit_pilots, which put a
+harvest in front of the read-out fit.  The read-out fit itself (readout.py) and the detector tail (bankbase.py) read
+no reservoir; the bank inherits them, and so do the windowed comparators (elm.py, fnn.py).
 
 torch is used for device memory and streams only.
 """
@@ -21,90 +25,27 @@ import numpy as np
 
 from . import _lib
 from ._lib import PRECISIONS, Shape, check, ptr
+from .bankbase import DetectorTail, DeviceBank, _as_dev
+from .readout import _HARVEST_TIMED_OUT, GramState, ReadoutFit, _lambdas  # noqa: F401  (GramState: importable from here)
 
 
-def _as_dev(x, torch, device, dtype=None):
-    if x is None:
-        return None
-    if isinstance(x, torch.Tensor):
-        t = x.to(device=device, dtype=dtype or torch.float64)
-    else:
-        a = np.ascontiguousarray(x)
-        if not a.flags.writeable:                 # (arrays out of an .npz are read-only; torch wants ownership)
-            a = a.copy()
-        t = torch.as_tensor(a, device=device).to(dtype or torch.float64)
-    return t.contiguous()
+class ReservoirBank(DeviceBank, ReadoutFit, DetectorTail):
+    W_out = None
+    # what the last harvest / fit left (device tensors; None until then, see those methods; ReadoutFit: the solve's)
+    harvest_timeout = _cluster_err = fit_ridge = fit_status = fit_rows = None
+    gram_state = None                           # fit_pilots(method="gram"): the GramState behind W_out
 
-
-_HARVEST_TIMED_OUT = ("harvest cluster kernel: a workgroup timed out waiting for the others "
-                      "(the device is oversubscribed); the extended states are invalid")
-
-
-def _lambdas(torch, device, lam, g, grid=False):
-    """The lambdas of G groups -- `ridge` (a scalar, [G] or [G, L]) or, with `grid`, `ridge_grid` (L candidates or
-    [G, L]), as an array, a sequence or a tensor -> (device float64 [G, L], whether the caller gave no L axis)."""
-    flat = not grid and (lam.ndim if isinstance(lam, torch.Tensor) else np.ndim(lam)) < 2
-    if isinstance(lam, torch.Tensor):
-        r = lam.to(device=device, dtype=torch.float64)
-    elif flat and np.ndim(lam) == 0:
-        r = torch.full((g, 1), float(lam), dtype=torch.float64, device=device)   # (no host copy)
-    else:
-        r = torch.as_tensor(np.array(lam, dtype=np.float64), device=device)
-    if r.ndim == 1:
-        r = r[None, :].expand(g, r.shape[0]) if grid else r[:, None]
-    elif r.ndim == 0 and not grid:
-        r = r.reshape(1, 1).expand(g, 1)
-    if r.ndim != 2 or r.shape[0] != g or (r.shape[1] < 1 and not grid):
-        raise ValueError(f"ridge_grid must hold L candidates or be [G, L] with G = {g}, not {tuple(r.shape)}" if grid else
-                         f"ridge must be a scalar, [G] or [G, L] with G = {g}, not {tuple(r.shape)}")
-    return r.contiguous(), flat
-
-
-class GramState:
-    """A read-out kept as running normal equations (ReservoirBank.gram_accumulate): G [groups, cols, cols] and
-    C [groups, n_out, cols], float64 on the device, and the teacher scalings (t_scale, t_shift: [groups, n_out] or None)
-    every segment was accumulated under.  Its size does not depend on the number of segments it has seen."""
-    __slots__ = ("G", "C", "t_scale", "t_shift")
-
-    def __init__(self, G, C, t_scale, t_shift):
-        self.G, self.C, self.t_scale, self.t_shift = G, C, t_scale, t_shift
-
-
-class ReservoirBank:
     def __init__(self, n_inputs, n_outputs, n_reservoir, W, W_in, W_feedb,
                  teacher_forcing=True, noise=0.001, device=None, leak_rate=1.0):
-        torch = _lib.require_gpu()
-        self.torch = torch
-        self.lib = _lib.load()
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        DeviceBank.__init__(self, device)
         self.n_inputs, self.n_outputs, self.n_reservoir = int(n_inputs), int(n_outputs), int(n_reservoir)
         self.noise = float(noise)
-        W = np.asarray(W, dtype=np.float64)
-        W_in = np.asarray(W_in, dtype=np.float64)
-        W_feedb = np.asarray(W_feedb, dtype=np.float64)
-        if W.ndim == 2:
-            W, W_in, W_feedb = W[None], W_in[None], W_feedb[None]
-        self.n_wsets = W.shape[0]
-        if W.shape[1:] != (n_reservoir, n_reservoir) or W_in.shape != (self.n_wsets, n_reservoir, n_inputs) \
-                or W_feedb.shape != (self.n_wsets, n_reservoir, n_outputs):
-            raise ValueError("weight shapes do not match (n_wsets, n_reservoir, ...)")
         if not 0.0 < float(leak_rate) <= 1.0:
             raise ValueError("leak_rate must be in (0, 1]")
         self.leak_rate = float(leak_rate)       # extension (the reference has none): float64 kernels only when != 1
-        self.shape = Shape(n_reservoir, n_inputs, n_outputs, 1 if teacher_forcing else 0, self.n_wsets, self.leak_rate)
-        with torch.cuda.device(self.device):
-            self._W = _as_dev(W, torch, self.device)
-            self._W_in = _as_dev(W_in, torch, self.device)
-            self._W_fb = _as_dev(W_feedb, torch, self.device)
-        self._packed = {}
+        self.shape = Shape(n_reservoir, n_inputs, n_outputs, 1 if teacher_forcing else 0, 0, self.leak_rate)
+        self.set_weights(W, W_in, W_feedb)
         self._packed_wout = {}
-        self.in_scale = self.in_shift = self.t_scale = self.t_shift = None
-        self.W_out = None
-        # what the last harvest / solve / fit left (device tensors; None until then, see those methods)
-        self.harvest_timeout = self._cluster_err = self.last_solve_status = None
-        self.last_ridge_choice = self.last_ridge_scores = self.last_ridge_status = None
-        self.last_ridge_grid = self.last_ridge_lambda = self.fit_ridge = self.fit_status = self.fit_rows = None
-        self.gram_state = None                  # fit_pilots(method="gram"): the GramState behind W_out
 
     def set_weights(self, W, W_in, W_feedb):
         """Swap the weight sets: [n_res, n_res] / [n_res, n_in] / [n_res, n_out], or each with a leading [n_wsets]
@@ -146,11 +87,8 @@ class ReservoirBank:
                                                        radius_precision=radius_precision,
                                                        n_squarings=reservoirs.N_SQUARINGS if n_squarings is None
                                                        else n_squarings)
-        n = int(n_reservoir)
-        # (placeholders of one set for __init__, which keeps its signature; the device tensors replace them at once)
-        bank = cls(n_inputs, n_outputs, n, np.zeros((n, n)), np.zeros((n, int(n_inputs))), np.zeros((n, int(n_outputs))),
-                   teacher_forcing=teacher_forcing, noise=noise, device=dev, leak_rate=leak_rate)
-        bank.set_weights(W, W_in, W_fb)
+        bank = cls(n_inputs, n_outputs, n_reservoir, W, W_in, W_fb, teacher_forcing=teacher_forcing, noise=noise,
+                   device=dev, leak_rate=leak_rate)
         bank.generated_radius = radius          # of the unscaled W, float64 [n_sets] on the device
         return bank
 
@@ -174,14 +112,6 @@ class ReservoirBank:
                       "esn_pack_weights")
             self._packed[precision] = buf
         return self._packed[precision]
-
-    def set_scaling(self, in_scale=None, in_shift=None, t_scale=None, t_shift=None):
-        """Per-group scalings, each [G, n] (or None = identity): pyESN.py:127-152."""
-        torch = self.torch
-        self.in_scale = _as_dev(in_scale, torch, self.device)
-        self.in_shift = _as_dev(in_shift, torch, self.device)
-        self.t_scale = _as_dev(t_scale, torch, self.device)
-        self.t_shift = _as_dev(t_shift, torch, self.device)
 
     def set_readout(self, W_out):
         """W_out [G, n_out, n_res + n_in] (float64)."""
@@ -249,156 +179,6 @@ class ReservoirBank:
         if self.harvest_timeout is not None and int(self.harvest_timeout.item()) != 0:
             raise _lib.EsnHipError(_HARVEST_TIMED_OUT)
 
-    def chol_fits(self, rows, cols):
-        """Shapes the Cholesky solve covers (esn_readout_solve_chol_batch): Gram dimension up to 128 in LDS,
-        up to 512 out of a workspace."""
-        return min(rows, cols) <= 512 and self.n_outputs <= 8
-
-    LOO_MAX_GRAM, LOO_MAX_GRID = 128, 16      # esn_readout_ridge_loo_batch: Gram dimension, candidates per group
-
-    # (kind, lambdas given, float32 E) -> (entry point, workspace query, the bank's scratch buffer; None: one per call)
-    _READOUT = {
-        ("qr", False, False): ("esn_readout_solve_batch", "esn_readout_solve_workspace_bytes", None),
-        ("qr", True, False): ("esn_readout_solve_ridge_batch", "esn_readout_solve_ridge_workspace_bytes", None),
-        ("chol", False, False): ("esn_readout_solve_chol_batch", "esn_readout_chol_workspace_bytes", "_chol_ws"),
-        ("chol", False, True): ("esn_readout_solve_chol_batch_f32", "esn_readout_chol_workspace_bytes", "_chol_ws"),
-        ("chol", True, False): ("esn_readout_solve_chol_ridge_batch", "esn_readout_chol_ridge_workspace_bytes", "_chol_ws"),
-        ("chol", True, True): ("esn_readout_solve_chol_ridge_batch_f32", "esn_readout_chol_ridge_workspace_bytes", "_chol_ws"),
-        ("loo", True, False): ("esn_readout_ridge_loo_batch", "esn_readout_ridge_loo_workspace_bytes", "_loo_ws"),
-        ("loo", True, True): ("esn_readout_ridge_loo_batch_f32", "esn_readout_ridge_loo_workspace_bytes", "_loo_ws"),
-    }
-
-    def _readout(self, E, D, transient, kind, lam, t_scale, t_shift):
-        """The one way into the read-out kernels.  kind "qr", "chol" or "loo" (leave-one-out among the lambdas); lam
-        None (pinv) or device float64 [G, L]; t_scale / t_shift the teacher scalings of these G groups.  Returns
-        (W_out, status) with an L axis after G where lam is given, for "loo" (W_out [G, n_out, cols], status [G, L],
-        scores [G, L], choice [G])."""
-        torch, lib, n_out = self.torch, self.lib, self.n_outputs
-        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32       # as written by harvest(e_dtype="f32")
-        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
-        if e32 and kind == "qr":
-            E, e32 = E.double(), False                                      # the QR kernel works in place on float64
-        D = _as_dev(D, torch, self.device)
-        g, t, cols = E.shape
-        nl = () if lam is None else (lam.shape[1],)
-        entry, query, scratch = self._READOUT[kind, lam is not None, e32]
-        with torch.cuda.device(self.device):
-            def new(dtype, *shape):
-                return torch.empty(shape, dtype=dtype, device=self.device)
-            W_out = new(torch.float64, g, *(nl if kind != "loo" else ()), n_out, cols)
-            status = new(torch.int32, g, *nl)
-            loo = (new(torch.float64, g, *nl), new(torch.int32, g)) if kind == "loo" else ()      # scores, choice
-            wbytes = getattr(lib, query)(g, *nl, t - transient, cols, *((n_out,) if kind == "qr" else ()))
-            ws = self._scratch(scratch, wbytes) if scratch else new(torch.uint8, wbytes)
-            check(getattr(lib, entry)(ptr(E), ptr(D), g, t, int(transient), cols, n_out, ptr(t_scale), ptr(t_shift),
-                                      *((ptr(lam), *nl) if nl else ()), ptr(W_out), *map(ptr, loo), ptr(status), ptr(ws),
-                                      *((wbytes,) if kind != "qr" else ()), _lib.stream_handle()),
-                  "esn_readout_solve_chol_batch" if (kind, nl) == ("chol", ()) else entry)
-        return (W_out, status, *loo)
-
-    def _solve_ridge_grid(self, E, D, transient, ridge_grid):
-        """solve(ridge_grid=...): leave-one-out choice among the candidates, one Gram pass per group."""
-        torch = self.torch
-        g, t, cols = np.shape(E)
-        rows = t - transient
-        lam, _ = _lambdas(torch, self.device, ridge_grid, g, grid=True)
-        nl = lam.shape[1]
-        if not 1 <= nl <= self.LOO_MAX_GRID:
-            raise ValueError(f"ridge_grid holds {nl} candidates per group, the kernel takes 1 to {self.LOO_MAX_GRID}")
-        if min(rows, cols) > self.LOO_MAX_GRAM:
-            raise ValueError(f"ridge_grid needs min(rows, cols) <= {self.LOO_MAX_GRAM}, not {min(rows, cols)}")
-        if self.n_outputs > 8:
-            raise ValueError(f"ridge_grid needs n_outputs <= 8, not {self.n_outputs}")
-        W_out, status_l, scores, choice = self._readout(E, D, transient, "loo", lam, self.t_scale, self.t_shift)
-        with torch.cuda.device(self.device):
-            self.last_ridge_choice = choice
-            self.last_ridge_scores = scores
-            self.last_ridge_status = status_l
-            self.last_ridge_grid = lam
-            # (device-side gather; NaN where no candidate survived)
-            picked = lam.gather(1, choice.clamp(min=0).long()[:, None])[:, 0]
-            self.last_ridge_lambda = torch.where(choice >= 0, picked, torch.full_like(picked, float("nan")))
-            status = (choice < 0).to(torch.int32)
-        self.last_solve_status = status
-        return W_out, status
-
-    def solve(self, E, D, transient, method="qr", ridge=None, ridge_grid=None):
-        """W_out[g] = (pinv(E[g][transient:]) @ scale(D[g][transient:])).T ; returns (W_out, status).
-
-        ridge (extension, the reference has none; None = the pinv solve above, untouched): lambda >= 0 of
-        W_out = argmin |E W^T - D_s|^2 + lambda |W|^2, absolute, in the units of the Gram matrix of the scaled states.
-        A float or a [G] array / tensor gives W_out [G, n_out, cols] and status [G]; a [G, L] one solves L lambdas
-        per group in one launch and gives W_out [G, L, n_out, cols] and status [G, L].  lambda = 0 is the pinv solve
-        bit for bit; a negative or non-finite lambda gives status 2 and a zero W_out for that entry.
-
-        method "qr": float64 Householder QR (accurate to cond(E) eps; the drop-in's choice).
-        method "chol": float64 normal equations on the float64 matrix pipe (min(rows, cols) <= 512, n_out <= 8;
-        Gram + factor in LDS up to 128, in a workspace beyond), an order of magnitude faster; groups whose pivot test fails are re-solved
-        with QR on the GPU.  "auto" = "chol" when the shape fits.
-
-        ridge_grid (extension): a sequence of L candidates, or a [G, L] array / tensor of them.  Each group takes the
-        candidate with the smallest leave-one-out score of its own pilot (esn_readout_ridge_loo_batch: one Gram pass,
-        min(rows, cols) <= 128, n_out <= 8, L <= 16; `method` does not apply) and the result is (W_out [G, n_out, cols],
-        status [G]) with status 0 where a choice was made and 1 where no candidate survived (W_out zero; see
-        resolve_failed).  last_ridge_choice (int32 [G], -1 = none), last_ridge_lambda (float64 [G]) and
-        last_ridge_scores ([G, L]) stay on the device."""
-        if ridge_grid is not None:
-            if ridge is not None:
-                raise ValueError("give ridge or ridge_grid, not both")
-            return self._solve_ridge_grid(E, D, transient, ridge_grid)
-        g, t, cols = np.shape(E)
-        fits = self.chol_fits(t - transient, cols)
-        if method == "auto":
-            method = "chol" if fits else "qr"
-        if method == "chol" and not fits:
-            raise ValueError("method='chol' needs min(rows, cols) <= 512 and n_outputs <= 8")
-        lam, flat = (None, False) if ridge is None else _lambdas(self.torch, self.device, ridge, g)
-        W_out, status = self._readout(E, D, transient, "chol" if method == "chol" else "qr", lam,
-                                      self.t_scale, self.t_shift)
-        if flat:
-            W_out, status = W_out[:, 0], status[:, 0]       # (L = 1: contiguous views)
-        if method == "chol":
-            self.last_solve_status = status        # checked lazily: no host sync on the fast path
-        return W_out, status
-
-    def resolve_failed(self, E, D, transient, W_out, status, ridge=None, ridge_grid=None):
-        """Re-solve with QR (on the GPU) the groups a "chol" solve flagged; returns their count.  `ridge` as given to
-        that solve: each flagged entry is re-solved with its own lambda, so a repaired group is a ridge solution too.
-        `ridge_grid` as given to a solve(ridge_grid=...): a group left without a choice (choice == -1, status 1) is
-        re-solved by QR at its largest finite candidate -- the most regularised fit the caller was willing to accept --
-        and last_ridge_lambda takes that value; the choice stays -1.  A status of -9 (fit: the harvest cluster kernel
-        timed out, the states were never written) is not repaired: EsnHipError, W_out and status untouched."""
-        torch = self.torch
-        if ridge is not None and ridge_grid is not None:
-            raise ValueError("give ridge or ridge_grid, not both")
-        at = torch.nonzero(status).unbind(1)        # (groups,) of a status [G], (groups, lambdas) of a [G, L] one
-        bad, nbad = at[0], int(at[0].numel())
-        if not nbad:
-            return 0
-        if bool(status.eq(-9).any()):
-            raise _lib.EsnHipError(_HARVEST_TIMED_OUT)
-        lam = None
-        if ridge_grid is not None:
-            lam = _lambdas(torch, self.device, ridge_grid, status.shape[0], grid=True)[0][bad]
-            # (no finite candidate at all: lambda stays negative, the QR solve answers status 2 and a zero W_out)
-            lam = torch.where(torch.isfinite(lam), lam, torch.full_like(lam, -1.0)).max(dim=1).values
-        elif ridge is not None:
-            lam = _lambdas(torch, self.device, ridge, status.shape[0])[0][bad, at[1] if len(at) > 1 else 0]
-        W_out[at], status[at] = self.resolve_failed_at(E, D, transient, bad, lam)
-        if ridge_grid is not None and self.last_ridge_lambda is not None \
-                and self.last_ridge_lambda.shape[0] == status.shape[0]:
-            self.last_ridge_lambda[bad] = lam
-        return nbad
-
-    def resolve_failed_at(self, E, D, transient, bad, lam):
-        """QR solve of the groups `bad` (device index tensor) at lam [len(bad)], or pinv for lam None, under those
-        groups' own teacher scalings; returns (W_out, status) of len(bad) groups."""
-        def sub(x):
-            return None if x is None else x[bad].contiguous()
-        out = self._readout(sub(E), sub(_as_dev(D, self.torch, self.device)), transient, "qr",
-                            None if lam is None else lam.reshape(-1, 1).contiguous(), sub(self.t_scale), sub(self.t_shift))
-        return out if lam is None else (out[0][:, 0], out[1][:, 0])
-
     def fit(self, U, D, transient=0, precision="f64", noise_mode="counter", noise_u=None, seed=0,
             method="qr", e_dtype="f64", group_offset=0, ridge=None, ridge_grid=None):
         """harvest + solve + set_readout.  ridge: None (pinv), a float or one lambda per group [G] -- see solve.
@@ -421,68 +201,6 @@ class ReservoirBank:
         return E
 
     # ------------------------------------------------------------------ running normal equations
-    GRAM_MAX_COLS, GRAM_MAX_GRID, GRAM_MAX_OUT = 544, 16, 16      # esn_gram_accumulate / esn_gram_solve
-
-    def gram_accumulate(self, E, D, transient, state=None, decay=1.0):
-        """One training segment into a read-out kept as running normal equations (esn_gram_accumulate): over rows
-        [transient, T) of E [G, T, cols] (float64, or float32 as harvest(e_dtype="f32") writes it) and the unscaled
-        teacher D [G, T, n_out],  G <- decay G + E^T E,  C <- decay C + D_s^T E.  state None: a new GramState under
-        this bank's teacher scalings, started with decay 0 (`decay` is not read).  Otherwise `state` is updated in
-        place, under the scalings it was started with, and returned; decay in [0, 1] is the forgetting factor, and
-        decay 0 starts the sum again without reading what the state held.  Nothing is read back."""
-        torch, n_out = self.torch, self.n_outputs
-        e32 = isinstance(E, torch.Tensor) and E.dtype == torch.float32
-        E = _as_dev(E, torch, self.device, torch.float32 if e32 else None)
-        D = _as_dev(D, torch, self.device)
-        if E.ndim != 3 or tuple(D.shape) != (E.shape[0], E.shape[1], n_out):
-            raise ValueError(f"gram_accumulate takes E [G, T, cols] and D [G, T, {n_out}], not {tuple(E.shape)} and "
-                             f"{tuple(D.shape)}")
-        g, t, cols = E.shape
-        if not 0.0 <= float(decay) <= 1.0:
-            raise ValueError(f"decay must lie in [0, 1], not {decay}")
-        with torch.cuda.device(self.device):
-            if state is None:
-                self._check_groups(g)
-                state = GramState(torch.empty((g, cols, cols), dtype=torch.float64, device=self.device),
-                                  torch.empty((g, n_out, cols), dtype=torch.float64, device=self.device),
-                                  None if self.t_scale is None else self.t_scale[:g],
-                                  None if self.t_shift is None else self.t_shift[:g])
-                decay = 0.0
-            elif tuple(state.G.shape) != (g, cols, cols) or tuple(state.C.shape) != (g, n_out, cols):
-                raise ValueError(f"the state holds G {tuple(state.G.shape)} and C {tuple(state.C.shape)}, the segment "
-                                 f"needs [{g}, {cols}, {cols}] and [{g}, {n_out}, {cols}]")
-            if E.data_ptr() % 16:               # (a view into a larger buffer: the kernel loads 16-byte units)
-                E = E.clone()
-            name = "esn_gram_accumulate_f32" if e32 else "esn_gram_accumulate"
-            check(getattr(self.lib, name)(ptr(E), ptr(D), g, t, int(transient), cols, n_out, ptr(state.t_scale),
-                                          ptr(state.t_shift), float(decay), ptr(state.G), ptr(state.C),
-                                          _lib.stream_handle()), name)
-        return state
-
-    def gram_solve(self, state, ridge):
-        """(G + lambda I) W^T = C^T for the groups of a GramState (esn_gram_solve): the ridge read-out of every row the
-        state has seen, weighted by its forgetting.  ridge as in solve: a scalar or [G] gives (W_out [G, n_out, cols],
-        status [G]); [G, L] (L <= 16) solves L lambdas per group from the one G and gives W_out [G, L, n_out, cols] and
-        status [G, L].  status 1: a pivot was rejected, that entry's W_out is zero (nothing is repaired: the state
-        keeps no rows); 2: a negative or non-finite lambda.  The state is only read."""
-        torch = self.torch
-        g, n_out, cols = state.C.shape
-        lam, flat = _lambdas(torch, self.device, ridge, g)
-        nl = lam.shape[1]
-        if not 1 <= nl <= self.GRAM_MAX_GRID:
-            raise ValueError(f"ridge holds {nl} candidates per group, the kernel takes 1 to {self.GRAM_MAX_GRID}")
-        with torch.cuda.device(self.device):
-            W_out = torch.empty((g, nl, n_out, cols), dtype=torch.float64, device=self.device)
-            status = torch.empty((g, nl), dtype=torch.int32, device=self.device)
-            wbytes = self.lib.esn_gram_solve_workspace_bytes(g, nl, cols)
-            ws = self._scratch("_gram_ws", max(wbytes, 16))
-            check(self.lib.esn_gram_solve(ptr(state.G), ptr(state.C), g, cols, n_out, ptr(lam), nl, ptr(W_out),
-                                          ptr(status), ptr(ws), wbytes, _lib.stream_handle()), "esn_gram_solve")
-        if flat:
-            W_out, status = W_out[:, 0], status[:, 0]
-        self.last_solve_status = status
-        return W_out, status
-
     def _fit_pilots_gram(self, U, D, transient, precision, noise_mode, noise_u, seed, e_dtype, group_offset, ridge,
                          ridge_grid):
         """fit_pilots(method="gram"): one harvest and one gram_accumulate per pilot, no stacked rows."""
@@ -515,22 +233,12 @@ class ReservoirBank:
                 scores, choice = self.holdout_choose(E, D_p, transient, W_cand, status_l)
                 del W_cand
             state = self.gram_accumulate(E, D_p, transient, state, 1.0)
-        with torch.cuda.device(self.device):
-            if ridge_grid is None:
-                W_out, status = self.gram_solve(state, ridge)
-                self.fit_ridge = ridge
-            else:
-                none = choice < 0
-                picked = lam.gather(1, choice.clamp(min=0).long()[:, None])[:, 0]
-                # (a group without a choice: solved at lambda 0 for the launch's sake, then zeroed and flagged)
-                W_out, status = self.gram_solve(state, torch.where(none, torch.zeros_like(picked), picked))
-                W_out = torch.where(none[:, None, None], torch.zeros_like(W_out), W_out)
-                status = torch.where(none, torch.ones_like(status), status)
-                self.last_ridge_choice, self.last_ridge_scores, self.last_ridge_status = choice, scores, status_l
-                self.last_ridge_grid = lam
-                self.last_ridge_lambda = torch.where(none, torch.full_like(picked, float("nan")), picked)
-                self.last_solve_status = status
-                self.fit_ridge = self.last_ridge_lambda
+        if ridge_grid is None:
+            W_out, status = self.gram_solve(state, ridge)
+            self.fit_ridge = ridge
+        else:
+            W_out, status = self._solve_at_winner(lam, status_l, scores, choice, lambda at: self.gram_solve(state, at))
+            self.fit_ridge = self.last_ridge_lambda
         self.set_readout(W_out)
         self.harvest_timeout = None if timed_out is None else timed_out.to(torch.int32)
         if timed_out is not None:
@@ -541,46 +249,6 @@ class ReservoirBank:
         return state
 
     # ------------------------------------------------------------------ several pilots per group
-    HOLDOUT_MAX_GRID = 16                     # esn_readout_holdout_score: candidates per group
-
-    def holdout_choose(self, E_val, D_val, transient, W_cand, status=None):
-        """Score the candidate read-outs W_cand [G, L, n_out, cols] (a multi-lambda solve's W_out) on rows
-        [transient, T) of a segment the fit has not seen -- E_val [G, T, cols] (float64, or float32 as
-        harvest(e_dtype="f32") writes it) and its unscaled teacher D_val [G, T, n_out] -- under this bank's teacher
-        scalings (esn_readout_holdout_score).  status: that solve's int32 [G, L], or None for all 0.  Returns
-        (scores float64 [G, L], +inf where the status is not 0 or the sum is not finite; choice int32 [G], the lowest
-        candidate with the smallest finite score, -1 if none).  Device tensors; nothing is read back."""
-        torch, n_out = self.torch, self.n_outputs
-        e32 = isinstance(E_val, torch.Tensor) and E_val.dtype == torch.float32
-        E = _as_dev(E_val, torch, self.device, torch.float32 if e32 else None)
-        D = _as_dev(D_val, torch, self.device)
-        W = _as_dev(W_cand, torch, self.device)
-        if E.ndim != 3 or W.ndim != 4:
-            raise ValueError("holdout_choose takes E_val [G, T, cols] and W_cand [G, L, n_out, cols]")
-        g, t, cols = E.shape
-        nl = W.shape[1]
-        if tuple(W.shape) != (g, nl, n_out, cols) or tuple(D.shape) != (g, t, n_out):
-            raise ValueError(f"W_cand must be [{g}, L, {n_out}, {cols}] and D_val [{g}, {t}, {n_out}], not "
-                             f"{tuple(W.shape)} and {tuple(D.shape)}")
-        if not 1 <= nl <= self.HOLDOUT_MAX_GRID:
-            raise ValueError(f"W_cand holds {nl} candidates per group, the kernel takes 1 to {self.HOLDOUT_MAX_GRID}")
-        status = _as_dev(status, torch, self.device, torch.int32)
-        if status is not None and tuple(status.shape) != (g, nl):
-            raise ValueError(f"status must be [{g}, {nl}], not {tuple(status.shape)}")
-        self._check_groups(g)
-        with torch.cuda.device(self.device):
-            if E.data_ptr() % 16:               # (a view into a larger buffer: the kernel loads 16-byte units)
-                E = E.clone()
-            if W.data_ptr() % 16:
-                W = W.clone()
-            scores = torch.empty((g, nl), dtype=torch.float64, device=self.device)
-            choice = torch.empty((g,), dtype=torch.int32, device=self.device)
-            name = "esn_readout_holdout_score_f32" if e32 else "esn_readout_holdout_score"
-            check(getattr(self.lib, name)(ptr(E), ptr(D), ptr(W), g, t, int(transient), cols, n_out, ptr(self.t_scale),
-                                          ptr(self.t_shift), nl, ptr(status), ptr(scores), ptr(choice),
-                                          _lib.stream_handle()), name)
-        return scores, choice
-
     def _pilot_fit_method(self, u_shape, d_shape, transient, method, ridge, ridge_grid):
         """The checks of fit_pilots that need no device, on the shapes alone; returns the solve kernel ("chol" or
         "qr") of the stacked system."""
@@ -601,7 +269,7 @@ class ReservoirBank:
         if method not in ("qr", "chol", "auto"):
             raise ValueError(f"method must be 'qr', 'chol' or 'auto', not {method!r}")
         rows, cols = p * (t - int(transient)), self.n_reservoir + self.n_inputs
-        fits = min(rows, cols) <= 512 and self.n_outputs <= 8
+        fits = self.chol_fits(rows, cols)
         if method == "chol" and not fits:
             raise ValueError(f"method='chol' needs min(rows, cols) <= 512 and n_outputs <= 8: {p} pilots stack to "
                              f"{rows} rows against {cols} columns")
@@ -674,17 +342,8 @@ class ReservoirBank:
                                              self.t_scale, self.t_shift)
             scores, choice = self.holdout_choose(Es[P - 1], D[:, P - 1].contiguous(), transient, W_cand, status_l)
             del W_cand
-            with torch.cuda.device(self.device):
-                none = choice < 0
-                picked = lam.gather(1, choice.clamp(min=0).long()[:, None])[:, 0]
-                # (a group without a choice: solved at lambda 0 for the launch's sake, then zeroed and flagged)
-                W_out, status = self.solve(E_all, D_all, 0, method=kind, ridge=torch.where(none, torch.zeros_like(picked), picked))
-                W_out = torch.where(none[:, None, None], torch.zeros_like(W_out), W_out)
-                status = torch.where(none, torch.ones_like(status), status)
-                self.last_ridge_choice, self.last_ridge_scores, self.last_ridge_status = choice, scores, status_l
-                self.last_ridge_grid = lam
-                self.last_ridge_lambda = torch.where(none, torch.full_like(picked, float("nan")), picked)
-            self.last_solve_status = status
+            W_out, status = self._solve_at_winner(lam, status_l, scores, choice,
+                                                  lambda at: self.solve(E_all, D_all, 0, method=kind, ridge=at))
             self.fit_ridge = self.last_ridge_lambda
         self.set_readout(W_out)
         self.harvest_timeout = None if timed_out is None else timed_out.to(torch.int32)
@@ -755,81 +414,11 @@ class ReservoirBank:
                 raise _lib.EsnHipError("single-sequence cluster kernel: a workgroup timed out waiting for the others "
                                        "(the device is oversubscribed); outputs are invalid")
 
-    # ------------------------------------------------------------------ detector tail
-    def detect_count(self, Y, tx_bits, p_i, frames_per_group, n_sub, n_t, bits_per_sym,
-                     err=None, bits=None, want_xhat=False):
-        """Y [B,N,2 n_t] -> per-group int64 (errors, bits) accumulated into err/bits.  A float32 Y (predict with
-        io="f32") is read as it is by esn_detect_count_f32: the counts and X_hat are those of the widened Y."""
-        torch = self.torch
-        y32 = getattr(Y, "dtype", None) in (torch.float32, np.float32)
-        Y = _as_dev(Y, torch, self.device, torch.float32 if y32 else None)
-        b = Y.shape[0]
-        g = (b + frames_per_group - 1) // frames_per_group
-        p_i = _as_dev(p_i, torch, self.device)
-        tx_bits = _as_dev(tx_bits, torch, self.device, dtype=torch.uint8)
-        with torch.cuda.device(self.device):
-            if err is None:
-                err = torch.zeros(g, dtype=torch.int64, device=self.device)
-            if bits is None:
-                bits = torch.zeros(g, dtype=torch.int64, device=self.device)
-            xh = torch.empty((b, n_sub, 2 * n_t), dtype=torch.float64, device=self.device) if want_xhat else None
-            fn = self.lib.esn_detect_count_f32 if y32 else self.lib.esn_detect_count
-            check(fn(ptr(Y), b, int(frames_per_group), int(n_sub), int(n_t),
-                     int(bits_per_sym), ptr(p_i), ptr(tx_bits), ptr(err), ptr(bits),
-                     ptr(xh), _lib.stream_handle()), "esn_detect_count_f32" if y32 else "esn_detect_count")
-        return (err, bits, xh) if want_xhat else (err, bits)
-
-    def detect_remod(self, Y, tx_bits, p_i, frames_per_group, n_sub, cp, delay, n_t, bits_per_sym,
-                     err=None, bits=None, want_xhat=False, want_bits=False):
-        """detect_count and, in the same launch, the decisions re-modulated (esn_detect_remod): Y [B, N, 2 n_t] float64
-        -> D_hat [B, delay + cp + N, 2 n_t], the time-domain teacher rows of the decided symbols in the layout harvest
-        takes (delay zero rows, cyclic prefix, body).  tx_bits None: nothing is counted.  Returns
-        (D_hat, err, bits[, X_hat][, dec_bits]) -- err / bits are None without tx_bits, dec_bits uint8 [B, N m, n_t]."""
-        torch = self.torch
-        if getattr(Y, "dtype", None) in (torch.float32, np.float32):
-            raise ValueError("detect_remod reads float64 Y (predict with io='f64'): the tracked path has no float32 I/O")
-        Y = _as_dev(Y, torch, self.device)
-        b = Y.shape[0]
-        g = (b + frames_per_group - 1) // frames_per_group
-        p_i = _as_dev(p_i, torch, self.device)
-        tx_bits = _as_dev(tx_bits, torch, self.device, dtype=torch.uint8)
-        with torch.cuda.device(self.device):
-            if tx_bits is not None:
-                if err is None:
-                    err = torch.zeros(g, dtype=torch.int64, device=self.device)
-                if bits is None:
-                    bits = torch.zeros(g, dtype=torch.int64, device=self.device)
-            else:
-                err = bits = None
-            xh = torch.empty((b, n_sub, 2 * n_t), dtype=torch.float64, device=self.device) if want_xhat else None
-            db = torch.empty((b, n_sub * bits_per_sym, n_t), dtype=torch.uint8, device=self.device) if want_bits else None
-            D_hat = torch.empty((b, int(delay) + int(cp) + int(n_sub), 2 * n_t), dtype=torch.float64, device=self.device)
-            check(self.lib.esn_detect_remod(ptr(Y), b, int(frames_per_group), int(n_sub), int(cp), int(delay), int(n_t),
-                                            int(bits_per_sym), ptr(p_i), ptr(tx_bits), ptr(err), ptr(bits), ptr(xh),
-                                            ptr(db), ptr(D_hat), _lib.stream_handle()), "esn_detect_remod")
-        return (D_hat, err, bits) + ((xh,) if want_xhat else ()) + ((db,) if want_bits else ())
-
     # ------------------------------------------------------------------ helpers
-    def _scratch(self, name, nbytes):
-        """The bank's device scratch `name`, grown on demand to nbytes (None for 0).  Called under the device guard."""
-        if not nbytes:
-            return None
-        ws = getattr(self, name, None)
-        if ws is None or ws.numel() < nbytes:
-            ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
-            setattr(self, name, ws)
-        return ws
-
     def _error_word(self, ws, wbytes):
         """int32 view [1] of the error word that the two cluster kernels (paths "cluster_f64", "harvest_cluster")
         keep 64 bytes before the end of their workspace: non-zero after a workgroup gave up waiting for its peers."""
         return ws[wbytes - 64:wbytes - 60].view(self.torch.int32)
-
-    def _check_groups(self, g):
-        for name in ("in_scale", "in_shift", "t_scale", "t_shift"):
-            t = getattr(self, name)
-            if t is not None and t.shape[0] < g:
-                raise ValueError(f"{name} holds {t.shape[0]} groups, batch has {g}")
 
     def _noise_args(self, noise_mode, noise_u, shape):
         if self.noise == 0.0 or noise_mode in (None, "none"):

@@ -8,16 +8,16 @@ Linear, trained per pilot by 50 full-batch Adam steps (lr 0.01, MSE).
     FNN            the reference's model surface on already-windowed NumPy matrices
     trainMIMOFNN   the reference's trainMIMOModel('FNN', ...) for any antenna count
 
-The definition every layer follows is in include/esn_hip.h; tests/fnn_ref.py restates it in NumPy.  Float64 training
-only, one pilot per group, no float32 I/O."""
+What the FNN shares with the windowed ELM (elm.py) is in windowed.py.  The definition every layer follows is in
+include/esn_hip.h; tests/fnn_ref.py restates it in NumPy.  Float64 training only, one pilot per group, no float32 I/O."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib
 from ._lib import PRECISIONS, check, ptr
-from .batched import ReservoirBank, _as_dev
-from .elm import mimo_io, window_rows
+from .bankbase import _as_dev
+from .windowed import WindowedBank, mimo_io, train_mimo_windowed, window_rows  # noqa: F401  (importable from here)
 
 LDS_BYTES = 160 * 1024
 
@@ -49,31 +49,13 @@ def init_weights(k, n_hidden, n_out):
     return tuple(t.detach().numpy().astype(np.float64) for t in (fc1.weight, fc1.bias, fc2.weight, fc2.bias))
 
 
-class FnnBank:
+class FnnBank(WindowedBank):
+    W1 = b1 = W2 = b2 = loss = None
+    _work = None
+
     def __init__(self, n_inputs, n_outputs, n_hidden, window, n_groups=1, device=None):
-        torch = _lib.require_gpu()
-        self.torch, self.lib = torch, _lib.load()
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-        self.n_inputs, self.n_outputs, self.n_hidden = int(n_inputs), int(n_outputs), int(n_hidden)
-        self.window, self.n_groups = int(window), int(n_groups)
-        # scalings and the detector tail are the ESN's (a one-unit bank is their carrier, as in ElmBank)
-        self._ro = ReservoirBank(self.n_inputs, self.n_outputs, 1, np.zeros((1, 1)), np.zeros((1, self.n_inputs)),
-                                 np.zeros((1, self.n_outputs)), noise=0.0, device=self.device)
-        self.in_scale = self.in_shift = self.t_scale = self.t_shift = None
-        self.W1 = self.b1 = self.W2 = self.b2 = self.loss = None
-        self._work = None
-
-    def set_scaling(self, in_scale=None, in_shift=None, t_scale=None, t_shift=None):
-        """Per-group scalings, each [G, n] (or None = identity), as ElmBank.set_scaling."""
-        self._ro.set_scaling(in_scale, in_shift, t_scale, t_shift)
-        self.in_scale, self.in_shift = self._ro.in_scale, self._ro.in_shift
-        self.t_scale, self.t_shift = self._ro.t_scale, self._ro.t_shift
-
-    def _check_groups(self, g):
-        for name in ("in_scale", "in_shift", "t_scale", "t_shift"):
-            t = getattr(self, name)
-            if t is not None and t.shape[0] < g:
-                raise ValueError(f"{name} holds {t.shape[0]} groups, batch has {g}")
+        WindowedBank.__init__(self, n_inputs, n_outputs, n_hidden, window, device)
+        self.n_groups = int(n_groups)
 
     def _sets(self, params):
         """(W1, b1, W2, b2), one set or [n_sets, ...] -> four contiguous device tensors [n_sets, ...]."""
@@ -132,35 +114,16 @@ class FnnBank:
     def predict(self, U, frames_per_group, T=None, transient=0, precision="f64", out=None):
         """U [B, T_in, n_in] (frames ordered by group) -> Y [B, T - transient, n_out] (device, unscaled); group g reads
         its own trained set."""
-        torch = self.torch
-        if precision not in ("f64", "f16"):
-            raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
-        U = _as_dev(U, torch, self.device)
-        b, t_in = U.shape[0], U.shape[1]
-        T = t_in if T is None else int(T)
-        if not (0 <= int(transient) < T and t_in <= T):
-            raise ValueError(f"need 0 <= transient < T and T_in <= T (transient={transient}, T_in={t_in}, T={T})")
-        g = (b + frames_per_group - 1) // frames_per_group
-        self._check_groups(g)
-        if self.W1 is None:
-            raise AttributeError("W1: train (or set_weights) before predict")
-        if self.W1.shape[0] < g:
-            raise ValueError(f"the bank holds {self.W1.shape[0]} trained sets, batch needs {g}")
-        with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((b, T - transient, self.n_outputs), dtype=torch.float64, device=self.device)
+        U, b, t_in, T, out = self._predict_args(U, frames_per_group, T, transient, precision, out, self.W1,
+                                                "W1: train (or set_weights) before predict",
+                                                "the bank holds {} trained sets, batch needs {}")
+        with self.torch.cuda.device(self.device):
             check(self.lib.esn_fnn_predict(PRECISIONS[precision], self.n_inputs, self.n_hidden, self.window,
                                            self.n_outputs, ptr(self.W1), ptr(self.b1), ptr(self.W2), ptr(self.b2),
                                            ptr(self.in_scale), ptr(self.in_shift), ptr(self.t_scale), ptr(self.t_shift),
                                            ptr(U), b, int(frames_per_group), t_in, T, int(transient), ptr(out),
                                            _lib.stream_handle()), "esn_fnn_predict")
         return out
-
-    def detect_count(self, Y, tx_bits, p_i, frames_per_group, n_sub, n_t, bits_per_sym, err=None, bits=None,
-                     want_xhat=False):
-        """ReservoirBank.detect_count: Y [B, N, 2 n_t] -> per-group int64 (errors, bits)."""
-        return self._ro.detect_count(Y, tx_bits, p_i, frames_per_group, n_sub, n_t, bits_per_sym, err=err, bits=bits,
-                                     want_xhat=want_xhat)
 
 
 class FNN:
@@ -199,17 +162,5 @@ def trainMIMOFNN(y_CP, x_CP, N, N_t, CyclicPrefixLen, IsiDuration, hidden_size=1
     [ESN_input, ESN_output, model, Delay, fixed_delay, Delay_Min, Delay_Max, nForgetPoints, NMSE].  Training uses all
     windowed rows, unscaled, as the reference does; nForgetPoints includes `+= window - 1`; NMSE is computed on the
     reference's rows [0, N) of the un-cut output (its slice, kept, as trainMIMOELM does)."""
-    Delay = [fixed_delay] * (2 * N_t)
-    ESN_input, ESN_output = mimo_io(y_CP, x_CP, N, N_t, CyclicPrefixLen, fixed_delay)
-    nForgetPoints = fixed_delay + CyclicPrefixLen
-    inputs_window = window_rows(ESN_input, window)
-    targets_window = ESN_output[window - 1:, :]
-    model = FNN(ESN_input.shape[1] * window, hidden_size, 2 * N_t, init=init)
-    model.fit(inputs_window, targets_window)
-    x_hat_temp = np.zeros(ESN_output.shape)
-    x_hat_temp[window - 1:, :] = model.predict(inputs_window)
-    nForgetPoints += window - 1
-    x_hat = x_hat_temp[0:N, 0::2] + 1j * x_hat_temp[0:N, 1::2]
-    x = np.asarray(x_CP)[IsiDuration - 1:, :]
-    NMSE = sum(np.linalg.norm(x_hat[:, i] - x[:, i]) ** 2 / np.linalg.norm(x[:, i]) ** 2 for i in range(N_t))
-    return [ESN_input, ESN_output, model, Delay, fixed_delay, fixed_delay, fixed_delay, nForgetPoints, NMSE]
+    model = FNN(2 * np.shape(y_CP)[1] * window, hidden_size, 2 * N_t, init=init)
+    return train_mimo_windowed(model, y_CP, x_CP, N, N_t, CyclicPrefixLen, IsiDuration, window, fixed_delay)

@@ -22,7 +22,8 @@
     elm_point       one Eb/No point of the windowed ELM (elm.py, esn_elm_features / esn_elm_predict), the          points.py
                     reference's pinv-trained comparator, on the frames a DetectorSweep of the same seed detects
     fnn_point       the same for the windowed FNN (fnn.py, esn_fnn_train / esn_fnn_predict), the reference's          points.py
-                    Adam-trained comparator: one training per block, all 50 epochs in one launch
+                    Adam-trained comparator: one training per block, all 50 epochs in one launch; argument checks and
+                    chunk loop are elm_point's (points._windowed_point), the two differ in how a chunk is trained
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the

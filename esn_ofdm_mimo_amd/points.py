@@ -193,6 +193,62 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     return out
 
 
+def _check_windowed_point_args(slice, weights, precision, window, n_blocks, first_block, chunk_blocks, frames_per_block):
+    """What elm_point and fnn_point refuse alike, from the arguments alone."""
+    if slice not in ("aligned", "reference"):
+        raise ValueError(f"slice must be 'aligned' or 'reference', not {slice!r}")
+    if weights not in ("shared", "per_block"):
+        raise ValueError(f"weights must be 'shared' or 'per_block', not {weights!r}")
+    if precision not in ("f64", "f16"):
+        raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
+    if not isinstance(window, int) or not 1 <= window <= 16:
+        raise ValueError(f"window must be an integer in 1..16, not {window!r}")
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+
+
+def _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision, slice, train):
+    """The chunk loop of elm_point and fnn_point over blocks first_block .. first_block + n_blocks - 1: per chunk of g
+    blocks from b0 on, blocks_fast, the pilots as U [g, T, 2 n_r] and D [g, T, 2 n_t] (T = t_frame + delay, the teacher
+    delayed), train(U, D, scaling, b0, g) -- which returns a windowed.WindowedBank trained on them under
+    set_scaling(*scaling), inputs and teacher scaled by 1 / sqrt(var_x) -- then one predict over the chunk's data
+    frames, cut as `slice` says, and the detector tail into that chunk's part of the counters.  Returns (errors, bits):
+    int64 [n_blocks] on the device; nothing is read back."""
+    import numpy as np
+    torch, p = src.torch, src.p
+    n_in, n_out = 2 * p.n_r, 2 * p.n_t
+    F = int(frames_per_block or p.coherence_symbols)
+    first_block, n_blocks = int(first_block), int(n_blocks)
+    chunk = int(chunk_blocks or min(n_blocks, 4096))
+    d, T = p.delay, p.t_frame + p.delay
+    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    scale = 1.0 / np.sqrt(p.var_x(ebno_db))
+    for b0 in range(first_block, first_block + n_blocks, chunk):
+        g = min(chunk, first_block + n_blocks - b0)
+        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F)
+        scaling = (torch.full((g, n_in), scale, dtype=torch.float64, device=src.device), None,
+                   torch.full((g, n_out), scale, dtype=torch.float64, device=src.device), None)
+        U = torch.zeros((g, T, n_in), dtype=torch.float64, device=src.device)
+        D = torch.zeros((g, T, n_out), dtype=torch.float64, device=src.device)
+        U[:, :p.t_frame] = _view_real(data["pilot_y"])
+        D[:, d:] = _view_real(data["pilot_x"])
+        bank = train(U, D, scaling, b0, g)
+        dy = _view_real(data["data_y"])
+        if slice == "aligned":
+            Y = bank.predict(dy, F, T=T, transient=p.forget, precision=precision)
+        else:
+            Y = bank.predict(dy, F, T=T, transient=0, precision=precision)[:, :p.n_sub].contiguous()
+        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
+        lo = b0 - first_block
+        bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g])
+    return errors, nbits
+
+
 def elm_weights(n_hidden, k, gain, seed, block=None):
     """W_in = gain U(-1, 1) [n_hidden, k], then b = U(-1, 1) [n_hidden], from RandomState(seed) -- or, for the set of
     one global block, RandomState([seed, block])."""
@@ -213,50 +269,30 @@ def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0
     :570-571), delay + cp rows early.  weights "shared": one (W_in, b) = elm_weights(seed); "per_block": one per global
     block.  Returns (errors, bits): int64 [n_blocks] on the device; nothing is read back inside the chunk loop (a fit
     the Cholesky solve flags has the whole point redone with method="qr" after it)."""
-    if slice not in ("aligned", "reference"):
-        raise ValueError(f"slice must be 'aligned' or 'reference', not {slice!r}")
-    if weights not in ("shared", "per_block"):
-        raise ValueError(f"weights must be 'shared' or 'per_block', not {weights!r}")
-    if precision not in ("f64", "f16"):
-        raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
+    _check_windowed_point_args(slice, weights, precision, window, n_blocks, first_block, chunk_blocks, frames_per_block)
     if method not in ("auto", "qr", "chol"):
         raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
-    if not isinstance(window, int) or not 1 <= window <= 16:
-        raise ValueError(f"window must be an integer in 1..16, not {window!r}")
     if not isinstance(n_hidden, int) or not 1 <= n_hidden <= 1024:
         raise ValueError(f"n_hidden must be an integer in 1..1024, not {n_hidden!r}")
     if not gain > 0:
         raise ValueError(f"gain = {gain} must be positive")
     if ridge is not None and not float(ridge) >= 0:
         raise ValueError(f"ridge = {ridge} must be None or non-negative")
-    if int(n_blocks) < 1 or int(first_block) < 0:
-        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
-    if chunk_blocks is not None and int(chunk_blocks) < 1:
-        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
-    if frames_per_block is not None and int(frames_per_block) < 1:
-        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
     import numpy as np
     from .elm import ElmBank
-    torch, p = src.torch, src.p
+    p = src.p
     n_in, n_out = 2 * p.n_r, 2 * p.n_t
-    if window * n_in > 256:
-        raise ValueError(f"window * 2 n_r = {window * n_in}: the ELM kernels serve up to 256")
-    F = int(frames_per_block or p.coherence_symbols)
-    first_block, n_blocks = int(first_block), int(n_blocks)
-    chunk = int(chunk_blocks or min(n_blocks, 4096))
-    d, T = p.delay, p.t_frame + p.delay
-    transient = max(p.forget, window - 1)
-    shared = elm_weights(n_hidden, window * n_in, gain, seed) if weights == "shared" else None
+    k, transient = window * n_in, max(p.forget, window - 1)
+    if k > 256:
+        raise ValueError(f"window * 2 n_r = {k}: the ELM kernels serve up to 256")
+    shared = elm_weights(n_hidden, k, gain, seed) if weights == "shared" else None
     bank = None
-    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    flagged = torch.zeros((), dtype=torch.int64, device=src.device)
-    scale = 1.0 / np.sqrt(p.var_x(ebno_db))
-    for b0 in range(first_block, first_block + n_blocks, chunk):
-        g = min(chunk, first_block + n_blocks - b0)
-        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F)
+    flagged = src.torch.zeros((), dtype=src.torch.int64, device=src.device)
+
+    def train(U, D, scaling, b0, g):
+        nonlocal bank
         if shared is None:
-            sets = [elm_weights(n_hidden, window * n_in, gain, seed, b0 + i) for i in range(g)]
+            sets = [elm_weights(n_hidden, k, gain, seed, b0 + i) for i in range(g)]
             W_in, b = np.stack([s[0] for s in sets]), np.stack([s[1] for s in sets])
         else:
             W_in, b = shared
@@ -264,22 +300,13 @@ def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0
             bank = ElmBank(n_in, n_out, n_hidden, window, W_in, b, n_groups=g, device=src.device)
         elif shared is None:
             bank.set_weights(W_in, b)
-        bank.set_scaling(torch.full((g, n_in), scale, dtype=torch.float64, device=src.device), None,
-                         torch.full((g, n_out), scale, dtype=torch.float64, device=src.device), None)
-        U = torch.zeros((g, T, n_in), dtype=torch.float64, device=src.device)
-        D = torch.zeros((g, T, n_out), dtype=torch.float64, device=src.device)
-        U[:, :p.t_frame] = _view_real(data["pilot_y"])
-        D[:, d:] = _view_real(data["pilot_x"])
+        bank.set_scaling(*scaling)
         bank.fit(U, D, transient=transient, method=method, ridge=ridge, repair=False)
-        flagged += bank.fit_status.ne(0).sum()
-        dy = _view_real(data["data_y"])
-        if slice == "aligned":
-            Y = bank.predict(dy, F, T=T, transient=p.forget, precision=precision)
-        else:
-            Y = bank.predict(dy, F, T=T, transient=0, precision=precision)[:, :p.n_sub].contiguous()
-        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
-        lo = b0 - first_block
-        bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g])
+        flagged.add_(bank.fit_status.ne(0).sum())
+        return bank
+
+    errors, nbits = _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks,
+                                    precision, slice, train)
     if method != "qr" and int(flagged) != 0:
         return elm_point(src, ebno_db, snr_idx, n_blocks, n_hidden=n_hidden, window=window, gain=gain, ridge=ridge,
                          method="qr", precision=precision, slice=slice, weights=weights, first_block=first_block,
@@ -307,65 +334,33 @@ def fnn_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, window=8, epochs
     weights as in elm_point ("reference": rows [0, N) of the un-cut output, the slice the reference's FNN branch
     takes).  precision is the prediction's; the training is float64.  Returns (errors, bits): int64 [n_blocks] on the
     device; nothing is read back inside the chunk loop."""
-    if slice not in ("aligned", "reference"):
-        raise ValueError(f"slice must be 'aligned' or 'reference', not {slice!r}")
-    if weights not in ("shared", "per_block"):
-        raise ValueError(f"weights must be 'shared' or 'per_block', not {weights!r}")
-    if precision not in ("f64", "f16"):
-        raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
-    if not isinstance(window, int) or not 1 <= window <= 16:
-        raise ValueError(f"window must be an integer in 1..16, not {window!r}")
+    _check_windowed_point_args(slice, weights, precision, window, n_blocks, first_block, chunk_blocks, frames_per_block)
     if not isinstance(n_hidden, int) or n_hidden < 1:
         raise ValueError(f"n_hidden must be a positive integer, not {n_hidden!r}")
     if not isinstance(epochs, int) or epochs < 1:
         raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
     if not lr >= 0:
         raise ValueError(f"lr = {lr} must be non-negative")
-    if int(n_blocks) < 1 or int(first_block) < 0:
-        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
-    if chunk_blocks is not None and int(chunk_blocks) < 1:
-        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
-    if frames_per_block is not None and int(frames_per_block) < 1:
-        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
     import numpy as np
     from .fnn import FnnBank, train_shape_error
-    torch, p = src.torch, src.p
+    p = src.p
     n_in, n_out = 2 * p.n_r, 2 * p.n_t
-    d, T = p.delay, p.t_frame + p.delay
-    why = train_shape_error(n_in, n_hidden, window, n_out, T)
+    why = train_shape_error(n_in, n_hidden, window, n_out, p.t_frame + p.delay)
     if why:
         raise ValueError("the FNN training kernel does not serve this shape: " + why)
-    F = int(frames_per_block or p.coherence_symbols)
-    first_block, n_blocks = int(first_block), int(n_blocks)
-    chunk = int(chunk_blocks or min(n_blocks, 4096))
-    transient = max(p.forget, window - 1)
-    k = window * n_in
+    k, transient = window * n_in, max(p.forget, window - 1)
     shared = fnn_weights(n_hidden, k, n_out, seed) if weights == "shared" else None
-    bank = FnnBank(n_in, n_out, n_hidden, window, n_groups=min(chunk, n_blocks), device=src.device)
-    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    scale = 1.0 / np.sqrt(p.var_x(ebno_db))
-    for b0 in range(first_block, first_block + n_blocks, chunk):
-        g = min(chunk, first_block + n_blocks - b0)
-        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F)
+    bank = FnnBank(n_in, n_out, n_hidden, window, n_groups=min(int(chunk_blocks or 4096), int(n_blocks)),
+                   device=src.device)
+
+    def train(U, D, scaling, b0, g):
         if shared is None:
             sets = [fnn_weights(n_hidden, k, n_out, seed, b0 + i) for i in range(g)]
             init = tuple(np.stack([s[j] for s in sets]) for j in range(4))
         else:
             init = shared
-        bank.set_scaling(torch.full((g, n_in), scale, dtype=torch.float64, device=src.device), None,
-                         torch.full((g, n_out), scale, dtype=torch.float64, device=src.device), None)
-        U = torch.zeros((g, T, n_in), dtype=torch.float64, device=src.device)
-        D = torch.zeros((g, T, n_out), dtype=torch.float64, device=src.device)
-        U[:, :p.t_frame] = _view_real(data["pilot_y"])
-        D[:, d:] = _view_real(data["pilot_x"])
-        bank.train(U, D, init, transient=transient, epochs=epochs, lr=lr)
-        dy = _view_real(data["data_y"])
-        if slice == "aligned":
-            Y = bank.predict(dy, F, T=T, transient=p.forget, precision=precision)
-        else:
-            Y = bank.predict(dy, F, T=T, transient=0, precision=precision)[:, :p.n_sub].contiguous()
-        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
-        lo = b0 - first_block
-        bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g])
-    return errors, nbits
+        bank.set_scaling(*scaling)
+        return bank.train(U, D, init, transient=transient, epochs=epochs, lr=lr)
+
+    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision,
+                           slice, train)

@@ -8,9 +8,10 @@ import numpy as np
 
 from . import _lib
 from . import reservoirs as _reservoirs
-from .batched import ReservoirBank, _lambdas
+from .batched import ReservoirBank
 from .frames import FrameSource, _view_real
 from .link import LinkParams
+from .readout import _lambdas
 
 
 def blocks_for_rank(rank, world_size, n_blocks):
