@@ -12,7 +12,7 @@ NOISE_NONE, NOISE_TENSOR, NOISE_COUNTER = 0, 1, 2
 ABI_VERSION = 10
 MEM_DEVICE, MEM_HOST = 0, 1
 # enum esn_path, by value: the recurrence kernel a call dispatches to (recur_path below)
-PATHS = ("mfma", "skew16", "f64_valu", "f64_mfma", "cluster_f64", "big_predict", "big_harvest", "harvest_cluster", "rs")
+PATHS = ("mfma", "skew16", "f64_valu", "f64_mfma", "cluster_f64", "big_predict", "big_harvest", "harvest_cluster")
 
 
 class Shape(C.Structure):

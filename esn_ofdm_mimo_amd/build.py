@@ -11,9 +11,6 @@ SOURCES = ["esn_api.hip", "esn_host.hip", "esn_pack.hip", "esn_recur_f64.hip", "
            "esn_recur_big.hip", "esn_recur_cluster.hip", "esn_recur_mfma_f32.hip", "esn_recur_mfma_f16.hip", "esn_recur_mfma_bf16.hip", "esn_recur_skew16.hip", "esn_harvest_cluster.hip",
            "esn_solve_qr.hip", "esn_solve_chol.hip", "esn_solve_chol_big.hip", "esn_loo.hip", "esn_holdout.hip", "esn_gram.hip", "esn_detect.hip", "esn_remod.hip", "esn_gen.hip", "esn_reservoir.hip", "esn_specrad_split.hip", "esn_baseline.hip", "esn_chantrack.hip", "esn_chanstat.hip", "esn_coded.hip",
            "esn_elm.hip", "esn_fnn.hip"]
-# the register-resident-state predict kernel is a kept negative result: it is compiled only into
-# experiment builds (`ESN_WITH_RS=1 python esn_ofdm_mimo_amd/build.py --variant rs`), never into the product library
-WITH_RS = os.environ.get("ESN_WITH_RS") == "1"
 # -fno-slp-vectorize: SLP turns adjacent float32 adds/fmas into v_pk_*_f32, which issue far slower
 # than two scalar ops beside MFMAs (measured: predict kernel 13.97 -> 13.42 ms)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -46,10 +43,7 @@ def _build(LIB, bdir, extra, verbose):
     objs = []
     procs = []
     os.makedirs(os.path.join(PKG, bdir), exist_ok=True)
-    sources = SOURCES + (["esn_recur_rs.hip"] if WITH_RS and LIB.endswith("_rs.so") else [])
-    if len(sources) > len(SOURCES):
-        extra = list(extra) + ["-DESN_WITH_RS"]
-    for src in sources:
+    for src in SOURCES:
         obj = os.path.join(PKG, bdir, src.replace(".hip", ".o"))
         objs.append(obj)
         per_file = os.environ.get("ESN_FLAGS_" + src.replace(".hip", "").upper(), "").split()

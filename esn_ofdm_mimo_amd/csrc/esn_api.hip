@@ -30,9 +30,7 @@ static int (&fail)(int, const char*, ...) = api_fail;
 enum KnobRule {
     KNOB_FLAG,       // first character '0' / '1', whichever the default is not, flips it; anything else: the default
     KNOB_INT,        // atoi
-    KNOB_TRIPLE,     // "a,b,c", all positive; anything else: {0, 0, 0}
-    KNOB_BIG_NT,     // "4": 4; anything else: 2
-    KNOB_HCLUSTER    // "0" off, "4" / "8" members per cluster; anything else: 1 (on, pairs)
+    KNOB_TRIPLE      // "a,b,c", all positive; anything else: {0, 0, 0}
 };
 struct KnobRow {
     const char* key;     // esn_debug_set
@@ -48,16 +46,11 @@ static const KnobRow kKnobTable[] = {
     {"chol_skip", "ESN_CHOL_SKIP", offsetof(Knobs, chol_skip), KNOB_INT, 0},
     {"chol_dma", "ESN_CHOL_DMA", offsetof(Knobs, chol_dma), KNOB_FLAG, 1},
     {"f64_mfma", "ESN_F64_MFMA", offsetof(Knobs, f64_mfma), KNOB_FLAG, 1},
-    // opt-in: measured slower than the skewed LDS-state kernel; read by ESN_WITH_RS=1 builds only
-    {"rs", "ESN_RS", offsetof(Knobs, rs), KNOB_FLAG, 0},
     {"big_gemm", "ESN_BIG_GEMM", offsetof(Knobs, big_gemm), KNOB_FLAG, 1},
     {"cluster", "ESN_CLUSTER", offsetof(Knobs, cluster), KNOB_FLAG, 1},
-    {"big_nt", "ESN_BIG_NT", offsetof(Knobs, big_nt), KNOB_BIG_NT, 2},
-    {"big_pipe", "ESN_BIG_PIPE", offsetof(Knobs, big_pipe), KNOB_FLAG, 1},
-    {"harvest_gemm", "ESN_HARVEST_GEMM", offsetof(Knobs, harvest_gemm), KNOB_FLAG, 0},
     {"gen_ko", nullptr, offsetof(Knobs, gen_ko), KNOB_INT, 0},
     {"s16", "ESN_S16", offsetof(Knobs, s16), KNOB_FLAG, 1},
-    {"hcluster", "ESN_HCLUSTER", offsetof(Knobs, hcluster), KNOB_HCLUSTER, 1},
+    {"hcluster", "ESN_HCLUSTER", offsetof(Knobs, hcluster), KNOB_FLAG, 1},
     {"detect_fixed", "ESN_DETECT_FIXED", offsetof(Knobs, detect_fixed), KNOB_FLAG, 1},
 };
 
@@ -72,8 +65,6 @@ static void knob_parse(const KnobRow& r, const char* v, Knobs& k) {
             for (int i = 0; i < 3; ++i) out[i] = ok ? t[i] : 0;
             break;
         }
-        case KNOB_BIG_NT: *out = (v && v[0] == '4') ? 4 : 2; break;
-        case KNOB_HCLUSTER: *out = (v && (v[0] == '0' || v[0] == '4' || v[0] == '8')) ? v[0] - '0' : 1; break;
     }
 }
 
@@ -135,11 +126,6 @@ int esn_abi_version(void) { return 10; }
 
 int esn_debug_set(const char* key, const char* value) {
     if (!key) return fail(-1, "esn_debug_set: null key");
-#ifndef ESN_WITH_RS
-    if (!strcmp(key, "rs"))
-        return (value && value[0] == '1')
-                   ? fail(-3, "esn_debug_set: the register-state kernel is not in this build (ESN_WITH_RS=1)") : 0;
-#endif
     for (const KnobRow& r : kKnobTable)
         if (!strcmp(key, r.key)) { knob_parse(r, value, knobs()); return 0; }
     return fail(-1, "esn_debug_set: unknown key '%s'", key);
@@ -261,32 +247,28 @@ static void fill_batch(RecurParams& p, int precision, int n_frames, int frames_p
 
 // ---- THE dispatch rule: which kernel serves a recurrence call (an esn_path) and how much workspace the size
 // queries advertise for it.  The launches, esn_*_workspace_bytes and esn_recur_path all ask here; the order of the
-// ladder is the specification.  `p` is filled by fill_common + fill_batch (+ noise_mode, S, transient on a launch;
-// zero in a query: only the ESN_WITH_RS experiment reads them).
+// ladder is the specification.  `p` is filled by fill_common + fill_batch.
 struct Plan {
     int path;                  // enum esn_path
     size_t workspace_bytes;    // what the size query answers; the path reads that many bytes iff path_uses_workspace
-    int hc_members;            // ESN_PATH_HARVEST_CLUSTER: workgroups per cluster
 };
 static bool path_uses_workspace(int path) {
     return path == ESN_PATH_CLUSTER_F64 || path == ESN_PATH_BIG_PREDICT || path == ESN_PATH_BIG_HARVEST ||
            path == ESN_PATH_HARVEST_CLUSTER;
 }
 
-static Plan plan_recur(int precision, const RecurParams& p, bool io32, bool workspace_lent) {
+static Plan plan_recur(int precision, const RecurParams& p, bool workspace_lent) {
     const Knobs& k = knobs();
     const bool half = precision == ESN_F16 || precision == ESN_BF16;
-    Plan pl = {ESN_PATH_MFMA, 0, 0};
+    Plan pl = {ESN_PATH_MFMA, 0};
     if (workspace_lent) {
         // ONE float64 sequence (the reference's own call pattern): the matrix resident in the LDS of a cluster of
         // workgroups that exchange the state through L2 every step (esn_recur_cluster.hip)
         if (k.cluster && cluster_applies(precision, p))
-            return {ESN_PATH_CLUSTER_F64, cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, p.harvest != 0), 0};
-        // harvest, 257..512 units, fp16/bf16: clusters of workgroups with the matrix resident in registers / LDS
-        if (p.harvest && k.hcluster && harvest_cluster_applies(precision, p)) {
-            const int members = k.hcluster == 1 ? 2 : k.hcluster;
-            return {ESN_PATH_HARVEST_CLUSTER, harvest_cluster_workspace_bytes(p.n_groups, members, p.n_wsets), members};
-        }
+            return {ESN_PATH_CLUSTER_F64, cluster_workspace_bytes(p.n_res, p.n_in, p.n_out, p.harvest != 0)};
+        // harvest, 257..512 units, fp16/bf16: pairs of workgroups with the matrix resident in registers / LDS
+        if (p.harvest && k.hcluster && harvest_cluster_applies(precision, p))
+            return {ESN_PATH_HARVEST_CLUSTER, harvest_cluster_workspace_bytes(p.n_groups, p.n_wsets)};
         // large reservoirs: one GEMM launch per step
         if (p.harvest ? big_harvest_applies(precision, p) : (p.g.big && big_path_applies(precision, p))) {
             pl.workspace_bytes = p.harvest ? big_harvest_workspace_bytes(p.n_groups, p.g.Kp)
@@ -298,17 +280,9 @@ static Plan plan_recur(int precision, const RecurParams& p, bool io32, bool work
         }
     }
     if (!p.harvest) {
-#ifdef ESN_WITH_RS
-        // N_res 257..512, fp16/bf16: state in registers, one wave per SIMD (tiles of 128 slots like the skewed kernel);
-        // its buffer descriptors are 31-bit
-        if (!io32 && k.rs && rs_path_applies(precision, p) &&
-            (size_t)p.n_frames * (p.S - p.transient) * p.n_out * 8 < 0x7fffffffu &&
-            (size_t)p.n_groups * p.wout_stride < 0x7fffffffu) { pl.path = ESN_PATH_RS; return pl; }
-#endif
         // N_res 257..512, fp16/bf16: the skewed schedule on 16x16x32 MFMAs (the chip holds a higher clock on that shape)
         if (p.g.s16 && p.g.skew && k.s16 && half) { pl.path = ESN_PATH_SKEW16; return pl; }
     }
-    (void)io32;
     pl.path = use_f64_mfma(precision, p) ? ESN_PATH_F64_MFMA : precision == ESN_F64 ? ESN_PATH_F64_VALU : ESN_PATH_MFMA;
     return pl;
 }
@@ -316,22 +290,19 @@ static Plan plan_recur(int precision, const RecurParams& p, bool io32, bool work
 // plan, the ONE workspace check, launch
 static int launch_plan(const char* who, const char* size_query, int precision, RecurParams& p, bool io32,
                        void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    const Plan pl = plan_recur(precision, p, io32, workspace != nullptr);
+    const Plan pl = plan_recur(precision, p, workspace != nullptr);
     if (path_uses_workspace(pl.path) && workspace_bytes < pl.workspace_bytes)
         return fail(-1, "%s: workspace holds %zu bytes, %s says %zu", who, workspace_bytes, size_query,
                     pl.workspace_bytes);
     int e = -1;
     switch (pl.path) {
         case ESN_PATH_CLUSTER_F64: e = launch_recur_cluster(p, workspace, stream); break;
-        case ESN_PATH_HARVEST_CLUSTER: e = launch_harvest_cluster(precision, p, pl.hc_members, workspace, stream); break;
+        case ESN_PATH_HARVEST_CLUSTER: e = launch_harvest_cluster(precision, p, workspace, stream); break;
         case ESN_PATH_BIG_HARVEST: e = launch_harvest_big(precision, p, workspace, stream); break;
         case ESN_PATH_BIG_PREDICT:
             p.Fpad = round_up(p.F, 16);
             e = launch_recur_big(precision, p, wout_big_offset(precision, p.n_out, p.g), workspace, stream, io32);
             break;
-#ifdef ESN_WITH_RS
-        case ESN_PATH_RS: e = launch_recur_rs(precision, p, wout_big_offset(precision, p.n_out, p.g), stream); break;
-#endif
         case ESN_PATH_SKEW16: e = launch_recur_skew16(precision, p, stream, io32); break;
         case ESN_PATH_F64_MFMA: e = launch_recur_f64_mfma(p, stream); break;
         case ESN_PATH_F64_VALU: e = launch_recur_f64(p, stream); break;
@@ -405,7 +376,7 @@ size_t esn_predict_workspace_bytes(int precision, const esn_shape_t* shape, int 
     if (n_frames <= 0 || frames_per_group <= 0) return 0;
     if (fill_common(p, precision, shape, "esn_predict_workspace_bytes")) return 0;
     fill_batch(p, precision, n_frames, frames_per_group);
-    return plan_recur(precision, p, false, true).workspace_bytes;
+    return plan_recur(precision, p, true).workspace_bytes;
 }
 
 size_t esn_harvest_workspace_bytes(int precision, const esn_shape_t* shape, int n_groups) {
@@ -413,7 +384,7 @@ size_t esn_harvest_workspace_bytes(int precision, const esn_shape_t* shape, int 
     if (n_groups <= 0) return 0;
     if (fill_common(p, precision, shape, "esn_harvest_workspace_bytes", true)) return 0;
     fill_batch(p, precision, n_groups, 1);
-    return plan_recur(precision, p, false, true).workspace_bytes;
+    return plan_recur(precision, p, true).workspace_bytes;
 }
 
 int esn_recur_path(int harvest, int precision, const esn_shape_t* shape, int n_sequences, int frames_per_group,
@@ -425,7 +396,7 @@ int esn_recur_path(int harvest, int precision, const esn_shape_t* shape, int n_s
     if (n_sequences <= 0 || frames_per_group <= 0)
         return fail(-1, "esn_recur_path: invalid sizes (n_sequences=%d F=%d)", n_sequences, frames_per_group);
     fill_batch(p, precision, n_sequences, frames_per_group);
-    return plan_recur(precision, p, false, have_workspace != 0).path;
+    return plan_recur(precision, p, have_workspace != 0).path;
 }
 
 static int harvest_common(int precision, const esn_shape_t* shape, const void* packed_w, const double* in_scale,

@@ -25,8 +25,6 @@ struct Geometry {
     int skew;        // predict: the two waves of a SIMD run one third of a step apart (esn_recur_mfma_impl.h)
     int big;         // fp16/bf16, N_res > 1024: the launch-per-step GEMM path (esn_recur_big.hip) serves this shape;
                      // the packed read-out then carries that path's image behind the persistent kernel's
-    int rs;          // fp16/bf16: the register-resident-state kernel (esn_recur_rs.hip) serves this shape; the packed
-                     // read-out then carries that kernel's image behind the persistent kernel's
     int s16;         // fp16/bf16: the 16x16x32 skewed predict kernel (esn_recur_skew16_impl.h) serves this shape; the
                      // packed weights and read-out then carry that kernel's images behind the 32x32x16 ones
     int m64;         // ESN_F64: 1 = the float64 matrix-pipe kernel (esn_recur_f64_mfma.hip) fits this shape;
@@ -306,17 +304,12 @@ struct Knobs {
     int chol_dma;          // 1 (default): the LDS Cholesky solve feeds its Gram and W_out passes of float32 E by LDS-DMA
                            // rings; 0: the register-staged passes (A/B and bitwise tests)
     int f64_mfma;          // 1 (default): float64 batches run on the matrix pipe; 0: vector-ALU kernel (A/B tests)
-    int rs;                // 1: fp16/bf16 predict at N_res 257..512 runs the register-resident-state kernel (default 0:
-                           // correct but 17 % slower than the skewed LDS-state kernel on MI355X)
     int big_gemm;          // 1 (default): N_res > 1024 predict runs as one GEMM launch per step when a workspace is given
     int cluster;           // 1 (default): ONE float64 sequence runs on the LDS-resident cluster kernel when a workspace is given
-    int big_nt;            // N_res > 1024 predict: 4 = the 4-wave 128 x 128 variant of big_step_kernel (slower: A/B only); default 2
-    int big_pipe;          // 1 (default): big_step_kernel's four-stage pipelined main loop; 0: the round-2 loop (A/B runs)
-    int harvest_gemm;      // 1: harvests of 257..1024 units (>= 64 pilots) also take the GEMM-per-step path (A/B; slower)
     int gen_ko;            // frame generator knock-out mask for tools/time_gen.py (timing only, wrong frames)
     int s16;               // 1 (default): fp16/bf16 predict at 257..512 units on the 16x16x32 kernel; 0: the 32x32x16 one (A/B)
     int hcluster;          // 1 (default): fp16/bf16 harvest at 257..512 units on the cluster kernel (two members per cluster)
-                           // when a workspace is given; 4 / 8: that many members (A/B); 0: the persistent kernel
+                           // when a workspace is given; 0: the persistent kernel (A/B and the tests' reference)
     int detect_fixed;      // 1 (default): the detector tail at (N 128, n_t 4, 16-QAM) runs its fixed-shape instance; 0: every
                            // call runs the generic kernel (A/B and bitwise tests)
 };

@@ -5,7 +5,7 @@
 // frames).  The persistent harvest kernel (esn_recur_mfma_impl.h, HARVEST) gives a tile of 32 pilots to one workgroup,
 // which re-streams the whole 557 KB weight image from L2 every timestep: 64 workgroups on 256 CUs, each bound by its
 // CU's L2 port (19 k cycles per step, 5 % of the MFMA peak); more, smaller tiles only multiply the aggregate stream
-// (DESIGN 3.1).  Here a CLUSTER of C co-resident workgroups owns 8 C pilots for all T - 1 steps: member c keeps rows
+// (DESIGN 3.1).  Here a CLUSTER of C = 2 co-resident workgroups owns 8 C pilots for all T - 1 steps: member c keeps rows
 // [512 c / C, 512 (c + 1) / C) of Wext = [W | W_in | W_feedb] -- fragments of the 16x16x32 weight image of
 // esn_pack_weights, as they are -- in REGISTERS, the fragment-major state image of the cluster's pilots in LDS (the
 // layout of esn_recur_skew16_impl.h), and per step
@@ -25,10 +25,11 @@
 
 namespace esn {
 
-// Cluster shapes: C workgroups (row slices of 512 / C rows) own P = 8 C pilots -- every member publishes 8 KB per step
-// whatever C is, and gathers (C - 1) x 8 KB.  C = 2 (256 rows and 16 pilots per workgroup, ONE peer, 8 KB gathered) is
-// the default: the step is the hand-off, and the hand-off is its bytes.  C = 8 (64 rows x 64 pilots, 56 KB gathered:
-// the first version) and C = 4 stay instantiated for A/B runs (debug knob hcluster = 8 / 4).
+// Cluster shape: C workgroups (row slices of 512 / C rows) own P = 8 C pilots -- every member publishes 8 KB per step
+// whatever C is, and gathers (C - 1) x 8 KB.  C = 2 (256 rows and 16 pilots per workgroup, ONE peer, 8 KB gathered): the
+// step is the hand-off, and the hand-off is its bytes.  (C = 8, the first version -- 64 rows x 64 pilots, 56 KB
+// gathered -- and C = 4 were slower: DESIGN.md 3.9.)
+constexpr int HC_C = 2;
 constexpr int HC_NT = 256;                        // 4 waves: NWR row groups x NWC pilot-tile groups
 constexpr int HC_NKK = 17;
 constexpr uint32_t HC_SPIN_LIMIT = 1u << 22;
@@ -36,12 +37,12 @@ constexpr unsigned long long HC_TAGMASK = 0x4000400040004000ULL;
 
 // clusters: the pilots of one weight set (groups g with (g + rot) % n_wsets == w; all of them when the reservoir is
 // shared) are cut into runs of 8 C; cluster k serves set k % n_wsets, run k / n_wsets
-static inline int hc_clusters(int n_pilots, int C, int n_wsets) {
+static inline int hc_clusters(int n_pilots, int n_wsets) {
     const int per_set = (n_pilots + n_wsets - 1) / n_wsets;
-    return n_wsets * ((per_set + 8 * C - 1) / (8 * C));
+    return n_wsets * ((per_set + 8 * HC_C - 1) / (8 * HC_C));
 }
-size_t harvest_cluster_workspace_bytes(int n_pilots, int C, int n_wsets) {
-    return (size_t)hc_clusters(n_pilots, C, n_wsets) * 2 * C * 8 * 1024 + 64;   // two parities x C members x 8 KB, + error word
+size_t harvest_cluster_workspace_bytes(int n_pilots, int n_wsets) {
+    return (size_t)hc_clusters(n_pilots, n_wsets) * 2 * HC_C * 8 * 1024 + 64;   // two parities x C members x 8 KB, + error word
 }
 
 __device__ __forceinline__ unsigned long long hc_tag_bits(int tag) {         // tag 1..15 -> bit 14 of each of four halves
@@ -49,8 +50,9 @@ __device__ __forceinline__ unsigned long long hc_tag_bits(int tag) {         // 
            ((unsigned long long)((tag >> 2) & 1) << 46) | ((unsigned long long)((tag >> 3) & 1) << 62);
 }
 
-template <typename TR, int NOISE, int C>
+template <typename TR, int NOISE>
 __global__ __launch_bounds__(HC_NT) void harvest_cluster_kernel(RecurParams p, int n_clusters, unsigned long long* xch) {
+    constexpr int C = HC_C;
     constexpr int ROWS = 512 / C;                  // rows of Wext per member
     constexpr int RT = ROWS / 16, CT = C / 2;      // 16-row tiles per member, 16-pilot tiles per cluster
     constexpr int P = 16 * CT;                     // pilots per cluster
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(HC_NT) void harvest_cluster_kernel(RecurParams p, i
     if (tid == 0) sh_dead = 0;
 
     // ---- resident operands: the wave's WR row tiles x 17 groups of weight fragments live in REGISTERS for the whole
-    // launch (136 or 272 of the 512 a lone wave per SIMD may hold): global row tile grt = c RT + vr WR + i of the 16x16x32
+    // launch (272 of the 512 a lone wave per SIMD may hold, less the LDS slab): global row tile grt = c RT + vr WR + i of the 16x16x32
     // image, fragment (kk, grt) at (((grt / 4) NKK + kk) 4 + grt % 4) KB.  Only the state image is in LDS.
     u32x4 areg[KREG][WR];
     char* wl = hsm + ZF_BYTES + (size_t)wave * WL_WAVE + lane16;             // this wave's slab: [kk - KREG][i][lane][16 B]
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(HC_NT) void harvest_cluster_kernel(RecurParams p, i
         }
     };
     // ---- [U ; F] staging: ALL 256 threads share the 32 positions x P pilots of the group: thread (pilot sf = tid % P,
-    // slice sq = tid / P) builds positions EPT sq .. EPT sq + EPT - 1 of its pilot (EPT = P / 8 = 2, 4 or 8 values: with
+    // slice sq = tid / P) builds positions EPT sq .. EPT sq + EPT - 1 of its pilot (EPT = P / 8 = 2 values: with
     // 64 threads doing eight each, as the first version had it, the staging state alone took 96 registers of every lane):
     // inputs row s + 1 scaled (pyESN.py:180-182), teacher row s scaled
     constexpr int EPT = P / 8;
@@ -409,11 +411,11 @@ bool harvest_cluster_applies(int precision, const RecurParams& p) {
            p.n_groups >= 1 && (p.n_res % 4) == 0 && (p.n_res + p.n_in) % 4 == 0;
 }
 
-template <typename TR, int C>
+template <typename TR>
 static int launch_hc(const RecurParams& p, int n_clusters, unsigned long long* xch, hipStream_t stream) {
     // state image + (four row tiles per wave) the LDS slab of the last weight groups: see KREG in the kernel
-    const size_t lds = (size_t)(C / 2) * HC_NKK * 1024 + (C <= 4 ? (size_t)4 * (HC_NKK - 12) * 4 * 1024 : 0);
-    const int grid = 8 * ((n_clusters + 7) / 8) * C;
+    const size_t lds = (size_t)(HC_C / 2) * HC_NKK * 1024 + (size_t)4 * (HC_NKK - 12) * 4 * 1024;
+    const int grid = 8 * ((n_clusters + 7) / 8) * HC_C;
     auto go = [&](auto kern) -> int {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
@@ -421,22 +423,19 @@ static int launch_hc(const RecurParams& p, int n_clusters, unsigned long long* x
         return (int)hipGetLastError();
     };
     switch (p.noise_mode) {
-        case ESN_NOISE_NONE: return go(harvest_cluster_kernel<TR, ESN_NOISE_NONE, C>);
-        case ESN_NOISE_TENSOR: return go(harvest_cluster_kernel<TR, ESN_NOISE_TENSOR, C>);
-        default: return go(harvest_cluster_kernel<TR, ESN_NOISE_COUNTER, C>);
+        case ESN_NOISE_NONE: return go(harvest_cluster_kernel<TR, ESN_NOISE_NONE>);
+        case ESN_NOISE_TENSOR: return go(harvest_cluster_kernel<TR, ESN_NOISE_TENSOR>);
+        default: return go(harvest_cluster_kernel<TR, ESN_NOISE_COUNTER>);
     }
 }
 
-// C = members per cluster: 2 (default), 4 or 8
-int launch_harvest_cluster(int precision, const RecurParams& p, int C, void* workspace, hipStream_t stream) {
-    const int n_clusters = hc_clusters(p.n_groups, C, p.n_wsets);
-    hipError_t e = hipMemsetAsync(workspace, 0, harvest_cluster_workspace_bytes(p.n_groups, C, p.n_wsets), stream);   // tags start at 1
+int launch_harvest_cluster(int precision, const RecurParams& p, void* workspace, hipStream_t stream) {
+    const int n_clusters = hc_clusters(p.n_groups, p.n_wsets);
+    hipError_t e = hipMemsetAsync(workspace, 0, harvest_cluster_workspace_bytes(p.n_groups, p.n_wsets), stream);   // tags start at 1
     if (e != hipSuccess) return (int)e;
     unsigned long long* xch = reinterpret_cast<unsigned long long*>(workspace);
-#define HC_CASE(TRv, Cv) if (C == Cv) return launch_hc<TRv, Cv>(p, n_clusters, xch, stream);
-    if (precision == ESN_F16) { HC_CASE(TraitsF16, 2) HC_CASE(TraitsF16, 4) HC_CASE(TraitsF16, 8) }
-    if (precision == ESN_BF16) { HC_CASE(TraitsBF16, 2) HC_CASE(TraitsBF16, 4) HC_CASE(TraitsBF16, 8) }
-#undef HC_CASE
+    if (precision == ESN_F16) return launch_hc<TraitsF16>(p, n_clusters, xch, stream);
+    if (precision == ESN_BF16) return launch_hc<TraitsBF16>(p, n_clusters, xch, stream);
     return -1;
 }
 

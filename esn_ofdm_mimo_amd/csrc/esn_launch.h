@@ -18,11 +18,6 @@ size_t recur_f64_lds_bytes(int FB, int n_res, int n_in, int n_out);
 // esn_recur_f64_mfma.hip
 bool f64_mfma_geometry(int n_res, int n_in, int n_out, bool harvest, Geometry* g);
 int launch_recur_f64_mfma(const RecurParams& p, hipStream_t stream);
-#ifdef ESN_WITH_RS
-// esn_recur_rs.hip (a kept negative result, DESIGN.md 3.1b: only in builds made with ESN_WITH_RS=1)
-bool rs_path_applies(int precision, const RecurParams& p);
-int launch_recur_rs(int precision, const RecurParams& p, size_t wo_rs_off, hipStream_t stream);
-#endif
 // esn_recur_big.hip
 bool big_path_applies(int precision, const RecurParams& p);
 int big_slots(const RecurParams& p);
@@ -45,8 +40,8 @@ int launch_recur_mfma_f16(const RecurParams& p, hipStream_t stream, bool io32);
 int launch_recur_mfma_bf16(const RecurParams& p, hipStream_t stream, bool io32);
 // esn_harvest_cluster.hip
 bool harvest_cluster_applies(int precision, const RecurParams& p);
-size_t harvest_cluster_workspace_bytes(int n_pilots, int C, int n_wsets);
-int launch_harvest_cluster(int precision, const RecurParams& p, int C, void* workspace, hipStream_t stream);
+size_t harvest_cluster_workspace_bytes(int n_pilots, int n_wsets);
+int launch_harvest_cluster(int precision, const RecurParams& p, void* workspace, hipStream_t stream);
 // esn_recur_skew16.hip
 int launch_recur_skew16(int precision, const RecurParams& p, hipStream_t stream, bool io32 = false);
 // esn_pack.hip

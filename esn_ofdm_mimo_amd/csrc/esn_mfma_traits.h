@@ -1,6 +1,6 @@
 // Vector typedefs and the per-precision operand traits of the MFMA kernels (float32 / fp16 / bf16 operands, float32
 // accumulate): the MFMA of a 32-byte k-group (mma32) and of a 64-byte read-out group (mma16), LDS stores / loads of the
-// state element type, and the activation.  Shared by the persistent kernel (esn_recur_mfma_impl.h), the 16x16x32 skewed kernel, the clustered harvest, the launch-per-step GEMM and the register-state kernel.
+// state element type, and the activation.  Shared by the persistent kernel (esn_recur_mfma_impl.h), the 16x16x32 skewed kernel, the clustered harvest and the launch-per-step GEMM.
 #pragma once
 #include <type_traits>
 #include "esn_common.h"

@@ -9,11 +9,11 @@
 //
 //   * both operands arrive by LDS-DMA in 1 KB fragments (the weight image of esn_pack_weights and
 //     the state image are already in the order a wave's ds_read_b128 consumes them: no swizzle, no
-//     conflicts), double-buffered 64-deep k-chunks, counted vmcnt + raw s_barrier;
+//     conflicts), four 32-deep stages in flight, counted vmcnt + one raw s_barrier per stage;
 //   * 8 waves = 2 (rows) x 4 (frames), 4 x 2 accumulator tiles of 32 x 32 each;
 //   * a small "prep" launch ahead of every GEMM launch turns the previous launch's read-out partials
 //     into Y_s (output row s-1 -> HBM, unscaled) and writes the [U_s ; F_s] k-groups of the state
-//     image (scaled inputs, fed-back output), so the GEMM sees ONE uniform operand: Kp/64 chunks;
+//     image (scaled inputs, fed-back output), so the GEMM sees ONE uniform operand: Kp/32 stages;
 //   * epilogue: tanh + state noise -> fp16 -> next state image (coalesced 8-byte pieces), and the
 //     read-out partial Wout[:, these 256 rows] x_{s+1} with the accumulator tile used directly as the
 //     B operand of a 32x32x16 MFMA (guide: "an accumulator tile as the next MFMA's operand");
@@ -48,8 +48,8 @@ __device__ __forceinline__ u32x2 pack4(float a, float b, float c, float d) {
     return __builtin_bit_cast(u32x2, v);
 }
 
-constexpr int BIG_STAGE = 65536;                      // one k-chunk: A 32 KB + B 32 KB
-constexpr int BIG_LDS = 2 * BIG_STAGE;                // (the epilogue's 8 KB scratch aliases stage 0)
+constexpr int BIG_STAGE = 32768;                      // one 32-deep stage: A 16 KB + B 16 KB
+constexpr int BIG_LDS = 4 * BIG_STAGE;                // (the epilogue's 8 KB scratch aliases stage 0)
 
 size_t big_workspace_bytes(int n_slots, int Mp, int Kp) {
     return 2 * ((size_t)n_slots * Kp * 2) + 2 * ((size_t)(Mp / 256) * n_slots * 8 * 4);
@@ -200,16 +200,14 @@ __global__ __launch_bounds__(256) void big_prep_kernel(BigParams bp) {
     }
 }
 
-// NT = column tiles (of 32 frames) per wave: 2 -> 8 waves of 128 x 64 (two per SIMD, 128 accumulator registers), the round-2
-// shape; 4 -> 4 waves of 128 x 128 (ONE per SIMD, 256 accumulator registers of its 512).  At NT = 2 a k-group costs a wave 6
-// fragment reads for 8 MFMAs: 8 waves x 24 KB per 64-deep chunk + the 64 KB the LDS-DMA writes = 256 KB per 1024 MFMA cycles,
-// i.e. the whole LDS bandwidth (256 B/clk) at full matrix rate -- the matrix pipe sat at 53 %.  At NT = 4 it is 8 reads for
-// 16 MFMAs: 192 KB per 2048 cycles = 94 B/clk.
-template <typename TR, int NOISE, int NT, bool PIPE>
-__global__ __launch_bounds__(1024 / NT) void big_step_kernel(BigParams bp) {
-    constexpr int NW = 16 / NT;                          // waves: 2 (rows) x NW/2 (frames)
-    constexpr int WNC = NW / 2;                          // wave columns
-    constexpr int DT = 8 / WNC;                          // 32-row / 32-frame operand tiles a wave fetches per chunk
+// 8 waves of 128 x 64 (two per SIMD, 128 accumulator registers each).  A k-group costs a wave 6 fragment reads for 8 MFMAs,
+// i.e. with the LDS-DMA's writes the whole LDS bandwidth at full matrix rate; 4 waves of 128 x 128 (8 reads per 16 MFMAs,
+// one wave per SIMD) were slower and are gone with the two-buffer main loop: DESIGN.md 3.5.
+template <typename TR, int NOISE>
+__global__ __launch_bounds__(512) void big_step_kernel(BigParams bp) {
+    constexpr int NT = 2;                                // column tiles (of 32 frames) per wave
+    constexpr int WNC = 4;                               // wave columns: 2 (rows) x 4 (frames) waves
+    constexpr int DT = 2;                                // 32-row / 32-frame operand tiles a wave fetches per stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const RecurParams& p = bp.r;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -226,17 +224,16 @@ __global__ __launch_bounds__(1024 / NT) void big_step_kernel(BigParams bp) {
     const int slot0 = n * 256;
     if (slot0 >= bp.n_slots) return;
 
-    char* stage = smem;                                               // [2][A 32 KB | B 32 KB]
+    char* stage = smem;                                               // [4][A 16 KB | B 16 KB]
     float* red = reinterpret_cast<float*>(stage);                     // epilogue: [256 frames][8] (aliases stage 0)
 
-    // ---- main loop: Kp/64 chunks of four k-groups, LDS-DMA double-buffered ---------------------------
+    // ---- main loop: Kp/32 stages of two k-groups, four LDS-DMA stages in flight ----------------------
     const int lane16 = lane * 16;
     const size_t x_bytes = (size_t)bp.n_slots * p.g.Kp * 2;
-    // the first half of the waves fetches DT row tiles of A each, the second half DT column tiles of B: 4 DT pieces each
+    // the first half of the waves fetches DT row tiles of A each, the second half DT column tiles of B: 2 DT pieces each
     const bool is_a = wave < WNC;
     const int pair = (wave % WNC) * DT;
     const int src_t0 = (is_a ? (m * 8 + pair) : ((slot0 >> 5) + pair)) * nkg;
-    const int dst_off = (is_a ? 0 : 32768) + pair * 4096;
     // one descriptor per wave, built from values the compiler can PROVE wave-uniform (readfirstlane of the
     // pointer halves and the size): otherwise every DMA is wrapped in a waterfall loop (guide T20)
     const uint64_t dma_ptr = is_a ? (uint64_t)reinterpret_cast<uintptr_t>(p.packed_w) : (uint64_t)reinterpret_cast<uintptr_t>(bp.x_in);
@@ -245,15 +242,6 @@ __global__ __launch_bounds__(1024 / NT) void big_step_kernel(BigParams bp) {
     const int dma_size = __builtin_amdgcn_readfirstlane(is_a ? (int)p.wset_stride : (int)x_bytes);
     const __amdgpu_buffer_rsrc_t dma_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<char*>((uintptr_t)(((uint64_t)dma_hi << 32) | dma_lo)), 0, dma_size, 0x00020000);
-    auto issue = [&](int c, int buf) {
-        char* dst = stage + (size_t)buf * BIG_STAGE + dst_off;
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int kg = 0; kg < 4; ++kg)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(dma_rsrc, (__attribute__((address_space(3))) void*)(dst + (t * 4 + kg) * 1024),
-                                                         16, lane16, (src_t0 + t * nkg + 4 * c + kg) * 1024, 0, 0);
-    };
     f32x16 acc[4][NT];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -261,115 +249,53 @@ __global__ __launch_bounds__(1024 / NT) void big_step_kernel(BigParams bp) {
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
-    auto compute = [&](int buf) {
-        const char* ab = stage + (size_t)buf * BIG_STAGE + (size_t)(wm * 4) * 4096 + lane16;
-        const char* bb = stage + (size_t)buf * BIG_STAGE + 32768 + (size_t)(wn * NT) * 4096 + lane16;
-        if constexpr (NT == 4) {
-            // one wave per SIMD: nobody else covers an LDS latency, so the fragments of k-group kg+1 are requested
-            // BEFORE the 16 MFMAs of k-group kg (two register sets); left to itself the compiler reads one B fragment
-            // at a time and waits for it in front of every four MFMAs
-            u32x4 a[2][4], b[2][NT];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) a[0][mt] = *reinterpret_cast<const u32x4*>(ab + mt * 4096);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b[0][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096);
-#pragma unroll
-            for (int kg = 0; kg < 4; ++kg) {
-                const int cur = kg & 1, nxt = cur ^ 1;
-                if (kg + 1 < 4) {
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) a[nxt][mt] = *reinterpret_cast<const u32x4*>(ab + mt * 4096 + (kg + 1) * 1024);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) b[nxt][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + (kg + 1) * 1024);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) TR::mma32(acc[mt][nt], a[cur][mt], b[cur][nt]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-#pragma unroll
-            for (int kg = 0; kg < 4; ++kg) {
-                u32x4 a[4], b[NT];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) a[mt] = *reinterpret_cast<const u32x4*>(ab + mt * 4096 + kg * 1024);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) b[nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + kg * 1024);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) TR::mma32(acc[mt][nt], a[mt], b[nt]);
-            }
-        }
+    // A loop that puts every wave's eight DMA launches of a 64-deep chunk c+1 in front of the wait and the barrier of
+    // chunk c (two buffers, two barriers per chunk) has all eight waves launch (8 x ~100 cycles each: the guide's
+    // LDS-DMA issue price inside a busy phase), THEN all eight compute (1024 MFMA cycles per wave) -- the matrix
+    // pipe idles through every launch burst (53 % busy).  Here a stage is 32 deep (32 KB), FOUR stages are in
+    // flight, a stage's four launches per wave are spread between the MFMAs of the stage being multiplied (the
+    // pipe keeps running while the wave issues them), a stage has a whole stage time to land before it is waited
+    // for, and there is ONE barrier per stage: a buffer is refilled three stages after it was read, behind the
+    // barrier every wave passes after reading it.
+    const int half_off = is_a ? 0 : 16384;
+    auto issue_piece = [&](int st, int j) {               // j < 4: operand tile pair + (j >> 1), k-group 2 st + (j & 1)
+        char* dst = stage + (size_t)(st & 3) * BIG_STAGE + half_off + (pair + (j >> 1)) * 2048 + (j & 1) * 1024;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(dma_rsrc, (__attribute__((address_space(3))) void*)dst, 16, lane16,
+                                                 (src_t0 + (j >> 1) * nkg + 2 * st + (j & 1)) * 1024, 0, 0);
     };
-    if constexpr (PIPE) {
-        // Round-3 main loop (NT = 2).  The round-2 loop below puts every wave's eight DMA launches of chunk c+1 in
-        // front of the wait and the barrier of chunk c: all eight waves launch (8 x ~100 cycles each: the guide's
-        // LDS-DMA issue price inside a busy phase), THEN all eight compute (1024 MFMA cycles per wave) -- the matrix
-        // pipe idles through every launch burst (53 % busy).  Here a stage is 32 deep (32 KB), FOUR stages are in
-        // flight, a stage's four launches per wave are spread between the MFMAs of the stage being multiplied (the
-        // pipe keeps running while the wave issues them), a stage has a whole stage time to land before it is waited
-        // for, and there is ONE barrier per stage: a buffer is refilled three stages after it was read, behind the
-        // barrier every wave passes after reading it.
-        static_assert(NT == 2, "pipelined main loop: 8 waves of 128 x 64");
-        constexpr int STG = 32768;
-        const int half_off = is_a ? 0 : 16384;
-        auto issue_piece = [&](int st, int j) {               // j < 4: operand tile pair + (j >> 1), k-group 2 st + (j & 1)
-            char* dst = stage + (size_t)(st & 3) * STG + half_off + (pair + (j >> 1)) * 2048 + (j & 1) * 1024;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(dma_rsrc, (__attribute__((address_space(3))) void*)dst, 16, lane16,
-                                                     (src_t0 + (j >> 1) * nkg + 2 * st + (j & 1)) * 1024, 0, 0);
-        };
-        const int nst = nkg / 2;
+    const int nst = nkg / 2;
 #pragma unroll
-        for (int st = 0; st < 3; ++st)
-            if (st < nst) {
+    for (int st = 0; st < 3; ++st)
+        if (st < nst) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) issue_piece(st, j);
-            }
-        for (int st = 0; st < nst; ++st) {
-            if (st + 2 < nst) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // this wave's pieces of stage st have landed
-            else if (st + 1 < nst) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                      // ... everybody's; and stage st-1 has been read by all
-            const bool more = st + 3 < nst;
-            const char* ab = stage + (size_t)(st & 3) * STG + (size_t)(wm * 4) * 2048 + lane16;
-            const char* bb = stage + (size_t)(st & 3) * STG + 16384 + (size_t)(wn * 2) * 2048 + lane16;
+            for (int j = 0; j < 4; ++j) issue_piece(st, j);
+        }
+    for (int st = 0; st < nst; ++st) {
+        if (st + 2 < nst) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // this wave's pieces of stage st have landed
+        else if (st + 1 < nst) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                      // ... everybody's; and stage st-1 has been read by all
+        const bool more = st + 3 < nst;
+        const char* ab = stage + (size_t)(st & 3) * BIG_STAGE + (size_t)(wm * 4) * 2048 + lane16;
+        const char* bb = stage + (size_t)(st & 3) * BIG_STAGE + 16384 + (size_t)(wn * 2) * 2048 + lane16;
 #pragma unroll
-            for (int kg = 0; kg < 2; ++kg) {
-                u32x4 a[4], b[2];
+        for (int kg = 0; kg < 2; ++kg) {
+            u32x4 a[4], b[2];
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) a[mt] = *reinterpret_cast<const u32x4*>(ab + mt * 2048 + kg * 1024);
+            for (int mt = 0; mt < 4; ++mt) a[mt] = *reinterpret_cast<const u32x4*>(ab + mt * 2048 + kg * 1024);
 #pragma unroll
-                for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const u32x4*>(bb + nt * 2048 + kg * 1024);
+            for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const u32x4*>(bb + nt * 2048 + kg * 1024);
 #pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
+            for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) {
-                        TR::mma32(acc[mt][nt], a[mt], b[nt]);
-                        if (mt == 1 && more) issue_piece(st + 3, kg * 2 + nt);      // in the issue shadow of the MFMAs
-                    }
+                for (int mt = 0; mt < 4; ++mt) {
+                    TR::mma32(acc[mt][nt], a[mt], b[nt]);
+                    if (mt == 1 && more) issue_piece(st + 3, kg * 2 + nt);      // in the issue shadow of the MFMAs
                 }
             }
         }
-        __syncthreads();                                           // stage buffers free (the epilogue's scratch aliases them)
-    } else {
-    const int nch = nkg / 4;
-    issue(0, 0);
-    for (int c = 0; c + 1 < nch; ++c) {
-        issue(c + 1, (c + 1) & 1);
-        if constexpr (DT == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // this wave's pieces of chunk c have landed
-        else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                          // ... and everybody else's
-        compute(c & 1);
-        __builtin_amdgcn_s_barrier();                          // chunk c read: its buffer may be refilled
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    compute((nch - 1) & 1);
     __syncthreads();                                           // stage buffers free (the epilogue's scratch aliases them)
-    }
 
     // ---- epilogue: activation + noise -> next state image; read-out partial ---------------------------
     const float noise = (float)p.noise;
@@ -471,18 +397,11 @@ static int launch_big_t(const RecurParams& rp, size_t wo_big_off, void* workspac
     if (e != hipSuccess) return (int)e;
     const int n_nt8 = (bp.n_slots / 256 + 7) / 8;
     const dim3 grid(8 * n_nt8 * bp.n_mt);
-    // main loop: 0 = round-2 (two 64-deep buffers, two barriers per chunk), 1 = round-3 pipeline (four 32-deep stages, DMA
-    // launches between the MFMAs, one barrier per stage; default), 2 = 4 waves of 128 x 128 (a kept negative result)
-    const int variant = knobs().big_nt == 4 ? 2 : (knobs().big_pipe ? 1 : 0);
-    const int ni = rp.noise_mode == ESN_NOISE_NONE ? 0 : rp.noise_mode == ESN_NOISE_TENSOR ? 1 : 2;
-#define ESN_BIG_K(NZ) {reinterpret_cast<const void*>(big_step_kernel<TR, NZ, 2, false>), \
-                       reinterpret_cast<const void*>(big_step_kernel<TR, NZ, 2, true>),  \
-                       reinterpret_cast<const void*>(big_step_kernel<TR, NZ, 4, false>)}
-    const void* kern[3][3] = {ESN_BIG_K(ESN_NOISE_NONE), ESN_BIG_K(ESN_NOISE_TENSOR), ESN_BIG_K(ESN_NOISE_COUNTER)};
-#undef ESN_BIG_K
-    e = hipFuncSetAttribute(kern[ni][variant], hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);
+    const void* kern = rp.noise_mode == ESN_NOISE_NONE ? reinterpret_cast<const void*>(big_step_kernel<TR, ESN_NOISE_NONE>)
+                     : rp.noise_mode == ESN_NOISE_TENSOR ? reinterpret_cast<const void*>(big_step_kernel<TR, ESN_NOISE_TENSOR>)
+                                                         : reinterpret_cast<const void*>(big_step_kernel<TR, ESN_NOISE_COUNTER>);
+    e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);
     if (e != hipSuccess) return (int)e;
-    const dim3 block(variant == 2 ? 256 : 512);
     for (int s = 0; s <= rp.S; ++s) {
         // prep(s): partials of X_s (from GEMM s-1, in YP[s & 1]) -> Y row s-1; [U_s ; F_s] -> image X[s & 1]
         bp.step = s;
@@ -494,7 +413,7 @@ static int launch_big_t(const RecurParams& rp, size_t wo_big_off, void* workspac
         bp.x_in = X[s & 1]; bp.x_out = X[(s + 1) & 1];
         bp.yp_out = YP[(s + 1) & 1];
         void* args[] = {&bp};
-        e = hipLaunchKernel(kern[ni][variant], grid, block, args, BIG_LDS, stream);
+        e = hipLaunchKernel(kern, grid, dim3(512), args, BIG_LDS, stream);
         if (e != hipSuccess) return (int)e;
     }
     return (int)hipGetLastError();
@@ -627,10 +546,9 @@ __global__ void bigh_fill_e_kernel(BigHarvestParams hp) {
     }
 }
 
-// KGC = k-groups per chunk: 4 (64 deep) where Kp is a multiple of 64 (reservoirs beyond 1024 units), 2 (32 deep) for the
-// persistent kernels' images (Kp a multiple of 32: N_res = 512 has 34 k-groups)
-template <typename TR, int NOISE, int KGC>
+template <typename TR, int NOISE>
 __global__ __launch_bounds__(256) void bigh_step_kernel(BigHarvestParams hp) {
+    constexpr int KGC = 4;                               // k-groups per chunk: 64 deep (Kp is a multiple of 64 beyond 1024 units)
     constexpr int TILE_B = KGC * 1024;                   // one 32-row / 32-pilot operand tile of a chunk
     constexpr int A_B = 4 * TILE_B, STAGE_B = 6 * TILE_B;
     constexpr int PPC = KGC + KGC / 2;                   // DMA pieces per wave and chunk
@@ -701,23 +619,13 @@ __global__ __launch_bounds__(256) void bigh_step_kernel(BigHarvestParams hp) {
     for (int c = 0; c < nch; ++c) {
         // this wave's six pieces of chunk c have landed when at most the later chunks' are outstanding
         const int later = nch - 1 - c < BH_NST - 2 ? nch - 1 - c : BH_NST - 2;
-        static_assert(PPC == 6 || PPC == 3, "DMA pieces per wave and chunk");
-        if constexpr (PPC == 6) {
-            switch (later) {
-                case 4: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-                case 3: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-                case 2: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-                case 1: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-                default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-            }
-        } else {
-            switch (later) {
-                case 4: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-                case 3: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-                case 2: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-                case 1: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-                default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-            }
+        static_assert(PPC == 6, "DMA pieces per wave and chunk");
+        switch (later) {
+            case 4: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
+            case 3: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
+            case 2: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
+            case 1: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+            default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
         }
         __builtin_amdgcn_s_barrier();                          // everybody's pieces of chunk c; chunk c-1 read by all
         if (c + BH_NST - 1 < nch) issue(c + BH_NST - 1, buf_issue);
@@ -823,16 +731,9 @@ static int launch_bigh_t(const RecurParams& rp, void* workspace, hipStream_t str
     hipLaunchKernelGGL(bigh_fill_e_kernel, dim3(1024), dim3(256), 0, stream, hp);
     const int n_ft = hp.n_slots / 64;
     const dim3 grid(hp.n_mt % 8 == 0 ? hp.n_mt * n_ft : 8 * ((n_ft + 7) / 8) * hp.n_mt);
-    const bool deep = (Kp % 64) == 0;                      // 64-deep chunks where the image allows, else 32-deep
-    const int ni = rp.noise_mode == ESN_NOISE_NONE ? 0 : rp.noise_mode == ESN_NOISE_TENSOR ? 1 : 2;
-    const void* kern[2][3] = {
-        {reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_NONE, 2>),
-         reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_TENSOR, 2>),
-         reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_COUNTER, 2>)},
-        {reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_NONE, 4>),
-         reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_TENSOR, 4>),
-         reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_COUNTER, 4>)}};
-    const void* kfn = kern[deep ? 1 : 0][ni];
+    const void* kfn = rp.noise_mode == ESN_NOISE_NONE ? reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_NONE>)
+                    : rp.noise_mode == ESN_NOISE_TENSOR ? reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_TENSOR>)
+                                                        : reinterpret_cast<const void*>(bigh_step_kernel<TR, ESN_NOISE_COUNTER>);
     const int lds = BH_LDS > 36 * 1024 ? BH_LDS : 36 * 1024;     // (the transpose scratch needs 33 KB whatever the stage size)
     hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
@@ -847,11 +748,10 @@ static int launch_bigh_t(const RecurParams& rp, void* workspace, hipStream_t str
 
 // shapes the harvest GEMM serves: fp16/bf16, shared reservoir, reservoirs beyond 1024 units
 bool big_harvest_applies(int precision, const RecurParams& p) {
-    // (Reservoirs of 257..1024 units can run here too -- 32-deep chunks, KGC = 2; debug knob "harvest_gemm" -- and were
-    //  measured at N_res = 512, 2048 pilots: 137 launches of 128 workgroups took ~1.8 ms against 1.16 ms for the persistent
-    //  kernel's 64 workgroups; the launch chain, not the tile, is the cost.  Off by default.)
-    return (precision == ESN_F16 || precision == ESN_BF16) && p.harvest && p.n_wsets == 1 &&
-           (p.n_res > 1024 || (knobs().harvest_gemm && p.n_res > 256 && p.n_groups >= 64)) &&
+    // (Reservoirs of 257..1024 units ran here once, on 32-deep chunks, and were measured at N_res = 512, 2048 pilots: 137
+    //  launches of 128 workgroups took ~1.8 ms against 1.16 ms for the persistent kernel's 64 workgroups; the launch chain,
+    //  not the tile, is the cost.)
+    return (precision == ESN_F16 || precision == ESN_BF16) && p.harvest && p.n_wsets == 1 && p.n_res > 1024 &&
            p.n_in <= 16 && p.n_out <= 8 && p.g.Mp % 128 == 0 && p.g.Kp % 32 == 0 && p.g.Kp / 64 >= BH_NST &&
            p.g.Kp - p.g.Mp >= 32 && p.g.kfb - p.g.kin + round_up(p.n_out, 4) <= 32 &&
            (size_t)round_up(p.n_groups, 64) * p.g.Kp * 2 < 0x7fffffffu && p.wset_stride < 0x7fffffffu;

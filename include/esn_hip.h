@@ -83,8 +83,7 @@ int esn_abi_version(void);
 /* Tuning / diagnostic knobs for benchmarks and A/B tests (no counterpart in the reference).  The
  * library reads the initial value of every key but "gen_ko" from the environment ONCE, at its first call -- the
  * variable is ESN_ + the key in capitals: ESN_SKEW, ESN_MFMA_GEOM, ESN_MFMA_GEOM_F32, ESN_CHOL_SKIP, ESN_CHOL_DMA,
- * ESN_F64_MFMA, ESN_RS, ESN_S16, ESN_BIG_GEMM, ESN_CLUSTER, ESN_BIG_PIPE, ESN_BIG_NT, ESN_HARVEST_GEMM, ESN_HCLUSTER,
- * ESN_DETECT_FIXED
+ * ESN_F64_MFMA, ESN_S16, ESN_BIG_GEMM, ESN_CLUSTER, ESN_HCLUSTER, ESN_DETECT_FIXED
  * (one table in csrc/esn_api.hip serves both) -- and afterwards only this call changes them:
  *   "skew"          "0" = in-step schedule for the fp16/bf16 predict kernel, else skewed (default)
  *   "mfma_geom"     "NW,MT,NT" re-cuts the fp16/bf16 predict tiling; ignored unless 32*NW*MT equals
@@ -95,19 +94,13 @@ int esn_abi_version(void);
  *   "chol_dma"      "0" = the Cholesky solve (Gram dimension <= 128, float32 E, rows < cols) stages E through
  *                   registers instead of LDS-DMA rings in its Gram and W_out passes (bitwise the same results; A/B runs)
  *   "f64_mfma"      "0" = ESN_F64 batches on the vector-ALU kernel instead of the float64 matrix pipe
- *   "rs"            "1" = fp16/bf16 predict at N_res 257..512 on the register-resident-state kernel
- *                   (esn_recur_rs.hip; an experiment kept for A/B runs, compiled only into ESN_WITH_RS=1 builds:
- *                   the product library answers -3) instead of the skewed LDS-state kernel
  *   "s16"           "0" = fp16/bf16 predict at 257..512 units on the 32x32x16 skewed kernel instead of the 16x16x32 one
  *                   (esn_recur_skew16_impl.h, the default: same schedule, 4 % less wall time at a higher clock; A/B runs)
  *   "big_gemm"      "0" = N_res > 1024 predict on the persistent kernel even when a workspace is given
  *   "cluster"       "0" = a single float64 sequence on the vector-ALU kernel even when a workspace is given
- *   "big_pipe"      "0" = N_res > 1024 predict with the round-2 main loop (two buffers, two barriers per chunk)
- *   "big_nt"        "4" = N_res > 1024 predict on the 4-wave 128 x 128 variant (slower; A/B runs)
- *   "harvest_gemm"  "1" = harvests of 257..1024 units (>= 64 pilots) on the GEMM-per-step path (slower; A/B runs)
- *   "hcluster"      "0" = fp16/bf16 harvest at 257..512 units on the persistent kernel even when a workspace is given;
- *                   "4" / "8" = clusters of that many workgroups instead of pairs (esn_harvest_cluster.hip; A/B runs).
- *                   esn_harvest_workspace_bytes follows the knob: ask for the size after setting it
+ *   "hcluster"      "0" = fp16/bf16 harvest at 257..512 units on the persistent kernel even when a workspace is given
+ *                   (default: pairs of workgroups, esn_harvest_cluster.hip).  esn_harvest_workspace_bytes follows the
+ *                   knob: ask for the size after setting it
  *   "gen_ko"        frame-generator knock-out mask for tools/time_gen.py (timing only, wrong frames)
  *   "detect_fixed"  "0" = esn_detect_count / esn_detect_count_f32 always on the generic kernel.  By default a call
  *                   at N = 128, N_t = 4, 16-QAM with 16-byte aligned tx_bits and Y (8-byte for float Y) runs the
@@ -121,10 +114,9 @@ int esn_debug_set(const char* key, const char* value);
  * caller lends a workspace; the first that applies, in this order:
  *   workspace lent:  CLUSTER_F64      ESN_F64, ONE sequence ("cluster")
  *                    HARVEST_CLUSTER  harvest, fp16/bf16, 257..512 units, n_in 2/4/8/16, n_out <= 8 ("hcluster")
- *                    BIG_PREDICT /    fp16/bf16, one weight set, n_in <= 16, n_out <= 8, beyond 1024 units ("big_gemm";
- *                    BIG_HARVEST      harvests of 257..1024 units and >= 64 pilots with "harvest_gemm")
- *   predict:         RS               the register-state experiment (ESN_WITH_RS=1 builds, "rs")
- *                    SKEW16           fp16/bf16, 257..512 units, n_in 2/4/8/16, n_out <= 8 ("s16", "skew")
+ *                    BIG_PREDICT /    fp16/bf16, one weight set, n_in <= 16, n_out <= 8, beyond 1024 units ("big_gemm")
+ *                    BIG_HARVEST
+ *   predict:         SKEW16           fp16/bf16, 257..512 units, n_in 2/4/8/16, n_out <= 8 ("s16", "skew")
  *   otherwise:       F64_MFMA         ESN_F64, more than 8 sequences, where the matrix-pipe tiling fits ("f64_mfma")
  *                    F64_VALU         ESN_F64
  *                    MFMA             ESN_F32 / ESN_F16 / ESN_BF16: in-step or 32x32x16 skewed schedule ("skew") */
@@ -136,16 +128,14 @@ enum esn_path {
     ESN_PATH_CLUSTER_F64 = 4,      /* single float64 sequence, workgroup cluster (esn_recur_cluster.hip)     */
     ESN_PATH_BIG_PREDICT = 5,      /* one GEMM launch per step, predict (esn_recur_big.hip)                  */
     ESN_PATH_BIG_HARVEST = 6,      /* one GEMM launch per step, harvest (esn_recur_big.hip)                  */
-    ESN_PATH_HARVEST_CLUSTER = 7,  /* fp16/bf16 harvest, workgroup clusters (esn_harvest_cluster.hip)        */
-    ESN_PATH_RS = 8                /* register-resident state, experiment builds only (esn_recur_rs.hip)     */
+    ESN_PATH_HARVEST_CLUSTER = 7   /* fp16/bf16 harvest, workgroup clusters (esn_harvest_cluster.hip)        */
 };
 /* Which kernel esn_predict_batch (harvest = 0) / esn_harvest_batch (harvest = 1) runs for this call when a
  * workspace of the advertised size is lent (have_workspace = 1) or not (0), under the current knobs: the answer of
  * the same function the calls dispatch through.  n_sequences = n_frames (predict) or n_groups (harvest, where
  * frames_per_group is ignored).  The paths CLUSTER_F64, BIG_PREDICT, BIG_HARVEST and HARVEST_CLUSTER read the
- * workspace; of these CLUSTER_F64 and HARVEST_CLUSTER keep an error word in its last 64 bytes.  In ESN_WITH_RS=1
- * experiment builds the answer assumes float64 I/O and no tensor noise (the RS kernel serves neither float32 I/O nor
- * ESN_NOISE_TENSOR).  Returns an esn_path value >= 0, or a negative error as the calls themselves would.  Diagnostic. */
+ * workspace; of these CLUSTER_F64 and HARVEST_CLUSTER keep an error word in its last 64 bytes.
+ * Returns an esn_path value >= 0, or a negative error as the calls themselves would.  Diagnostic. */
 int esn_recur_path(int harvest, int precision, const esn_shape_t* shape, int n_sequences,
                    int frames_per_group, int have_workspace);
 

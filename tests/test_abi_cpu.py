@@ -52,7 +52,7 @@ def test_geometry_and_sizes(lib):
     assert lib.esn_packed_weights_bytes(BF16, C.byref(sh)) == 2 * (2 * 512 * 544)
     assert lib.esn_packed_readout_bytes(F64, C.byref(sh)) == 8 * 8 * 528 + 8 * 16 * 536
     assert lib.esn_packed_readout_bytes(F32, C.byref(sh)) == 16 * 544 * 4 + 16
-    # hi rows 0-7, lo rows 8-15 (the register-state kernel's image exists only in ESN_WITH_RS=1 experiment builds)
+    # hi rows 0-7, lo rows 8-15; behind it the 16x16x32 kernel's image
     assert lib.esn_packed_readout_bytes(F16, C.byref(sh)) == (16 * 544 * 2 + 16) + (17 * 1024 + 16)
     assert lib.esn_packed_readout_bytes(F16, C.byref(Shape(256, 16, 8, 1, 1))) == 16 * 288 * 2 + 16
     small = Shape(100, 2, 2, 1, 1)

@@ -16,10 +16,10 @@ N_RES = [64, 128, 129, 256, 257, 300, 512, 513, 1024, 1025, 1500, 2048, 2049]
 IO = [[2, 2], [3, 2], [4, 4], [16, 8], [16, 16]]
 N_WSETS = [1, 3]
 FRAMES = [[1, 1], [8, 1], [9, 4], [150, 75], [4096, 64]]
-DEFAULTS = {"cluster": "1", "big_gemm": "1", "harvest_gemm": "0", "hcluster": "1", "f64_mfma": "1", "s16": "1",
-            "skew": "1"}
-MOVED = [["cluster", "0"], ["big_gemm", "0"], ["harvest_gemm", "1"], ["hcluster", "0"], ["hcluster", "4"],
-         ["hcluster", "8"], ["f64_mfma", "0"], ["s16", "0"], ["skew", "0"]]
+DEFAULTS = {"cluster": "1", "big_gemm": "1", "hcluster": "1", "f64_mfma": "1", "s16": "1", "skew": "1"}
+MOVED = [["cluster", "0"], ["big_gemm", "0"], ["hcluster", "0"], ["f64_mfma", "0"], ["s16", "0"], ["skew", "0"]]
+# keys of knobs that went with the kernels they selected: unknown like any other
+RETIRED = ["rs", "big_pipe", "big_nt", "harvest_gemm"]
 WORKSPACE_PATHS = {"cluster_f64", "big_predict", "big_harvest", "harvest_cluster"}
 
 
@@ -71,7 +71,7 @@ def test_golden_covers_the_grid(golden):
 
 
 def test_size_queries_answer_as_recorded(lib, golden):
-    """All 26 000 combinations (520 shapes x 5 batches x default + 9 moved knobs), entry by entry."""
+    """All 18 200 combinations (520 shapes x 5 batches x default + 6 moved knobs), entry by entry."""
     from esn_ofdm_mimo_amd import _lib
     checked = 0
     for setting in [None] + MOVED:
@@ -94,7 +94,7 @@ def test_size_queries_answer_as_recorded(lib, golden):
                     assert got == want, (setting, key, nf, f, got, want)
                     checked += 1
         assert used == len(diffs), setting
-    assert checked == 26000
+    assert checked == 520 * 5 * 7
 
 
 # (harvest, precision, (n_res, n_in, n_out, n_wsets), n_sequences, F, have_workspace, knobs moved, path), each row
@@ -132,17 +132,11 @@ PATH_TABLE = [
     (0, "f64", (512, 16, 8, 1), 1, 1, 1, {"cluster": "0"}, "f64_valu"),
     (1, "f64", (512, 16, 8, 1), 1, 1, 1, {}, "cluster_f64"),
     (1, "f64", (512, 16, 8, 1), 150, 1, 1, {}, "f64_mfma"),
-    # harvest, fp16/bf16 at 257..512 units: the cluster kernel, whatever "harvest_gemm" says
+    # harvest, fp16/bf16 at 257..512 units: the cluster kernel
     (1, "f16", (512, 16, 8, 1), 70, 1, 1, {}, "harvest_cluster"),
     (1, "bf16", (300, 16, 8, 1), 64, 1, 1, {}, "harvest_cluster"),
-    (1, "f16", (512, 16, 8, 1), 70, 1, 1, {"hcluster": "8"}, "harvest_cluster"),
-    (1, "f16", (512, 16, 8, 1), 70, 1, 1, {"harvest_gemm": "1"}, "harvest_cluster"),
     (1, "f16", (512, 16, 8, 1), 70, 1, 0, {}, "mfma"),
     (1, "f16", (512, 16, 8, 1), 70, 1, 1, {"hcluster": "0"}, "mfma"),
-    (1, "f16", (512, 16, 8, 1), 70, 1, 1, {"hcluster": "0", "harvest_gemm": "1"}, "big_harvest"),
-    (1, "f16", (300, 16, 8, 1), 64, 1, 1, {"hcluster": "0", "harvest_gemm": "1"}, "big_harvest"),
-    (1, "f16", (512, 16, 8, 1), 63, 1, 1, {"hcluster": "0", "harvest_gemm": "1"}, "mfma"),     # fewer than 64 pilots
-    (1, "bf16", (1024, 8, 4, 1), 65, 1, 1, {"harvest_gemm": "1"}, "big_harvest"),
     (1, "f16", (256, 16, 8, 1), 70, 1, 1, {}, "mfma"),
     (1, "f16", (2048, 16, 8, 1), 70, 1, 1, {}, "big_harvest"),
     (1, "f16", (2048, 16, 8, 1), 70, 1, 0, {}, "mfma"),
@@ -226,12 +220,10 @@ def test_sizes_and_paths_agree(lib):
 # every knob: key -> spellings esn_debug_set accepts (None = NULL: back to the default)
 KNOB_SPELLINGS = {
     "skew": ["0", "1", None], "chol_dma": ["0", "1", None], "f64_mfma": ["0", "1", None],
-    "big_gemm": ["0", "1", None], "cluster": ["0", "1", None], "big_pipe": ["0", "1", None],
-    "harvest_gemm": ["1", "0", None], "s16": ["0", "1", None],
+    "big_gemm": ["0", "1", None], "cluster": ["0", "1", None], "s16": ["0", "1", None],
     "mfma_geom": ["8,2,4", "junk", None], "mfma_geom_f32": ["8,2,2", None],
     "chol_skip": ["3", "0", None], "gen_ko": ["5", "0", None],
-    "big_nt": ["4", "2", None], "hcluster": ["0", "4", "8", "1", None],
-    "rs": ["0", None],
+    "hcluster": ["0", "4", "8", "1", None],
 }
 
 
@@ -248,22 +240,20 @@ def test_every_knob_parses(lib):
     assert lib.esn_debug_set(b"nope", b"1") == -1
     assert lib.esn_last_error() == b"esn_debug_set: unknown key 'nope'"
     assert lib.esn_debug_set(None, b"1") == -1 and lib.esn_last_error() == b"esn_debug_set: null key"
-    # the register-state experiment is not in the product library
-    assert lib.esn_debug_set(b"rs", b"1") == -3 and b"ESN_WITH_RS=1" in lib.esn_last_error()
+    for key in RETIRED:
+        assert lib.esn_debug_set(key.encode(), b"1") == -1, key
+        assert lib.esn_last_error() == b"esn_debug_set: unknown key '" + key.encode() + b"'"
     # the header documents every key of the table
     doc = open(os.path.join(ROOT, "include", "esn_hip.h")).read()
     for key in KNOB_SPELLINGS:
         assert f'"{key}"' in doc, key
         if key != "gen_ko":
             assert "ESN_" + key.upper() in doc, key
-    # parse rules seen through the plan: on-unless-"0", off-unless-"1", hcluster's own
+    # the parse rule seen through the plan: on unless "0" (hcluster's "4" / "8" once chose the members of a cluster)
     sh = _lib.Shape(512, 16, 8, 1, 1, 1.0)
     for v, want in (("2", "skew16"), ("0", "mfma"), (None, "skew16")):
         with knobs_set(_lib, s16=v):
             assert _lib.recur_path(False, "f16", sh, 150, 75) == want, v
-    for v, want in (("2", "mfma"), ("1", "big_harvest"), (None, "mfma")):
-        with knobs_set(_lib, hcluster="0", harvest_gemm=v):
-            assert _lib.recur_path(True, "f16", sh, 70) == want, v
-    for v, want in (("2", 163904), ("1", 163904), (None, 163904), ("0", 0)):      # pairs: ceil(70 / 16) * 32768 + 64
+    for v, want in (("2", 163904), ("1", 163904), ("4", 163904), ("8", 163904), (None, 163904), ("0", 0)):      # pairs: ceil(70 / 16) * 32768 + 64
         with knobs_set(_lib, hcluster=v):
             assert lib.esn_harvest_workspace_bytes(_lib.F16, C.byref(sh), 70) == want, v

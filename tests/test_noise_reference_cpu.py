@@ -168,8 +168,8 @@ def test_table_names_the_dispatched_kernel_and_covers_every_path():
             for k in c.knobs:
                 _lib.debug_set(k, None)
         assert got == c.path, (c.id, got)
-    assert {c.path for c in nr.CASES} == set(_lib.PATHS) - {"rs"}        # "rs": ESN_WITH_RS builds only
-    for path in set(_lib.PATHS) - {"rs"}:
+    assert {c.path for c in nr.CASES} == set(_lib.PATHS)
+    for path in _lib.PATHS:
         kinds = {c.kind for c in nr.CASES if c.path == path}
         assert kinds, path
     # the ragged last group and the seed's high half are what the table promises

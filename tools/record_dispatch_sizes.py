@@ -23,10 +23,8 @@ N_RES = (64, 128, 129, 256, 257, 300, 512, 513, 1024, 1025, 1500, 2048, 2049)
 IO = ((2, 2), (3, 2), (4, 4), (16, 8), (16, 16))
 N_WSETS = (1, 3)
 FRAMES = ((1, 1), (8, 1), (9, 4), (150, 75), (4096, 64))            # (n_frames, frames_per_group)
-DEFAULTS = {"cluster": "1", "big_gemm": "1", "harvest_gemm": "0", "hcluster": "1", "f64_mfma": "1", "s16": "1",
-            "skew": "1"}
-MOVED = (("cluster", "0"), ("big_gemm", "0"), ("harvest_gemm", "1"), ("hcluster", "0"), ("hcluster", "4"),
-         ("hcluster", "8"), ("f64_mfma", "0"), ("s16", "0"), ("skew", "0"))
+DEFAULTS = {"cluster": "1", "big_gemm": "1", "hcluster": "1", "f64_mfma": "1", "s16": "1", "skew": "1"}
+MOVED = (("cluster", "0"), ("big_gemm", "0"), ("hcluster", "0"), ("f64_mfma", "0"), ("s16", "0"), ("skew", "0"))
 
 
 def shapes():
