@@ -141,6 +141,16 @@ SIGNATURES = {
     # frames_per_group, T_in, T, transient, Y, stream
     "esn_fnn_predict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                   _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp]),
+    # windowed CNN: n_in, c1, c2, n_out, kernel, n_groups, n_frames, T -> bytes of the workspace of train / predict
+    "esn_cnn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # precision, n_in, c1, c2, n_out, kernel, n_isets, W1_0, b1_0, W2_0, b2_0, W3_0, b3_0, in_scale, in_shift, t_scale,
+    # t_shift, U, D, n_groups, T_in, T, transient, group_offset, epochs, lr, beta1, beta2, eps, W1, b1, W2, b2, W3, b3,
+    # loss, workspace, workspace_bytes, stream
+    "esn_cnn_train": (C.c_int, [C.c_int] * 7 + [_dp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                                C.c_double, C.c_double, C.c_double, C.c_double] + [_dp] * 7 + [_vp, C.c_size_t, _vp]),
+    # precision, n_in, c1, c2, n_out, kernel, W1, b1, W2, b2, W3, b3, in_scale, in_shift, t_scale, t_shift, U, n_frames,
+    # frames_per_group, T_in, T, transient, Y, workspace, workspace_bytes, stream
+    "esn_cnn_predict": (C.c_int, [C.c_int] * 6 + [_dp] * 11 + [C.c_int] * 5 + [_dp, _vp, C.c_size_t, _vp]),
     "esn_ldpc_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "esn_qam_llr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _vp]),
     "esn_ldpc_decode_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp,

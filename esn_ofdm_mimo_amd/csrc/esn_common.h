@@ -214,6 +214,25 @@ struct FnnTrainParams {
     double* loss;                // [groups][epochs] or nullptr
     double* workspace;           // the moments of W1: fnn_train_workspace_bytes
 };
+// windowed CNN (esn_cnn.hip): three Conv1d layers n_in -> c1 -> c2 -> n_out of one odd kernel size over the whole
+// sequence, zero padded, ReLU after the first two; trained per group by full-batch Adam (T_in .. group_offset, epochs ..
+// loss as in FnnTrainParams) or evaluated per frame (n_frames, frames_per_group, Y)
+struct CnnParams {
+    int n_in, c1, c2, n_out, kernel, n_isets, n_groups, T_in, T, transient, epochs;
+    int n_frames, frames_per_group;                  // predict: frame f reads the set of group f / frames_per_group
+    unsigned long long group_offset;
+    double lr, beta1, beta2, eps;
+    const double* W0[3];         // train: [n_isets][c_l][c_{l-1}][kernel] initial;  predict: [groups][...] trained
+    const double* b0[3];         // [..][c_l]
+    const double *in_scale, *in_shift, *t_scale, *t_shift;   // [groups][n] or nullptr
+    const double* U;             // [groups | n_frames][T_in][n_in]
+    const double* D;             // [groups][T][n_out]                              (train)
+    double* W[3];                // [groups][c_l][c_{l-1}][kernel]                  (train)
+    double* b[3];                // [groups][c_l]
+    double* loss;                // [groups][epochs] or nullptr
+    double* Y;                   // [n_frames][T - transient][n_out]                (predict)
+    double* workspace;           // cnn_workspace_bytes
+};
 
 // coded leg (esn_coded.hip)
 struct LdpcEncodeParams {
@@ -281,6 +300,15 @@ template <bool IO32> __device__ __forceinline__ io_elem<IO32>* out_ptr(const Rec
 }
 
 inline __host__ __device__ int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// one Adam step of one parameter with gradient q (include/esn_hip.h, the FNN block): step = lr / (1 - beta1^e),
+// rs2 = sqrt(1 - beta2^e).  Shared by the trainings of the windowed FNN and CNN.
+__device__ __forceinline__ void fnn_adam(double& prm, double& m, double& v, double q, double beta1, double beta2,
+                                         double step, double rs2, double eps) {
+    m = beta1 * m + (1.0 - beta1) * q;
+    v = beta2 * v + (1.0 - beta2) * (q * q);
+    prm -= step * (m / (sqrt(v) / rs2 + eps));
+}
 
 // k order of the 16x16x32 skewed kernel (esn_recur_skew16_impl.h): position of natural column k inside the padded
 // K axis.  State rows: R = 32 kk + 16 t + 4 g + e  ->  32 kk + 8 g + 4 t + e (the accumulator rows 4 g .. 4 g + 3 of two

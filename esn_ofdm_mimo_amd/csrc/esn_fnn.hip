@@ -72,12 +72,7 @@ __device__ __forceinline__ double fnn_quad_sum(double a) {
     return a;
 }
 
-__device__ __forceinline__ void fnn_adam(double& prm, double& m, double& v, double q, double beta1, double beta2,
-                                         double step, double rs2, double eps) {
-    m = beta1 * m + (1.0 - beta1) * q;
-    v = beta2 * v + (1.0 - beta2) * (q * q);
-    prm -= step * (m / (sqrt(v) / rs2 + eps));
-}
+// (fnn_adam, the Adam step, is in esn_common.h: the windowed CNN shares it)
 
 __global__ __launch_bounds__(FNN_THREADS) void fnn_train_kernel(FnnTrainParams p) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];

@@ -146,4 +146,10 @@ int launch_fnn_predict(int precision, const ElmParams& p, hipStream_t stream);
 size_t fnn_train_lds_bytes(int n_in, int n_hidden, int window, int n_out, int T);
 size_t fnn_train_workspace_bytes(int n_in, int n_hidden, int window, int n_groups);
 int launch_fnn_train(const FnnTrainParams& p, hipStream_t stream);
+// esn_cnn.hip: the windowed CNN.  cnn_shape_limit: nullptr if the shape is served, else the limit it misses;
+// cnn_workspace_bytes: what n_groups trainings or a prediction of n_frames frames (either may be 0) need
+const char* cnn_shape_limit(int n_in, int c1, int c2, int n_out, int kernel, int T);
+size_t cnn_workspace_bytes(int n_in, int c1, int c2, int n_out, int kernel, int n_groups, int n_frames, int T);
+int launch_cnn_train(const CnnParams& p, hipStream_t stream);
+int launch_cnn_predict(const CnnParams& p, hipStream_t stream);
 }  // namespace esn

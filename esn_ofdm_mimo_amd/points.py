@@ -4,8 +4,8 @@ driver's coded + uncoded ESN against LS/MMSE (coded_ber_point) and the block-fad
 through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says.
 Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, uncoded, detected symbol by symbol with its
 channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
-only.  And elm_point / fnn_point: the windowed ELM (elm.py) and the windowed FNN (fnn.py), the reference's pinv-trained and
-Adam-trained comparators, on the same frames."""
+only.  And elm_point / fnn_point / cnn_point: the windowed ELM (elm.py), FNN (fnn.py) and CNN (cnn.py), the reference's
+pinv-trained and Adam-trained comparators, on the same frames."""
 from __future__ import annotations
 
 from .frames import _view_real, summarize_channel_metrics
@@ -364,3 +364,60 @@ def fnn_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, window=8, epochs
 
     return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision,
                            slice, train)
+
+
+def cnn_weights(channels, kernel, n_in, n_out, seed, block=None):
+    """(W1 [c1, n_in, k], b1, W2 [c2, c1, k], b2, W3 [n_out, c2, k], b3), each U(+-1 / sqrt(fan_in)) with
+    fan_in = c_in k -- the distribution of torch.nn.Conv1d -- drawn in that order from RandomState(seed) or, for the set
+    of one global block, RandomState([seed, block])."""
+    import numpy as np
+    rs = np.random.RandomState(seed if block is None else [seed, block])
+    c = (n_in, channels[0], channels[1], n_out)
+    out = []
+    for l in range(3):
+        a = 1.0 / np.sqrt(c[l] * kernel)
+        out += [rs.uniform(-a, a, (c[l + 1], c[l], kernel)), rs.uniform(-a, a, c[l + 1])]
+    return tuple(out)
+
+
+def cnn_point(src, ebno_db, snr_idx, n_blocks, *, channels=(32, 64), kernel=5, epochs=50, lr=0.01, slice="aligned",
+              weights="shared", first_block=0, seed=0, frames_per_block=None, chunk_blocks=None):
+    """One Eb/No point of the windowed CNN (cnn.CnnBank), the reference's third learned comparator, on the frames
+    elm_point, fnn_point and a DetectorSweep over the same FrameSource seed detect: per chunk the pilot of every block
+    gives one training (inputs and teacher scaled by 1 / sqrt(var_x), the loss over rows from delay + cp on, `epochs`
+    Adam steps from cnn_weights), then all data frames are predicted in one launch and counted by the detector tail.
+    slice and weights as in elm_point ("reference": rows [0, N) of the un-cut output, the slice the reference's CNN
+    branch takes, :535-536).  Float64 throughout.  Returns (errors, bits): int64 [n_blocks] on the device; nothing is
+    read back inside the chunk loop."""
+    _check_windowed_point_args(slice, weights, "f64", 1, n_blocks, first_block, chunk_blocks, frames_per_block)
+    channels = tuple(channels)
+    if len(channels) != 2 or not all(isinstance(c, int) and c >= 1 for c in channels):
+        raise ValueError(f"channels must be two positive integers, not {channels!r}")
+    if not isinstance(kernel, int):
+        raise ValueError(f"kernel must be an integer, not {kernel!r}")
+    if not isinstance(epochs, int) or epochs < 1:
+        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
+    if not lr >= 0:
+        raise ValueError(f"lr = {lr} must be non-negative")
+    import numpy as np
+    from .cnn import CnnBank, train_shape_error
+    p = src.p
+    n_in, n_out = 2 * p.n_r, 2 * p.n_t
+    why = train_shape_error(n_in, channels[0], channels[1], n_out, kernel, p.t_frame + p.delay)
+    if why:
+        raise ValueError("the CNN kernels do not serve this shape: " + why)
+    shared = cnn_weights(channels, kernel, n_in, n_out, seed) if weights == "shared" else None
+    bank = CnnBank(n_in, n_out, channels, kernel, n_groups=min(int(chunk_blocks or 4096), int(n_blocks)),
+                   device=src.device)
+
+    def train(U, D, scaling, b0, g):
+        if shared is None:
+            sets = [cnn_weights(channels, kernel, n_in, n_out, seed, b0 + i) for i in range(g)]
+            init = tuple(np.stack([s[j] for s in sets]) for j in range(6))
+        else:
+            init = shared
+        bank.set_scaling(*scaling)
+        return bank.train(U, D, init, transient=p.forget, epochs=epochs, lr=lr)
+
+    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, "f64", slice,
+                           train)

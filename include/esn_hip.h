@@ -782,6 +782,53 @@ int esn_fnn_predict(int precision, int n_in, int n_hidden, int window, int n_out
                     const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
                     double* Y, void* stream);
 
+/* ---- Windowed CNN (the reference's third learned comparator: class CNNModel, system_model_2_all_comparision.py:14-27,
+ * trained as trainMIMOModel('CNN') does, :93-113): three Conv1d layers over the whole pilot sequence, trained per group
+ * by `epochs` full-batch Adam steps on the mean squared error.  Channels c0 = n_in, c1, c2, c3 = n_out; the kernel size k
+ * is odd, p = (k - 1) / 2; parameters in torch's Conv1d layout W_l [c_l][c_{l-1}][k], b_l [c_l].  For group g:
+ *   x_0[t][i] = u[t][i] in_scale[g][i] + in_shift[g][i]   0 <= t < T, u = 0 for T_in <= t < T (zero rows BEFORE scaling)
+ *   z_l[t][o] = b_l[o] + sum_i sum_j W_l[o][i][j] x_{l-1}[t + j - p][i]     x_l = max(z_l, 0), l = 1, 2;   ys = z_3
+ *   every x_l (l = 0, 1, 2) exactly 0 outside [0, T): torch's zero padding of each layer's input, not the scaled zero row
+ *   loss = sum_{transient <= t < T, o} (ys[t][o] - (D[g][t][o] t_scale[g][o] + t_shift[g][o]))^2 / ((T - transient) n_out)
+ *   Adam exactly as in the FNN block above (the gradient of ReLU at 0 is 0), epoch e = 1..epochs; loss[g][e] is the loss
+ *   BEFORE step e.  The reference's values: k = 5, c1 = 32, c2 = 64, transient = 0, epochs = 50, lr = 0.01.
+ *   predict: Y[f][t - transient][o] = (ys[t][o] - t_shift[g][o]) / t_scale[g][o], g = f / frames_per_group.
+ * A parameter whose gradient is exactly 0 in every epoch (a channel that is never active, and the next layer's weights
+ * that read it) comes out bitwise as it went in.
+ * esn_cnn_train    group g starts from the initial set (group_offset + g) % n_isets of W1_0 .. b3_0 [n_isets][...] and
+ *                  writes W1 .. b3 [G][...]; loss [G][epochs] may be NULL; U [G][T_in][n_in], D [G][T][n_out], scalings
+ *                  [G][n] or NULL.  One workgroup per group and one launch for all epochs, float64; all three layers'
+ *                  forward, input-gradient and weight-gradient products run on v_mfma_f64_16x16x4_f64.  Every sum in an
+ *                  order that depends on the shape alone, no atomics, nothing shared between workgroups: a group is
+ *                  bitwise the same alone and inside any batch.  ESN_F64 only: every other precision returns -2.
+ *                  workspace: device memory of esn_cnn_workspace_bytes(..., n_groups, 0, T) bytes (per group the
+ *                  parameters, Adam's moments, the padded activations and their gradients: nothing of this fits on
+ *                  chip), not initialised by the caller and of no meaning afterwards.
+ * esn_cnn_predict  the same forward functions, a workgroup per frame, the inner activations in that workgroup's part of
+ *                  the workspace (esn_cnn_workspace_bytes(..., 0, n_frames, T) bytes: at most 512 parts).  A frame is
+ *                  bitwise the same alone and inside any batch.  ESN_F64 only (-2 otherwise): there is no fp16 instance.
+ * esn_cnn_workspace_bytes   the larger of what n_groups trainings and what a prediction of n_frames frames need (either
+ *                  count may be 0); 0 for an unserved shape.
+ * Served: 1 <= n_in <= 64, 1 <= c1, c2 <= 128, 1 <= n_out <= 8, k in {1, 3, 5, 7}, 1 <= T_in <= T <= 4096,
+ * 0 <= transient < T (T may be below k), epochs >= 1, lr >= 0, 0 <= beta < 1, eps > 0.  Anything else returns -1 before
+ * any HIP call, the limit in esn_last_error().  No float32 I/O variant, no _mem front end, one pilot per group.  These
+ * are additions: the ABI version is unchanged. */
+size_t esn_cnn_workspace_bytes(int n_in, int c1, int c2, int n_out, int kernel, int n_groups, int n_frames, int T);
+int esn_cnn_train(int precision, int n_in, int c1, int c2, int n_out, int kernel, int n_isets,
+                  const double* W1_0, const double* b1_0, const double* W2_0, const double* b2_0,
+                  const double* W3_0, const double* b3_0,
+                  const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                  const double* U, const double* D, int n_groups, int T_in, int T, int transient,
+                  uint64_t group_offset, int epochs, double lr, double beta1, double beta2, double eps,
+                  double* W1, double* b1, double* W2, double* b2, double* W3, double* b3, double* loss,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int esn_cnn_predict(int precision, int n_in, int c1, int c2, int n_out, int kernel,
+                    const double* W1, const double* b1, const double* W2, const double* b2,
+                    const double* W3, const double* b3,
+                    const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                    const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
+                    double* Y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; the 4x8 ChannelRank driver is
  * named after it), float64.  H complex [G][N][n_r][n_t] in the layout of the function above, 16-byte aligned; p_i [G]
  * on the device as in the detectors; per subcarrier k the singular values s_1 >= ... of H_k by one-sided complex
