@@ -261,10 +261,11 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
                 idx |= (uint32_t)(fp.bits_in[((size_t)frame * N * m + (size_t)sc * m + b) * n_t + tx] & 1) << b;
             place(e, idx);
         }
-    } else if (m == 4 && n_t == 4) {
+    } else if (m == 4 && n_t == 4 && N >= 8) {
         // headline shape: a call's 32 symbols are 8 whole subcarriers; a subcarrier's 16 bit-bytes (bit b of tx at
         // b n_t + tx) leave as ONE 16-byte store instead of 16 byte stores (2 048 byte stores per frame were half of
-        // the kernel's floor)
+        // the kernel's floor).  N is a power of two, so N >= 8 is a whole number of calls; N = 2 and 4 are less than
+        // one call and take the general branch, which guards every element (same counters, same word use)
         for (int call = tid; call * 32 < N * 4; call += nth) {
             uint32_t w[4];
             ph((uint32_t)gf, (uint32_t)(gf >> 32), PURPOSE_BITS, (uint32_t)call, w);

@@ -4,6 +4,9 @@ Deterministic leg: bits, noise and tap gains are supplied, so the kernels must r
 oracle's transmitter / channel arithmetic to float64 round-off (1e-12 of max|y|).
 Statistical leg: the Philox streams -- bit balance, unit-variance noise, unit-energy TDL-B taps,
 and stream independence from the launch shape (a block generated alone == generated in a batch).
+The draws themselves are pinned elsewhere: tests/philox_ref.py is a host model of every stream,
+tests/test_philox_reference_cpu.py checks the model (known answers, distribution), and
+tests/test_gpu_philox_streams.py compares each kernel drawing for itself with the kernel fed the model.
 What is pinned here is that the HIP generator equals the oracle restatement; the oracle's recipe and
 the generator are each held to the reference drivers' own loop statements, sample for sample, by the
 loop_*.npz fixtures (tests/test_oracle_driver_loop.py, tests/test_gpu_driver_loop.py)."""
