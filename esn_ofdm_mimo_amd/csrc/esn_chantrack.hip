@@ -303,16 +303,8 @@ int launch_channel_track(const ChanTrackParams& cp_in, hipStream_t stream) {
     if (threads > CT_MAX_THREADS) return -1;
     // the LDS ceiling is raised once per device, to the most any shape may ask for: the tracking loop launches per symbol
     static std::atomic<unsigned long long> raised{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    const unsigned long long bit = 1ULL << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(channel_track_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT_MAX_LDS);
-        if (e != hipSuccess) return (int)e;
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
+    const int e = raise_dynamic_lds_once(reinterpret_cast<const void*>(channel_track_kernel), CT_MAX_LDS, raised);
+    if (e) return e;
     hipLaunchKernelGGL(channel_track_kernel, dim3(cp.n_est), dim3(threads), lds, stream, cp);
     return (int)hipGetLastError();
 }

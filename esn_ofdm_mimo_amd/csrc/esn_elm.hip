@@ -429,22 +429,12 @@ __global__ __launch_bounds__(64 * ELM16_WAVES) void elm_f16_kernel(ElmParams p, 
     }
 }
 
-// the dynamic-LDS ceiling of `kernel` is raised once per device, to the most any shape may ask for
-static int elm_raise_lds(const void* kernel, std::atomic<unsigned long long>& raised, int* cu_count) {
+// the CU count of the current device, which sizes the persistent grid of the fp16 kernels
+static int elm_cu_count(int* cu_count) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (cu_count) {
-        e = hipDeviceGetAttribute(cu_count, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return (int)e;
-    }
-    const unsigned long long bit = 1ULL << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ELM_MAX_LDS);
-        if (e != hipSuccess) return (int)e;
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
-    return 0;
+    if (e == hipSuccess) e = hipDeviceGetAttribute(cu_count, hipDeviceAttributeMultiprocessorCount, dev);
+    return (int)e;
 }
 
 int launch_elm_features(const ElmParams& p, hipStream_t stream) {
@@ -458,7 +448,10 @@ template <int NT, int KK, bool W_LDS, bool RELU>
 static int launch_elm16(const ElmParams& p, hipStream_t stream) {
     static std::atomic<unsigned long long> raised{0};
     int cus = 0;
-    const int e = elm_raise_lds(reinterpret_cast<const void*>(elm_f16_kernel<NT, KK, W_LDS, RELU>), raised, &cus);
+    int e = elm_cu_count(&cus);
+    if (!e)
+        e = raise_dynamic_lds_once(reinterpret_cast<const void*>(elm_f16_kernel<NT, KK, W_LDS, RELU>), ELM_MAX_LDS,
+                                   raised);
     if (e) return e;
     const size_t lds = elm16_lds_bytes<NT, KK>(p, W_LDS);
     const int n_batches = (p.T + 16 * NT - 1) / (16 * NT);
@@ -475,7 +468,8 @@ template <bool RELU>
 static int launch_predict(int precision, const ElmParams& p, hipStream_t stream) {
     if (precision == ESN_F64) {
         static std::atomic<unsigned long long> raised{0};
-        const int e = elm_raise_lds(reinterpret_cast<const void*>((elm_f64_kernel<true, RELU>)), raised, nullptr);
+        const int e = raise_dynamic_lds_once(reinterpret_cast<const void*>((elm_f64_kernel<true, RELU>)), ELM_MAX_LDS,
+                                             raised);
         if (e) return e;
         const int n_tiles = (p.T + ELM_TR - 1) / ELM_TR;
         hipLaunchKernelGGL((elm_f64_kernel<true, RELU>), dim3((unsigned)(p.n_seq * n_tiles)), dim3(ELM_THREADS),

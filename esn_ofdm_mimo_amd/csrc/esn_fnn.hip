@@ -298,16 +298,8 @@ __global__ __launch_bounds__(FNN_THREADS) void fnn_train_kernel(FnnTrainParams p
 
 int launch_fnn_train(const FnnTrainParams& p, hipStream_t stream) {
     static std::atomic<unsigned long long> raised{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    const unsigned long long bit = 1ULL << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(fnn_train_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)FNN_MAX_LDS);
-        if (e != hipSuccess) return (int)e;
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
+    const int e = raise_dynamic_lds_once(reinterpret_cast<const void*>(fnn_train_kernel), FNN_MAX_LDS, raised);
+    if (e) return e;
     hipLaunchKernelGGL(fnn_train_kernel, dim3((unsigned)p.n_groups), dim3(FNN_THREADS),
                        fnn_train_lds_bytes(p.n_in, p.n_hidden, p.window, p.n_out, p.T), stream, p);
     return (int)hipGetLastError();

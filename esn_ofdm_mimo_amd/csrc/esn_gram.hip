@@ -13,14 +13,16 @@
 //       load of the state) and one write, the mirror image of an off-diagonal element written from the same register.
 //   gram_solve_kernel        one workgroup per group, the candidates one after the other over one factor buffer in the
 //       caller's workspace: left-looking blocked Cholesky of Gm + lambda I, panel products, diagonal block and panel
-//       solve as in esn_solve_chol_big.hip (Gm itself is only read: a left-looking factorisation never updates the
-//       trailing matrix), then the substitutions, one wave per right-hand side.
+//       solve by chol_panel_factor (esn_chol_panel.h, shared with readout_chol_big_kernel; Gm itself is only read: a
+//       left-looking factorisation never updates the trailing matrix), then the substitutions, one wave per right-hand
+//       side, as in esn_solve_chol_big.hip.
 //
 // Every sum runs in an order fixed by the shape alone (the row chunks in order, one accumulator per element), there are
-// no atomics, a group's result does not depend on the batch it is in, and no load sits behind a branch: addresses are
-// clamped and what lies outside is a select.
-#include <atomic>
-#include "esn_solve.h"
+// no atomics and a group's result does not depend on the batch it is in.  Loads of E, D_s, Gm and Cm do not sit behind a
+// branch: addresses are clamped and what lies outside is a select.  The factor columns of the substitutions are
+// predicated loads, as in esn_solve_chol_big.hip (a third faster than the clamped form: profiles/chol_panel_time.txt).
+#include "esn_chol_panel.h"
+#include "esn_stage.h"
 
 namespace esn {
 
@@ -39,8 +41,6 @@ constexpr int GA_TPW = (GA_BAND * (GR_TMAX + 1) + GA_NW - 1) / GA_NW;      // ti
 static_assert(GR_NMAX % 16 == 0 && GA_LD % 32 == 16 && GA_KC % 4 == 0 && GA_KC * 16 <= GA_NT, "layout");
 
 typedef double gr_f64x4 __attribute__((ext_vector_type(4)));
-typedef double gr_f64x2 __attribute__((ext_vector_type(2)));
-typedef float gr_f32x4 __attribute__((ext_vector_type(4)));
 
 struct GramAccParams {
     const double* E; const float* E32; const double* D;
@@ -49,37 +49,17 @@ struct GramAccParams {
     double decay; double* Gm; double* Cm;
 };
 
-__device__ __forceinline__ const float* ga_src(const GramAccParams& p, float*) { return p.E32; }
-__device__ __forceinline__ const double* ga_src(const GramAccParams& p, double*) { return p.E; }
-
-// 16 bytes per lane where the row length allows it (VEC: cols % 4 == 0, every row and every unit 16-byte aligned)
-template <typename T, bool VEC> struct GaUnit { static constexpr int V = 1; };
-template <> struct GaUnit<double, true> { static constexpr int V = 2; };
-template <> struct GaUnit<float, true> { static constexpr int V = 4; };
-
-__device__ __forceinline__ void ga_fetch(const double* p, double (&v)[1]) { v[0] = *p; }
-__device__ __forceinline__ void ga_fetch(const float* p, double (&v)[1]) { v[0] = (double)*p; }
-__device__ __forceinline__ void ga_fetch(const double* p, double (&v)[2]) {
-    const gr_f64x2 x = *reinterpret_cast<const gr_f64x2*>(p);
-    v[0] = x[0]; v[1] = x[1];
-}
-__device__ __forceinline__ void ga_fetch(const float* p, double (&v)[4]) {
-    const gr_f32x4 x = *reinterpret_cast<const gr_f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (double)x[i];
-}
-
 template <typename TE, bool VEC, bool FRESH>
 __global__ __launch_bounds__(GA_NT) void gram_accumulate_kernel(GramAccParams sp) {
     __shared__ __attribute__((aligned(16))) double Es[GA_KC * GA_LD];      // 35 840 B
-    constexpr int V = GaUnit<TE, VEC>::V;
+    constexpr int V = StageUnit<TE, VEC>::V;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
     const int rows = sp.T - sp.transient, cols = sp.cols, nrhs = sp.n_out;
     const int ntile = (cols + 15) / 16, nband = (ntile + GA_BAND - 1) / GA_BAND;
     const int g = blockIdx.x / nband, band = blockIdx.x - g * nband;
-    const TE* Eg = ga_src(sp, (TE*)nullptr) + ((size_t)g * sp.T + sp.transient) * cols;       // [rows][cols]
+    const TE* Eg = stage_src(sp, (TE*)nullptr) + ((size_t)g * sp.T + sp.transient) * cols;    // [rows][cols]
     const double* Dg = sp.D + ((size_t)g * sp.T + sp.transient) * nrhs;
     double* Gg = sp.Gm + (size_t)g * cols * cols;
     double* Cg = sp.Cm + (size_t)g * nrhs * cols;
@@ -118,7 +98,7 @@ __global__ __launch_bounds__(GA_NT) void gram_accumulate_kernel(GramAccParams sp
             const int e = e0 + tid, ec = e < total ? e : 0;
             const int kk = ec / upr, c = (ec - kk * upr) * V, r = r0 + kk;
             double v[V];
-            ga_fetch(Eg + (size_t)(r < rows ? r : rows - 1) * cols + c, v);
+            stage_fetch(Eg + (size_t)(r < rows ? r : rows - 1) * cols + c, v);
             if (e < total) {
 #pragma unroll
                 for (int x = 0; x < V; ++x) Es[kk * GA_LD + c + x] = r < rows ? v[x] : 0.0;
@@ -193,9 +173,9 @@ int launch_gram_accumulate(const GramAccArgs& a) {
 }
 
 // ---- solve ----------------------------------------------------------------------------------------------------------
-constexpr int GS_NT = 512;                  // 8 waves, as the workspace Cholesky kernel
-constexpr int GS_NW = GS_NT / 64;
-constexpr int GS_PLD = 17;                  // LDS row stride of the panel (doubles)
+constexpr int GS_NT = CP_NT;                // 8 waves, as the workspace Cholesky kernel
+constexpr int GS_NW = CP_NW;
+constexpr int GS_PLD = CP_PLD;              // LDS row stride of the panel (doubles)
 constexpr int GS_RHS = 16;                  // right-hand sides at most
 constexpr int GS_NS = (GR_NMAX + 63) / 64;  // rows per lane in the substitutions
 constexpr size_t GS_LDS = sizeof(double) * ((size_t)GS_RHS * GR_NMAX + (size_t)GR_NMAX * GS_PLD);         // 143 616 B
@@ -230,15 +210,9 @@ __global__ __launch_bounds__(GS_NT) void gram_solve_kernel(GramSolveParams sp) {
     const double* Cg = sp.Cm + (size_t)g * nrhs * n;
     double* Lw = sp.work + (size_t)g * sp.work_stride;                  // [np][np] column-major factor, lower part
 
+    const CholPanelLds lds = {P, sh_invd, sh_linv, &sh_bad};
     // the largest diagonal entry of Gm (the candidates add their lambda to it)
-    double gmax = 0.0;
-    for (int i = tid; i < n; i += GS_NT) gmax = fmax(gmax, Gg[(size_t)i * n + i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) gmax = fmax(gmax, __shfl_down(gmax, off));
-    if (lane == 0) sh_red[wv] = gmax;
-    __syncthreads();
-    gmax = 0.0;
-    for (int w = 0; w < GS_NW; ++w) gmax = fmax(gmax, sh_red[w]);
+    const double gmax = chol_diag_max([&](int i) { return Gg[(size_t)i * n + i]; }, n, sh_red);
 
     for (int l = 0; l < sp.n_ridge; ++l) {
         const int slot = g * sp.n_ridge + l;
@@ -258,68 +232,15 @@ __global__ __launch_bounds__(GS_NT) void gram_solve_kernel(GramSolveParams sp) {
         }
         __syncthreads();
 
-        // ---- left-looking panel Cholesky of Gm + lambda I ---------------------------------------------------------
-        for (int j = 0; j < ntile; ++j) {
-            const int j0 = 16 * j;
-            // (1) panel tiles: (Gm + lambda I)(rt, j) - L(rt, :j0) L(j, :j0)^T; element (row, col) of Gm is read as
-            // (col, row), which is the same number and puts a lane group's 16 rows on one 128-byte segment
-            for (int rt = j + wvu; rt < ntile; rt += GS_NW) {
-                gr_f64x4 c;
-                const int col = j0 + lr;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int row = rt * 16 + 4 * i + lq;
-                    const bool in = row < n && col < n;
-                    const double v = Gg[(size_t)(in ? col : 0) * n + (in ? row : 0)];
-                    c[i] = in ? (row == col ? v + lam : v) : 0.0;
-                }
-                const double* la = Lw + (size_t)lq * ld + rt * 16 + lr;      // L[rt*16 + lr][k + lq]
-                const double* lb = Lw + (size_t)lq * ld + j0 + lr;           // L[j0 + lr][k + lq]
-#pragma unroll 4
-                for (int k = 0; k < j0; k += 4)
-                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(-la[(size_t)k * ld], lb[(size_t)k * ld], c, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) P[(rt * 16 + 4 * i + lq) * GS_PLD + lr] = c[i];
-            }
-            __syncthreads();
-            // (2) diagonal block: factorise and invert in registers (wave 0)
-            if (wv == 0) {
-                const int r = lane & 15;
-                double a[16], x[16], my_invd;
-#pragma unroll
-                for (int c = 0; c < 16; ++c) a[c] = P[(j0 + r) * GS_PLD + c];
-                const unsigned rejected = ch_diag_regs<false, true>(a, x, my_invd, j0, n, piv_tol, r);
-                if (lane < 16) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) P[(j0 + r) * GS_PLD + c] = a[c];
-                    sh_invd[j0 + r] = my_invd;
-                }
-                if (rejected && lane == 0) sh_bad = 1;
-                if (lane < 16) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sh_linv[i][r] = x[i];
-                }
-            }
-            __syncthreads();
-            // (3) panel solve: L(rt, j) = P(rt) L11^-T
-            for (int rt = j + 1 + wvu; rt < ntile; rt += GS_NW) {
-                gr_f64x4 c = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int k0 = 0; k0 < 16; k0 += 4)
-                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(P[(rt * 16 + lr) * GS_PLD + k0 + lq], sh_linv[lr][k0 + lq], c, 0, 0, 0);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int i = 0; i < 4; ++i) P[(rt * 16 + 4 * i + lq) * GS_PLD + lr] = c[i];
-            }
-            __syncthreads();
-            // (4) the finished panel (rows j0 .. np-1, 16 columns) to the workspace, column-major
-            for (int e = tid; e < (np - j0) * 16; e += GS_NT) {
-                const int c = e / (np - j0), rr = j0 + e % (np - j0);
-                Lw[(size_t)(j0 + c) * ld + rr] = P[rr * GS_PLD + c];
-            }
-            __threadfence_block();
-            __syncthreads();
-        }
+        // ---- left-looking panel Cholesky of Gm + lambda I; element (row, col) of Gm is read as (col, row), which is the
+        // same number and puts a lane group's 16 rows on one 128-byte segment; the address is clamped, padding a select
+        for (int j = 0; j < ntile; ++j)
+            chol_panel_factor(Lw, ld, n, np, piv_tol, lds, wvu, j, [&](int rt, int j0, int i) {
+                const int row = rt * 16 + 4 * i + lq, col = j0 + lr;
+                const bool in = row < n && col < n;
+                const double v = Gg[(size_t)(in ? col : 0) * n + (in ? row : 0)];
+                return in ? (row == col ? v + lam : v) : 0.0;
+            });
 
         // ---- L L^T x = b, one wave per right-hand side at a time; lane holds rows lane + 64 s ----------------------
         for (int o = wvu; o < nrhs; o += GS_NW) {
@@ -329,13 +250,10 @@ __global__ __launch_bounds__(GS_NT) void gram_solve_kernel(GramSolveParams sp) {
 #pragma unroll
             for (int s2 = 0; s2 < GS_NS; ++s2) b[s2] = (s2 < ns && lane + 64 * s2 < np) ? xb[lane + 64 * s2] : 0.0;
             auto load_col = [&](double (&dst)[GS_NS], int jc) {
-                const bool on = jc >= 0 && jc < n;
 #pragma unroll
                 for (int s2 = 0; s2 < GS_NS; ++s2) {
                     const int i = lane + 64 * s2;
-                    const bool in = on && i < n;
-                    const double v = Lw[(size_t)(in ? jc : 0) * ld + (in ? i : 0)];
-                    dst[s2] = in ? v : 0.0;
+                    dst[s2] = (s2 < ns && jc >= 0 && jc < n && i < n) ? Lw[(size_t)jc * ld + i] : 0.0;
                 }
             };
             auto pick = [&](const double (&v)[GS_NS], int jc) -> double {      // element jc of the distributed vector
@@ -394,16 +312,8 @@ int launch_gram_solve(const GramSolveArgs& a) {
                                 reinterpret_cast<double*>(a.workspace), gram_solve_work_doubles(a.cols)};
     // the LDS ceiling is raised once per device: the tracked loop launches per symbol
     static std::atomic<unsigned long long> raised{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    const unsigned long long bit = 1ULL << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(gram_solve_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS_LDS);
-        if (e != hipSuccess) return (int)e;
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
+    const int e = raise_dynamic_lds_once(reinterpret_cast<const void*>(gram_solve_kernel), GS_LDS, raised);
+    if (e) return e;
     hipLaunchKernelGGL(gram_solve_kernel, dim3(a.n_groups), dim3(GS_NT), GS_LDS, a.stream, sp);
     return (int)hipGetLastError();
 }

@@ -12,6 +12,7 @@
 // group's scores and choice do not depend on the batch it is scored in; there are no atomics.
 #include "esn_common.h"
 #include "esn_launch.h"
+#include "esn_stage.h"
 
 namespace esn {
 
@@ -35,8 +36,6 @@ static_assert(HO_LD % 2 == 0 && HO_LD % 32 == 2 && HO_BUF % 2 == 0, "aligned row
 static_assert(HO_LDS <= 160 * 1024, "the LDS of a CU");
 
 typedef double ho_f64x4 __attribute__((ext_vector_type(4)));
-typedef double ho_f64x2 __attribute__((ext_vector_type(2)));
-typedef float ho_f32x4 __attribute__((ext_vector_type(4)));
 
 struct HoldoutParams {
     const double* E; const float* E32; const double* D; const double* W;
@@ -44,26 +43,6 @@ struct HoldoutParams {
     const double* t_scale; const double* t_shift; const int* status_in;
     double* score; int* choice;
 };
-
-__device__ __forceinline__ const float* ho_src(const HoldoutParams& p, float*) { return p.E32; }
-__device__ __forceinline__ const double* ho_src(const HoldoutParams& p, double*) { return p.E; }
-
-// 16 bytes per lane where the row length allows it (VEC: cols % 4 == 0, so every row and every unit is 16-byte aligned)
-template <typename T, bool VEC> struct HoUnit { static constexpr int V = 1; };
-template <> struct HoUnit<double, true> { static constexpr int V = 2; };
-template <> struct HoUnit<float, true> { static constexpr int V = 4; };
-
-__device__ __forceinline__ void ho_fetch(const double* p, double (&v)[1]) { v[0] = *p; }
-__device__ __forceinline__ void ho_fetch(const float* p, double (&v)[1]) { v[0] = (double)*p; }
-__device__ __forceinline__ void ho_fetch(const double* p, double (&v)[2]) {
-    const ho_f64x2 x = *reinterpret_cast<const ho_f64x2*>(p);
-    v[0] = x[0]; v[1] = x[1];
-}
-__device__ __forceinline__ void ho_fetch(const float* p, double (&v)[4]) {
-    const ho_f32x4 x = *reinterpret_cast<const ho_f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (double)x[i];
-}
 
 // Rows [0, n_rows) x columns [k0, k0 + HO_KC) of a row-major [.][cols] matrix into registers, zero outside it.  Every
 // lane loads -- from a clamped, valid address -- and the zero is a select, so no load sits behind a branch.
@@ -76,7 +55,7 @@ __device__ __forceinline__ void ho_load(const T* __restrict__ base, int n_rows, 
         const int e = tid + HO_NT * u, i = e / UPR, k = k0 + (e % UPR) * V;
         const bool in = i < n_rows && k < cols;
         double v[V];
-        ho_fetch(base + (size_t)(i < n_rows ? i : n_rows - 1) * cols + (k < cols ? k : 0), v);
+        stage_fetch(base + (size_t)(i < n_rows ? i : n_rows - 1) * cols + (k < cols ? k : 0), v);
 #pragma unroll
         for (int x = 0; x < V; ++x) r[u * V + x] = in ? v[x] : 0.0;
     }
@@ -94,7 +73,7 @@ __device__ __forceinline__ void ho_store(double* __restrict__ dst, int tid, cons
         } else {
 #pragma unroll
             for (int x = 0; x < V; x += 2)
-                *reinterpret_cast<ho_f64x2*>(d + x) = ho_f64x2{r[u * V + x], r[u * V + x + 1]};
+                *reinterpret_cast<stage_f64x2*>(d + x) = stage_f64x2{r[u * V + x], r[u * V + x + 1]};
         }
     }
 }
@@ -106,13 +85,13 @@ __global__ __launch_bounds__(HO_NT) void holdout_score_kernel(HoldoutParams sp) 
     double* Ws = Es + HO_OFF_W;                                     // [HO_N][HO_LD]
     double* Ps = Es + HO_OFF_P;                                     // [2][HO_N] column sums of the two wave rows
     double* Ss = Es + HO_OFF_S;                                     // [16] scores
-    constexpr int VE = HoUnit<TE, VEC>::V, VW = HoUnit<double, VEC>::V;
+    constexpr int VE = StageUnit<TE, VEC>::V, VW = StageUnit<double, VEC>::V;
     const int g = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
     const int wr = wv >> 2, wc = wv & 3;                            // the wave's 64 rows and 32 columns of the product
     const int rows = sp.T - sp.transient, cols = sp.cols, nrhs = sp.n_out, L = sp.n_ridge, N = L * nrhs;
-    const TE* Eg = ho_src(sp, (TE*)nullptr) + ((size_t)g * sp.T + sp.transient) * cols;       // [rows][cols]
+    const TE* Eg = stage_src(sp, (TE*)nullptr) + ((size_t)g * sp.T + sp.transient) * cols;       // [rows][cols]
     const double* Wg = sp.W + (size_t)g * N * cols;                                            // [N][cols]
     const double* Dg = sp.D + ((size_t)g * sp.T + sp.transient) * nrhs;
 

@@ -4,9 +4,24 @@
 // caller sees; default arguments live here only.  Launchers return 0, a hipError_t (> 0), or -1 for "no kernel
 // instance for this shape".
 #pragma once
+#include <atomic>
 #include "esn_common.h"
 
 namespace esn {
+// Raises the dynamic-LDS ceiling of `kernel` to `bytes` (the most any shape may ask for) once per device: `raised`, a
+// static of the calling launcher, holds one bit per device.  For launchers that run per symbol of a tracking loop.
+inline int raise_dynamic_lds_once(const void* kernel, size_t bytes, std::atomic<unsigned long long>& raised) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    const unsigned long long bit = 1ULL << (dev & 63);
+    if (!(raised.load(std::memory_order_relaxed) & bit)) {
+        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return (int)e;
+        raised.fetch_or(bit, std::memory_order_relaxed);
+    }
+    return 0;
+}
 // esn_api.hip: sets esn_last_error(), returns `code`
 int api_fail(int code, const char* fmt, ...);
 #ifdef ESN_STAMPS

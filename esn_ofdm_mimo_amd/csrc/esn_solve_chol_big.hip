@@ -4,24 +4,22 @@
 // (L2 / Infinity Cache resident), every O(n^3) part on the float64 matrix pipe:
 //   phase 1  G (lower 16x16 tiles) in passes of four tile columns: the k-chunks of A stream through
 //            LDS once per pass (double-buffered, register-prefetched), <= 8 accumulator tiles per wave
-//   phase 3  left-looking Cholesky by 16-column panels: panel tile (rt, j) = G(rt, j) - L(rt, :16j) L(j, :16j)^T
-//            with both operands read straight from the workspace in MFMA layout (column-major storage makes a
-//            lane group's 16 rows one 128-byte segment), then the 16x16 diagonal factorisation / inversion in
-//            registers and the panel solve by MFMA exactly as in the LDS kernel; the finished panel goes back
-//            to the workspace
+//   phase 3  left-looking Cholesky by 16-column panels, in place (esn_chol_panel.h, shared with gram_solve_kernel):
+//            panel tile (rt, j) = G(rt, j) - L(rt, :16j) L(j, :16j)^T, the 16x16 diagonal factorisation / inversion
+//            in registers and the panel solve by MFMA exactly as in the LDS kernel
 //   phase 4  column-oriented substitutions, one wave per right-hand side, the next column prefetched
 //   phase 5  W_out^T = A^T alpha (wide) -- the LDS kernel's pass over A
 // Same pivot rule (v <= 1e-14 max diag: direction dropped, group flagged) and the same arithmetic order per
 // tile as the LDS kernel, so the two agree to round-off where both apply.
-#include "esn_solve.h"
+#include "esn_chol_panel.h"
 
 namespace esn {
 
 constexpr int CB_NMAX = 512;      // largest Gram dimension
 constexpr int CB_KC = 8;          // k-chunk staged per pass
-constexpr int CB_PLD = 17;        // LDS row stride of the panel (doubles)
-constexpr int CB_NT = 512;        // threads: 8 waves, two per SIMD -> 256 registers per lane (16 accumulator tiles)
-constexpr int CB_NW = CB_NT / 64;
+constexpr int CB_PLD = CP_PLD;    // LDS row stride of the panel (doubles)
+constexpr int CB_NT = CP_NT;      // threads: 8 waves, two per SIMD -> 256 registers per lane (16 accumulator tiles)
+constexpr int CB_NW = CP_NW;
 constexpr int CB_EPT = CB_NMAX * CB_KC / CB_NT;     // staged elements per thread
 constexpr int CB_TPW = 16;        // Gram tiles per wave and pass: ceil((32 + 31 + 30 + 29) / 8)
 
@@ -170,72 +168,14 @@ __global__ __launch_bounds__(CB_NT) void readout_chol_big_kernel(SolveParams sp)
     __syncthreads();
     double* Bs = reinterpret_cast<double*>(cb_smem);                    // [nrhs][np]          (32 KB)
     double* P = Bs + (size_t)8 * CB_NMAX;                                // [np][CB_PLD] panel  (68 KB)
+    const CholPanelLds lds = {P, sh_invd, sh_linv, &sh_bad};
     // pivot tolerance from the largest diagonal entry
-    double dmax = 0.0;
-    for (int i = tid; i < n; i += CB_NT) dmax = fmax(dmax, Gw[(size_t)i * ld + i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dmax = fmax(dmax, __shfl_down(dmax, off));
-    if (lane == 0) sh_red[wv] = dmax;
-    __syncthreads();
-    double piv_tol = 0.0;
-    for (int w = 0; w < CB_NW; ++w) piv_tol = fmax(piv_tol, sh_red[w]);
-    piv_tol *= 1e-14;
+    const double piv_tol = 1e-14 * chol_diag_max([&](int i) { return Gw[(size_t)i * ld + i]; }, n, sh_red);
 
-    // ---- phase 3: left-looking panel Cholesky ---------------------------------------------------------
-    for (int j = 0; j < ntile; ++j) {
-        const int j0 = 16 * j;
-        // (1) panel tiles: G(rt, j) - L(rt, :j0) L(j, :j0)^T
-        for (int rt = j + wvu; rt < ntile; rt += CB_NW) {
-            f64x4 c;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) c[i] = Gw[(size_t)(j0 + lr) * ld + rt * 16 + 4 * i + lq];
-            const double* la = Gw + (size_t)lq * ld + rt * 16 + lr;       // L[rt*16 + lr][k + lq]
-            const double* lb = Gw + (size_t)lq * ld + j0 + lr;            // L[j0 + lr][k + lq]
-#pragma unroll 4
-            for (int k = 0; k < j0; k += 4)
-                c = __builtin_amdgcn_mfma_f64_16x16x4f64(-la[(size_t)k * ld], lb[(size_t)k * ld], c, 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) P[(rt * 16 + 4 * i + lq) * CB_PLD + lr] = c[i];
-        }
-        __syncthreads();
-        // (2) diagonal block: factorise and invert in registers (wave 0), as in the LDS kernel
-        if (wv == 0) {
-            const int r = lane & 15;
-            double a[16], x[16], my_invd;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) a[c] = P[(j0 + r) * CB_PLD + c];
-            const unsigned rejected = ch_diag_regs<false, true>(a, x, my_invd, j0, n, piv_tol, r);
-            if (lane < 16) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) P[(j0 + r) * CB_PLD + c] = a[c];
-                sh_invd[j0 + r] = my_invd;
-            }
-            if (rejected && lane == 0) sh_bad = 1;
-            if (lane < 16) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh_linv[i][r] = x[i];
-            }
-        }
-        __syncthreads();
-        // (3) panel solve: L(rt, j) = P(rt) L11^-T
-        for (int rt = j + 1 + wvu; rt < ntile; rt += CB_NW) {
-            f64x4 c = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int k0 = 0; k0 < 16; k0 += 4)
-                c = __builtin_amdgcn_mfma_f64_16x16x4f64(P[(rt * 16 + lr) * CB_PLD + k0 + lq], sh_linv[lr][k0 + lq], c, 0, 0, 0);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) P[(rt * 16 + 4 * i + lq) * CB_PLD + lr] = c[i];
-        }
-        __syncthreads();
-        // (4) the finished panel (rows j0 .. np-1, 16 columns) back to the workspace, column-major
-        for (int e = tid; e < (np - j0) * 16; e += CB_NT) {
-            const int c = e / (np - j0), rr = j0 + e % (np - j0);
-            Gw[(size_t)(j0 + c) * ld + rr] = P[rr * CB_PLD + c];
-        }
-        __threadfence_block();
-        __syncthreads();
-    }
+    // ---- phase 3: left-looking panel Cholesky, in place: the Gram matrix is the factor buffer ------------
+    for (int j = 0; j < ntile; ++j)
+        chol_panel_factor(Gw, ld, n, np, piv_tol, lds, wvu, j,
+                          [&](int rt, int j0, int i) { return Gw[(size_t)(j0 + lr) * ld + rt * 16 + 4 * i + lq]; });
 
     // ---- phase 4: L L^T x = b, one wave per right-hand side; lane holds rows lane + 64 s ---------------
     if (wv < nrhs) {

@@ -3,8 +3,8 @@ which its diagonal-block factorisation can go wrong, exactly the W_out and statu
 tests/golden/chol_parent_digests.json wrote: the DPP form of the factorisation -- and any later rewrite that is meant
 to keep the results -- changes no output bit.  The sample and the inputs are those of tools/record_chol_digests.py
 (one tile and ragged tiles, wide and tall, the residency tail, a rejected pivot by a duplicated row, a zero row and a
-duplicated column, the ridge instances, the workspace kernel, the W_out passes that cols 528 and 60 never take; float64
-and float32 E).  Every status is 0 except the
+duplicated column, the ridge instances, the workspace kernel, the W_out passes that cols 528 and 60 never take, the
+workspace kernel's ridge instance, exactly-zero pivot, idle substitution waves and full 512 rows; float64 and float32 E).  Every status is 0 except the
 singular group of the rejected-pivot cases, which is 1."""
 import importlib.util
 import json
@@ -48,6 +48,13 @@ def test_sample_covers_what_the_factorisation_can_get_wrong():
             assert ("big", r, c, 8, 2, e32, None, None) in key
         for r, c, o in ((40, 61, 3), (20, 600, 8), (20, 800, 8)):
             assert ("wide", r, c, o, 3, e32, None, None) in key
+        for r, c in ((144, 528), (600, 144)):
+            for lam in (0.0, 1e-3):
+                assert ("big-ridge", r, c, 8, 2, e32, None, lam) in key
+        assert ("big-drop", 144, 528, 8, 5, e32, "zero", None) in key
+        assert ("big-drop", 600, 144, 8, 5, e32, "zerocol", None) in key
+        for r, c, o in ((130, 200, 3), (129, 528, 8), (512, 528, 8)):
+            assert ("big", r, c, o, 2, e32, None, None) in key
     assert ("tail", 128, 528, 8, 513, True, None, None) in key
 
 

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """ISA summary of the LDS Cholesky read-out kernel (readout_chol_kernel in esn_solve_chol.hip).  Needs hipcc, no GPU.
 
-Compiles esn_solve_chol.hip and esn_solve_chol_big.hip (--all: esn_solve_qr.hip too) to gfx950 assembly with the
+Compiles esn_solve_chol.hip and esn_solve_chol_big.hip (--all: esn_solve_qr.hip, esn_loo.hip, esn_gram.hip and
+esn_holdout.hip too, whose kernels share code with them or must not notice a change to them) to gfx950 assembly with the
 product flags of esn_ofdm_mimo_amd/build.py and prints, per
-instance of readout_chol_kernel and readout_chol_big_kernel: VGPRs, spilled VGPRs / SGPRs and scratch bytes; and for
+kernel instance: VGPRs, spilled VGPRs / SGPRs and scratch bytes; and for
 the instances of readout_chol_kernel the instruction mix of the stretch between the two s_barrier that bracket the
 diagonal-block factorisation (the last barrier in front of the first v_rsq_f64 -- the square root of the pivot, the
 kernel has no other -- and the first barrier behind the last one).  tests/test_chol_structure.py holds the scratch
@@ -25,7 +26,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HEADLINE = "_ZN3esn19readout_chol_kernelIfLb1ELb0EEEvNS_11SolveParamsE"      # float32 E, wide, no ridge
-SOURCES = ("esn_solve_chol.hip", "esn_solve_chol_big.hip", "esn_solve_qr.hip")
+SOURCES = ("esn_solve_chol.hip", "esn_solve_chol_big.hip", "esn_solve_qr.hip", "esn_loo.hip", "esn_gram.hip",
+           "esn_holdout.hip")
 
 
 def compile_asm(out, sources=SOURCES[:2]):
@@ -44,10 +46,11 @@ def compile_asm(out, sources=SOURCES[:2]):
 
 
 def functions(lines):
-    """{name: (body lines, {metadata key: value})} of the Cholesky kernels (and of the QR kernel, where compiled in)"""
+    """{name: (body lines, {metadata key: value})} of every esn::*_kernel in the assembly: the Cholesky kernels and,
+    where compiled in, those of the QR, leave-one-out, running-normal-equations and hold-out files"""
     out, name, body = {}, None, []
     for ln in lines:
-        m = re.match(r"^(_ZN3esn(?:19readout_chol_kernel|23readout_chol_big_kernel|17readout_qr_kernel)\w+):", ln)
+        m = re.match(r"^(_ZN3esn\d+[a-z0-9_]+_kernel\w+):", ln)
         if m:
             name, body = m.group(1), []
             out[name] = (body, {})
@@ -102,7 +105,7 @@ def compare(old, new):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--asm", help="read this assembly file instead of compiling")
-    ap.add_argument("--all", action="store_true", help="compile the QR kernel's file as well")
+    ap.add_argument("--all", action="store_true", help="compile the other read-out files as well")
     ap.add_argument("--against", help="an earlier assembly file: print the comparison table instead of the summary")
     args = ap.parse_args()
     if args.asm:

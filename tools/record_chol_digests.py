@@ -20,6 +20,10 @@ The sample (rows x cols is the system after the transient; E is seeded randn wit
          runs: scalar Gram fetch and scalar W_out loop); 20 x 600 (float32: DMA Gram, then the scalar loop, three parts
          do not fit the tile area; float64: the vector pass with one part); 20 x 800 (float32: two parts through the
          W_out ring, two rows per chunk)
+  big-ridge / big-drop / big   what the three `big` shapes leave out of readout_chol_big_kernel, G 2, n_out 8: its ridge
+         instance (144 x 528 and 600 x 144 at lambda 0.0 and 1e-3); a rejected pivot that is exactly 0 (G 5, group 2:
+         144 x 528 with row 90 zero, 600 x 144 with column 60 zero); idle substitution waves (130 x 200, n_out 3); one
+         live row in the last tile (129 x 528); all eight row slots of a lane (512 x 528)
 each with float64 and float32 E, except G 513.  Inputs come from seeded NumPy generators, so this tool and the test
 build the same arrays."""
 import argparse
@@ -41,7 +45,7 @@ BAD_GROUP = 2
 
 
 def cases():
-    """The sample, a list of dicts: kind, rows, cols, n_out, G, e32, drop (None, "row", "zero", "col"), ridge."""
+    """The sample, a list of dicts: kind, rows, cols, n_out, G, e32, drop (None, "row", "zero", "col", "zerocol"), ridge."""
     shapes = [("wide", n, 528, 8, 3) for n in (16, 17, 100, 127, 128)] + [("wide", 40, 60, 3, 3)]
     shapes += [("tall", 300, 100, 8, 3), ("tall", 140, 37, 8, 3), ("tall", 512, 128, 8, 3)]
     shapes += [("tail", 128, 528, 8, 5)]
@@ -58,6 +62,14 @@ def cases():
     # the W_out paths no shape above takes (appended: inputs are seeded by case index)
     for r, c, o in ((40, 61, 3), (20, 600, 8), (20, 800, 8)):
         out += [dict(kind="wide", rows=r, cols=c, n_out=o, G=3, e32=e32, drop=None, ridge=None) for e32 in (False, True)]
+    # readout_chol_big_kernel beyond the three `big` shapes (appended)
+    for r, c in ((144, 528), (600, 144)):
+        out += [dict(kind="big-ridge", rows=r, cols=c, n_out=8, G=2, e32=e32, drop=None, ridge=lam)
+                for lam in (0.0, 1e-3) for e32 in (False, True)]
+    for drop, r, c in (("zero", 144, 528), ("zerocol", 600, 144)):
+        out += [dict(kind="big-drop", rows=r, cols=c, n_out=8, G=5, e32=e32, drop=drop, ridge=None) for e32 in (False, True)]
+    for r, c, o in ((130, 200, 3), (129, 528, 8), (512, 528, 8)):
+        out += [dict(kind="big", rows=r, cols=c, n_out=o, G=2, e32=e32, drop=None, ridge=None) for e32 in (False, True)]
     for c in out:
         c["id"] = (f"{c['kind']}-{c['rows']}x{c['cols']}-o{c['n_out']}-G{c['G']}-{'f32' if c['e32'] else 'f64'}"
                    + (f"-drop_{c['drop']}" if c["drop"] else "") + (f"-ridge{c['ridge']:g}" if c["ridge"] is not None else ""))
@@ -81,6 +93,8 @@ def arrays(i, c):
         E[BAD_GROUP, TRANSIENT + 90] = 0
     elif c["drop"] == "col":
         E[BAD_GROUP, :, 60] = E[BAD_GROUP, :, 17]
+    elif c["drop"] == "zerocol":
+        E[BAD_GROUP, :, 60] = 0
     return E, D, t_scale
 
 
