@@ -299,10 +299,7 @@ static int launch_plan(const char* who, const char* size_query, int precision, R
         case ESN_PATH_CLUSTER_F64: e = launch_recur_cluster(p, workspace, stream); break;
         case ESN_PATH_HARVEST_CLUSTER: e = launch_harvest_cluster(precision, p, workspace, stream); break;
         case ESN_PATH_BIG_HARVEST: e = launch_harvest_big(precision, p, workspace, stream); break;
-        case ESN_PATH_BIG_PREDICT:
-            p.Fpad = round_up(p.F, 16);
-            e = launch_recur_big(precision, p, wout_big_offset(precision, p.n_out, p.g), workspace, stream, io32);
-            break;
+        case ESN_PATH_BIG_PREDICT: e = launch_recur_big(precision, p, workspace, stream, io32); break;
         case ESN_PATH_SKEW16: e = launch_recur_skew16(precision, p, stream, io32); break;
         case ESN_PATH_F64_MFMA: e = launch_recur_f64_mfma(p, stream); break;
         case ESN_PATH_F64_VALU: e = launch_recur_f64(p, stream); break;

@@ -23,8 +23,8 @@ struct Geometry {
     int ro_parts;    // readout images per group: 1, or 2 (hi + lo) for fp16/bf16 with n_out > 8
     int ro_fold;     // fp16/bf16, n_out <= 8: rows 0-7 = hi, rows 8-15 = lo of ONE 16-row image
     int skew;        // predict: the two waves of a SIMD run one third of a step apart (esn_recur_mfma_impl.h)
-    int big;         // fp16/bf16, N_res > 1024: the launch-per-step GEMM path (esn_recur_big.hip) serves this shape;
-                     // the packed read-out then carries that path's image behind the persistent kernel's
+    int big;         // fp16/bf16, N_res > 1024: the launch-per-step GEMM path (esn_big_predict.hip, esn_big_harvest.hip)
+                     // serves this shape; the packed read-out then carries that path's image behind the persistent kernel's
     int s16;         // fp16/bf16: the 16x16x32 skewed predict kernel (esn_recur_skew16_impl.h) serves this shape; the
                      // packed weights and read-out then carry that kernel's images behind the 32x32x16 ones
     int m64;         // ESN_F64: 1 = the float64 matrix-pipe kernel (esn_recur_f64_mfma.hip) fits this shape;
@@ -375,8 +375,11 @@ __device__ __forceinline__ uint32_t noise_mix(uint32_t s) {
     s ^= s >> 16;
     return s;
 }
+// the additive counter's step per row quad: a schedule may fold part of row4 into its key ahead of time
+// (key + part * NOISE_ROW4_STRIDE) and pass noise_quad the rest
+constexpr uint32_t NOISE_ROW4_STRIDE = 0x9E3779B9U;
 __device__ __forceinline__ uint32_t noise_quad(uint32_t k, uint32_t row4) {
-    return noise_mix(k + row4 * 0x9E3779B9U);
+    return noise_mix(k + row4 * NOISE_ROW4_STRIDE);
 }
 // uniform in (0,1) with 8-bit resolution for byte `b` (0..3) of a quad: (byte + 0.5) / 256
 __device__ __forceinline__ float noise_byte(uint32_t quad, int b) {

@@ -20,7 +20,7 @@
 // blocks of one XCD (block id mod 8).
 // Arithmetic, noise stream (counter noise keyed by (seed, global pilot, step, row)) and the rounding of the states to
 // the operand type are those of the persistent harvest kernel; only the summation order inside a dot product differs.
-#include "esn_mfma_traits.h"
+#include "esn_state_noise.h"
 #include "esn_launch.h"
 
 namespace esn {
@@ -203,8 +203,7 @@ __global__ __launch_bounds__(HC_NT) void harvest_cluster_kernel(RecurParams p, i
     stage_uf(0, raw_cur);
     fetch_uf(1, raw_cur);
 
-    const float noise = (float)p.noise;
-    const float n_c1 = noise * (1.0f / 256.0f), n_c0 = noise * (0.5f / 256.0f - 0.5f);
+    const NoiseCoef nc = noise_coef(p.noise);
     // the WC pilots of this lane (tiles vc WC + n, column col): frame index and step-independent key half
     int fr2[WC];
     uint32_t key1[WC];
@@ -331,7 +330,7 @@ __global__ __launch_bounds__(HC_NT) void harvest_cluster_kernel(RecurParams p, i
             const int t = vc * WC + n;
             uint32_t key = 0;
             const double* nz = nullptr;
-            if (NOISE == ESN_NOISE_COUNTER) key = mix32(key1[n] ^ step_mix) + (uint32_t)((ROWS * c + 16 * WR * vr) / 4 + g4) * 0x9E3779B9U;
+            if (NOISE == ESN_NOISE_COUNTER) key = mix32(key1[n] ^ step_mix) + (uint32_t)((ROWS * c + 16 * WR * vr) / 4 + g4) * NOISE_ROW4_STRIDE;
             if (NOISE == ESN_NOISE_TENSOR && fr2[n] >= 0) nz = p.noise_u + ((size_t)fr2[n] * p.S + s) * n_res;
 #pragma unroll
             for (int pr = 0; pr < WR / 2; ++pr) {
@@ -342,17 +341,7 @@ __global__ __launch_bounds__(HC_NT) void harvest_cluster_kernel(RecurParams p, i
                     float v[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = TR::act(acc[m][n][j]);
-                    if (NOISE == ESN_NOISE_COUNTER) {
-                        const uint32_t sq4 = noise_mix(key + (uint32_t)(4 * m) * 0x9E3779B9U);
-                        v[0] = fmaf((float)(sq4 & 0xffU), n_c1, v[0] + n_c0);
-                        v[1] = fmaf((float)((sq4 >> 8) & 0xffU), n_c1, v[1] + n_c0);
-                        v[2] = fmaf((float)((sq4 >> 16) & 0xffU), n_c1, v[2] + n_c0);
-                        v[3] = fmaf((float)(sq4 >> 24), n_c1, v[3] + n_c0);
-                    } else if (NOISE == ESN_NOISE_TENSOR) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (nz && row + j < n_res) v[j] += noise * ((float)nz[row + j] - 0.5f);
-                    }
+                    add_state_noise<NOISE>(v, noise_quad(key, (uint32_t)(4 * m)), nz, p.noise_u, row, n_res, nc);
                     outw[n][pr][2 * tt] = TR::pack2(v[0], v[1]);
                     outw[n][pr][2 * tt + 1] = TR::pack2(v[2], v[3]);
                 }

@@ -33,13 +33,13 @@ size_t recur_f64_lds_bytes(int FB, int n_res, int n_in, int n_out);
 // esn_recur_f64_mfma.hip
 bool f64_mfma_geometry(int n_res, int n_in, int n_out, bool harvest, Geometry* g);
 int launch_recur_f64_mfma(const RecurParams& p, hipStream_t stream);
-// esn_recur_big.hip
+// esn_big_predict.hip (the read-out image at p.wo16_off of a group's packed read-out)
 bool big_path_applies(int precision, const RecurParams& p);
 int big_slots(const RecurParams& p);
 size_t big_workspace_bytes(int n_slots, int Mp, int Kp);
 size_t big_wout_image_bytes(int Mp);
-int launch_recur_big(int precision, const RecurParams& p, size_t wo_big_off, void* workspace, hipStream_t stream,
-                     bool io32 = false);
+int launch_recur_big(int precision, const RecurParams& p, void* workspace, hipStream_t stream, bool io32 = false);
+// esn_big_harvest.hip
 bool big_harvest_applies(int precision, const RecurParams& p);
 size_t big_harvest_workspace_bytes(int n_groups, int Kp);
 int launch_harvest_big(int precision, const RecurParams& p, void* workspace, hipStream_t stream);

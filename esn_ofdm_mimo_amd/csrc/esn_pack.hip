@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void pack_wout_mfma_kernel(const double* Wout,
         }
     }
     if (ES == 2 && g.big) {
-        // image of the launch-per-step GEMM path (esn_recur_big.hip): A operand of a 32x32x16 MFMA whose B
+        // image of the launch-per-step GEMM path (esn_big_predict.hip): A operand of a 32x32x16 MFMA whose B
         // operand is an accumulator tile -- [row tile of 32 k][k-step s2][lane (o = lane & 31, h)][8 elements],
         // element e <-> k = 32 rt + 16 s2 + 8 (e >> 2) + 4 h + (e & 3); rows 0-7 hi, 8-15 rounding residual
         char* big = out + (packed_wout_persistent_bytes(ES, n_out, g) + 15) / 16 * 16;

@@ -42,7 +42,7 @@ bool mfma_geometry(int precision, int n_res, int n_in, int n_out, bool harvest, 
     g->Mp = 32 * MT * NW;
     g->kin = g->Mp;
     g->kfb = g->kin + round_up(n_in, 4);
-    // (reservoirs beyond 1024: K padded to whole 64-deep chunks of the launch-per-step GEMM, esn_recur_big.hip)
+    // (reservoirs beyond 1024: K padded to whole 64-deep chunks of the launch-per-step GEMM, esn_big_predict.hip / esn_big_harvest.hip)
     g->Kp = round_up(g->kfb + round_up(n_out, 4), (es == 2 && n_res > 1024) ? 64 : 32);
     // the 16x16x32 skewed predict kernel (esn_recur_skew16_impl.h): a function of the shape alone -- pack, harvest and
     // predict agree on the images whatever the knobs say

@@ -25,7 +25,7 @@
 // 1 x v_mfma_f32_32x32x16_{f16,bf16}.  (The k order inside a group is a fixed
 // permutation applied to both operands, which a dot product does not see.)
 #pragma once
-#include "esn_mfma_traits.h"
+#include "esn_state_noise.h"
 
 namespace esn {
 
@@ -295,8 +295,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
     }
     __syncthreads();
 
-    const float noise = (float)p.noise;
-    const float n_c1 = noise * (1.0f / 256.0f), n_c0 = noise * (0.5f / 256.0f - 0.5f);
+    const NoiseCoef nc = noise_coef(p.noise);
     const char* bbase = zt + (size_t)r * row_bytes + 16 * h;
     // readout B rows of the owned tiles: frame c*16 + ofc, bytes 64 kk + 16 oq
     const char* zrow0 = zt + (size_t)(wave * 16 + ofc) * row_bytes + 16 * oq;
@@ -582,19 +581,9 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) loadA(abuf[j], j);
         };
-        // E for column tiles [NT0, NT1).  fp16 + counter noise takes a packed-half tail: the four noise
-        // bytes of a quad become two pairs of halves 1 + byte/1024 (one v_perm_b32 each, high byte
-        // 0x3C), and   x = tanh + noise ((byte + 1/2)/256 - 1/2)   is one v_pk_fma_f16 per pair,
-        //   x = (1 + byte/1024) c1 + t,   t = half(1 - 2/(1 + 2^z) + c0 - c1),  c1 = half(4 noise)
-        // instead of four conversions, four adds and four fmas in float32.  (c1 is a normal half --
-        // noise/256 itself would be subnormal -- and t is offset by the ROUNDED c1, so the rounding
-        // of c1 changes the noise width by 2^-11 relative and adds no bias.)
+        // E for column tiles [NT0, NT1).  fp16 + counter noise takes the packed-half tail of esn_state_noise.h.
         constexpr bool PK_NOISE = NOISE == ESN_NOISE_COUNTER && std::is_same<TR, TraitsF16>::value;
-        typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const _Float16 c1s = (_Float16)(1024.0f * n_c1);
-        const h16x2 c1h = {c1s, c1s};
-        const float t_bias = 1.0f + n_c0 - (float)c1s;
+        const NoiseCoefHalf nh = noise_coef_half(nc);
         auto activate = [&](int s, auto nt0_tag, auto nt1_tag, const int (&frs)[NT / 2], int r, int h) {
             // (r, h: the lane coordinates, re-derived per step by the caller so that the store addresses
             //  below are computed here and do not occupy registers across the GEMM phases)
@@ -606,7 +595,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                 uint32_t key = 0;
                 const double* nz = nullptr;
                 if (NOISE == ESN_NOISE_COUNTER)
-                    key = noise_key(p.seed, (uint32_t)fr + p.frame_off, (uint32_t)s) + (uint32_t)(wave * MT * 8 + h) * 0x9E3779B9U;
+                    key = noise_key(p.seed, (uint32_t)fr + p.frame_off, (uint32_t)s) + (uint32_t)(wave * MT * 8 + h) * NOISE_ROW4_STRIDE;
                 if (NOISE == ESN_NOISE_TENSOR && fr >= 0)
                     nz = p.noise_u + ((size_t)fr * p.S + s) * n_res;
                 // (Tried: a packed-half odd Taylor series for tanh on small pre-activations -- 5 v_pk instructions per
@@ -620,40 +609,26 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                     for (int q = 0; q < 4; ++q) {
                         const int row = (wave * MT + mt) * 32 + 8 * q + 4 * h;
                         char* dst = zt + (size_t)col * row_bytes + (size_t)row * ES;
+                        // row/4 = (wave*MT*8 + h) + (mt*8 + 2q): the second term folds at compile time
                         if constexpr (PK_NOISE) {
                             float t[4];
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                if constexpr (KO_E) {
-                                    t[j] = acc[mt][nt][4 * q + j] + t_bias;
-                                } else {
-                                    const float e = __builtin_amdgcn_exp2f(acc[mt][nt][4 * q + j]);
-                                    t[j] = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), t_bias);
-                                }
-                            }
-                            const uint32_t sq = noise_mix(key + (uint32_t)(mt * 8 + 2 * q) * 0x9E3779B9U);
-                            const h16x2 w01 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x3C3C3C3Cu, sq, 0x04010400u));
-                            const h16x2 w23 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x3C3C3C3Cu, sq, 0x04030402u));
-                            const h16x2 t01 = __builtin_convertvector(f32x2{t[0], t[1]}, h16x2);
-                            const h16x2 t23 = __builtin_convertvector(f32x2{t[2], t[3]}, h16x2);
-                            const h16x2 x01 = __builtin_elementwise_fma(w01, c1h, t01);
-                            const h16x2 x23 = __builtin_elementwise_fma(w23, c1h, t23);
-                            *reinterpret_cast<u32x2*>(dst) =
-                                u32x2{__builtin_bit_cast(uint32_t, x01), __builtin_bit_cast(uint32_t, x23)};
+                            for (int j = 0; j < 4; ++j)
+                                t[j] = KO_E ? acc[mt][nt][4 * q + j] + nh.t_bias : biased_tanh(acc[mt][nt][4 * q + j], nh);
+                            *reinterpret_cast<u32x2*>(dst) = noised_half_quad(t, noise_quad(key, (uint32_t)(mt * 8 + 2 * q)), nh);
                         } else {
                             float v[4];
 #pragma unroll
                             for (int j = 0; j < 4; ++j) v[j] = TR::act(acc[mt][nt][4 * q + j]);
-                            if (NOISE == ESN_NOISE_COUNTER) {
-                                const uint32_t sq = noise_mix(key + (uint32_t)(mt * 8 + 2 * q) * 0x9E3779B9U);
-                                v[0] = fmaf((float)(sq & 0xffU), n_c1, v[0] + n_c0);
-                                v[1] = fmaf((float)((sq >> 8) & 0xffU), n_c1, v[1] + n_c0);
-                                v[2] = fmaf((float)((sq >> 16) & 0xffU), n_c1, v[2] + n_c0);
-                                v[3] = fmaf((float)(sq >> 24), n_c1, v[3] + n_c0);
-                            } else if (NOISE == ESN_NOISE_TENSOR) {
+                            // (tensor mode keeps its per-lane branch in this kernel, here and in the in-step
+                            //  schedule: add_state_noise's branch-free form, or this text behind a call, costs the
+                            //  tensor instances more spilled SGPRs than tests/golden/mfma_parent_regs.json records)
+                            if (NOISE == ESN_NOISE_TENSOR) {
 #pragma unroll
                                 for (int j = 0; j < 4; ++j)
-                                    if (nz && row + j < n_res) v[j] += noise * ((float)nz[row + j] - 0.5f);
+                                    if (nz && row + j < n_res) v[j] += nc.amp * ((float)nz[row + j] - 0.5f);
+                            } else {
+                                add_state_noise<NOISE>(v, noise_quad(key, (uint32_t)(mt * 8 + 2 * q)), nullptr, nullptr, row, n_res, nc);
                             }
                             TR::store4(dst, v[0], v[1], v[2], v[3]);
                         }
@@ -1141,7 +1116,7 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                 uint32_t key = 0;
                 const double* nz = nullptr;
                 if (NOISE == ESN_NOISE_COUNTER)
-                    key = noise_key(p.seed, (uint32_t)fr + p.frame_off, (uint32_t)s) + (uint32_t)(wave * MT * 8 + h) * 0x9E3779B9U;
+                    key = noise_key(p.seed, (uint32_t)fr + p.frame_off, (uint32_t)s) + (uint32_t)(wave * MT * 8 + h) * NOISE_ROW4_STRIDE;
                 if (NOISE == ESN_NOISE_TENSOR && fr >= 0)
                     nz = p.noise_u + ((size_t)fr * p.S + s) * n_res;
 #pragma unroll
@@ -1154,18 +1129,13 @@ __global__ __launch_bounds__(NW * 64) void recur_mfma_kernel(RecurParams p) {
                         for (int j = 0; j < 4; ++j) v[j] = SMALL ? TR::act_small(acc[mt][nt][4 * q + j]) : TR::act(acc[mt][nt][4 * q + j]);
                         // (state rows >= n_res are padding: their columns of Wext / W_out are zero, so the
                         //  noise they pick up is never read -- no masking needed)
-                        if (NOISE == ESN_NOISE_COUNTER) {
-                            // row/4 = (wave*MT*8 + h) + (mt*8 + 2q): the second term folds at compile time
-                            const uint32_t sq = noise_mix(key + (uint32_t)(mt * 8 + 2 * q) * 0x9E3779B9U);
-                            // + noise*((byte+0.5)/256 - 0.5) = byte*n_c1 + n_c0
-                            v[0] = fmaf((float)(sq & 0xffU), n_c1, v[0] + n_c0);
-                            v[1] = fmaf((float)((sq >> 8) & 0xffU), n_c1, v[1] + n_c0);
-                            v[2] = fmaf((float)((sq >> 16) & 0xffU), n_c1, v[2] + n_c0);
-                            v[3] = fmaf((float)(sq >> 24), n_c1, v[3] + n_c0);
-                        } else if (NOISE == ESN_NOISE_TENSOR) {
+                        // row/4 = (wave*MT*8 + h) + (mt*8 + 2q): the second term folds at compile time
+                        if (NOISE == ESN_NOISE_TENSOR) {
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
-                                if (nz && row + j < n_res) v[j] += noise * ((float)nz[row + j] - 0.5f);
+                                if (nz && row + j < n_res) v[j] += nc.amp * ((float)nz[row + j] - 0.5f);
+                        } else {
+                            add_state_noise<NOISE>(v, noise_quad(key, (uint32_t)(mt * 8 + 2 * q)), nullptr, nullptr, row, n_res, nc);
                         }
                         TR::store4(zt + (size_t)col * row_bytes + (size_t)row * ES, v[0], v[1], v[2], v[3]);
                     }

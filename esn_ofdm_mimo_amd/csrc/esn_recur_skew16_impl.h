@@ -20,7 +20,7 @@
 // LDS-DMA input staging, packed-half noise tail, the counter noise as a function of (seed, frame, step, row) --
 // is the 32x32x16 kernel's, and the two are compared bit-for-bit-tolerance in tests/test_gpu_parity.py.
 #pragma once
-#include "esn_mfma_traits.h"
+#include "esn_state_noise.h"
 
 namespace esn {
 
@@ -168,8 +168,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
         TR::store1(zf + ((size_t)((f >> 4) * NKK + 16) * 64 + (ci >> 3) * 16 + (f & 15)) * 16 + 2 * (ci & 7), v);
     }
 
-    const float noise = (float)p.noise;
-    const float n_c1 = noise * (1.0f / 256.0f), n_c0 = noise * (0.5f / 256.0f - 0.5f);
+    const NoiseCoef nc = noise_coef(p.noise);
     f32x4 yacc = {0.f, 0.f, 0.f, 0.f};
     const int lane16 = lane * 16;
     constexpr int OOB = 0x7ffffff0;
@@ -368,11 +367,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
 
     // phase E for tile positions [N0, N1): eight values per lane and row-tile pair -> one 16-byte store
     constexpr bool PK_NOISE = NOISE == ESN_NOISE_COUNTER && std::is_same<TR, TraitsF16>::value;
-    typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const _Float16 c1s = (_Float16)(1024.0f * n_c1);
-    const h16x2 c1h = {c1s, c1s};
-    const float t_bias = 1.0f + n_c0 - (float)c1s;
+    const NoiseCoefHalf nh = noise_coef_half(nc);
     const uint32_t seed_hi = (uint32_t)(p.seed >> 32);
     auto activate = [&](int s, auto n0_tag, auto n1_tag, int ln) S16_INLINE {
         constexpr int N0 = decltype(n0_tag)::value, N1 = decltype(n1_tag)::value;
@@ -391,7 +386,7 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
             uint32_t key = 0;
             const double* nz = nullptr;
             if (NOISE == ESN_NOISE_COUNTER)        // noise_key(seed, frame, step) + row4 stride: row4 = 16 wave + 4 m + g4
-                key = k1[n - N0] + (uint32_t)(16 * wave + g4) * 0x9E3779B9U;
+                key = k1[n - N0] + (uint32_t)(16 * wave + g4) * NOISE_ROW4_STRIDE;
             if (NOISE == ESN_NOISE_TENSOR && frs[n - N0] >= 0)
                 nz = p.noise_u + ((size_t)frs[n - N0] * p.S + s) * n_res;
             char* dst = zf + (size_t)t * TILE_B + (size_t)(2 * wave) * 1024 + (size_t)ln * 16;
@@ -405,38 +400,16 @@ __global__ __launch_bounds__(512) void recur_skew16_kernel(RecurParams p) {
                     if constexpr (PK_NOISE) {
                         float tv[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float e = __builtin_amdgcn_exp2f(a4[j]);
-                            tv[j] = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), t_bias);
-                        }
-                        const uint32_t sq = noise_mix(key + (uint32_t)(4 * m) * 0x9E3779B9U);
-                        const h16x2 w01 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x3C3C3C3Cu, sq, 0x04010400u));
-                        const h16x2 w23 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x3C3C3C3Cu, sq, 0x04030402u));
-                        const h16x2 t01 = __builtin_convertvector(f32x2{tv[0], tv[1]}, h16x2);
-                        const h16x2 t23 = __builtin_convertvector(f32x2{tv[2], tv[3]}, h16x2);
-                        out[2 * tt] = __builtin_bit_cast(uint32_t, __builtin_elementwise_fma(w01, c1h, t01));
-                        out[2 * tt + 1] = __builtin_bit_cast(uint32_t, __builtin_elementwise_fma(w23, c1h, t23));
+                        for (int j = 0; j < 4; ++j) tv[j] = biased_tanh(a4[j], nh);
+                        const u32x2 x = noised_half_quad(tv, noise_quad(key, (uint32_t)(4 * m)), nh);
+                        out[2 * tt] = x[0];
+                        out[2 * tt + 1] = x[1];
                     } else {
                         float v[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[j] = TR::act(a4[j]);
-                        const int row = 64 * wave + 16 * m + 4 * g4;
-                        if (NOISE == ESN_NOISE_COUNTER) {
-                            const uint32_t sq = noise_mix(key + (uint32_t)(4 * m) * 0x9E3779B9U);
-                            v[0] = fmaf((float)(sq & 0xffU), n_c1, v[0] + n_c0);
-                            v[1] = fmaf((float)((sq >> 8) & 0xffU), n_c1, v[1] + n_c0);
-                            v[2] = fmaf((float)((sq >> 16) & 0xffU), n_c1, v[2] + n_c0);
-                            v[3] = fmaf((float)(sq >> 24), n_c1, v[3] + n_c0);
-                        } else if (NOISE == ESN_NOISE_TENSOR) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {      // branch-free: a lane without noise (padding frame, row
-                                                               // past n_res) reads element 0 of the tensor and drops it
-                                const bool on = nz && row + j < n_res;
-                                const double u = (on ? nz : p.noise_u)[on ? row + j : 0];
-                                const float w = v[j] + noise * ((float)u - 0.5f);
-                                v[j] = on ? w : v[j];
-                            }
-                        }
+                        add_state_noise<NOISE>(v, noise_quad(key, (uint32_t)(4 * m)), nz, p.noise_u, 64 * wave + 16 * m + 4 * g4,
+                                               n_res, nc);
                         out[2 * tt] = TR::pack2(v[0], v[1]);
                         out[2 * tt + 1] = TR::pack2(v[2], v[3]);
                     }

@@ -126,8 +126,8 @@ enum esn_path {
     ESN_PATH_F64_VALU = 2,         /* float64 on the vector ALU (esn_recur_f64.hip)                          */
     ESN_PATH_F64_MFMA = 3,         /* float64 matrix pipe (esn_recur_f64_mfma.hip)                           */
     ESN_PATH_CLUSTER_F64 = 4,      /* single float64 sequence, workgroup cluster (esn_recur_cluster.hip)     */
-    ESN_PATH_BIG_PREDICT = 5,      /* one GEMM launch per step, predict (esn_recur_big.hip)                  */
-    ESN_PATH_BIG_HARVEST = 6,      /* one GEMM launch per step, harvest (esn_recur_big.hip)                  */
+    ESN_PATH_BIG_PREDICT = 5,      /* one GEMM launch per step, predict (esn_big_predict.hip)                */
+    ESN_PATH_BIG_HARVEST = 6,      /* one GEMM launch per step, harvest (esn_big_harvest.hip)                */
     ESN_PATH_HARVEST_CLUSTER = 7   /* fp16/bf16 harvest, workgroup clusters (esn_harvest_cluster.hip)        */
 };
 /* Which kernel esn_predict_batch (harvest = 0) / esn_harvest_batch (harvest = 1) runs for this call when a

@@ -1,5 +1,5 @@
 """Reservoirs beyond 1024 units (BASELINE configs[4], N_res = 2048): the launch-per-step GEMM path
-(csrc/esn_recur_big.hip) against the persistent fp16 kernel on identical inputs and identical noise
+(csrc/esn_big_predict.hip) against the persistent fp16 kernel on identical inputs and identical noise
 draws (debug knob big_gemm=0), against the CPU oracle, and -- through tests/test_gpu_parity.py's c5 case
 -- against the reference's own predictions."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The launch-per-step GEMM kernels beyond 1024 units (esn_recur_big.hip: predict and harvest) and the harvest cluster
+"""The launch-per-step GEMM kernels beyond 1024 units (esn_big_predict.hip, esn_big_harvest.hip) and the harvest cluster
 kernel (esn_harvest_cluster.hip) write, at the shapes of tools/record_big_cluster_digests.py, exactly the bytes that the
 commit named in tests/golden/big_cluster_parent_digests.json wrote: a clean-up of these kernels that is meant to keep the
 results changes no output bit.  (tests/test_gpu_big.py and tests/test_gpu_harvest_cluster.py compare them with the

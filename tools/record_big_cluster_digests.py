@@ -1,13 +1,14 @@
-"""Records SHA-256 digests of what the launch-per-step GEMM kernels (esn_recur_big.hip: big_step_kernel of predict,
-bigh_step_kernel of harvest) and the harvest cluster kernel (esn_harvest_cluster.hip) write at a few small shapes into
-tests/golden/big_cluster_parent_digests.json, for tests/test_gpu_big_cluster_digests.py to compare against: a clean-up of
-these kernels that is meant to keep their results keeps every output byte.  Needs a GPU.
+"""Records SHA-256 digests of what the launch-per-step GEMM kernels (big_step_kernel of esn_big_predict.hip,
+bigh_step_kernel of esn_big_harvest.hip) and the harvest cluster kernel (esn_harvest_cluster.hip) write at a few small
+shapes into tests/golden/big_cluster_parent_digests.json, for tests/test_gpu_big_cluster_digests.py to compare against: a
+clean-up of these kernels that is meant to keep their results keeps every output byte.  Needs a GPU.
 
 Run it with the library of the commit whose results are to be pinned (ESN_HIP_LIB selects another build):
 
     ESN_HIP_LIB=<that tree>/esn_ofdm_mimo_amd/libesn_hip.so python tools/record_big_cluster_digests.py --commit <hash>
 
-The cases (CASES below, each with f16 and bf16 and with noise `none` and `counter`, every knob at its default):
+The cases (SHAPES below, each with f16 and bf16 and with noise `none` and `counter`, then each once more with noise
+`tensor`, every knob at its default):
   big predict      1100 units, 2 groups of 20 frames with the last group short (one 256-slot tile, 5 row tiles)
   big harvest      1100 units, 65 pilots (a second, nearly empty pilot tile), float64 and float32 extended states
   cluster harvest  512 units with 17 pilots (a partial second cluster), 300 units with a lone pilot, and 3 weight sets
@@ -41,11 +42,15 @@ SHAPES = (
 )
 PRECISIONS = ("f16", "bf16")
 NOISE_MODES = ("none", "counter")
+# appended behind the product of the modes above: the case index seeds the arrays and the kernel, so a mode added to
+# NOISE_MODES would move every digest recorded before it
+LATER_NOISE_MODES = ("tensor",)
 
 
 def cases():
     out = []
-    for s, precision, noise_mode in itertools.product(SHAPES, PRECISIONS, NOISE_MODES):
+    for s, precision, noise_mode in itertools.chain(itertools.product(SHAPES, PRECISIONS, NOISE_MODES),
+                                                    itertools.product(SHAPES, PRECISIONS, LATER_NOISE_MODES)):
         c = dict(dict(e_dtype="f64", n_wsets=1, group_offset=0), **s, precision=precision, noise_mode=noise_mode)
         c["id"] = "{path}-n{n_res}-b{B}-e{e_dtype}-w{n_wsets}-{precision}-{noise_mode}".format(**c)
         out.append(c)
@@ -76,7 +81,8 @@ def arrays(i, c):
         in_scale=rng.random((G, n_in)) * 0.2 + 0.1, in_shift=rng.standard_normal((G, n_in)) * 0.05,
         t_scale=rng.random((G, n_out)) + 0.5, t_shift=rng.standard_normal((G, n_out)) * 0.1,
         u=rng.standard_normal((B, T, n_in)), d=np.tanh(rng.standard_normal((B, T, n_out))),
-        x0=rng.standard_normal((G, n)) * 0.1, y0=rng.standard_normal((G, n_out)) * 0.1)
+        x0=rng.standard_normal((G, n)) * 0.1, y0=rng.standard_normal((G, n_out)) * 0.1,
+        noise_u=rng.random((B, T - 1, n) if c["kind"] == "harvest" else (B, T, n)))       # drawn last, read in tensor mode
 
 
 def digest(i, c):
@@ -88,16 +94,17 @@ def digest(i, c):
     bank = batched.ReservoirBank(c["n_in"], c["n_out"], c["n_res"], a["w"], a["w_in"], a["w_fb"],
                                  noise=0.0 if c["noise_mode"] == "none" else 1e-3)
     bank.set_scaling(a["in_scale"], a["in_shift"], a["t_scale"], a["t_shift"])
+    noise_u = a["noise_u"] if c["noise_mode"] == "tensor" else None
     if c["kind"] == "harvest":
-        y = bank.harvest(a["u"], a["d"], precision=c["precision"], noise_mode=c["noise_mode"], seed=5 + i,
-                         e_dtype=c["e_dtype"], group_offset=c["group_offset"])
+        y = bank.harvest(a["u"], a["d"], precision=c["precision"], noise_mode=c["noise_mode"], noise_u=noise_u,
+                         seed=5 + i, e_dtype=c["e_dtype"], group_offset=c["group_offset"])
         if c["path"] == "harvest_cluster":
             bank.raise_if_harvest_timed_out()
         want, dtype = (c["B"], c["T"], c["n_res"] + c["n_in"]), (np.float32 if c["e_dtype"] == "f32" else np.float64)
     else:
         bank.set_readout(a["w_out"])
         y = bank.predict(a["u"], c["F"], T=c["T"], transient=c["transient"], precision=c["precision"], x0=a["x0"],
-                         y0=a["y0"], noise_mode=c["noise_mode"], seed=5 + i)
+                         y0=a["y0"], noise_mode=c["noise_mode"], noise_u=noise_u, seed=5 + i)
         want, dtype = (c["B"], c["T"] - c["transient"], c["n_out"]), np.float64
     y = y.cpu().numpy()
     assert y.shape == want and y.dtype == dtype and np.isfinite(y).all(), c["id"]
