@@ -752,17 +752,28 @@ int esn_scale_reservoirs(double* W, int n_sets, int n_res, double rho, const dou
     return hip_fail(launch_scale_reservoirs(W, n_sets, n_res, rho, radius, status, (hipStream_t)stream), who);
 }
 
+static int pow2_log(int n) { int l = 0; while ((1 << l) < n) ++l; return ((1 << l) == n) ? l : -1; }
+
+// the checks the OFDM entry points share: 0 (and *log2n = log2 N), or the failure recorded
+static int check_n_sub(const char* who, int n_sub, int* log2n) {
+    *log2n = pow2_log(n_sub);
+    if (*log2n < 1 || n_sub > 2048) return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
+    return 0;
+}
+static int check_square_qam(const char* who, int bits_per_sym) {
+    if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
+        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
+    return 0;
+}
+
 static int detect_common(const char* who, bool io32, const void* Y, int n_frames, int frames_per_group, int n_sub,
                          int n_t, int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
                          long long* bit_count, double* X_hat, void* stream) {
     if (!Y || !p_i || !tx_bits || !err_count || !bit_count) return fail(-1, "%s: null pointer", who);
     if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0) return fail(-1, "%s: invalid sizes", who);
-    int log2n = 0;
-    while ((1 << log2n) < n_sub) ++log2n;
-    if ((1 << log2n) != n_sub || n_sub < 2 || n_sub > 2048)
-        return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
-    if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
-        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
+    int log2n;
+    if (int rc = check_n_sub(who, n_sub, &log2n)) return rc;
+    if (int rc = check_square_qam(who, bits_per_sym)) return rc;
     if (io32 && ((uintptr_t)Y & 7) != 0) return fail(-1, "%s: Y must be 8-byte aligned", who);
     DetectParams dp;
     if (io32) dp.Y32 = static_cast<const float*>(Y); else dp.Y = static_cast<const double*>(Y);
@@ -794,12 +805,9 @@ int esn_detect_remod(const double* Y, int n_frames, int frames_per_group, int n_
     if (tx_bits && (!err_count || !bit_count)) return fail(-1, "%s: tx_bits given without err_count / bit_count", who);
     if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0) return fail(-1, "%s: invalid sizes", who);
     if (n_t > 16) return fail(-1, "%s: n_t=%d, served up to 16", who, n_t);
-    int log2n = 0;
-    while ((1 << log2n) < n_sub) ++log2n;
-    if ((1 << log2n) != n_sub || n_sub < 2 || n_sub > 2048)
-        return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
-    if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
-        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
+    int log2n;
+    if (int rc = check_n_sub(who, n_sub, &log2n)) return rc;
+    if (int rc = check_square_qam(who, bits_per_sym)) return rc;
     if (cp < 0 || cp >= n_sub) return fail(-1, "%s: cp=%d must be in [0, N) with N=%d", who, cp, n_sub);
     if (delay < 0 || delay > (1 << 20)) return fail(-1, "%s: delay=%d must be in [0, %d]", who, delay, 1 << 20);
     RemodParams rp;
@@ -881,12 +889,9 @@ static int gen_common(const char* who, bool c64, int n_frames, int frames_per_bl
                       double no, const double* taps, const uint8_t* bits_in, const double* noise_in, uint64_t seed,
                       uint64_t frame_offset, uint8_t* bits, void* x_cp, void* y_cp, void* stream) {
     if (!p_i || !a_clip || !taps || !bits || !y_cp) return fail(-1, "%s: null pointer", who);
-    int log2n = 0;
-    while ((1 << log2n) < n_sub) ++log2n;
-    if ((1 << log2n) != n_sub || n_sub < 2 || n_sub > 2048)
-        return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
-    if (bits_per_sym < 2 || bits_per_sym > 10 || (bits_per_sym & 1))
-        return fail(-1, "%s: bits_per_sym=%d must be even (square QAM)", who, bits_per_sym);
+    int log2n;
+    if (int rc = check_n_sub(who, n_sub, &log2n)) return rc;
+    if (int rc = check_square_qam(who, bits_per_sym)) return rc;
     if (n_frames <= 0 || frames_per_block <= 0 || cp < 0 || cp >= n_sub || n_t <= 0 || n_r <= 0 || isi <= 0)
         return fail(-1, "%s: invalid sizes", who);
     if (c64 && ((((uintptr_t)y_cp) | ((uintptr_t)x_cp)) & 7) != 0)
@@ -921,14 +926,12 @@ int esn_gen_frames_c64(int n_frames, int frames_per_block, int n_sub, int cp, in
                       ls_pattern, p_i, a_clip, no, taps, bits_in, noise_in, seed, frame_offset, bits, x_cp, y_cp, stream);
 }
 
-static int pow2_log(int n) { int l = 0; while ((1 << l) < n) ++l; return ((1 << l) == n) ? l : -1; }
-
 int esn_channel_estimate(int n_blocks, int n_sub, int cp, int n_t, int n_r, int isi, int bits_per_sym,
                          const double* p_i, double no, const uint8_t* pilot_bits, const double* y_ls_cp,
                          int ls_only, double* H, void* stream) {
     if (!p_i || !pilot_bits || !y_ls_cp || !H) return fail(-1, "esn_channel_estimate: null pointer");
-    const int l2 = pow2_log(n_sub);
-    if (l2 < 1 || n_sub > 2048) return fail(-1, "esn_channel_estimate: N=%d must be a power of two in [2, 2048]", n_sub);
+    int l2;
+    if (int rc = check_n_sub("esn_channel_estimate", n_sub, &l2)) return rc;
     if (n_blocks <= 0 || cp < 0 || cp >= n_sub || n_t <= 0 || n_r <= 0 || isi <= 0 || isi > 64 || n_sub / n_t < 2 ||
         bits_per_sym < 2 || (bits_per_sym & 1))
         return fail(-1, "esn_channel_estimate: invalid sizes");
@@ -945,8 +948,8 @@ static int linear_detect(const char* who, int zf, int n_frames, int frames_per_g
                          void* stream) {
     if (!p_i || !H || !y_cp || !tx_bits || !err_count || !bit_count)
         return fail(-1, "%s: null pointer", who);
-    const int l2 = pow2_log(n_sub);
-    if (l2 < 1 || n_sub > 2048) return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
+    int l2;
+    if (int rc = check_n_sub(who, n_sub, &l2)) return rc;
     if (n_frames <= 0 || frames_per_group <= 0 || cp < 0 || cp >= n_sub || n_t <= 0 || n_r <= 0 ||
         bits_per_sym < 2 || (bits_per_sym & 1))
         return fail(-1, "%s: invalid sizes", who);
@@ -983,8 +986,8 @@ int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bi
     if (n_est <= 0 || est_per_group <= 0) return fail(-1, "%s: invalid sizes", who);
     if (window < 1 || window > 8) return fail(-1, "%s: window=%d must be in [1, 8]", who, window);
     if ((long long)n_est * window > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 frames", who);
-    const int l2 = pow2_log(n_sub);
-    if (l2 < 1 || n_sub > 2048) return fail(-1, "%s: N=%d must be a power of two in [2, 2048]", who, n_sub);
+    int l2;
+    if (int rc = check_n_sub(who, n_sub, &l2)) return rc;
     if (n_t < 1 || n_t > 4) return fail(-1, "%s: n_t=%d must be in [1, 4]", who, n_t);
     if (n_r < 1 || n_r > 8) return fail(-1, "%s: n_r=%d must be in [1, 8]", who, n_r);
     if (isi < 1 || isi > 16) return fail(-1, "%s: isi=%d must be in [1, 16]", who, isi);

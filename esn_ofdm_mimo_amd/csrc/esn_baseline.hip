@@ -9,6 +9,7 @@
 //       binary LSB-first bits, error count vs TxBits (:95-103, :451-456)
 #include "esn_common.h"
 #include "esn_launch.h"
+#include "esn_ofdm_math.h"
 
 namespace esn {
 
@@ -20,28 +21,6 @@ __device__ __forceinline__ double2 cdiv(double2 a, double2 b) {
     return make_double2((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
 }
 
-// in-place radix-2 DIT FFT of `count` length-N sequences stored back to back in LDS, input already in
-// bit-reversed order; sign = -1 forward, +1 inverse (un-normalised).  All threads of the block call it.
-__device__ __forceinline__ void fft_lds(double2* buf, int count, int N, int log2n, double sign) {
-    const int half = N >> 1;
-    for (int s = 1; s <= log2n; ++s) {
-        const int hm = 1 << (s - 1);
-        for (int e = threadIdx.x; e < count * half; e += blockDim.x) {
-            const int q = e / half, b = e % half;
-            const int j = b & (hm - 1);
-            const int base = ((b >> (s - 1)) << s) + j;
-            double sn, cs;
-            sincospi(sign * (double)j / (double)hm, &sn, &cs);
-            double2* xx = buf + (size_t)q * N;
-            const double2 a = xx[base], c = xx[base + hm];
-            const double tr = c.x * cs - c.y * sn, ti = c.x * sn + c.y * cs;
-            xx[base] = make_double2(a.x + tr, a.y + ti);
-            xx[base + hm] = make_double2(a.x - tr, a.y - ti);
-        }
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(256) void channel_estimate_kernel(ChanEstParams cp) {
     extern __shared__ __attribute__((aligned(16))) char csm[];
     const int N = cp.n_sub, T = N + cp.cp, n_t = cp.n_t, n_r = cp.n_r, isi = cp.isi, m = cp.m;
@@ -49,18 +28,20 @@ __global__ __launch_bounds__(256) void channel_estimate_kernel(ChanEstParams cp)
     double2* full = Yf + N;                                // [N]  interpolated LS estimate
     double2* hls = full + N;                               // [N / n_t + 1] LS at the pilot subcarriers
     double2* ctd = hls + (N / n_t + 1);                    // [isi] time-domain taps
+    double2* tw = ctd + isi;                               // [N/2] exp(-2 pi i k / N)
     const int tid = threadIdx.x, nth = blockDim.x;
     const int blk = blockIdx.x / n_r, rx = blockIdx.x % n_r;
     const double p_i = cp.p_i[blk], sp = sqrt(p_i);
     const int side = 1 << (m / 2);
-    const double norm = sqrt(2.0 * (double)(side * side - 1) / 3.0);
+    const double norm = det_norm(side);
     const double* y = cp.y_ls_cp + ((size_t)blk * T + cp.cp) * n_r * 2 + 2 * rx;
+    ofdm_twiddles(tw, N >> 1, N, -1.0);
     for (int i = tid; i < N; i += nth) {
         const int rv = (int)(__brev((unsigned)i) >> (32 - cp.log2n));
         Yf[rv] = make_double2(y[(size_t)i * n_r * 2] / N, y[(size_t)i * n_r * 2 + 1] / N);
     }
     __syncthreads();
-    fft_lds(Yf, 1, N, cp.log2n, -1.0);
+    ofdm_fft_lds(Yf, 1, N, tw, N, cp.log2n);
     const int n_p = (N + n_t - 1) / n_t;                   // pilots per tx (sc = tx + n_t i < N)
     // prior: r_h[k] = exp(-k / (cp/9)) / sum_{j<=cp} exp(-j / (cp/9)), k < isi   (driver:212-214,279)
     const double tc = fmax((double)cp.cp / 9.0, 1e-12);
@@ -71,11 +52,9 @@ __global__ __launch_bounds__(256) void channel_estimate_kernel(ChanEstParams cp)
         const int np_tx = (N - tx + n_t - 1) / n_t;
         for (int i = tid; i < np_tx; i += nth) {
             const int sc = tx + n_t * i;
-            uint32_t idx = 0;
-            for (int b = 0; b < m; ++b)
-                idx |= (uint32_t)(cp.pilot_bits[((size_t)blk * N * m + (size_t)sc * m + b) * n_t + tx] & 1) << b;
-            const double2 xp = make_double2((2.0 * (int)(idx / side) - (side - 1)) / norm * sp + 1e-12,
-                                            (2.0 * (int)(idx % side) - (side - 1)) / norm * sp);
+            const int idx = det_bits_index(cp.pilot_bits + ((size_t)blk * N * m + (size_t)sc * m) * n_t + tx, n_t, m);
+            const double2 xp = make_double2(det_level(idx / side, side, norm) * sp + 1e-12,
+                                            det_level(idx % side, side, norm) * sp);
             hls[i] = cdiv(Yf[sc], xp);
         }
         __syncthreads();
@@ -99,29 +78,17 @@ __global__ __launch_bounds__(256) void channel_estimate_kernel(ChanEstParams cp)
         }
         // c_LS[j] = (1/N) sum_k full[k] e^{+2 pi i jk/N}, j < isi; then shrink
         if (tid < isi) {
-            double ar = 0.0, ai = 0.0;
-            for (int k = 0; k < N; ++k) {
-                double sn, cs;
-                sincospi(2.0 * (double)((tid * k) % N) / (double)N, &sn, &cs);
-                ar += full[k].x * cs - full[k].y * sn;
-                ai += full[k].x * sn + full[k].y * cs;
-            }
+            const double2 a = ofdm_dft_point([&](int k) { return full[k]; }, N, tid, N, 2.0);
             const double rh = exp(-(double)tid / tc) / rsum;
             const double g = 1.0 / (scaler / rh + 1.0);
-            ctd[tid] = make_double2(ar / N * g, ai / N * g);
+            ctd[tid] = make_double2(a.x / N * g, a.y / N * g);
         }
         __syncthreads();
         // H[k] = sum_{j<isi} c[j] e^{-2 pi i jk/N}
         for (int k = tid; k < N; k += nth) {
-            double hr = 0.0, hi = 0.0;
-            for (int j = 0; j < isi; ++j) {
-                double sn, cs;
-                sincospi(-2.0 * (double)((j * k) % N) / (double)N, &sn, &cs);
-                hr += ctd[j].x * cs - ctd[j].y * sn;
-                hi += ctd[j].x * sn + ctd[j].y * cs;
-            }
+            const double2 h = ofdm_dft_point([&](int j) { return ctd[j]; }, isi, k, N, -2.0);
             double* ho = cp.H + ((((size_t)blk * N + k) * n_r + rx) * n_t + tx) * 2;
-            ho[0] = hr; ho[1] = hi;
+            ho[0] = h.x; ho[1] = h.y;
         }
         __syncthreads();
     }
@@ -135,19 +102,21 @@ __global__ __launch_bounds__(256) void mmse_detect_kernel(MmseParams mp) {
     __shared__ int red[4];
     const int N = mp.n_sub, T = N + mp.cp, n_t = mp.n_t, n_r = mp.n_r, m = mp.m;
     double2* Y = reinterpret_cast<double2*>(msm);          // [n_r][N]
+    double2* tw = Y + (size_t)n_r * N;                     // [N/2] exp(-2 pi i k / N)
     const int tid = threadIdx.x, nth = blockDim.x;
     const int frame = blockIdx.x, blk = frame / mp.frames_per_group;
     const double* y = mp.y_cp + ((size_t)frame * T + mp.cp) * n_r * 2;
+    ofdm_twiddles(tw, N >> 1, N, -1.0);
     for (int e = tid; e < N * n_r; e += nth) {
         const int i = e / n_r, rx = e % n_r;
         const int rv = (int)(__brev((unsigned)i) >> (32 - mp.log2n));
         Y[(size_t)rx * N + rv] = make_double2(y[(size_t)e * 2] / N, y[(size_t)e * 2 + 1] / N);
     }
     __syncthreads();
-    fft_lds(Y, n_r, N, mp.log2n, -1.0);
+    ofdm_fft_lds(Y, n_r, N, tw, N, mp.log2n);
     const double p_i = mp.p_i[blk], lam = mp.zf ? 1e-12 : mp.no / p_i, isp = 1.0 / sqrt(p_i);
     const int side = 1 << (m / 2);
-    const double norm = sqrt(2.0 * (double)(side * side - 1) / 3.0);
+    const double norm = det_norm(side);
     int errs = 0;
     for (int k = tid; k < N; k += nth) {
         // G = H^H H + lam I (Hermitian, n_t x n_t), r = H^H Y
@@ -216,25 +185,11 @@ __global__ __launch_bounds__(256) void mmse_detect_kernel(MmseParams mp) {
                 double* xo = mp.X_hat + (((size_t)frame * N + k) * n_t + tx) * 2;
                 xo[0] = re; xo[1] = im;
             }
-            int i = (int)rint((re * norm + (double)(side - 1)) * 0.5);
-            int j = (int)rint((im * norm + (double)(side - 1)) * 0.5);
-            i = min(max(i, 0), side - 1);
-            j = min(max(j, 0), side - 1);
-            const int idx = i * side + j;
-            const uint8_t* tb = mp.tx_bits + ((size_t)frame * N * m + (size_t)k * m) * n_t + tx;
-            for (int b = 0; b < m; ++b) errs += (((idx >> b) & 1) != (int)tb[(size_t)b * n_t]);
+            const int idx = det_slice(re, norm, side) * side + det_slice(im, norm, side);
+            errs += det_bit_errors(idx, mp.tx_bits + ((size_t)frame * N * m + (size_t)k * m) * n_t + tx, n_t, m);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) errs += __shfl_down(errs, off);
-    if ((tid & 63) == 0) red[tid >> 6] = errs;
-    __syncthreads();
-    if (tid == 0) {
-        int e = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) e += red[w];
-        atomicAdd(reinterpret_cast<unsigned long long*>(mp.err + blk), (unsigned long long)e);
-        atomicAdd(reinterpret_cast<unsigned long long*>(mp.bits + blk), (unsigned long long)(N * m * n_t));
-    }
+    det_count_tail(true, errs, red, mp.err + blk, mp.bits + blk, N * m * n_t);
 }
 
 // Perfect-CSI channel: H[k] = sum_j c[j] e^{-2 pi i jk/N} per link (H_true of OFDM_MIMO_2-2_NBF_LDPC.py:273-279)
@@ -245,14 +200,8 @@ __global__ __launch_bounds__(256) void taps_to_freq_kernel(TapsFreqParams tp) {
         const int tx = (int)(e % n_t), rx = (int)((e / n_t) % n_r), k = (int)((e / ((size_t)n_t * n_r)) % N);
         const size_t blk = e / ((size_t)n_t * n_r * N);
         const double* c = tp.taps + (((blk * n_r + rx) * n_t + tx) * isi) * 2;
-        double hr = 0.0, hi = 0.0;
-        for (int j = 0; j < isi; ++j) {
-            double sn, cs;
-            sincospi(-2.0 * (double)((j * k) % N) / (double)N, &sn, &cs);
-            hr += c[2 * j] * cs - c[2 * j + 1] * sn;
-            hi += c[2 * j] * sn + c[2 * j + 1] * cs;
-        }
-        tp.H[2 * e] = hr; tp.H[2 * e + 1] = hi;
+        const double2 h = ofdm_dft_point([&](int j) { return make_double2(c[2 * j], c[2 * j + 1]); }, isi, k, N, -2.0);
+        tp.H[2 * e] = h.x; tp.H[2 * e + 1] = h.y;
     }
 }
 
@@ -264,14 +213,14 @@ int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream) {
 }
 
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream) {
-    const size_t lds = sizeof(double2) * ((size_t)2 * cp.n_sub + cp.n_sub / cp.n_t + 1 + cp.isi);
+    const size_t lds = sizeof(double2) * ((size_t)2 * cp.n_sub + cp.n_sub / cp.n_t + 1 + cp.isi + cp.n_sub / 2);
     hipLaunchKernelGGL(channel_estimate_kernel, dim3(cp.n_blocks * cp.n_r), dim3(256), lds, stream, cp);
     return (int)hipGetLastError();
 }
 
 int launch_mmse_detect(const MmseParams& mp, hipStream_t stream) {
     if (mp.n_t > MMSE_NT) return -1;
-    const size_t lds = sizeof(double2) * (size_t)mp.n_r * mp.n_sub;
+    const size_t lds = sizeof(double2) * ((size_t)mp.n_r * mp.n_sub + mp.n_sub / 2);
     if (lds > 150 * 1024) return -1;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmse_detect_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -14,7 +14,7 @@
 #include <atomic>
 #include "esn_common.h"
 #include "esn_launch.h"
-#include "esn_detect_math.h"
+#include "esn_ofdm_math.h"
 
 namespace esn {
 
@@ -53,7 +53,7 @@ __device__ __forceinline__ void ct_csub(double2& a, const double2 b) { a.x -= b.
 __global__ __launch_bounds__(CT_MAX_THREADS) void channel_track_kernel(ChanTrackParams cp) {
     extern __shared__ __attribute__((aligned(16))) char tsm[];
     const int N = cp.n_sub, n_t = cp.n_t, n_r = cp.n_r, L = cp.isi, m = cp.m, S = cp.n_seg;
-    const int T = N + cp.cp, ld = N + 1, mask = N - 1, half = N >> 1;
+    const int T = N + cp.cp, ld = N + 1, mask = N - 1;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int PB = n_t * n_r, P = PB + n_t * n_t, M = n_t * L;
     const int lg = cp.log2m2, M2 = 1 << lg, ldg = M2 + 1;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(CT_MAX_THREADS) void channel_track_kernel(ChanTrack
     const int side = 1 << (m / 2);
     const double norm = det_norm(side);
 
-    for (int j = tid; j < N; j += nthr) om[j] = det_twiddle(j, N);
+    ofdm_twiddles(om, N, N, -1.0);                         // (the lag sums read the upper half too)
 
     // the sum this thread owns: pair (b: t, r; lag: t, t') and k range
     const int seg = tid / P, pair = tid - seg * P;
@@ -96,33 +96,19 @@ __global__ __launch_bounds__(CT_MAX_THREADS) void channel_track_kernel(ChanTrack
             const double2* xh = reinterpret_cast<const double2*>(cp.X_hat) + frame * N * n_t;
             for (int e = tid; e < N * n_t; e += nthr) {
                 const double2 v = xh[e];
-                const int ir = det_slice(v.x, norm, side), ii = det_slice(v.y, norm, side);
-                Xs[e] = make_double2((double)(2 * ir - (side - 1)) / norm, (double)(2 * ii - (side - 1)) / norm);
+                Xs[e] = make_double2(det_level(det_slice(v.x, norm, side), side, norm),
+                                     det_level(det_slice(v.y, norm, side), side, norm));
             }
         } else {
             const uint8_t* bt = cp.bits + frame * N * m * n_t;
             for (int e = tid; e < N * n_t; e += nthr) {
                 const int k = e / n_t, t = e - k * n_t;
-                int idx = 0;
-                for (int bb = 0; bb < m; ++bb) idx |= (int)(bt[((size_t)k * m + bb) * n_t + t] & 1) << bb;
-                const int ir = idx >> (m / 2), ii = idx & (side - 1);
-                Xs[e] = make_double2((double)(2 * ir - (side - 1)) / norm, (double)(2 * ii - (side - 1)) / norm);
+                const int idx = det_bits_index(bt + (size_t)k * m * n_t + t, n_t, m);
+                Xs[e] = make_double2(det_level(idx >> (m / 2), side, norm), det_level(idx & (side - 1), side, norm));
             }
         }
         __syncthreads();
-        for (int s = 1; s <= cp.log2n; ++s) {              // radix-2, decimation in time on the bit-reversed frames
-            const int hm = 1 << (s - 1), tstep = N >> s;
-            for (int e = tid; e < n_r * half; e += nthr) {
-                const int r = e / half, t = e - r * half;
-                const int j = t & (hm - 1);
-                const int base = ((t >> (s - 1)) << s) + j;
-                double2* b = Yf + (size_t)r * ld;
-                double2 a = b[base], c = b[base + hm];
-                det_bfly(a, c, om[j * tstep]);
-                b[base] = a; b[base + hm] = c;
-            }
-            __syncthreads();
-        }
+        ofdm_fft_lds(Yf, n_r, ld, om, N, cp.log2n);        // (reads om[0 .. N/2))
         if (owner) {
             const double sgn = is_b ? -1.0 : 1.0;          // b takes w^{-kl}, the lag sums w^{kd}
             for (int k = k_lo; k < k_hi; ++k) {

@@ -8,6 +8,7 @@
 //                        bits (get_message); info-bit errors accumulated per group (:495-511)
 #include "esn_common.h"
 #include "esn_launch.h"
+#include "esn_ofdm_math.h"
 
 namespace esn {
 
@@ -36,17 +37,15 @@ __global__ __launch_bounds__(256) void qam_llr_kernel(LlrParams lp) {
     __shared__ double s_sigma2;
     const int N = lp.n_sub, n_t = lp.n_t, m = lp.m, half = m / 2;
     const int side = 1 << half;
-    const double norm = sqrt(2.0 * (double)(side * side - 1) / 3.0);
+    const double norm = det_norm(side);
     const int frame = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
     const double* x = lp.X_hat + (size_t)frame * N * n_t * 2;
     // decision-directed noise estimate: mean over (subcarrier, tx) of |x - nearest point|^2
     double part = 0.0;
     for (int e = tid; e < N * n_t; e += nth) {
         const double re = x[2 * e], im = x[2 * e + 1];
-        int i = (int)rint((re * norm + (double)(side - 1)) * 0.5);
-        int j = (int)rint((im * norm + (double)(side - 1)) * 0.5);
-        i = min(max(i, 0), side - 1); j = min(max(j, 0), side - 1);
-        const double dr = re - (2.0 * i - (side - 1)) / norm, di = im - (2.0 * j - (side - 1)) / norm;
+        const double dr = re - det_level(det_slice(re, norm, side), side, norm);
+        const double di = im - det_level(det_slice(im, norm, side), side, norm);
         part += dr * dr + di * di;
     }
 #pragma unroll
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(256) void qam_llr_kernel(LlrParams lp) {
             const int bb = (b < half) ? b : b - half;
             double d0 = 1e300, d1 = 1e300;
             for (int a = 0; a < side; ++a) {
-                const double d = t - (2.0 * a - (side - 1)) / norm;
+                const double d = t - det_level(a, side, norm);
                 const double dd = d * d;
                 if ((a >> bb) & 1) d1 = fmin(d1, dd); else d0 = fmin(d0, dd);
             }

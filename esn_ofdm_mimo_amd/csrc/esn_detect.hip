@@ -6,16 +6,14 @@
 // float64 throughout, radix-2 FFT in LDS.
 #include "esn_common.h"
 #include "esn_launch.h"
-#include "esn_detect_math.h"
+#include "esn_ofdm_math.h"
 #include <type_traits>
 
 namespace esn {
 
 // One workgroup per frame, 32 threads per tx antenna (n_t <= 16): the frame's rows are read once,
 // fully coalesced (a row is n_t complex doubles), the twiddles come from one table per workgroup
-// (same sincospi arguments as the reference order).  The radix-2 stages are taken two at a time
-// on four points in registers -- the same butterflies in the same order, so the spectrum is
-// bit-identical to the plain radix-2 loop, with half the LDS round trips and barriers.
+// (same sincospi arguments as the reference order), the transform is ofdm_fft_lds of esn_ofdm_math.h.
 // IO32: float32 Y (esn_detect_count_f32), widened on load into the same float64 buffer -- counts and X_hat are those
 // of the float64 entry point on the widened Y
 template <bool IO32>
@@ -49,9 +47,7 @@ __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
         }
     }
     const double p_i_g = dp.p_i[group];
-    for (int k = tid; k < half; k += nthr) {
-        tw[k] = det_twiddle(k, N);
-    }
+    ofdm_twiddles(tw, half, N, -1.0);
     for (int i = tid; i < N * na; i += nthr) {               // bit-reversed load, element i = (row, antenna)
         const int row = i / na, ant = i - row * na;
         const int rv = (int)(__brev((unsigned)row) >> (32 - dp.log2n));
@@ -63,39 +59,7 @@ __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
         }
     }
     __syncthreads();
-    const int lane = tid & 63, wv = tid >> 6;
-    const int sub = tid & 31, av = tid >> 5;                 // 32 threads per antenna
-    double2* b = buf + (size_t)av * ld;
-    const int quarter = N >> 2;
-    auto bfly = [](double2& a, double2& c, const double2 w) { det_bfly(a, c, w); };
-    int s = 1;
-    for (; s + 1 <= dp.log2n; s += 2) {                      // stages s and s+1 on {base, +hm, +2hm, +3hm}
-        const int hm = 1 << (s - 1);
-        for (int t = sub; t < (av < na ? quarter : 0); t += 32) {
-            const int j = t & (hm - 1);
-            const int base = ((t >> (s - 1)) << (s + 1)) + j;
-            double2 p0 = b[base], p1 = b[base + hm], p2 = b[base + 2 * hm], p3 = b[base + 3 * hm];
-            const double2 w1 = tw[j * (N >> s)];             // exp(-2 pi i j / 2^s)
-            bfly(p0, p1, w1);
-            bfly(p2, p3, w1);
-            const int ts2 = N >> (s + 1);
-            bfly(p0, p2, tw[j * ts2]);                       // exp(-2 pi i j / 2^(s+1))
-            bfly(p1, p3, tw[(j + hm) * ts2]);
-            b[base] = p0; b[base + hm] = p1; b[base + 2 * hm] = p2; b[base + 3 * hm] = p3;
-        }
-        __syncthreads();
-    }
-    if (s <= dp.log2n) {                                     // odd number of stages: the last one alone
-        const int hm = 1 << (s - 1), tstep = N >> s;
-        for (int t = sub; t < (av < na ? half : 0); t += 32) {
-            const int j = t & (hm - 1);
-            const int base = ((t >> (s - 1)) << s) + j;
-            double2 a = b[base], c = b[base + hm];
-            bfly(a, c, tw[j * tstep]);
-            b[base] = a; b[base + hm] = c;
-        }
-        __syncthreads();
-    }
+    ofdm_fft_lds(buf, na, ld, tw, N, dp.log2n);
 
     const int side = 1 << (dp.m / 2);
     const double norm = det_norm(side);
@@ -117,21 +81,10 @@ __global__ __launch_bounds__(1024) void detect_count_kernel(DetectParams dp) {
 #pragma unroll
             for (int bb = 0; bb < 4; ++bb) errs += (int)(((uint32_t)(idx >> bb) & 1u) != ((wd[bb] >> (8 * ant)) & 0xffu));
         } else {
-            const uint8_t* tb = dp.tx_bits + ((size_t)frame * N + k) * dp.m * n_t + ant;
-            for (int bb = 0; bb < dp.m; ++bb) errs += (((idx >> bb) & 1) != (int)tb[(size_t)bb * n_t]);
+            errs += det_bit_errors(idx, dp.tx_bits + ((size_t)frame * N + k) * dp.m * n_t + ant, n_t, dp.m);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) errs += __shfl_down(errs, off);
-    const int nwv = (nthr + 63) >> 6;
-    if (lane == 0) red[wv] = errs;
-    __syncthreads();
-    if (tid == 0) {
-        int e = 0;
-        for (int w = 0; w < nwv; ++w) e += red[w];
-        atomicAdd(reinterpret_cast<unsigned long long*>(dp.err + group), (unsigned long long)e);
-        atomicAdd(reinterpret_cast<unsigned long long*>(dp.bits + group), (unsigned long long)(N * dp.m * na));
-    }
+    det_count_tail(true, errs, red, dp.err + group, dp.bits + group, N * dp.m * na);
 }
 
 // ---- fixed-shape instances -------------------------------------------------------------------------------------------
@@ -326,6 +279,17 @@ static const void* detect_fixed_kernel_for(const DetectParams& dp, bool io32) {
     return nullptr;
 }
 
+bool detect_geometry(const DetectParams& dp, DetectGeometry* g) {
+    int na = dp.n_t < 16 ? dp.n_t : 16;
+    auto lds_of = [&](int a) { return sizeof(double2) * ((size_t)a * (dp.n_sub + 1) + dp.n_sub / 2); };
+    while (na > 1 && lds_of(na) > 150 * 1024) --na;
+    g->na_wg = na;
+    g->lds = lds_of(na);
+    g->grid = dim3(dp.n_frames * ((dp.n_t + na - 1) / na));
+    g->block = dim3(32 * na < 64 ? 64 : 32 * na);
+    return g->lds <= 150 * 1024;
+}
+
 int launch_detect_count(const DetectParams& dp_in, hipStream_t stream, bool io32) {
     DetectParams dp = dp_in;
     if (const void* fixed = detect_fixed_kernel_for(dp, io32)) {
@@ -334,20 +298,15 @@ int launch_detect_count(const DetectParams& dp_in, hipStream_t stream, bool io32
         const dim3 grid((dp.n_frames + kDetFixedFrames - 1) / kDetFixedFrames), block(64);
         return (int)hipLaunchKernel(fixed, grid, block, args, 0, stream);
     }
-    int na = dp.n_t < 16 ? dp.n_t : 16;                      // antennas per workgroup
-    auto lds_of = [&](int a) { return sizeof(double2) * ((size_t)a * (dp.n_sub + 1) + dp.n_sub / 2); };
-    while (na > 1 && lds_of(na) > 150 * 1024) --na;
-    const size_t lds = lds_of(na);
-    if (lds > 150 * 1024) return -1;
-    const int n_chunks = (dp.n_t + na - 1) / na;
-    dp.na_wg = na;
+    DetectGeometry g;
+    if (!detect_geometry(dp, &g)) return -1;
+    dp.na_wg = g.na_wg;
     const void* kern = io32 ? reinterpret_cast<const void*>(detect_count_kernel<true>)
                             : reinterpret_cast<const void*>(detect_count_kernel<false>);
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(dp.n_frames * n_chunks), block(32 * na < 64 ? 64 : 32 * na);
-    if (io32) hipLaunchKernelGGL(detect_count_kernel<true>, grid, block, lds, stream, dp);
-    else hipLaunchKernelGGL(detect_count_kernel<false>, grid, block, lds, stream, dp);
+    if (io32) hipLaunchKernelGGL(detect_count_kernel<true>, g.grid, g.block, g.lds, stream, dp);
+    else hipLaunchKernelGGL(detect_count_kernel<false>, g.grid, g.block, g.lds, stream, dp);
     return (int)hipGetLastError();
 }
 

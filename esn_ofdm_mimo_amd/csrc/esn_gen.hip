@@ -11,6 +11,7 @@
 //                      -> per-link FIR, zero initial state (:422-425) -> AWGN (:426)
 #include "esn_common.h"
 #include "esn_launch.h"
+#include "esn_ofdm_math.h"
 #include <type_traits>
 
 namespace esn {
@@ -229,14 +230,9 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
     const uint64_t gf = fp.frame_offset + frame;
     const Philox ph{(uint32_t)fp.seed, (uint32_t)(fp.seed >> 32)};
     const int side = 1 << (m / 2);
-    const double norm = sqrt(2.0 * (double)(side * side - 1) / 3.0);
-    const int half = N >> 1;
+    const double norm = det_norm(side);
 
-    for (int k = tid; k < half; k += nth) {
-        double sn, cs;
-        sincospi(2.0 * (double)k / (double)N, &sn, &cs);
-        tw[k] = make_double2(cs, sn);
-    }
+    ofdm_twiddles(tw, N >> 1, N, 1.0);
     for (int i = tid; i < n_r * n_t * isi; i += nth)
         ctap[i] = reinterpret_cast<const double2*>(fp.taps)[(size_t)blk * n_r * n_t * isi + i];
     // ---- bits -> constellation point (index = sum_b bit_b 2^b = i*side + j; Re = pam[i], Im = pam[j])
@@ -250,16 +246,13 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
         const int pi_ = (int)(idx / side), pj = (int)(idx % side);
         const int rv = (int)(__brev((unsigned)sc) >> (32 - fp.log2n));
         const bool on = !fp.ls_pattern || (sc % n_t == tx);
-        X[(size_t)tx * N + rv] = on ? make_double2((2.0 * pi_ - (side - 1)) / norm, (2.0 * pj - (side - 1)) / norm)
+        X[(size_t)tx * N + rv] = on ? make_double2(det_level(pi_, side, norm), det_level(pj, side, norm))
                                     : make_double2(0.0, 0.0);
     };
     if (fp.bits_in) {
         for (int e = tid; e < N * n_t; e += nth) {
             const int sc = e / n_t, tx = e % n_t;
-            uint32_t idx = 0;
-            for (int b = 0; b < m; ++b)
-                idx |= (uint32_t)(fp.bits_in[((size_t)frame * N * m + (size_t)sc * m + b) * n_t + tx] & 1) << b;
-            place(e, idx);
+            place(e, (uint32_t)det_bits_index(fp.bits_in + ((size_t)frame * N * m + (size_t)sc * m) * n_t + tx, n_t, m));
         }
     } else if (m == 4 && n_t == 4 && N >= 8) {
         // headline shape: a call's 32 symbols are 8 whole subcarriers; a subcarrier's 16 bit-bytes (bit b of tx at
@@ -286,7 +279,7 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
                     for (int tx = 0; tx < 4; ++tx) {
                         const uint32_t idx = (four >> (4 * tx)) & 15u;
                         const bool on = !fp.ls_pattern || ((sc & 3) == tx);
-                        X[(size_t)tx * N + rv] = on ? make_double2((2.0 * (int)(idx >> 2) - 3.0) / norm, (2.0 * (int)(idx & 3) - 3.0) / norm)
+                        X[(size_t)tx * N + rv] = on ? make_double2(det_level((int)(idx >> 2), 4, norm), det_level((int)(idx & 3), 4, norm))
                                                     : make_double2(0.0, 0.0);
                     }
                 }
@@ -305,21 +298,7 @@ __global__ __launch_bounds__(256) void gen_frames_kernel(FrameGenParams fp) {
     }
     __syncthreads();
     // ---- x = N * ifft(X): un-normalised inverse DFT, radix-2 DIT on bit-reversed input, per tx
-    for (int s = 1; s <= ((fp.ko & 4) ? 0 : fp.log2n); ++s) {
-        const int hm = 1 << (s - 1), tstep = N >> s;
-        for (int e = tid; e < n_t * half; e += nth) {
-            const int tx = e / half, b = e % half;
-            const int j = b & (hm - 1);
-            const int base = ((b >> (s - 1)) << s) + j;
-            const double2 w = tw[j * tstep];                 // exp(+2 pi i j / 2^s), same argument as sincospi(j / hm)
-            double2* xx = X + (size_t)tx * N;
-            const double2 a = xx[base], c = xx[base + hm];
-            const double tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
-            xx[base] = make_double2(a.x + tr, a.y + ti);
-            xx[base + hm] = make_double2(a.x - tr, a.y - ti);
-        }
-        __syncthreads();
-    }
+    if (!(fp.ko & 4)) ofdm_fft_lds(X, n_t, N, tw, N, fp.log2n);
     // ---- cyclic prefix, power scaling, PA
     const double sp = sqrt(fp.p_i[blk]), aclip = fp.a_clip[blk];
     for (int e = tid; e < T * n_t; e += nth) {

@@ -143,7 +143,11 @@ int launch_channel_metrics(const ChanStatParams& cp, hipStream_t stream);
 int launch_ldpc_encode(const LdpcEncodeParams& ep, hipStream_t stream);
 int launch_qam_llr(const LlrParams& lp, hipStream_t stream);
 int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
-// esn_detect.hip
+// esn_detect.hip; detect_geometry: the launch of the generic detector kernels (detect_count_kernel, detect_remod_kernel) --
+// as many antennas per workgroup as fit LDS (rows [na][N + 1] and N/2 twiddles, double2), one workgroup per (frame,
+// chunk of antennas), 32 threads per antenna; false where not even one antenna fits
+struct DetectGeometry { int na_wg; size_t lds; dim3 grid, block; };
+bool detect_geometry(const DetectParams& dp, DetectGeometry* g);
 int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
 // esn_remod.hip
 int launch_detect_remod(const RemodParams& rp, hipStream_t stream);

@@ -11,7 +11,7 @@
 // which the row writer undoes -- so no second buffer and no reordering pass is needed.
 #include "esn_common.h"
 #include "esn_launch.h"
-#include "esn_detect_math.h"
+#include "esn_ofdm_math.h"
 
 namespace esn {
 
@@ -41,49 +41,15 @@ __global__ __launch_bounds__(512) void detect_remod_kernel(RemodParams rp) {
     const int group = frame / dp.frames_per_group;
     const double2* y = reinterpret_cast<const double2*>(dp.Y) + (size_t)frame * N * n_t;
     const double p_i_g = dp.p_i[group];
-    for (int k = tid; k < half; k += nthr) {
-        tw[k] = det_twiddle(k, N);
-    }
+    ofdm_twiddles(tw, half, N, -1.0);
     for (int i = tid; i < N * na; i += nthr) {               // bit-reversed load, element i = (row, antenna)
         const int row = i / na, ant = i - row * na;
         const int rv = (int)(__brev((unsigned)row) >> (32 - dp.log2n));
         buf[ant * ld + rv] = y[(size_t)row * n_t + a0 + ant];
     }
     __syncthreads();
-    const int lane = tid & 63, wv = tid >> 6;
-    const int sub = tid & 31, av = tid >> 5;                 // 32 threads per antenna
-    double2* b = buf + (size_t)(av < na ? av : 0) * ld;
-    const int quarter = N >> 2;
-    const int n_quarter = av < na ? quarter : 0, n_half = av < na ? half : 0;
-    // ---- forward: the stages of detect_count_kernel, two at a time on four points in registers
-    int s = 1;
-    for (; s + 1 <= dp.log2n; s += 2) {                      // stages s and s+1 on {base, +hm, +2hm, +3hm}
-        const int hm = 1 << (s - 1);
-        for (int t = sub; t < n_quarter; t += 32) {
-            const int j = t & (hm - 1);
-            const int base = ((t >> (s - 1)) << (s + 1)) + j;
-            double2 p0 = b[base], p1 = b[base + hm], p2 = b[base + 2 * hm], p3 = b[base + 3 * hm];
-            const double2 w1 = tw[j * (N >> s)];             // exp(-2 pi i j / 2^s)
-            det_bfly(p0, p1, w1);
-            det_bfly(p2, p3, w1);
-            const int ts2 = N >> (s + 1);
-            det_bfly(p0, p2, tw[j * ts2]);                   // exp(-2 pi i j / 2^(s+1))
-            det_bfly(p1, p3, tw[(j + hm) * ts2]);
-            b[base] = p0; b[base + hm] = p1; b[base + 2 * hm] = p2; b[base + 3 * hm] = p3;
-        }
-        __syncthreads();
-    }
-    if (s <= dp.log2n) {                                     // odd number of stages: the last one alone
-        const int hm = 1 << (s - 1), tstep = N >> s;
-        for (int t = sub; t < n_half; t += 32) {
-            const int j = t & (hm - 1);
-            const int base = ((t >> (s - 1)) << s) + j;
-            double2 a = b[base], c = b[base + hm];
-            det_bfly(a, c, tw[j * tstep]);
-            b[base] = a; b[base + hm] = c;
-        }
-        __syncthreads();
-    }
+    // ---- forward: the transform of detect_count_kernel
+    ofdm_fft_lds(buf, na, ld, tw, N, dp.log2n);
 
     // ---- slice: X_hat, counters and decided bits as the tail gives them; the decision replaces X in place
     const int side = 1 << (dp.m / 2);
@@ -99,55 +65,40 @@ __global__ __launch_bounds__(512) void detect_remod_kernel(RemodParams rp) {
         const int ir = det_slice(re, norm, side), ii = det_slice(im, norm, side);
         const int idx = ir * side + ii;
         const size_t bit0 = ((size_t)frame * N + k) * dp.m * n_t + ant;      // bit bb of this element: + bb n_t
-        if (dp.tx_bits)
-            for (int bb = 0; bb < dp.m; ++bb) errs += (((idx >> bb) & 1) != (int)dp.tx_bits[bit0 + (size_t)bb * n_t]);
+        if (dp.tx_bits) errs += det_bit_errors(idx, dp.tx_bits + bit0, n_t, dp.m);
         if (rp.dec_bits)
             for (int bb = 0; bb < dp.m; ++bb) rp.dec_bits[bit0 + (size_t)bb * n_t] = (uint8_t)((idx >> bb) & 1);
-        // level i of the grid is (2 i - (side - 1)) / norm (unit mean power)
-        buf[(ant - a0) * ld + k] = make_double2((double)(2 * ir - (side - 1)) / norm, (double)(2 * ii - (side - 1)) / norm);
+        buf[(ant - a0) * ld + k] = make_double2(det_level(ir, side, norm), det_level(ii, side, norm));
     }
-    if (dp.tx_bits) {                                        // (uniform over the launch)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) errs += __shfl_down(errs, off);
-        if (lane == 0) red[wv] = errs;
-    }
-    __syncthreads();
-    if (dp.tx_bits && tid == 0) {
-        const int nwv = (nthr + 63) >> 6;
-        int e = 0;
-        for (int w = 0; w < nwv; ++w) e += red[w];
-        atomicAdd(reinterpret_cast<unsigned long long*>(dp.err + group), (unsigned long long)e);
-        atomicAdd(reinterpret_cast<unsigned long long*>(dp.bits + group), (unsigned long long)(N * dp.m * na));
-    }
+    det_count_tail(dp.tx_bits != nullptr, errs, red, dp.err + group, dp.bits + group, N * dp.m * na);
 
     // ---- inverse: decimation in frequency, stages log2n .. 1, natural order in, bit-reversed order out; the unpaired
-    // stage of an odd count goes first, the others two at a time on the same four points as the forward pass
-    s = dp.log2n;
+    // stage of an odd count goes first, the others two at a time on the same four points as the forward pass; 32
+    // threads per antenna
+    const int sub = tid & 31, av = tid >> 5;
+    double2* b = buf + (size_t)(av < na ? av : 0) * ld;
+    const int n_quarter = av < na ? N >> 2 : 0, n_half = av < na ? half : 0;
+    int s = dp.log2n;
     if (s & 1) {
-        const int hm = 1 << (s - 1), tstep = N >> s;
         for (int t = sub; t < n_half; t += 32) {
-            const int j = t & (hm - 1);
-            const int base = ((t >> (s - 1)) << s) + j;
-            double2 a = b[base], c = b[base + hm];
-            remod_ibfly(a, c, tw[j * tstep]);
-            b[base] = a; b[base + hm] = c;
+            const OfdmPair p = ofdm_pair(t, s, N);
+            double2 a = b[p.base], c = b[p.base + p.hm];
+            remod_ibfly(a, c, tw[p.k]);
+            b[p.base] = a; b[p.base + p.hm] = c;
         }
         __syncthreads();
         --s;
     }
-    for (s -= 1; s >= 1; s -= 2) {                           // stages s+1, then s, on {base, +hm, +2hm, +3hm}
-        const int hm = 1 << (s - 1);
+    for (s -= 1; s >= 1; s -= 2) {                           // stages s+1, then s
         for (int t = sub; t < n_quarter; t += 32) {
-            const int j = t & (hm - 1);
-            const int base = ((t >> (s - 1)) << (s + 1)) + j;
-            double2 p0 = b[base], p1 = b[base + hm], p2 = b[base + 2 * hm], p3 = b[base + 3 * hm];
-            const int ts2 = N >> (s + 1);
-            remod_ibfly(p0, p2, tw[j * ts2]);
-            remod_ibfly(p1, p3, tw[(j + hm) * ts2]);
-            const double2 w1 = tw[j * (N >> s)];
+            const OfdmQuad q = ofdm_quad(t, s, N);
+            double2 p0 = b[q.base], p1 = b[q.base + q.hm], p2 = b[q.base + 2 * q.hm], p3 = b[q.base + 3 * q.hm];
+            remod_ibfly(p0, p2, tw[q.k2]);
+            remod_ibfly(p1, p3, tw[q.k3]);
+            const double2 w1 = tw[q.k1];
             remod_ibfly(p0, p1, w1);
             remod_ibfly(p2, p3, w1);
-            b[base] = p0; b[base + hm] = p1; b[base + 2 * hm] = p2; b[base + 3 * hm] = p3;
+            b[q.base] = p0; b[q.base + q.hm] = p1; b[q.base + 2 * q.hm] = p2; b[q.base + 3 * q.hm] = p3;
         }
         __syncthreads();
     }
@@ -172,19 +123,13 @@ __global__ __launch_bounds__(512) void detect_remod_kernel(RemodParams rp) {
 
 int launch_detect_remod(const RemodParams& rp_in, hipStream_t stream) {
     RemodParams rp = rp_in;
-    const DetectParams& dp = rp.d;
-    int na = dp.n_t < 16 ? dp.n_t : 16;                      // antennas per workgroup
-    auto lds_of = [&](int a) { return sizeof(double2) * ((size_t)a * (dp.n_sub + 1) + dp.n_sub / 2); };
-    while (na > 1 && lds_of(na) > 150 * 1024) --na;
-    const size_t lds = lds_of(na);
-    if (lds > 150 * 1024) return -1;
-    const int n_chunks = (dp.n_t + na - 1) / na;
-    rp.d.na_wg = na;
+    DetectGeometry g;
+    if (!detect_geometry(rp.d, &g)) return -1;
+    rp.d.na_wg = g.na_wg;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detect_remod_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(dp.n_frames * n_chunks), block(32 * na < 64 ? 64 : 32 * na);
-    hipLaunchKernelGGL(detect_remod_kernel, grid, block, lds, stream, rp);
+    hipLaunchKernelGGL(detect_remod_kernel, g.grid, g.block, g.lds, stream, rp);
     return (int)hipGetLastError();
 }
 
