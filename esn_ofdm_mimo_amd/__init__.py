@@ -14,4 +14,4 @@ the library, or calling them without a GPU, raises.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["pyESN", "helper_mimo_esn_generic", "batched", "montecarlo", "elm", "fnn", "cnn"]
+__all__ = ["pyESN", "helper_mimo_esn_generic", "batched", "montecarlo", "elm", "fnn", "cnn", "lstm"]

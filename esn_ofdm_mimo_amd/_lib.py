@@ -151,6 +151,16 @@ SIGNATURES = {
     # precision, n_in, c1, c2, n_out, kernel, W1, b1, W2, b2, W3, b3, in_scale, in_shift, t_scale, t_shift, U, n_frames,
     # frames_per_group, T_in, T, transient, Y, workspace, workspace_bytes, stream
     "esn_cnn_predict": (C.c_int, [C.c_int] * 6 + [_dp] * 11 + [C.c_int] * 5 + [_dp, _vp, C.c_size_t, _vp]),
+    # LSTM comparator: n_in, n_hidden, n_out, n_groups, n_frames, T -> bytes of the workspace of train / predict
+    "esn_lstm_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # precision, n_in, n_hidden, n_out, n_isets, W_ih_0, W_hh_0, b_ih_0, b_hh_0, W_fc_0, b_fc_0, in_scale, in_shift,
+    # t_scale, t_shift, U, D, n_groups, T_in, T, transient, group_offset, epochs, lr, beta1, beta2, eps, W_ih, W_hh, b_ih,
+    # b_hh, W_fc, b_fc, loss, workspace, workspace_bytes, stream
+    "esn_lstm_train": (C.c_int, [C.c_int] * 5 + [_dp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                                 C.c_double, C.c_double, C.c_double, C.c_double] + [_dp] * 7 + [_vp, C.c_size_t, _vp]),
+    # precision, n_in, n_hidden, n_out, W_ih, W_hh, b_ih, b_hh, W_fc, b_fc, in_scale, in_shift, t_scale, t_shift, U,
+    # n_frames, frames_per_group, T_in, T, transient, Y, workspace, workspace_bytes, stream
+    "esn_lstm_predict": (C.c_int, [C.c_int] * 4 + [_dp] * 11 + [C.c_int] * 5 + [_dp, _vp, C.c_size_t, _vp]),
     "esn_ldpc_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "esn_qam_llr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _vp]),
     "esn_ldpc_decode_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp,

@@ -1217,6 +1217,83 @@ int esn_cnn_predict(int precision, int n_in, int c1, int c2, int n_out, int kern
     return hip_fail(launch_cnn_predict(p, (hipStream_t)stream), who);
 }
 
+// what esn_lstm_train and esn_lstm_predict check alike; n_seq: groups or frames
+static int lstm_check(const char* who, int precision, int n_in, int n_hidden, int n_out, int n_seq, int T_in, int T,
+                      int transient, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (precision != ESN_F64 && precision != ESN_F32 && precision != ESN_F16 && precision != ESN_BF16)
+        return fail(-1, "%s: unknown precision %d", who, precision);
+    const char* why = lstm_shape_limit(n_in, n_hidden, n_out, T);
+    if (why) return fail(-1, "%s: n_in=%d n_hidden=%d n_out=%d T=%d: %s", who, n_in, n_hidden, n_out, T, why);
+    if (n_seq < 1) return fail(-1, "%s: invalid sizes (groups, frames)", who);
+    if (T_in < 1 || T_in > T) return fail(-1, "%s: need 1 <= T_in <= T (T_in=%d, T=%d)", who, T_in, T);
+    if (transient < 0 || transient >= T) return fail(-1, "%s: transient=%d must be in [0, T) with T=%d", who, transient, T);
+    if (precision != ESN_F64) return fail(-2, "%s: float64 (ESN_F64) only; precision %d is not built", who, precision);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        return fail(-1, "%s: workspace of %zu bytes (8-byte aligned) needed, esn_lstm_workspace_bytes; got %zu", who, need,
+                    workspace ? workspace_bytes : (size_t)0);
+    return 0;
+}
+
+size_t esn_lstm_workspace_bytes(int n_in, int n_hidden, int n_out, int n_groups, int n_frames, int T) {
+    if (lstm_shape_limit(n_in, n_hidden, n_out, T) || n_groups < 0 || n_frames < 0) return 0;
+    return lstm_workspace_bytes(n_in, n_hidden, n_out, n_groups, n_frames, T);
+}
+
+int esn_lstm_train(int precision, int n_in, int n_hidden, int n_out, int n_isets, const double* W_ih_0,
+                   const double* W_hh_0, const double* b_ih_0, const double* b_hh_0, const double* W_fc_0,
+                   const double* b_fc_0, const double* in_scale, const double* in_shift, const double* t_scale,
+                   const double* t_shift, const double* U, const double* D, int n_groups, int T_in, int T, int transient,
+                   uint64_t group_offset, int epochs, double lr, double beta1, double beta2, double eps, double* W_ih,
+                   double* W_hh, double* b_ih, double* b_hh, double* W_fc, double* b_fc, double* loss, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    const char* who = "esn_lstm_train";
+    if (!W_ih_0 || !W_hh_0 || !b_ih_0 || !b_hh_0 || !W_fc_0 || !b_fc_0 || !U || !D || !W_ih || !W_hh || !b_ih || !b_hh ||
+        !W_fc || !b_fc)
+        return fail(-1, "%s: null pointer", who);
+    if (n_isets < 1) return fail(-1, "%s: n_isets=%d must be positive", who, n_isets);
+    if (epochs < 1) return fail(-1, "%s: epochs=%d must be positive", who, epochs);
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
+        return fail(-1, "%s: need lr >= 0, 0 <= beta1, beta2 < 1 and eps > 0", who);
+    const int rc = lstm_check(who, precision, n_in, n_hidden, n_out, n_groups, T_in, T, transient, workspace,
+                              workspace_bytes,
+                              lstm_shape_limit(n_in, n_hidden, n_out, T) || n_groups < 1
+                                  ? 0 : lstm_workspace_bytes(n_in, n_hidden, n_out, n_groups, 0, T));
+    if (rc) return rc;
+    LstmParams p;
+    memset(&p, 0, sizeof(p));
+    p.n_in = n_in; p.n_hidden = n_hidden; p.n_out = n_out; p.n_isets = n_isets; p.n_groups = n_groups;
+    p.T_in = T_in; p.T = T; p.transient = transient; p.epochs = epochs; p.group_offset = group_offset;
+    p.lr = lr; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
+    p.W0[0] = W_ih_0; p.W0[1] = W_hh_0; p.W0[2] = W_fc_0; p.b0[0] = b_ih_0; p.b0[1] = b_hh_0; p.b0[2] = b_fc_0;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.D = D;
+    p.W[0] = W_ih; p.W[1] = W_hh; p.W[2] = W_fc; p.b[0] = b_ih; p.b[1] = b_hh; p.b[2] = b_fc; p.loss = loss;
+    p.workspace = reinterpret_cast<double*>(workspace);
+    return hip_fail(launch_lstm_train(p, (hipStream_t)stream), who);
+}
+
+int esn_lstm_predict(int precision, int n_in, int n_hidden, int n_out, const double* W_ih, const double* W_hh,
+                     const double* b_ih, const double* b_hh, const double* W_fc, const double* b_fc,
+                     const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                     const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient, double* Y,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "esn_lstm_predict";
+    if (!W_ih || !W_hh || !b_ih || !b_hh || !W_fc || !b_fc || !U || !Y) return fail(-1, "%s: null pointer", who);
+    if (frames_per_group < 1) return fail(-1, "%s: frames_per_group=%d must be positive", who, frames_per_group);
+    const int rc = lstm_check(who, precision, n_in, n_hidden, n_out, n_frames, T_in, T, transient, workspace,
+                              workspace_bytes,
+                              lstm_shape_limit(n_in, n_hidden, n_out, T) || n_frames < 1
+                                  ? 0 : lstm_workspace_bytes(n_in, n_hidden, n_out, 0, n_frames, T));
+    if (rc) return rc;
+    LstmParams p;
+    memset(&p, 0, sizeof(p));
+    p.n_in = n_in; p.n_hidden = n_hidden; p.n_out = n_out; p.T_in = T_in; p.T = T;
+    p.transient = transient; p.n_frames = n_frames; p.frames_per_group = frames_per_group;
+    p.W0[0] = W_ih; p.W0[1] = W_hh; p.W0[2] = W_fc; p.b0[0] = b_ih; p.b0[1] = b_hh; p.b0[2] = b_fc;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
+    p.workspace = reinterpret_cast<double*>(workspace);
+    return hip_fail(launch_lstm_predict(p, (hipStream_t)stream), who);
+}
+
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream) {
     if (!taps || !H) return fail(-1, "esn_taps_to_freq: null pointer");
     if (n_blocks <= 0 || n_sub <= 0 || n_t <= 0 || n_r <= 0 || isi <= 0 || isi > n_sub)

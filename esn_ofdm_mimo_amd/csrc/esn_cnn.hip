@@ -12,7 +12,8 @@
 //                                      P'[j' c_out + o][i] = W[o][i][k - 1 - j']
 //   weight grad.  dP [c_out x (K + 1)] = dz^T [c_out x T] . [xp-view | 1]
 // are plain products, all on v_mfma_f64_16x16x4_f64 (A[l % 16][l / 16], B[l / 16][l % 16], C register i: row
-// 4 i + l / 16, column l % 16), for all three layers: a wave takes a strip of CNN_NB tiles that share the A operand,
+// 4 i + l / 16, column l % 16), for all three layers (the forward and the weight-gradient product are in
+// esn_f64_strip.h, which the LSTM's training shares): a wave takes a strip of CNN_NB tiles that share the A operand,
 // operands straight from memory.  Sums run over the inner index in ascending groups of four, whatever wave takes the
 // strip: every sum's order depends on the shape alone.
 //
@@ -29,13 +30,11 @@
 // cnn_predict_kernel  the same forward functions, a workgroup per frame (at most CNN_PRED_WGS workgroups take the frames
 //   in turn), the frame's group's parameters re-laid into the workgroup's scratch, activations there too.
 #include "esn_common.h"
+#include "esn_f64_strip.h"
 #include "esn_launch.h"
 
 namespace esn {
 
-typedef double cnn_f64x4 __attribute__((ext_vector_type(4)));
-constexpr int CNN_THREADS = 512, CNN_WAVES = CNN_THREADS / 64;
-constexpr int CNN_NB = 2;                      // tiles of a strip: they share the A operand
 constexpr int CNN_PRED_WGS = 512;              // workgroups (and scratch regions) of a prediction at most
 
 // the served shapes, stated once (include/esn_hip.h restates them in words, cnn.train_shape_error on the host)
@@ -78,53 +77,6 @@ size_t cnn_workspace_bytes(int n_in, int c1, int c2, int n_out, int kernel, int 
     return (tr > pr ? tr : pr) * sizeof(double);
 }
 
-__device__ __forceinline__ cnn_f64x4 cnn_mfma(double a, double b, cnn_f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// z [T x c_out] = [xp-view | 1] . P^T: epi(t, o, z) once for every t < T, o < c_out, by the lane that holds it
-template <class Epi>
-__device__ __forceinline__ void cnn_forward(const double* xp, const double* P, int T, int c_in, int c_out, int K, int wave,
-                                            int lane, Epi epi) {
-    const int lr = lane & 15, lq = lane >> 4, KS = K + 1;
-    const int nrt = (T + 15) / 16, nct = (c_out + 15) / 16, ncs = (nct + CNN_NB - 1) / CNN_NB;
-    for (int s = wave; s < nrt * ncs; s += CNN_WAVES) {
-        const int rt = s / ncs, ct0 = (s - rt * ncs) * CNN_NB;
-        const int t = 16 * rt + lr < T ? 16 * rt + lr : T - 1;             // rows and columns beyond the end read the
-        const double* a = xp + (size_t)t * c_in + lq;                      // last one; their results are dropped
-        const double* b[CNN_NB];
-        cnn_f64x4 acc[CNN_NB];
-#pragma unroll
-        for (int q = 0; q < CNN_NB; ++q) {
-            const int o = 16 * (ct0 + q) + lr < c_out ? 16 * (ct0 + q) + lr : c_out - 1;
-            b[q] = P + (size_t)o * KS + lq;
-            acc[q] = cnn_f64x4{0.0, 0.0, 0.0, 0.0};
-        }
-        int kk = 0;
-        for (; kk + 4 <= K; kk += 4) {
-            const double av = a[kk];
-#pragma unroll
-            for (int q = 0; q < CNN_NB; ++q)
-                if (ct0 + q < nct) acc[q] = cnn_mfma(av, b[q][kk], acc[q]);
-        }
-        for (; kk < KS; kk += 4) {                                         // the last inputs, the bias column, zeros
-            const int k1 = kk + lq;
-            const double av = k1 < K ? a[kk] : (k1 == K ? 1.0 : 0.0);
-#pragma unroll
-            for (int q = 0; q < CNN_NB; ++q)
-                if (ct0 + q < nct) acc[q] = cnn_mfma(av, k1 <= K ? b[q][kk] : 0.0, acc[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < CNN_NB; ++q) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = 16 * rt + 4 * i + lq, col = 16 * (ct0 + q) + lr;
-                if (row < T && col < c_out) epi(row, col, acc[q][i]);
-            }
-        }
-    }
-}
-
 // the layer's input gradient behind the ReLU that made its input: dzin[(t + p) c_in + i] = (sum_j' sum_o
 // dzp[(t + j') c_out + o] W[o][i][k - 1 - j']) [xp[(t + p) c_in + i] > 0], j' and within it o ascending
 __device__ __forceinline__ void cnn_input_grad(const double* dzp, const double* P, const double* xp, double* dzin, int T,
@@ -162,54 +114,6 @@ __device__ __forceinline__ void cnn_input_grad(const double* dzp, const double* 
                     const size_t at = (size_t)(row + pad) * c_in + col;
                     dzin[at] = xp[at] > 0.0 ? acc[q][i] : 0.0;
                 }
-            }
-        }
-    }
-}
-
-struct CnnAdam { double beta1, beta2, step, rs2, eps; bool first; };
-
-// strip s of the layer's weight gradient dP [c_out x (K + 1)] = dz^T . [xp-view | 1], rows t in ascending groups of four,
-// and the Adam step of its elements by the lanes that hold them
-__device__ __forceinline__ void cnn_weight_grad_strip(int s, const double* dzp, const double* xp, double* P, double* M,
-                                                      double* V, int T, int c_in, int c_out, int kernel, int lane,
-                                                      const CnnAdam& ad) {
-    const int lr = lane & 15, lq = lane >> 4, K = kernel * c_in, KS = K + 1, pad = (kernel - 1) / 2;
-    const int nct = (KS + 15) / 16, ncs = (nct + CNN_NB - 1) / CNN_NB;
-    const int rt = s / ncs, ct0 = (s - rt * ncs) * CNN_NB;
-    const int o = 16 * rt + lr < c_out ? 16 * rt + lr : c_out - 1;
-    const double* a = dzp + (size_t)pad * c_out + o;
-    int kc[CNN_NB];
-    cnn_f64x4 acc[CNN_NB];
-#pragma unroll
-    for (int q = 0; q < CNN_NB; ++q) {
-        kc[q] = 16 * (ct0 + q) + lr < KS ? 16 * (ct0 + q) + lr : K;
-        acc[q] = cnn_f64x4{0.0, 0.0, 0.0, 0.0};
-    }
-    for (int t0 = 0; t0 < T; t0 += 4) {
-        const int t = t0 + lq;
-        const bool in = t < T;
-        const double av = in ? a[(size_t)t * c_out] : 0.0;
-#pragma unroll
-        for (int q = 0; q < CNN_NB; ++q) {
-            if (ct0 + q < nct) {
-                const double bv = in ? (kc[q] < K ? xp[(size_t)t * c_in + kc[q]] : 1.0) : 0.0;
-                acc[q] = cnn_mfma(av, bv, acc[q]);
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < CNN_NB; ++q) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = 16 * rt + 4 * i + lq, col = 16 * (ct0 + q) + lr;
-            if (row < c_out && col < KS) {
-                const size_t at = (size_t)row * KS + col;
-                double prm = P[at], m = ad.first ? 0.0 : M[at], v = ad.first ? 0.0 : V[at];
-                fnn_adam(prm, m, v, acc[q][i], ad.beta1, ad.beta2, ad.step, ad.rs2, ad.eps);
-                P[at] = prm;
-                M[at] = m;
-                V[at] = v;
             }
         }
     }

@@ -233,6 +233,25 @@ struct CnnParams {
     double* Y;                   // [n_frames][T - transient][n_out]                (predict)
     double* workspace;           // cnn_workspace_bytes
 };
+// LSTM comparator (esn_lstm.hip): one LSTM layer n_in -> n_hidden and a linear read-out n_hidden -> n_out over the whole
+// sequence, parameters in torch's layout (gate order i, f, g, o), sets l = 0, 1, 2 = (W_ih, b_ih), (W_hh, b_hh),
+// (W_fc, b_fc); trained per group by full-batch Adam or evaluated per frame, every other field as in CnnParams
+struct LstmParams {
+    int n_in, n_hidden, n_out, n_isets, n_groups, T_in, T, transient, epochs;
+    int n_frames, frames_per_group;
+    unsigned long long group_offset;
+    double lr, beta1, beta2, eps;
+    const double* W0[3];         // train: [n_isets][4H][n_in], [n_isets][4H][H], [n_isets][n_out][H] initial;  predict: [groups]
+    const double* b0[3];         // [..][4H], [..][4H], [..][n_out]
+    const double *in_scale, *in_shift, *t_scale, *t_shift;   // [groups][n] or nullptr
+    const double* U;             // [groups | n_frames][T_in][n_in]
+    const double* D;             // [groups][T][n_out]                              (train)
+    double* W[3];                // [groups][...]                                   (train)
+    double* b[3];
+    double* loss;                // [groups][epochs] or nullptr
+    double* Y;                   // [n_frames][T - transient][n_out]                (predict)
+    double* workspace;           // lstm_workspace_bytes
+};
 
 // coded leg (esn_coded.hip)
 struct LdpcEncodeParams {

@@ -171,4 +171,9 @@ const char* cnn_shape_limit(int n_in, int c1, int c2, int n_out, int kernel, int
 size_t cnn_workspace_bytes(int n_in, int c1, int c2, int n_out, int kernel, int n_groups, int n_frames, int T);
 int launch_cnn_train(const CnnParams& p, hipStream_t stream);
 int launch_cnn_predict(const CnnParams& p, hipStream_t stream);
+// esn_lstm.hip: the LSTM comparator, with the CNN's contract
+const char* lstm_shape_limit(int n_in, int n_hidden, int n_out, int T);
+size_t lstm_workspace_bytes(int n_in, int n_hidden, int n_out, int n_groups, int n_frames, int T);
+int launch_lstm_train(const LstmParams& p, hipStream_t stream);
+int launch_lstm_predict(const LstmParams& p, hipStream_t stream);
 }  // namespace esn

@@ -26,6 +26,8 @@
                     chunk loop are elm_point's (points._windowed_point), the two differ in how a chunk is trained
     cnn_point       the same for the windowed CNN (cnn.py, esn_cnn_train / esn_cnn_predict), the reference's          points.py
                     three-layer Conv1d comparator, float64 throughout
+    lstm_point      the same for the LSTM (lstm.py, esn_lstm_train / esn_lstm_predict), the reference's recurrent          points.py
+                    comparator (its RNN curve), float64 throughout
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -38,4 +40,5 @@ from .link import LinkParams  # noqa: F401
 from .points import baseline_tracking_point, block_fading_point, coded_ber_point, elm_point  # noqa: F401
 from .points import fnn_point, fnn_weights  # noqa: F401
 from .points import cnn_point, cnn_weights  # noqa: F401
+from .points import lstm_point, lstm_weights  # noqa: F401
 from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters  # noqa: F401

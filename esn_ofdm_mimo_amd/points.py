@@ -4,8 +4,8 @@ driver's coded + uncoded ESN against LS/MMSE (coded_ber_point) and the block-fad
 through the sweep's bank as it stands; frames and ESN legs stay float64 / complex128 whatever the sweep's io says.
 Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, uncoded, detected symbol by symbol with its
 channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
-only.  And elm_point / fnn_point / cnn_point: the windowed ELM (elm.py), FNN (fnn.py) and CNN (cnn.py), the reference's
-pinv-trained and Adam-trained comparators, on the same frames."""
+only.  And elm_point / fnn_point / cnn_point / lstm_point: the windowed ELM (elm.py), FNN (fnn.py) and CNN (cnn.py) and
+the LSTM (lstm.py), the reference's pinv-trained and Adam-trained comparators, on the same frames."""
 from __future__ import annotations
 
 from .frames import _view_real, summarize_channel_metrics
@@ -413,6 +413,55 @@ def cnn_point(src, ebno_db, snr_idx, n_blocks, *, channels=(32, 64), kernel=5, e
     def train(U, D, scaling, b0, g):
         if shared is None:
             sets = [cnn_weights(channels, kernel, n_in, n_out, seed, b0 + i) for i in range(g)]
+            init = tuple(np.stack([s[j] for s in sets]) for j in range(6))
+        else:
+            init = shared
+        bank.set_scaling(*scaling)
+        return bank.train(U, D, init, transient=p.forget, epochs=epochs, lr=lr)
+
+    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, "f64", slice,
+                           train)
+
+
+def lstm_weights(n_hidden, n_in, n_out, seed, block=None):
+    """(W_ih [4H, n_in], W_hh [4H, H], b_ih [4H], b_hh [4H], W_fc [n_out, H], b_fc [n_out]), each U(+-1 / sqrt(H)) -- the
+    distribution of torch.nn.LSTM and of torch.nn.Linear(H, .) -- drawn in that order from RandomState(seed) or, for the
+    set of one global block, RandomState([seed, block])."""
+    import numpy as np
+    rs = np.random.RandomState(seed if block is None else [seed, block])
+    a, h = 1.0 / np.sqrt(n_hidden), n_hidden
+    return tuple(rs.uniform(-a, a, s) for s in ((4 * h, n_in), (4 * h, h), (4 * h,), (4 * h,), (n_out, h), (n_out,)))
+
+
+def lstm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, epochs=50, lr=0.01, slice="aligned", weights="shared",
+               first_block=0, seed=0, frames_per_block=None, chunk_blocks=None):
+    """One Eb/No point of the LSTM (lstm.LstmBank), the reference's fourth learned comparator (its RNN curve), on the
+    frames elm_point, fnn_point, cnn_point and a DetectorSweep over the same FrameSource seed detect: per chunk the pilot
+    of every block gives one training (inputs and teacher scaled by 1 / sqrt(var_x), the loss over rows from delay + cp
+    on, `epochs` Adam steps from lstm_weights), then all data frames are predicted in one launch and counted by the
+    detector tail.  slice and weights as in elm_point ("reference": rows [0, N) of the un-cut output, the slice the
+    reference's RNN branch takes, :544-545).  Float64 throughout.  Returns (errors, bits): int64 [n_blocks] on the device;
+    nothing is read back inside the chunk loop."""
+    _check_windowed_point_args(slice, weights, "f64", 1, n_blocks, first_block, chunk_blocks, frames_per_block)
+    if not isinstance(n_hidden, int) or n_hidden < 1:
+        raise ValueError(f"n_hidden must be a positive integer, not {n_hidden!r}")
+    if not isinstance(epochs, int) or epochs < 1:
+        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
+    if not lr >= 0:
+        raise ValueError(f"lr = {lr} must be non-negative")
+    import numpy as np
+    from .lstm import LstmBank, train_shape_error
+    p = src.p
+    n_in, n_out = 2 * p.n_r, 2 * p.n_t
+    why = train_shape_error(n_in, n_hidden, n_out, p.t_frame + p.delay)
+    if why:
+        raise ValueError("the LSTM kernels do not serve this shape: " + why)
+    shared = lstm_weights(n_hidden, n_in, n_out, seed) if weights == "shared" else None
+    bank = LstmBank(n_in, n_out, n_hidden, n_groups=min(int(chunk_blocks or 4096), int(n_blocks)), device=src.device)
+
+    def train(U, D, scaling, b0, g):
+        if shared is None:
+            sets = [lstm_weights(n_hidden, n_in, n_out, seed, b0 + i) for i in range(g)]
             init = tuple(np.stack([s[j] for s in sets]) for j in range(6))
         else:
             init = shared

@@ -829,6 +829,76 @@ int esn_cnn_predict(int precision, int n_in, int c1, int c2, int n_out, int kern
                     const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
                     double* Y, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LSTM comparator (the reference's fourth learned comparator, its curve BER_RNN: class RNNModel,
+ * system_model_2_all_comparision.py:29-38, trained as trainMIMOModel('RNN') does, :93-113): nn.LSTM(n_in, H, batch_first)
+ * followed by nn.Linear(H, n_out) over the whole pilot sequence, trained per group by `epochs` full-batch Adam steps on
+ * the mean squared error.  H = n_hidden.  Parameters in torch's layout and gate order i, f, g, o: W_ih [4H][n_in],
+ * W_hh [4H][H], b_ih [4H], b_hh [4H], W_fc [n_out][H], b_fc [n_out]; both bias vectors are kept, as the reference trains
+ * both.  Rows q H .. q H + H - 1 of W_ih, W_hh, b_ih, b_hh belong to gate q = 0 (i), 1 (f), 2 (g), 3 (o).  For group g:
+ *   x[t][i]  = u[t][i] in_scale[g][i] + in_shift[g][i]     0 <= t < T;  u = 0 for T_in <= t < T (zero rows BEFORE scaling)
+ *   z[t]     = W_ih x[t] + b_ih + W_hh h[t-1] + b_hh       h[-1] = c[-1] = 0 for every sequence (training, each frame)
+ *   i, f, o  = sigma(z_i), sigma(z_f), sigma(z_o)          sigma(a) = 1 / (1 + exp(-a))
+ *   gg       = tanh(z_g)
+ *   c[t]     = f c[t-1] + i gg
+ *   h[t]     = o tanh(c[t])
+ *   ys[t]    = W_fc h[t] + b_fc
+ *   loss     = sum_{transient <= t < T, o} (ys[t][o] - (D[g][t][o] t_scale[g][o] + t_shift[g][o]))^2 / ((T - transient) n_out)
+ *   Adam exactly as in the FNN block above, epoch e = 1..epochs; loss[g][e] is the loss BEFORE step e.  The reference's
+ *   values: H = 100, transient = 0, epochs = 50, lr = 0.01.
+ *   predict: Y[f][t - transient][o] = (ys[t][o] - t_shift[g][o]) / t_scale[g][o], g = f / frames_per_group.
+ * The gradients are exact backpropagation through time of this loss.  With dys[t][o] = 2 (ys[t][o] - Ds[t][o]) /
+ * ((T - transient) n_out) for t >= transient and 0 before, dz[T] = 0 and dc_next[T] = 0, for t = T-1 .. 0:
+ *   dh[t]   = W_fc^T dys[t] + W_hh^T dz[t+1]
+ *   d_o     = dh[t] tanh(c[t])                              dc[t] = dc_next[t+1] + dh[t] o (1 - tanh(c[t])^2)
+ *   d_i     = dc[t] gg       d_g = dc[t] i       d_f = dc[t] c[t-1]       dc_next[t] = dc[t] f
+ *   dz_i    = d_i i (1 - i)  dz_f = d_f f (1 - f)  dz_g = d_g (1 - gg^2)  dz_o = d_o o (1 - o)
+ * and  dW_hh = sum_t dz[t] h[t-1]^T,  dW_ih = sum_t dz[t] x[t]^T,  db_ih = db_hh = sum_t dz[t],
+ *      dW_fc = sum_t dys[t] h[t]^T,   db_fc = sum_t dys[t].
+ * A parameter whose gradient is exactly 0 in every epoch keeps m = v = 0 and comes out bitwise as it went in: with T = 1
+ * that is all of W_hh (h[-1] = 0) and the forget-gate rows of W_ih, b_ih, b_hh (c[-1] = 0).
+ * esn_lstm_train    group g starts from the initial set (group_offset + g) % n_isets of W_ih_0 .. b_fc_0 [n_isets][...]
+ *                   and writes W_ih .. b_fc [G][...]; loss [G][epochs] may be NULL; U [G][T_in][n_in], D [G][T][n_out],
+ *                   scalings [G][n] or NULL.  One workgroup per group and one launch for all epochs, float64.  The
+ *                   products over all T rows (the input projection, the read-out with the loss, the weight gradients)
+ *                   run on v_mfma_f64_16x16x4_f64; the 2 T dependent steps of an epoch's two sweeps run against a copy
+ *                   of W_hh that stays in registers and LDS from one Adam step to the next (H <= 104: all of it; above,
+ *                   columns 96 .. H - 1 are read from the L2 each step).  Every sum in an order that depends on the
+ *                   shape alone, no atomics, nothing shared between workgroups: a group is bitwise the same alone, in
+ *                   any batch and in any chunking, with or without `loss`.  ESN_F64 only: every other precision
+ *                   returns -2.  workspace: device memory of esn_lstm_workspace_bytes(..., n_groups, 0, T) bytes, per
+ *                   group 8 (3 (4H (n_in + 1) + 4H (H + 1) + n_out (H + 1)) + T n_in + 8 H T + (3 T + 2) H + T n_out)
+ *                   bytes (the parameters and Adam's moments, the scaled input, gates, dz, c, tanh c, h, dys), not
+ *                   initialised by the caller and of no meaning afterwards.
+ * esn_lstm_predict  forward only: a workgroup takes up to 16 frames of one group through all T steps, each step's
+ *                   [16 x 4H] = [h | x | 1] . [W_hh | W_ih | b_ih + b_hh]^T on v_mfma_f64_16x16x4_f64 with the frames as
+ *                   rows; W_hh's operand stays in registers and LDS across steps (H <= 104: all of it), hidden rows
+ *                   never reach memory.  A frame is bitwise the same alone and inside any batch.  ESN_F64 only (-2
+ *                   otherwise).  workspace: esn_lstm_workspace_bytes(..., 0, n_frames, T) bytes = min(n_frames, 1024)
+ *                   parts of 2048 ceil(H / 16) (ceil((n_in + 1) / 4) + r) bytes, r the k-steps of four columns of W_hh
+ *                   beyond the 16 in registers and the floor((163840 - 128 (4 ceil(H / 4) + 1)) / (2048 ceil(H / 16)))
+ *                   in LDS (r = 0 for H <= 104).
+ * esn_lstm_workspace_bytes   the larger of what n_groups trainings and what a prediction of n_frames frames need (either
+ *                   count may be 0); 0 for an unserved shape.
+ * Served: 1 <= n_in <= 64, 1 <= n_hidden <= 128, 1 <= n_out <= 8, 1 <= T_in <= T <= 4096, 0 <= transient < T,
+ * epochs >= 1, lr >= 0, 0 <= beta < 1, eps > 0.  Anything else returns -1 before any HIP call, the limit in
+ * esn_last_error(); a short workspace returns -1 too.  No float32 I/O variant, no _mem front end, one pilot per group,
+ * one layer.  These are additions: the ABI version is unchanged. */
+size_t esn_lstm_workspace_bytes(int n_in, int n_hidden, int n_out, int n_groups, int n_frames, int T);
+int esn_lstm_train(int precision, int n_in, int n_hidden, int n_out, int n_isets,
+                   const double* W_ih_0, const double* W_hh_0, const double* b_ih_0, const double* b_hh_0,
+                   const double* W_fc_0, const double* b_fc_0,
+                   const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                   const double* U, const double* D, int n_groups, int T_in, int T, int transient,
+                   uint64_t group_offset, int epochs, double lr, double beta1, double beta2, double eps,
+                   double* W_ih, double* W_hh, double* b_ih, double* b_hh, double* W_fc, double* b_fc, double* loss,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int esn_lstm_predict(int precision, int n_in, int n_hidden, int n_out,
+                     const double* W_ih, const double* W_hh, const double* b_ih, const double* b_hh,
+                     const double* W_fc, const double* b_fc,
+                     const double* in_scale, const double* in_shift, const double* t_scale, const double* t_shift,
+                     const double* U, int n_frames, int frames_per_group, int T_in, int T, int transient,
+                     double* Y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Channel record of the block-fading drivers (OFDM_MIMO_2-2_NBF_LDPC.py:369-385; the 4x8 ChannelRank driver is
  * named after it), float64.  H complex [G][N][n_r][n_t] in the layout of the function above, 16-byte aligned; p_i [G]
  * on the device as in the detectors; per subcarrier k the singular values s_1 >= ... of H_k by one-sided complex

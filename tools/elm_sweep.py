@@ -11,15 +11,17 @@ seed; the ELM and the baseline read the blocks the sweep detects):
                          "aligned" and "reference"
     cnn, cnn reference slice   with --cnn: points.cnn_point (channels 32 and 64, kernel 5, 50 Adam epochs per pilot,
                          float64), slices "aligned" and "reference"
+    lstm, lstm reference slice   with --lstm: points.lstm_point (--lstm-hidden units, 50 Adam epochs per pilot, float64),
+                         slices "aligned" and "reference" -- the reference's RNN curve
 
     python tools/elm_sweep.py [--preset 4x8|2x2] [--blocks 256] [--ebno 0:30:3] [--hidden H] [--window 8]
                               [--gain 0.05,0.02] [--ridge 1e-3] [--n-res 512] [--precision f64|f16] [--out file.json]
-                              [--fnn [--fnn-hidden 100]] [--cnn]
+                              [--fnn [--fnn-hidden 100]] [--cnn] [--lstm [--lstm-hidden 100]]
 
 Presets: 4x8 = LinkParams() (TDL-B, N = 128, 16-QAM), 512 hidden units against N_res 512; 2x2 = the block-fading 2x2
 configuration at N = 512 (exponential PDP, 16-QAM), 100 hidden units as the reference's ELM(4 * window), N_res 100.
-Writes profiles/elm_sweep_<preset>.json (with --fnn: profiles/fnn_sweep_<preset>.json; with --cnn: profiles/cnn_sweep_<preset>.json) unless --out is given.  Needs an
-MI355X."""
+Writes profiles/elm_sweep_<preset>.json (with --fnn: profiles/fnn_sweep_<preset>.json; with --cnn: profiles/cnn_sweep_<preset>.json;
+with --lstm: profiles/lstm_sweep_<preset>.json) unless --out is given.  Needs an MI355X."""
 import argparse
 import json
 import os
@@ -48,6 +50,8 @@ def main():
     ap.add_argument("--fnn", action="store_true", help="add the windowed FNN's curves")
     ap.add_argument("--fnn-hidden", type=int, default=100)
     ap.add_argument("--cnn", action="store_true", help="add the windowed CNN's curves")
+    ap.add_argument("--lstm", action="store_true", help="add the LSTM's curves (the reference's RNN)")
+    ap.add_argument("--lstm-hidden", type=int, default=100)
     a = ap.parse_args()
     from esn_ofdm_mimo_amd import _lib
     from esn_ofdm_mimo_amd.montecarlo import DetectorSweep, LinkParams, baseline_tracking_point, elm_point
@@ -105,12 +109,21 @@ def main():
                 ber.append(float(e.sum()) / float(n.sum()))
             add("cnn" + ("" if sl == "aligned" else " reference slice"), ber, channels=[32, 64], kernel=5, epochs=50,
                 lr=0.01, slice=sl)
+    if a.lstm:
+        from esn_ofdm_mimo_amd.montecarlo import lstm_point
+        for sl in ("aligned", "reference"):
+            ber = []
+            for si, eb in enumerate(points):
+                e, n = lstm_point(src, eb, si, a.blocks, n_hidden=a.lstm_hidden, slice=sl, seed=a.seed, frames_per_block=F)
+                ber.append(float(e.sum()) / float(n.sum()))
+            add("lstm" + ("" if sl == "aligned" else " reference slice"), ber, n_hidden=a.lstm_hidden, epochs=50, lr=0.01,
+                slice=sl)
     result = {"config": dict(preset=a.preset, n_t=params.n_t, n_r=params.n_r, n_sub=params.n_sub, bits_per_symbol=params.m,
                              channel=params.channel, blocks=a.blocks, frames_per_block=F, n_hidden=o["hidden"],
                              window=a.window, n_reservoir=o["n_res"], elm_precision=a.precision, seed=a.seed,
                              device=_lib.device_info()["arch"], commit=a.commit),
               "ebno_db": points, "curves": curves}
-    kind = "cnn" if a.cnn else "fnn" if a.fnn else "elm"
+    kind = "lstm" if a.lstm else "cnn" if a.cnn else "fnn" if a.fnn else "elm"
     out = a.out or os.path.join(ROOT, "profiles", f"{kind}_sweep_{a.preset}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
