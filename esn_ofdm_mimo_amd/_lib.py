@@ -169,6 +169,9 @@ SIGNATURES = {
                                    _vp, _vp, _dp, _vp]),
     "esn_detect_count_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
                                        _vp, _vp, _dp, _vp]),
+    # ensemble tail: Y [K, B, N, 2 n_t], K, B, F, N, n_t, m, p_i, weights, tx_bits, err, bits, member_err, X_hat, stream
+    "esn_detect_count_ens": (C.c_int, [_dp] + [C.c_int] * 6 + [_dp, _dp, _vp, _vp, _vp, _vp, _dp, _vp]),
+    "esn_detect_count_ens_f32": (C.c_int, [_vp] + [C.c_int] * 6 + [_dp, _dp, _vp, _vp, _vp, _vp, _dp, _vp]),
     # decide and re-modulate: Y, B, F, N, cp, delay, n_t, m, p_i, tx_bits, err, bits, X_hat, dec_bits, D_hat, stream
     "esn_detect_remod": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
                                    _vp, _vp, _dp, _vp, _dp, _vp]),

@@ -797,6 +797,44 @@ int esn_detect_count_f32(const float* Y, int n_frames, int frames_per_group, int
                          tx_bits, err_count, bit_count, X_hat, stream);
 }
 
+static int detect_ens_common(const char* who, bool io32, const void* Y, int n_members, int n_frames,
+                             int frames_per_group, int n_sub, int n_t, int bits_per_sym, const double* p_i,
+                             const double* weights, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                             long long* member_err, double* X_hat, void* stream) {
+    if (!Y || !p_i || !tx_bits || !err_count || !bit_count) return fail(-1, "%s: null pointer", who);
+    if (n_members < 1 || n_members > 16) return fail(-1, "%s: n_members=%d, 1 to 16 are served", who, n_members);
+    if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_t > 16) return fail(-1, "%s: n_t=%d, served up to 16", who, n_t);
+    int log2n;
+    if (int rc = check_n_sub(who, n_sub, &log2n)) return rc;
+    if (int rc = check_square_qam(who, bits_per_sym)) return rc;
+    if (((uintptr_t)Y & (io32 ? 7 : 15)) != 0) return fail(-1, "%s: Y must be %d-byte aligned", who, io32 ? 8 : 16);
+    EnsParams ep;
+    DetectParams& dp = ep.d;
+    if (io32) dp.Y32 = static_cast<const float*>(Y); else dp.Y = static_cast<const double*>(Y);
+    dp.n_frames = n_frames; dp.frames_per_group = frames_per_group; dp.n_sub = n_sub;
+    dp.log2n = log2n; dp.n_t = n_t; dp.m = bits_per_sym; dp.p_i = p_i; dp.tx_bits = tx_bits;
+    dp.err = err_count; dp.bits = bit_count; dp.X_hat = X_hat; dp.na_wg = 0;
+    ep.n_members = n_members; ep.weights = weights; ep.member_err = member_err;
+    return hip_fail(launch_detect_count_ens(ep, (hipStream_t)stream, io32), who);
+}
+
+int esn_detect_count_ens(const double* Y, int n_members, int n_frames, int frames_per_group, int n_sub, int n_t,
+                         int bits_per_sym, const double* p_i, const double* weights, const uint8_t* tx_bits,
+                         long long* err_count, long long* bit_count, long long* member_err, double* X_hat,
+                         void* stream) {
+    return detect_ens_common("esn_detect_count_ens", false, Y, n_members, n_frames, frames_per_group, n_sub, n_t,
+                             bits_per_sym, p_i, weights, tx_bits, err_count, bit_count, member_err, X_hat, stream);
+}
+
+int esn_detect_count_ens_f32(const float* Y, int n_members, int n_frames, int frames_per_group, int n_sub, int n_t,
+                             int bits_per_sym, const double* p_i, const double* weights, const uint8_t* tx_bits,
+                             long long* err_count, long long* bit_count, long long* member_err, double* X_hat,
+                             void* stream) {
+    return detect_ens_common("esn_detect_count_ens_f32", true, Y, n_members, n_frames, frames_per_group, n_sub, n_t,
+                             bits_per_sym, p_i, weights, tx_bits, err_count, bit_count, member_err, X_hat, stream);
+}
+
 int esn_detect_remod(const double* Y, int n_frames, int frames_per_group, int n_sub, int cp, int delay, int n_t,
                      int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
                      long long* bit_count, double* X_hat, uint8_t* dec_bits, double* D_hat, void* stream) {

@@ -91,6 +91,13 @@ struct DetectParams {
     long long* err; long long* bits; double* X_hat;
     int na_wg;             // antennas per workgroup (set by the launcher: all of them unless LDS is short)
 };
+// ensemble tail (esn_ensemble.hip): d.Y holds n_members slabs [K][B][N][2 n_t], d.err / d.bits / d.X_hat are the combination's
+struct EnsParams {
+    DetectParams d;
+    int n_members;
+    const double* weights;     // [groups][K], or nullptr: 1 / K each
+    long long* member_err;     // [groups][K], or nullptr: no member is transformed on its own
+};
 // decide and re-modulate (esn_remod.hip): the tail above, then the decisions back in the time domain
 struct RemodParams {
     DetectParams d;        // tx_bits may be nullptr (nothing is counted; err and bits are then not touched)

@@ -149,6 +149,8 @@ int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
 struct DetectGeometry { int na_wg; size_t lds; dim3 grid, block; };
 bool detect_geometry(const DetectParams& dp, DetectGeometry* g);
 int launch_detect_count(const DetectParams& dp, hipStream_t stream, bool io32 = false);
+// esn_ensemble.hip: the generic tail's geometry; with member_err a second row buffer per antenna
+int launch_detect_count_ens(const EnsParams& ep, hipStream_t stream, bool io32);
 // esn_remod.hip
 int launch_detect_remod(const RemodParams& rp, hipStream_t stream);
 // esn_chantrack.hip: the k ranges a sum is split into and the LDS of one workgroup, functions of the shape alone

@@ -28,6 +28,9 @@
                     three-layer Conv1d comparator, float64 throughout
     lstm_point      the same for the LSTM (lstm.py, esn_lstm_train / esn_lstm_predict), the reference's recurrent          points.py
                     comparator (its RNN curve), float64 throughout
+    ensemble_point  one Eb/No point of a reservoir ensemble (ensemble.py, esn_detect_count_ens): K small ESNs per          points.py
+                    block, each fitted on the block's pilot, outputs averaged before the FFT; member 0 is the ESN of a
+                    DetectorSweep of the same seed
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -41,4 +44,5 @@ from .points import baseline_tracking_point, block_fading_point, coded_ber_point
 from .points import fnn_point, fnn_weights  # noqa: F401
 from .points import cnn_point, cnn_weights  # noqa: F401
 from .points import lstm_point, lstm_weights  # noqa: F401
-from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters  # noqa: F401
+from .points import ensemble_point  # noqa: F401
+from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters, stream_seed  # noqa: F401

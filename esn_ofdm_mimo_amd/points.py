@@ -470,3 +470,127 @@ def lstm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, epochs=50, lr=0
 
     return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, "f64", slice,
                            train)
+
+
+MEMBER_SEED_STRIDE = 104729     # member k of an ensemble draws its reservoirs from reservoir_seed + MEMBER_SEED_STRIDE k
+MEMBER_LEG_SHIFT = 24           # ... and its state noise from stream_seed(snr_idx, leg + (k << MEMBER_LEG_SHIFT))
+
+
+def ensemble_point(src, ebno_db, snr_idx, n_blocks, *, n_members=4, n_reservoir=256, spectral_radius=0.9, sparsity=0.1,
+                   noise=0.001, precision="f32", fit_precision="f64", method="auto", ridge=None, ridge_grid=None,
+                   reservoirs="shared", pool=8, io="f64", first_block=0, frames_per_block=None, chunk_blocks=None,
+                   member_counts=False):
+    """One Eb/No point of a reservoir ensemble (ensemble.EnsembleBank) on the frames a DetectorSweep over the same
+    FrameSource seed detects: K independently drawn ESNs per coherence block, each with its own read-out fitted on the
+    block's one pilot (K harvests and solves per chunk), K predict launches over the chunk's data frames into the slabs
+    of one Y [K, B, N, 2 n_t], and one esn_detect_count_ens launch that averages the slabs before the FFT.
+
+    Member k's reservoirs follow the sweep's rule with reservoir_seed + 104729 k (host draw for "shared" / "per_block",
+    reservoirs.generate(first_set=global block) for "fresh") and its state-noise streams are
+    sweep.stream_seed(seed, snr_idx, leg + (k << 24)), leg 0 for training and 1 for detection: member 0 is the
+    reservoir and the streams of DetectorSweep(seed=src.seed), and ensemble_point(n_members=1) returns the counters of
+    that sweep's run() on the same blocks bit for bit.  Scalings, fit (method, ridge, ridge_grid, fit_precision and the
+    float32 states of the fp16 Cholesky path), predict and io are the sweep's.  One pilot per block; params.continuation
+    is refused.  Returns (errors, bits): int64 [n_blocks] on the device, and with member_counts also int64
+    [n_blocks, K], each member's own errors on the same frames.  chunk_blocks defaults to min(n_blocks, 4096 // K) --
+    a chunk holds K slabs of Y -- and under "fresh" to what keeps K reservoirs per block within the sweep's budget.
+    The counters do not depend on chunk_blocks or on how
+    first_block cuts the blocks; nothing is read back inside the chunk loop (a flagged fit has the whole point redone
+    with method="qr" after it)."""
+    import numpy as np
+    from . import reservoirs as _reservoirs
+    from .batched import ReservoirBank
+    from .ensemble import MAX_MEMBERS, EnsembleBank
+    from .readout import _lambdas
+    from .sweep import DetectorSweep, draw_reservoir, stream_seed
+    K = n_members
+    if not isinstance(K, int) or not 1 <= K <= MAX_MEMBERS:
+        raise ValueError(f"n_members must be an integer in 1..{MAX_MEMBERS}, not {n_members!r}")
+    if reservoirs not in ("shared", "per_block", "fresh"):
+        raise ValueError(f"reservoirs must be 'shared', 'per_block' or 'fresh', not {reservoirs!r}")
+    if method not in ("auto", "qr", "chol"):
+        raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
+    if io not in ("f64", "f32"):
+        raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
+    if io == "f32" and precision == "f64":
+        raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
+    if ridge is not None and ridge_grid is not None:
+        raise ValueError("give ridge or ridge_grid, not both")
+    if ridge is not None and not float(ridge) >= 0:
+        raise ValueError(f"ridge = {ridge} must be None or non-negative")
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    torch, p = src.torch, src.p
+    if p.continuation:
+        raise ValueError("ensemble_point does not go with params.continuation: every member predicts from a zero state")
+    n_in, n_out, n = 2 * p.n_r, 2 * p.n_t, int(n_reservoir)
+    F = int(frames_per_block or p.coherence_symbols)
+    first_block, n_blocks = int(first_block), int(n_blocks)
+    chunk = int(chunk_blocks or min(n_blocks, max(1, 4096 // K)))      # (Y holds K slabs per chunk)
+    res_args = (n_in, n_out, n, float(spectral_radius), float(sparsity))
+    res_seed = [src.seed * 7919 + 17 + MEMBER_SEED_STRIDE * k for k in range(K)]
+    kw = dict(teacher_forcing=True, noise=noise, device=src.device)
+    fresh = reservoirs == "fresh"
+    if fresh:
+        if chunk_blocks is None:        # K reservoirs per block live on the device for the length of a chunk
+            per_block = K * DetectorSweep.FRESH_BYTES_PER_BLOCK_N2 * n * n
+            chunk = min(chunk, max(1, DetectorSweep.FRESH_BUDGET_BYTES // per_block))
+        ens = None
+    else:
+        banks = []
+        for k in range(K):
+            ws = [draw_reservoir(n_in, n_out, n, res_args[3], res_args[4], res_seed[k] + i)
+                  for i in range(1 if reservoirs == "shared" else int(pool))]
+            banks.append(ReservoirBank(n_in, n_out, n, *(np.stack([w[j] for w in ws]) for j in range(3)), **kw))
+        ens = EnsembleBank(banks)
+    grid_t = None
+    if ridge_grid is not None:
+        grid_t = _lambdas(torch, src.device, np.array(ridge_grid, dtype=np.float64).reshape(-1), 1, grid=True)[0][0]
+    seeds = [[stream_seed(src.seed, snr_idx, leg + (k << MEMBER_LEG_SHIFT)) for k in range(K)] for leg in (0, 1)]
+    d, t = p.delay, p.t_frame
+    rows, cols = t + d - p.forget, n + n_in
+    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    merr = torch.zeros((n_blocks, K), dtype=torch.int64, device=src.device) if member_counts else None
+    flagged = torch.zeros((), dtype=torch.int64, device=src.device)
+    for b0 in range(first_block, first_block + n_blocks, chunk):
+        g = min(chunk, first_block + n_blocks - b0)
+        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, io="c64" if io == "f32" else "c128")
+        if fresh:       # block b in slot b % g, the set the kernels pick for it under group_offset = b0
+            sets = [_reservoirs.generate(*res_args, seed=res_seed[k], first_set=b0, n_sets=g, device=src.device,
+                                         check_status=method == "qr", n_squarings=24) for k in range(K)]
+            if ens is None:
+                ens = EnsembleBank([ReservoirBank(n_in, n_out, n, *s[:3], **kw) for s in sets])
+            else:
+                for m, s in zip(ens.members, sets):
+                    m.set_weights(*s[:3])
+            for s in sets:
+                flagged += s[4].ne(0).sum()
+        ens.set_scaling(torch.full((g, n_in), p.input_scaling(ebno_db), dtype=torch.float64, device=src.device), None,
+                        torch.full((g, n_out), p.teacher_scale, dtype=torch.float64, device=src.device), None)
+        U = torch.zeros((g, t + d, n_in), dtype=torch.float64, device=src.device)
+        D = torch.zeros((g, t + d, n_out), dtype=torch.float64, device=src.device)
+        U[:, :t] = _view_real(data["pilot_y"])
+        D[:, d:d + t] = _view_real(data["pilot_x"])
+        chol = method == "chol" or (method == "auto" and ens.members[0].chol_fits(rows, cols))
+        e_dtype = "f32" if (chol and fit_precision in ("f16", "bf16")) else "f64"
+        ens.fit(U, D, transient=p.forget, precision=fit_precision, noise_mode="counter", seed=seeds[0], method=method,
+                e_dtype=e_dtype, group_offset=b0, ridge=None if ridge is None else float(ridge), ridge_grid=grid_t)
+        flagged += ens.fit_status.ne(0).sum()
+        Y = ens.predict(_view_real(data["data_y"]), F, T=t + d, transient=p.forget, precision=precision,
+                        noise_mode="counter", seed=seeds[1], group_offset=b0, io=io)
+        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
+        lo = b0 - first_block
+        ens.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g],
+                         member_err=None if merr is None else merr[lo:lo + g])
+    if method != "qr" and int(flagged) != 0:
+        return ensemble_point(src, ebno_db, snr_idx, n_blocks, n_members=K, n_reservoir=n_reservoir,
+                              spectral_radius=spectral_radius, sparsity=sparsity, noise=noise, precision=precision,
+                              fit_precision=fit_precision, method="qr", ridge=ridge, ridge_grid=ridge_grid,
+                              reservoirs=reservoirs, pool=pool, io=io, first_block=first_block,
+                              frames_per_block=frames_per_block, chunk_blocks=chunk_blocks, member_counts=member_counts)
+    return (errors, nbits, merr) if member_counts else (errors, nbits)

@@ -45,6 +45,17 @@ def draw_reservoir(n_in, n_out, n_res, spectral_radius, sparsity, seed):
     return w, rs.rand(n_res, n_in) * 2 - 1, rs.rand(n_res, n_out) * 2 - 1
 
 
+def stream_seed(seed, snr_idx, leg):
+    """64-bit seed of the state-noise stream of one Eb/No point of the sweep with seed `seed`; leg 0 = training
+    (harvest), 1 = detection.  With the kernels' global frame index this makes the noise a function of (seed, snr, leg,
+    global frame, step, row) -- independent of chunking and world size.  Member k of an ensemble
+    (points.ensemble_point) takes leg + (k << 24)."""
+    h = (int(seed) * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) % (2 ** 64)
+    for k in (snr_idx, leg):
+        h = ((h ^ (h >> 31)) * 0xBF58476D1CE4E5B9 + int(k) + 1) % (2 ** 64)
+    return h
+
+
 class RadiusCache:
     """The spectral radii of one run() with reservoirs="fresh": radius float64 [n] and status int32 [n] on `device` for
     the n contiguous blocks from `base` on (a rank's own), and on the host which of them are filled, so that no
@@ -353,13 +364,8 @@ class DetectorSweep:
         return float(self.ridge(ebno_db)) if callable(self.ridge) else float(self.ridge)
 
     def stream_seed(self, snr_idx, leg):
-        """64-bit seed of the state-noise stream of one Eb/No point; leg 0 = training (harvest), 1 = detection.
-        With the kernels' global frame index this makes the noise a function of (seed, snr, leg, global frame,
-        step, row) -- independent of chunking and world size."""
-        h = (int(self.seed) * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) % (2 ** 64)
-        for k in (snr_idx, leg):
-            h = ((h ^ (h >> 31)) * 0xBF58476D1CE4E5B9 + int(k) + 1) % (2 ** 64)
-        return h
+        """stream_seed (the module's function) of this sweep's seed."""
+        return stream_seed(self.seed, snr_idx, leg)
 
     def train(self, pilot_y, pilot_x, seed=0, group_offset=0):
         """helper_mimo_esn_generic.py:58-86 for G blocks: delay d, nForget = d + CP, one harvest + solve.

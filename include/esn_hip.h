@@ -506,6 +506,33 @@ int esn_detect_count_f32(const float* Y, int n_frames, int frames_per_group,
                          long long* err_count, long long* bit_count,
                          double* X_hat, void* stream);
 
+/* Ensemble tail (extension: K independently drawn reservoirs per coherence block, each with its own read-out fitted on
+ * the block's pilot; their time-domain outputs are combined and the tail of esn_detect_count runs once).
+ *   Y        [K][B][N][2 N_t], member-major: slab k is what member k's esn_predict_batch wrote; 16-byte aligned
+ *            (8-byte for the float entry point, whose members are widened to double first)
+ *   weights  [groups][K] float64, or NULL: 1 / K each
+ *   acc = weights[g][0] y_0, then acc = acc + weights[g][k] y_k for k = 1 .. K-1 in this order, per element, every
+ *   product and every sum rounded on its own (no contraction): float64 NumPy reproduces acc bit for bit.  acc then
+ *   goes through the transform, scale, slicer and counters of esn_detect_count -- one FFT per frame and antenna whatever
+ *   K is -- so err_count, bit_count and X_hat are bitwise those of esn_detect_count on the combined Y, and with K = 1
+ *   and NULL weights (1.0 y = y) those of esn_detect_count / esn_detect_count_f32 on the slab.
+ *   member_err  optional [groups][K] int64, accumulated like err_count: member k's own error count, that of
+ *            esn_detect_count on slab k alone.  Each member is then transformed and sliced as well (K + 1 transforms
+ *            per frame and antenna, each slab still read once); when NULL no extra transform is issued.
+ * Served: K in [1, 16], N a power of two in [2, 2048], N_t <= 16, m even in [2, 10]; anything else, a null Y, p_i,
+ * tx_bits or counter, or a misaligned Y returns -1 before any HIP call, the reason in esn_last_error().  There is no
+ * fixed-shape instance and no esn_*_mem front end. */
+int esn_detect_count_ens(const double* Y, int n_members, int n_frames, int frames_per_group,
+                         int n_sub, int n_t, int bits_per_sym,
+                         const double* p_i, const double* weights, const uint8_t* tx_bits,
+                         long long* err_count, long long* bit_count, long long* member_err,
+                         double* X_hat, void* stream);
+int esn_detect_count_ens_f32(const float* Y, int n_members, int n_frames, int frames_per_group,
+                             int n_sub, int n_t, int bits_per_sym,
+                             const double* p_i, const double* weights, const uint8_t* tx_bits,
+                             long long* err_count, long long* bit_count, long long* member_err,
+                             double* X_hat, void* stream);
+
 /* Decide and re-modulate (extension: decision-directed tracking of the read-out).  The tail of esn_detect_count --
  * err_count, bit_count and X_hat are bitwise those of esn_detect_count on the same Y -- and then, in the same launch
  * (the spectrum never leaves the chip), the decisions back in the time domain as the teacher of a re-fit:
