@@ -109,6 +109,30 @@ static bool geometry_for(int precision, const esn_shape_t* s, Geometry* g, bool 
     return mfma_geometry(precision, s->n_res, s->n_in, s->n_out, harvest, g);
 }
 
+// the fields CnnParams and LstmParams have under the same names, for esn_{cnn,lstm}_{train,predict} below (templates have
+// C++ linkage, so they stand ahead of the extern "C" block): the sequence, the scalings, three weight and three bias
+// arrays in (W0, b0), and the workspace
+template <typename P>
+static void sequence_params(P& p, int T_in, int T, int transient, const double* const (&W0)[3],
+                            const double* const (&b0)[3], const double* in_scale, const double* in_shift,
+                            const double* t_scale, const double* t_shift, const double* U, void* workspace) {
+    memset(&p, 0, sizeof(p));
+    p.T_in = T_in; p.T = T; p.transient = transient;
+    for (int l = 0; l < 3; ++l) { p.W0[l] = W0[l]; p.b0[l] = b0[l]; }
+    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U;
+    p.workspace = reinterpret_cast<double*>(workspace);
+}
+
+// ... and those of a training beside them
+template <typename P>
+static void training_params(P& p, int n_isets, int n_groups, uint64_t group_offset, int epochs, double lr, double beta1,
+                            double beta2, double eps, const double* D, double* const (&W)[3], double* const (&b)[3],
+                            double* loss) {
+    p.n_isets = n_isets; p.n_groups = n_groups; p.group_offset = group_offset; p.epochs = epochs;
+    p.lr = lr; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps; p.D = D; p.loss = loss;
+    for (int l = 0; l < 3; ++l) { p.W[l] = W[l]; p.b[l] = b[l]; }
+}
+
 #ifdef ESN_STAMPS
 static unsigned long long* g_stamp_buf = nullptr;
 extern "C" void esn_debug_set_stamp_buffer(void* dev) { g_stamp_buf = (unsigned long long*)dev; }
@@ -1047,6 +1071,12 @@ int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bi
     return hip_fail(launch_channel_track(c, (hipStream_t)stream), who);
 }
 
+// n_out ahead of elm_check, where esn_elm_predict and the FNN pair call with it (elm_check reads n_out = 0 as "features")
+static int n_out_check(const char* who, int n_out) {
+    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
+    return 0;
+}
+
 // the checks esn_elm_features and esn_elm_predict share; n_out = 0: features
 static int elm_check(const char* who, int precision, int n_in, int n_hidden, int window, int bias_col, int n_wsets,
                      int n_out, int e_cols, int n_seq, int seq_per_group, int T_in, int T, int transient) {
@@ -1099,7 +1129,7 @@ int esn_elm_predict(int precision, int n_in, int n_hidden, int window, int bias_
                     int frames_per_group, int T_in, int T, int transient, uint64_t group_offset, double* Y, void* stream) {
     const char* who = "esn_elm_predict";
     if (!W_in || !b || !W_out || !U || !Y) return fail(-1, "%s: null pointer", who);
-    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
+    if (int rc = n_out_check(who, n_out)) return rc;
     const int rc = elm_check(who, precision, n_in, n_hidden, window, bias_col, n_wsets, n_out, e_cols, n_frames,
                              frames_per_group, T_in, T, transient);
     if (rc) return rc;
@@ -1111,6 +1141,51 @@ int esn_elm_predict(int precision, int n_in, int n_hidden, int window, int bias_
     p.transient = transient; p.group_offset = group_offset; p.W_in = W_in; p.b = b; p.W_out = W_out;
     p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
     return hip_fail(launch_elm_predict(precision, p, (hipStream_t)stream), who);
+}
+
+// ---- the Adam-trained comparators (FNN, CNN, LSTM): the checks their six entry points share
+
+// the optimiser's arguments; n_isets = 1 where another check has already answered for it
+static int adam_check(const char* who, int n_isets, int epochs, double lr, double beta1, double beta2, double eps) {
+    if (n_isets < 1) return fail(-1, "%s: n_isets=%d must be positive", who, n_isets);
+    if (epochs < 1) return fail(-1, "%s: epochs=%d must be positive", who, epochs);
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
+        return fail(-1, "%s: need lr >= 0, 0 <= beta1, beta2 < 1 and eps > 0", who);
+    return 0;
+}
+
+// the workspace against what `query` (the name of the entry point that says it) answers for the call
+static int workspace_check(const char* who, const char* query, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        return fail(-1, "%s: workspace of %zu bytes (8-byte aligned) needed, %s; got %zu", who, need, query,
+                    workspace ? workspace_bytes : (size_t)0);
+    return 0;
+}
+
+// what the train and predict entry points of the sequence models (CNN, LSTM) check alike.  shape: the call's sizes as
+// the message gives them; why: the answer of the model's *_shape_limit; n_seq: groups or frames
+static int sequence_check(const char* who, int precision, const char* shape, const char* why, int n_seq, int T_in, int T,
+                          int transient) {
+    if (precision != ESN_F64 && precision != ESN_F32 && precision != ESN_F16 && precision != ESN_BF16)
+        return fail(-1, "%s: unknown precision %d", who, precision);
+    if (why) return fail(-1, "%s: %s: %s", who, shape, why);
+    if (n_seq < 1) return fail(-1, "%s: invalid sizes (groups, frames)", who);
+    if (T_in < 1 || T_in > T) return fail(-1, "%s: need 1 <= T_in <= T (T_in=%d, T=%d)", who, T_in, T);
+    if (transient < 0 || transient >= T) return fail(-1, "%s: transient=%d must be in [0, T) with T=%d", who, transient, T);
+    if (precision != ESN_F64) return fail(-2, "%s: float64 (ESN_F64) only; precision %d is not built", who, precision);
+    return 0;
+}
+
+struct ShapeText { char text[160]; };
+static ShapeText cnn_shape_text(int n_in, int c1, int c2, int n_out, int kernel, int T) {
+    ShapeText s;
+    snprintf(s.text, sizeof(s.text), "n_in=%d c1=%d c2=%d n_out=%d kernel=%d T=%d", n_in, c1, c2, n_out, kernel, T);
+    return s;
+}
+static ShapeText lstm_shape_text(int n_in, int n_hidden, int n_out, int T) {
+    ShapeText s;
+    snprintf(s.text, sizeof(s.text), "n_in=%d n_hidden=%d n_out=%d T=%d", n_in, n_hidden, n_out, T);
+    return s;
 }
 
 size_t esn_fnn_workspace_bytes(int n_in, int n_hidden, int window, int n_out, int n_groups, int T) {
@@ -1127,10 +1202,10 @@ int esn_fnn_train(int precision, int n_in, int n_hidden, int window, int n_out, 
                   size_t workspace_bytes, void* stream) {
     const char* who = "esn_fnn_train";
     if (!W1_0 || !b1_0 || !W2_0 || !b2_0 || !U || !D || !W1 || !b1 || !W2 || !b2) return fail(-1, "%s: null pointer", who);
-    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
-    const int rc = elm_check(who, precision == ESN_F16 ? ESN_F64 : precision, n_in, n_hidden, window, 1, n_isets, n_out,
-                             n_hidden + 1, n_groups, 1, T_in, T, transient);
-    if (rc) return rc;
+    if (int rc = n_out_check(who, n_out)) return rc;
+    if (int rc = elm_check(who, precision == ESN_F16 ? ESN_F64 : precision, n_in, n_hidden, window, 1, n_isets, n_out,
+                           n_hidden + 1, n_groups, 1, T_in, T, transient))
+        return rc;
     if (precision != ESN_F64) return fail(-2, "%s: the training is float64 (ESN_F64); precision %d is not built", who, precision);
     const int K = window * n_in;
     if (n_hidden > 512 || n_out * n_hidden > 1024 || ((n_hidden + 3) / 4) * ((K + 7) / 8) > 512)
@@ -1141,13 +1216,10 @@ int esn_fnn_train(int precision, int n_in, int n_hidden, int window, int n_out, 
         return fail(-1, "%s: n_hidden=%d K=%d T=%d n_out=%d needs more than the served %d bytes of LDS "
                     "(8 (n_hidden (K | 1) + T n_in + n_out n_hidden + n_hidden + n_out + 32 (n_hidden | 1) + 257))", who,
                     n_hidden, K, T, n_out, 160 * 1024);
-    if (epochs < 1) return fail(-1, "%s: epochs=%d must be positive", who, epochs);
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
-        return fail(-1, "%s: need lr >= 0, 0 <= beta1, beta2 < 1 and eps > 0", who);
-    const size_t need = fnn_train_workspace_bytes(n_in, n_hidden, window, n_groups);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
-        return fail(-1, "%s: workspace of %zu bytes (8-byte aligned) needed, esn_fnn_workspace_bytes; got %zu", who, need,
-                    workspace ? workspace_bytes : (size_t)0);
+    if (int rc = adam_check(who, 1, epochs, lr, beta1, beta2, eps)) return rc;      // (n_isets: elm_check's n_wsets)
+    if (int rc = workspace_check(who, "esn_fnn_workspace_bytes", workspace, workspace_bytes,
+                                 fnn_train_workspace_bytes(n_in, n_hidden, window, n_groups)))
+        return rc;
     FnnTrainParams p;
     memset(&p, 0, sizeof(p));
     p.n_in = n_in; p.n_hidden = n_hidden; p.window = window; p.n_out = n_out; p.n_isets = n_isets; p.n_groups = n_groups;
@@ -1166,10 +1238,10 @@ int esn_fnn_predict(int precision, int n_in, int n_hidden, int window, int n_out
                     int T_in, int T, int transient, double* Y, void* stream) {
     const char* who = "esn_fnn_predict";
     if (!W1 || !b1 || !W2 || !b2 || !U || !Y) return fail(-1, "%s: null pointer", who);
-    if (n_out < 1 || n_out > 8) return fail(-1, "%s: n_out=%d must be in [1, 8]", who, n_out);
-    const int rc = elm_check(who, precision, n_in, n_hidden, window, 1, 1, n_out, n_hidden + 1, n_frames, frames_per_group,
-                             T_in, T, transient);
-    if (rc) return rc;
+    if (int rc = n_out_check(who, n_out)) return rc;
+    if (int rc = elm_check(who, precision, n_in, n_hidden, window, 1, 1, n_out, n_hidden + 1, n_frames, frames_per_group,
+                           T_in, T, transient))
+        return rc;
     if ((uintptr_t)Y & 15) return fail(-1, "%s: Y must be 16-byte aligned", who);
     ElmParams p;
     memset(&p, 0, sizeof(p));
@@ -1180,23 +1252,6 @@ int esn_fnn_predict(int precision, int n_in, int n_hidden, int window, int n_out
     p.group_offset = 0; p.W_in = W1; p.b = b1; p.W_out = W2; p.b_out = b2;
     p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
     return hip_fail(launch_fnn_predict(precision, p, (hipStream_t)stream), who);
-}
-
-// what esn_cnn_train and esn_cnn_predict check alike; n_seq: groups or frames
-static int cnn_check(const char* who, int precision, int n_in, int c1, int c2, int n_out, int kernel, int n_seq, int T_in,
-                     int T, int transient, const void* workspace, size_t workspace_bytes, size_t need) {
-    if (precision != ESN_F64 && precision != ESN_F32 && precision != ESN_F16 && precision != ESN_BF16)
-        return fail(-1, "%s: unknown precision %d", who, precision);
-    const char* why = cnn_shape_limit(n_in, c1, c2, n_out, kernel, T);
-    if (why) return fail(-1, "%s: n_in=%d c1=%d c2=%d n_out=%d kernel=%d T=%d: %s", who, n_in, c1, c2, n_out, kernel, T, why);
-    if (n_seq < 1) return fail(-1, "%s: invalid sizes (groups, frames)", who);
-    if (T_in < 1 || T_in > T) return fail(-1, "%s: need 1 <= T_in <= T (T_in=%d, T=%d)", who, T_in, T);
-    if (transient < 0 || transient >= T) return fail(-1, "%s: transient=%d must be in [0, T) with T=%d", who, transient, T);
-    if (precision != ESN_F64) return fail(-2, "%s: float64 (ESN_F64) only; precision %d is not built", who, precision);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
-        return fail(-1, "%s: workspace of %zu bytes (8-byte aligned) needed, esn_cnn_workspace_bytes; got %zu", who, need,
-                    workspace ? workspace_bytes : (size_t)0);
-    return 0;
 }
 
 size_t esn_cnn_workspace_bytes(int n_in, int c1, int c2, int n_out, int kernel, int n_groups, int n_frames, int T) {
@@ -1213,23 +1268,18 @@ int esn_cnn_train(int precision, int n_in, int c1, int c2, int n_out, int kernel
     const char* who = "esn_cnn_train";
     if (!W1_0 || !b1_0 || !W2_0 || !b2_0 || !W3_0 || !b3_0 || !U || !D || !W1 || !b1 || !W2 || !b2 || !W3 || !b3)
         return fail(-1, "%s: null pointer", who);
-    if (n_isets < 1) return fail(-1, "%s: n_isets=%d must be positive", who, n_isets);
-    if (epochs < 1) return fail(-1, "%s: epochs=%d must be positive", who, epochs);
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
-        return fail(-1, "%s: need lr >= 0, 0 <= beta1, beta2 < 1 and eps > 0", who);
-    const bool served = !cnn_shape_limit(n_in, c1, c2, n_out, kernel, T) && n_groups >= 1;
-    const int rc = cnn_check(who, precision, n_in, c1, c2, n_out, kernel, n_groups, T_in, T, transient, workspace,
-                             workspace_bytes, served ? cnn_workspace_bytes(n_in, c1, c2, n_out, kernel, n_groups, 0, T) : 0);
-    if (rc) return rc;
+    if (int rc = adam_check(who, n_isets, epochs, lr, beta1, beta2, eps)) return rc;
+    if (int rc = sequence_check(who, precision, cnn_shape_text(n_in, c1, c2, n_out, kernel, T).text,
+                                cnn_shape_limit(n_in, c1, c2, n_out, kernel, T), n_groups, T_in, T, transient))
+        return rc;
+    if (int rc = workspace_check(who, "esn_cnn_workspace_bytes", workspace, workspace_bytes,
+                                 cnn_workspace_bytes(n_in, c1, c2, n_out, kernel, n_groups, 0, T)))
+        return rc;
     CnnParams p;
-    memset(&p, 0, sizeof(p));
-    p.n_in = n_in; p.c1 = c1; p.c2 = c2; p.n_out = n_out; p.kernel = kernel; p.n_isets = n_isets; p.n_groups = n_groups;
-    p.T_in = T_in; p.T = T; p.transient = transient; p.epochs = epochs; p.group_offset = group_offset;
-    p.lr = lr; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
-    p.W0[0] = W1_0; p.W0[1] = W2_0; p.W0[2] = W3_0; p.b0[0] = b1_0; p.b0[1] = b2_0; p.b0[2] = b3_0;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.D = D;
-    p.W[0] = W1; p.W[1] = W2; p.W[2] = W3; p.b[0] = b1; p.b[1] = b2; p.b[2] = b3; p.loss = loss;
-    p.workspace = reinterpret_cast<double*>(workspace);
+    sequence_params(p, T_in, T, transient, {W1_0, W2_0, W3_0}, {b1_0, b2_0, b3_0}, in_scale, in_shift, t_scale, t_shift, U,
+                    workspace);
+    training_params(p, n_isets, n_groups, group_offset, epochs, lr, beta1, beta2, eps, D, {W1, W2, W3}, {b1, b2, b3}, loss);
+    p.n_in = n_in; p.c1 = c1; p.c2 = c2; p.n_out = n_out; p.kernel = kernel;
     return hip_fail(launch_cnn_train(p, (hipStream_t)stream), who);
 }
 
@@ -1241,35 +1291,17 @@ int esn_cnn_predict(int precision, int n_in, int c1, int c2, int n_out, int kern
     const char* who = "esn_cnn_predict";
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !U || !Y) return fail(-1, "%s: null pointer", who);
     if (frames_per_group < 1) return fail(-1, "%s: frames_per_group=%d must be positive", who, frames_per_group);
-    const bool served = !cnn_shape_limit(n_in, c1, c2, n_out, kernel, T) && n_frames >= 1;
-    const int rc = cnn_check(who, precision, n_in, c1, c2, n_out, kernel, n_frames, T_in, T, transient, workspace,
-                             workspace_bytes, served ? cnn_workspace_bytes(n_in, c1, c2, n_out, kernel, 0, n_frames, T) : 0);
-    if (rc) return rc;
+    if (int rc = sequence_check(who, precision, cnn_shape_text(n_in, c1, c2, n_out, kernel, T).text,
+                                cnn_shape_limit(n_in, c1, c2, n_out, kernel, T), n_frames, T_in, T, transient))
+        return rc;
+    if (int rc = workspace_check(who, "esn_cnn_workspace_bytes", workspace, workspace_bytes,
+                                 cnn_workspace_bytes(n_in, c1, c2, n_out, kernel, 0, n_frames, T)))
+        return rc;
     CnnParams p;
-    memset(&p, 0, sizeof(p));
-    p.n_in = n_in; p.c1 = c1; p.c2 = c2; p.n_out = n_out; p.kernel = kernel; p.T_in = T_in; p.T = T;
-    p.transient = transient; p.n_frames = n_frames; p.frames_per_group = frames_per_group;
-    p.W0[0] = W1; p.W0[1] = W2; p.W0[2] = W3; p.b0[0] = b1; p.b0[1] = b2; p.b0[2] = b3;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
-    p.workspace = reinterpret_cast<double*>(workspace);
+    sequence_params(p, T_in, T, transient, {W1, W2, W3}, {b1, b2, b3}, in_scale, in_shift, t_scale, t_shift, U, workspace);
+    p.n_in = n_in; p.c1 = c1; p.c2 = c2; p.n_out = n_out; p.kernel = kernel;
+    p.n_frames = n_frames; p.frames_per_group = frames_per_group; p.Y = Y;
     return hip_fail(launch_cnn_predict(p, (hipStream_t)stream), who);
-}
-
-// what esn_lstm_train and esn_lstm_predict check alike; n_seq: groups or frames
-static int lstm_check(const char* who, int precision, int n_in, int n_hidden, int n_out, int n_seq, int T_in, int T,
-                      int transient, const void* workspace, size_t workspace_bytes, size_t need) {
-    if (precision != ESN_F64 && precision != ESN_F32 && precision != ESN_F16 && precision != ESN_BF16)
-        return fail(-1, "%s: unknown precision %d", who, precision);
-    const char* why = lstm_shape_limit(n_in, n_hidden, n_out, T);
-    if (why) return fail(-1, "%s: n_in=%d n_hidden=%d n_out=%d T=%d: %s", who, n_in, n_hidden, n_out, T, why);
-    if (n_seq < 1) return fail(-1, "%s: invalid sizes (groups, frames)", who);
-    if (T_in < 1 || T_in > T) return fail(-1, "%s: need 1 <= T_in <= T (T_in=%d, T=%d)", who, T_in, T);
-    if (transient < 0 || transient >= T) return fail(-1, "%s: transient=%d must be in [0, T) with T=%d", who, transient, T);
-    if (precision != ESN_F64) return fail(-2, "%s: float64 (ESN_F64) only; precision %d is not built", who, precision);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
-        return fail(-1, "%s: workspace of %zu bytes (8-byte aligned) needed, esn_lstm_workspace_bytes; got %zu", who, need,
-                    workspace ? workspace_bytes : (size_t)0);
-    return 0;
 }
 
 size_t esn_lstm_workspace_bytes(int n_in, int n_hidden, int n_out, int n_groups, int n_frames, int T) {
@@ -1288,24 +1320,19 @@ int esn_lstm_train(int precision, int n_in, int n_hidden, int n_out, int n_isets
     if (!W_ih_0 || !W_hh_0 || !b_ih_0 || !b_hh_0 || !W_fc_0 || !b_fc_0 || !U || !D || !W_ih || !W_hh || !b_ih || !b_hh ||
         !W_fc || !b_fc)
         return fail(-1, "%s: null pointer", who);
-    if (n_isets < 1) return fail(-1, "%s: n_isets=%d must be positive", who, n_isets);
-    if (epochs < 1) return fail(-1, "%s: epochs=%d must be positive", who, epochs);
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
-        return fail(-1, "%s: need lr >= 0, 0 <= beta1, beta2 < 1 and eps > 0", who);
-    const int rc = lstm_check(who, precision, n_in, n_hidden, n_out, n_groups, T_in, T, transient, workspace,
-                              workspace_bytes,
-                              lstm_shape_limit(n_in, n_hidden, n_out, T) || n_groups < 1
-                                  ? 0 : lstm_workspace_bytes(n_in, n_hidden, n_out, n_groups, 0, T));
-    if (rc) return rc;
+    if (int rc = adam_check(who, n_isets, epochs, lr, beta1, beta2, eps)) return rc;
+    if (int rc = sequence_check(who, precision, lstm_shape_text(n_in, n_hidden, n_out, T).text,
+                                lstm_shape_limit(n_in, n_hidden, n_out, T), n_groups, T_in, T, transient))
+        return rc;
+    if (int rc = workspace_check(who, "esn_lstm_workspace_bytes", workspace, workspace_bytes,
+                                 lstm_workspace_bytes(n_in, n_hidden, n_out, n_groups, 0, T)))
+        return rc;
     LstmParams p;
-    memset(&p, 0, sizeof(p));
-    p.n_in = n_in; p.n_hidden = n_hidden; p.n_out = n_out; p.n_isets = n_isets; p.n_groups = n_groups;
-    p.T_in = T_in; p.T = T; p.transient = transient; p.epochs = epochs; p.group_offset = group_offset;
-    p.lr = lr; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
-    p.W0[0] = W_ih_0; p.W0[1] = W_hh_0; p.W0[2] = W_fc_0; p.b0[0] = b_ih_0; p.b0[1] = b_hh_0; p.b0[2] = b_fc_0;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.D = D;
-    p.W[0] = W_ih; p.W[1] = W_hh; p.W[2] = W_fc; p.b[0] = b_ih; p.b[1] = b_hh; p.b[2] = b_fc; p.loss = loss;
-    p.workspace = reinterpret_cast<double*>(workspace);
+    sequence_params(p, T_in, T, transient, {W_ih_0, W_hh_0, W_fc_0}, {b_ih_0, b_hh_0, b_fc_0}, in_scale, in_shift, t_scale,
+                    t_shift, U, workspace);
+    training_params(p, n_isets, n_groups, group_offset, epochs, lr, beta1, beta2, eps, D, {W_ih, W_hh, W_fc},
+                    {b_ih, b_hh, b_fc}, loss);
+    p.n_in = n_in; p.n_hidden = n_hidden; p.n_out = n_out;
     return hip_fail(launch_lstm_train(p, (hipStream_t)stream), who);
 }
 
@@ -1317,18 +1344,17 @@ int esn_lstm_predict(int precision, int n_in, int n_hidden, int n_out, const dou
     const char* who = "esn_lstm_predict";
     if (!W_ih || !W_hh || !b_ih || !b_hh || !W_fc || !b_fc || !U || !Y) return fail(-1, "%s: null pointer", who);
     if (frames_per_group < 1) return fail(-1, "%s: frames_per_group=%d must be positive", who, frames_per_group);
-    const int rc = lstm_check(who, precision, n_in, n_hidden, n_out, n_frames, T_in, T, transient, workspace,
-                              workspace_bytes,
-                              lstm_shape_limit(n_in, n_hidden, n_out, T) || n_frames < 1
-                                  ? 0 : lstm_workspace_bytes(n_in, n_hidden, n_out, 0, n_frames, T));
-    if (rc) return rc;
+    if (int rc = sequence_check(who, precision, lstm_shape_text(n_in, n_hidden, n_out, T).text,
+                                lstm_shape_limit(n_in, n_hidden, n_out, T), n_frames, T_in, T, transient))
+        return rc;
+    if (int rc = workspace_check(who, "esn_lstm_workspace_bytes", workspace, workspace_bytes,
+                                 lstm_workspace_bytes(n_in, n_hidden, n_out, 0, n_frames, T)))
+        return rc;
     LstmParams p;
-    memset(&p, 0, sizeof(p));
-    p.n_in = n_in; p.n_hidden = n_hidden; p.n_out = n_out; p.T_in = T_in; p.T = T;
-    p.transient = transient; p.n_frames = n_frames; p.frames_per_group = frames_per_group;
-    p.W0[0] = W_ih; p.W0[1] = W_hh; p.W0[2] = W_fc; p.b0[0] = b_ih; p.b0[1] = b_hh; p.b0[2] = b_fc;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.t_scale = t_scale; p.t_shift = t_shift; p.U = U; p.Y = Y;
-    p.workspace = reinterpret_cast<double*>(workspace);
+    sequence_params(p, T_in, T, transient, {W_ih, W_hh, W_fc}, {b_ih, b_hh, b_fc}, in_scale, in_shift, t_scale, t_shift, U,
+                    workspace);
+    p.n_in = n_in; p.n_hidden = n_hidden; p.n_out = n_out;
+    p.n_frames = n_frames; p.frames_per_group = frames_per_group; p.Y = Y;
     return hip_fail(launch_lstm_predict(p, (hipStream_t)stream), who);
 }
 

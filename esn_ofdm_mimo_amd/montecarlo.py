@@ -22,8 +22,10 @@
     elm_point       one Eb/No point of the windowed ELM (elm.py, esn_elm_features / esn_elm_predict), the          points.py
                     reference's pinv-trained comparator, on the frames a DetectorSweep of the same seed detects
     fnn_point       the same for the windowed FNN (fnn.py, esn_fnn_train / esn_fnn_predict), the reference's          points.py
-                    Adam-trained comparator: one training per block, all 50 epochs in one launch; argument checks and
-                    chunk loop are elm_point's (points._windowed_point), the two differ in how a chunk is trained
+                    Adam-trained comparator: one training per block, all 50 epochs in one launch; the chunk loop is
+                    elm_point's (points._windowed_point); what the three Adam-trained points share -- optimiser and
+                    shape checks, shared or per-block initial sets, the training of a chunk -- is points._trained_point
+                    over a trained.TrainedBank
     cnn_point       the same for the windowed CNN (cnn.py, esn_cnn_train / esn_cnn_predict), the reference's          points.py
                     three-layer Conv1d comparator, float64 throughout
     lstm_point      the same for the LSTM (lstm.py, esn_lstm_train / esn_lstm_predict), the reference's recurrent          points.py

@@ -194,7 +194,7 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
 
 
 def _check_windowed_point_args(slice, weights, precision, window, n_blocks, first_block, chunk_blocks, frames_per_block):
-    """What elm_point and fnn_point refuse alike, from the arguments alone."""
+    """What the comparator points refuse alike, from the arguments alone."""
     if slice not in ("aligned", "reference"):
         raise ValueError(f"slice must be 'aligned' or 'reference', not {slice!r}")
     if weights not in ("shared", "per_block"):
@@ -212,7 +212,7 @@ def _check_windowed_point_args(slice, weights, precision, window, n_blocks, firs
 
 
 def _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision, slice, train):
-    """The chunk loop of elm_point and fnn_point over blocks first_block .. first_block + n_blocks - 1: per chunk of g
+    """The chunk loop of the comparator points over blocks first_block .. first_block + n_blocks - 1: per chunk of g
     blocks from b0 on, blocks_fast, the pilots as U [g, T, 2 n_r] and D [g, T, 2 n_t] (T = t_frame + delay, the teacher
     delayed), train(U, D, scaling, b0, g) -- which returns a windowed.WindowedBank trained on them under
     set_scaling(*scaling), inputs and teacher scaled by 1 / sqrt(var_x) -- then one predict over the chunk's data
@@ -249,6 +249,38 @@ def _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_blo
     return errors, nbits
 
 
+def _stack_sets(sets):
+    """Per-block parameter sets, each a tuple of arrays -> one tuple of arrays [len(sets), ...]."""
+    import numpy as np
+    return tuple(np.stack(a) for a in zip(*sets))
+
+
+def _trained_point(src, ebno_db, snr_idx, n_blocks, shape_error, make_bank, draw, transient, *, epochs, lr, precision,
+                   slice, weights, first_block, frames_per_block, chunk_blocks):
+    """_windowed_point for an Adam-trained comparator (a trained.TrainedBank), after the checks fnn_point, cnn_point and
+    lstm_point share: shape_error(T) says why the training kernel does not serve the link's shape (or None),
+    make_bank(n_groups) builds the bank, draw(None) is the shared initial set and draw(block) the one of a global block
+    (stacked per array over a chunk's blocks); every chunk is trained from them over rows [transient, T) by `epochs` Adam
+    steps of size lr and predicted at `precision`."""
+    if not isinstance(epochs, int) or epochs < 1:
+        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
+    if not lr >= 0:
+        raise ValueError(f"lr = {lr} must be non-negative")
+    why = shape_error(src.p.t_frame + src.p.delay)
+    if why:
+        raise ValueError("the training kernel does not serve this shape: " + why)
+    shared = draw(None) if weights == "shared" else None
+    bank = make_bank(min(int(chunk_blocks or 4096), int(n_blocks)))
+
+    def train(U, D, scaling, b0, g):
+        init = shared if shared is not None else _stack_sets([draw(b0 + i) for i in range(g)])
+        bank.set_scaling(*scaling)
+        return bank.train(U, D, init, transient=transient, epochs=epochs, lr=lr)
+
+    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision, slice,
+                           train)
+
+
 def elm_weights(n_hidden, k, gain, seed, block=None):
     """W_in = gain U(-1, 1) [n_hidden, k], then b = U(-1, 1) [n_hidden], from RandomState(seed) -- or, for the set of
     one global block, RandomState([seed, block])."""
@@ -278,7 +310,6 @@ def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0
         raise ValueError(f"gain = {gain} must be positive")
     if ridge is not None and not float(ridge) >= 0:
         raise ValueError(f"ridge = {ridge} must be None or non-negative")
-    import numpy as np
     from .elm import ElmBank
     p = src.p
     n_in, n_out = 2 * p.n_r, 2 * p.n_t
@@ -292,8 +323,7 @@ def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0
     def train(U, D, scaling, b0, g):
         nonlocal bank
         if shared is None:
-            sets = [elm_weights(n_hidden, k, gain, seed, b0 + i) for i in range(g)]
-            W_in, b = np.stack([s[0] for s in sets]), np.stack([s[1] for s in sets])
+            W_in, b = _stack_sets([elm_weights(n_hidden, k, gain, seed, b0 + i) for i in range(g)])
         else:
             W_in, b = shared
         if bank is None:
@@ -337,33 +367,15 @@ def fnn_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, window=8, epochs
     _check_windowed_point_args(slice, weights, precision, window, n_blocks, first_block, chunk_blocks, frames_per_block)
     if not isinstance(n_hidden, int) or n_hidden < 1:
         raise ValueError(f"n_hidden must be a positive integer, not {n_hidden!r}")
-    if not isinstance(epochs, int) or epochs < 1:
-        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
-    if not lr >= 0:
-        raise ValueError(f"lr = {lr} must be non-negative")
-    import numpy as np
     from .fnn import FnnBank, train_shape_error
-    p = src.p
-    n_in, n_out = 2 * p.n_r, 2 * p.n_t
-    why = train_shape_error(n_in, n_hidden, window, n_out, p.t_frame + p.delay)
-    if why:
-        raise ValueError("the FNN training kernel does not serve this shape: " + why)
-    k, transient = window * n_in, max(p.forget, window - 1)
-    shared = fnn_weights(n_hidden, k, n_out, seed) if weights == "shared" else None
-    bank = FnnBank(n_in, n_out, n_hidden, window, n_groups=min(int(chunk_blocks or 4096), int(n_blocks)),
-                   device=src.device)
-
-    def train(U, D, scaling, b0, g):
-        if shared is None:
-            sets = [fnn_weights(n_hidden, k, n_out, seed, b0 + i) for i in range(g)]
-            init = tuple(np.stack([s[j] for s in sets]) for j in range(4))
-        else:
-            init = shared
-        bank.set_scaling(*scaling)
-        return bank.train(U, D, init, transient=transient, epochs=epochs, lr=lr)
-
-    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision,
-                           slice, train)
+    n_in, n_out = 2 * src.p.n_r, 2 * src.p.n_t
+    return _trained_point(src, ebno_db, snr_idx, n_blocks,
+                          lambda T: train_shape_error(n_in, n_hidden, window, n_out, T),
+                          lambda g: FnnBank(n_in, n_out, n_hidden, window, n_groups=g, device=src.device),
+                          lambda block: fnn_weights(n_hidden, window * n_in, n_out, seed, block),
+                          max(src.p.forget, window - 1), epochs=epochs, lr=lr, precision=precision, slice=slice,
+                          weights=weights, first_block=first_block, frames_per_block=frames_per_block,
+                          chunk_blocks=chunk_blocks)
 
 
 def cnn_weights(channels, kernel, n_in, n_out, seed, block=None):
@@ -395,32 +407,14 @@ def cnn_point(src, ebno_db, snr_idx, n_blocks, *, channels=(32, 64), kernel=5, e
         raise ValueError(f"channels must be two positive integers, not {channels!r}")
     if not isinstance(kernel, int):
         raise ValueError(f"kernel must be an integer, not {kernel!r}")
-    if not isinstance(epochs, int) or epochs < 1:
-        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
-    if not lr >= 0:
-        raise ValueError(f"lr = {lr} must be non-negative")
-    import numpy as np
     from .cnn import CnnBank, train_shape_error
-    p = src.p
-    n_in, n_out = 2 * p.n_r, 2 * p.n_t
-    why = train_shape_error(n_in, channels[0], channels[1], n_out, kernel, p.t_frame + p.delay)
-    if why:
-        raise ValueError("the CNN kernels do not serve this shape: " + why)
-    shared = cnn_weights(channels, kernel, n_in, n_out, seed) if weights == "shared" else None
-    bank = CnnBank(n_in, n_out, channels, kernel, n_groups=min(int(chunk_blocks or 4096), int(n_blocks)),
-                   device=src.device)
-
-    def train(U, D, scaling, b0, g):
-        if shared is None:
-            sets = [cnn_weights(channels, kernel, n_in, n_out, seed, b0 + i) for i in range(g)]
-            init = tuple(np.stack([s[j] for s in sets]) for j in range(6))
-        else:
-            init = shared
-        bank.set_scaling(*scaling)
-        return bank.train(U, D, init, transient=p.forget, epochs=epochs, lr=lr)
-
-    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, "f64", slice,
-                           train)
+    n_in, n_out = 2 * src.p.n_r, 2 * src.p.n_t
+    return _trained_point(src, ebno_db, snr_idx, n_blocks,
+                          lambda T: train_shape_error(n_in, channels[0], channels[1], n_out, kernel, T),
+                          lambda g: CnnBank(n_in, n_out, channels, kernel, n_groups=g, device=src.device),
+                          lambda block: cnn_weights(channels, kernel, n_in, n_out, seed, block),
+                          src.p.forget, epochs=epochs, lr=lr, precision="f64", slice=slice, weights=weights,
+                          first_block=first_block, frames_per_block=frames_per_block, chunk_blocks=chunk_blocks)
 
 
 def lstm_weights(n_hidden, n_in, n_out, seed, block=None):
@@ -445,31 +439,13 @@ def lstm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=100, epochs=50, lr=0
     _check_windowed_point_args(slice, weights, "f64", 1, n_blocks, first_block, chunk_blocks, frames_per_block)
     if not isinstance(n_hidden, int) or n_hidden < 1:
         raise ValueError(f"n_hidden must be a positive integer, not {n_hidden!r}")
-    if not isinstance(epochs, int) or epochs < 1:
-        raise ValueError(f"epochs must be a positive integer, not {epochs!r}")
-    if not lr >= 0:
-        raise ValueError(f"lr = {lr} must be non-negative")
-    import numpy as np
     from .lstm import LstmBank, train_shape_error
-    p = src.p
-    n_in, n_out = 2 * p.n_r, 2 * p.n_t
-    why = train_shape_error(n_in, n_hidden, n_out, p.t_frame + p.delay)
-    if why:
-        raise ValueError("the LSTM kernels do not serve this shape: " + why)
-    shared = lstm_weights(n_hidden, n_in, n_out, seed) if weights == "shared" else None
-    bank = LstmBank(n_in, n_out, n_hidden, n_groups=min(int(chunk_blocks or 4096), int(n_blocks)), device=src.device)
-
-    def train(U, D, scaling, b0, g):
-        if shared is None:
-            sets = [lstm_weights(n_hidden, n_in, n_out, seed, b0 + i) for i in range(g)]
-            init = tuple(np.stack([s[j] for s in sets]) for j in range(6))
-        else:
-            init = shared
-        bank.set_scaling(*scaling)
-        return bank.train(U, D, init, transient=p.forget, epochs=epochs, lr=lr)
-
-    return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, "f64", slice,
-                           train)
+    n_in, n_out = 2 * src.p.n_r, 2 * src.p.n_t
+    return _trained_point(src, ebno_db, snr_idx, n_blocks, lambda T: train_shape_error(n_in, n_hidden, n_out, T),
+                          lambda g: LstmBank(n_in, n_out, n_hidden, n_groups=g, device=src.device),
+                          lambda block: lstm_weights(n_hidden, n_in, n_out, seed, block),
+                          src.p.forget, epochs=epochs, lr=lr, precision="f64", slice=slice, weights=weights,
+                          first_block=first_block, frames_per_block=frames_per_block, chunk_blocks=chunk_blocks)
 
 
 MEMBER_SEED_STRIDE = 104729     # member k of an ensemble draws its reservoirs from reservoir_seed + MEMBER_SEED_STRIDE k

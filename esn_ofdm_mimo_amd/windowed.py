@@ -1,10 +1,11 @@
-"""What the reference's two windowed comparators (elm.py, fnn.py) share: a model over the last `window` received rows,
-trained per pilot, with the ESN's scalings and detector tail.
+"""What the reference's learned comparators (elm.py, and through trained.py fnn.py, cnn.py, lstm.py) share: a model over
+the last `window` received rows, trained per pilot, with the ESN's scalings and detector tail.
 
-    WindowedBank        the device bank both build on: sizes, scalings, the checks of predict, detect_count
+    WindowedBank        the device bank all build on: sizes, scalings, the checks of predict, detect_count
     mimo_io             the reference's ESN_input / ESN_output of one pilot
     window_rows         its inputs_window
-    train_mimo_windowed its trainMIMOModel(...) around a constructed model, for any antenna count"""
+    train_mimo_windowed its trainMIMOModel(...) around a constructed model on windowed rows, for any antenna count
+    train_mimo_sequence the same around a model that reads the whole sequence (CNN, LSTM)"""
 from __future__ import annotations
 
 import numpy as np
@@ -78,3 +79,19 @@ def train_mimo_windowed(model, y_CP, x_CP, N, N_t, CyclicPrefixLen, IsiDuration,
     x = np.asarray(x_CP)[IsiDuration - 1:, :]
     NMSE = sum(np.linalg.norm(x_hat[:, i] - x[:, i]) ** 2 / np.linalg.norm(x[:, i]) ** 2 for i in range(N_t))
     return [ESN_input, ESN_output, model, Delay, fixed_delay, fixed_delay, fixed_delay, nForgetPoints, NMSE]
+
+
+def train_mimo_sequence(model, y_CP, x_CP, N, N_t, CyclicPrefixLen, IsiDuration, fixed_delay):
+    """trainMIMOModel(...) of the reference (:72-113, :151-159) around `model`, which has the reference's fit / predict
+    on whole sequences of 2 n_r inputs and 2 N_t outputs: returns its 9-list as train_mimo_windowed does.  Training uses
+    every row, unscaled, as the reference does; nForgetPoints = delay + CP, with no window term (:91); NMSE is computed
+    on the reference's rows [0, N) of the output (its slice, kept)."""
+    Delay = [fixed_delay] * (2 * N_t)
+    ESN_input, ESN_output = mimo_io(y_CP, x_CP, N, N_t, CyclicPrefixLen, fixed_delay)
+    model.fit(ESN_input, ESN_output)
+    x_hat_temp = model.predict(ESN_input)
+    x_hat = x_hat_temp[0:N, 0::2] + 1j * x_hat_temp[0:N, 1::2]
+    x = np.asarray(x_CP)[IsiDuration - 1:, :]
+    NMSE = sum(np.linalg.norm(x_hat[:, i] - x[:, i]) ** 2 / np.linalg.norm(x[:, i]) ** 2 for i in range(N_t))
+    return [ESN_input, ESN_output, model, Delay, fixed_delay, fixed_delay, fixed_delay, fixed_delay + CyclicPrefixLen,
+            NMSE]

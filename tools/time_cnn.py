@@ -30,6 +30,7 @@ import torch  # noqa: E402
 
 from esn_ofdm_mimo_amd import _lib  # noqa: E402
 from esn_ofdm_mimo_amd.cnn import NAMES, CnnBank  # noqa: E402
+from esn_ofdm_mimo_amd import fnn as fnn_mod  # noqa: E402
 from esn_ofdm_mimo_amd.fnn import FnnBank  # noqa: E402
 from esn_ofdm_mimo_amd.montecarlo import FrameSource, LinkParams, _view_real  # noqa: E402
 from esn_ofdm_mimo_amd.points import cnn_weights, fnn_weights  # noqa: E402
@@ -88,7 +89,7 @@ def main():
     big_c = scaled(CnnBank(n_in, n_out, CHANNELS, KERNEL, n_groups=G), G)
     big_c.set_weights(*[getattr(cnn, n)[idx] for n in NAMES])
     big_f = scaled(FnnBank(n_in, n_out, HIDDEN, WINDOW, n_groups=G), G)
-    big_f.set_weights(*[getattr(fnn, n)[idx] for n in ("W1", "b1", "W2", "b2")])
+    big_f.set_weights(*[getattr(fnn, n)[idx] for n in fnn_mod.NAMES])
     Yc = torch.empty((B, prm.n_sub, n_out), dtype=torch.float64, device=dev)
     Yf = torch.empty_like(Yc)
     src_p = torch.empty(U.numel() * 8 // 2, dtype=torch.uint8, device=dev)

@@ -37,6 +37,7 @@ import torch  # noqa: E402
 
 from esn_ofdm_mimo_amd import _lib  # noqa: E402
 from esn_ofdm_mimo_amd import cnn as cnn_mod  # noqa: E402
+from esn_ofdm_mimo_amd import fnn as fnn_mod  # noqa: E402
 from esn_ofdm_mimo_amd import lstm as lstm_mod  # noqa: E402
 from esn_ofdm_mimo_amd.cnn import CnnBank  # noqa: E402
 from esn_ofdm_mimo_amd.fnn import FnnBank  # noqa: E402
@@ -129,7 +130,7 @@ def main():
     big_c = scaled(CnnBank(n_in, n_out, CHANNELS, KERNEL, n_groups=G), G)
     big_c.set_weights(*[getattr(cnn, n)[idx] for n in cnn_mod.NAMES])
     big_f = scaled(FnnBank(n_in, n_out, HIDDEN, WINDOW, n_groups=G), G)
-    big_f.set_weights(*[getattr(fnn, n)[idx] for n in ("W1", "b1", "W2", "b2")])
+    big_f.set_weights(*[getattr(fnn, n)[idx] for n in fnn_mod.NAMES])
     Y = [torch.empty((B, prm.n_sub, n_out), dtype=torch.float64, device=dev) for _ in range(3)]
     src_p = torch.empty(U.numel() * 8 // 2, dtype=torch.uint8, device=dev)
     dst_p = torch.empty_like(src_p)
