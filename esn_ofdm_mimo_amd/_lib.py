@@ -114,6 +114,11 @@ SIGNATURES = {
                                         C.c_double, _dp, _dp, _vp, _vp, _vp, _dp, _vp]),
     "esn_zf_detect_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                       _dp, _dp, _vp, _vp, _vp, _dp, _vp]),
+    # equalised time-domain rows: n_frames, frames_per_group, N, cp, pad, n_t, n_r, p_i, no, H, y_cp, U_eq, X_hat, stream
+    "esn_mmse_equalize_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
+                                         C.c_double, _dp, _dp, _dp, _dp, _vp]),
+    "esn_mmse_equalize_rows_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
+                                             C.c_double, _dp, _dp, _vp, _dp, _vp]),
     "esn_taps_to_freq": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp]),
     "esn_channel_metrics": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp, _dp, _vp, _dp, _vp]),
     # decision-directed channel estimate: y_cp, X_hat | bits, n_est, window, est_per_group, N, cp, n_t, n_r, isi, m, p_i,

@@ -1039,6 +1039,43 @@ int esn_zf_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, i
                          0.0, H, y_cp, tx_bits, err_count, bit_count, X_hat, stream);
 }
 
+static int equalize_rows(const char* who, bool io32, int n_frames, int frames_per_group, int n_sub, int cp, int pad,
+                         int n_t, int n_r, const double* p_i, double no, const double* H, const double* y_cp,
+                         void* U_eq, double* X_hat, void* stream) {
+    if (!p_i || !H || !y_cp || !U_eq) return fail(-1, "%s: null pointer", who);
+    int l2;
+    if (int rc = check_n_sub(who, n_sub, &l2)) return rc;
+    if (n_frames <= 0 || frames_per_group <= 0 || n_t <= 0 || n_r <= 0) return fail(-1, "%s: invalid sizes", who);
+    if (n_t > 4) return fail(-1, "%s: n_t=%d, served up to 4", who, n_t);
+    if (cp < 0 || cp >= n_sub) return fail(-1, "%s: cp=%d must be in [0, N) with N=%d", who, cp, n_sub);
+    if (pad < 0 || pad > (1 << 20)) return fail(-1, "%s: pad=%d must be in [0, %d]", who, pad, 1 << 20);
+    if (equalize_rows_lds_bytes(n_sub, n_t, n_r) > MMSE_LDS_MAX)
+        return fail(-1, "%s: n_r=%d needs 16 (max(n_r, n_t) N + N/2) = %zu bytes of LDS; N=%d serves n_r up to %d (%zu bytes)",
+                    who, n_r, equalize_rows_lds_bytes(n_sub, n_t, n_r), n_sub,
+                    (int)((MMSE_LDS_MAX - (size_t)n_sub * 8) / ((size_t)n_sub * 16)), MMSE_LDS_MAX);
+    if (((uintptr_t)U_eq & (io32 ? 7 : 15)) != 0)
+        return fail(-1, "%s: U_eq must be %d-byte aligned", who, io32 ? 8 : 16);
+    EqRowsParams ep;
+    ep.n_frames = n_frames; ep.frames_per_group = frames_per_group; ep.n_sub = n_sub; ep.log2n = l2; ep.cp = cp;
+    ep.pad = pad; ep.n_t = n_t; ep.n_r = n_r; ep.p_i = p_i; ep.no = no; ep.H = H; ep.y_cp = y_cp; ep.U_eq = U_eq;
+    ep.X_hat = X_hat;
+    return hip_fail(launch_equalize_rows(ep, (hipStream_t)stream, io32), who);
+}
+
+int esn_mmse_equalize_rows(int n_frames, int frames_per_group, int n_sub, int cp, int pad, int n_t, int n_r,
+                           const double* p_i, double no, const double* H, const double* y_cp, double* U_eq,
+                           double* X_hat, void* stream) {
+    return equalize_rows("esn_mmse_equalize_rows", false, n_frames, frames_per_group, n_sub, cp, pad, n_t, n_r, p_i, no,
+                         H, y_cp, U_eq, X_hat, stream);
+}
+
+int esn_mmse_equalize_rows_f32(int n_frames, int frames_per_group, int n_sub, int cp, int pad, int n_t, int n_r,
+                               const double* p_i, double no, const double* H, const double* y_cp, float* U_eq,
+                               double* X_hat, void* stream) {
+    return equalize_rows("esn_mmse_equalize_rows_f32", true, n_frames, frames_per_group, n_sub, cp, pad, n_t, n_r, p_i,
+                         no, H, y_cp, U_eq, X_hat, stream);
+}
+
 int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bits, int n_est, int window,
                       int est_per_group, int n_sub, int cp, int n_t, int n_r, int isi, int bits_per_sym,
                       const double* p_i, const double* reg, double* taps, double* H, int* status, void* stream) {

@@ -9,17 +9,10 @@
 //       binary LSB-first bits, error count vs TxBits (:95-103, :451-456)
 #include "esn_common.h"
 #include "esn_launch.h"
+#include "esn_mmse_solve.h"
 #include "esn_ofdm_math.h"
 
 namespace esn {
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cdiv(double2 a, double2 b) {
-    const double d = b.x * b.x + b.y * b.y;
-    return make_double2((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
-}
 
 __global__ __launch_bounds__(256) void channel_estimate_kernel(ChanEstParams cp) {
     extern __shared__ __attribute__((aligned(16))) char csm[];
@@ -95,8 +88,6 @@ __global__ __launch_bounds__(256) void channel_estimate_kernel(ChanEstParams cp)
     (void)n_p;
 }
 
-constexpr int MMSE_NT = 4;     // transmit antennas handled in registers
-
 __global__ __launch_bounds__(256) void mmse_detect_kernel(MmseParams mp) {
     extern __shared__ __attribute__((aligned(16))) char msm[];
     __shared__ int red[4];
@@ -105,78 +96,14 @@ __global__ __launch_bounds__(256) void mmse_detect_kernel(MmseParams mp) {
     double2* tw = Y + (size_t)n_r * N;                     // [N/2] exp(-2 pi i k / N)
     const int tid = threadIdx.x, nth = blockDim.x;
     const int frame = blockIdx.x, blk = frame / mp.frames_per_group;
-    const double* y = mp.y_cp + ((size_t)frame * T + mp.cp) * n_r * 2;
-    ofdm_twiddles(tw, N >> 1, N, -1.0);
-    for (int e = tid; e < N * n_r; e += nth) {
-        const int i = e / n_r, rx = e % n_r;
-        const int rv = (int)(__brev((unsigned)i) >> (32 - mp.log2n));
-        Y[(size_t)rx * N + rv] = make_double2(y[(size_t)e * 2] / N, y[(size_t)e * 2 + 1] / N);
-    }
-    __syncthreads();
-    ofdm_fft_lds(Y, n_r, N, tw, N, mp.log2n);
+    mmse_spectrum(Y, tw, mp.y_cp + ((size_t)frame * T + mp.cp) * n_r * 2, N, mp.log2n, n_r);
     const double p_i = mp.p_i[blk], lam = mp.zf ? 1e-12 : mp.no / p_i, isp = 1.0 / sqrt(p_i);
     const int side = 1 << (m / 2);
     const double norm = det_norm(side);
     int errs = 0;
     for (int k = tid; k < N; k += nth) {
-        // G = H^H H + lam I (Hermitian, n_t x n_t), r = H^H Y
-        double2 G[MMSE_NT][MMSE_NT], rhs[MMSE_NT];
-#pragma unroll
-        for (int a = 0; a < MMSE_NT; ++a) {
-            rhs[a] = make_double2(0.0, 0.0);
-#pragma unroll
-            for (int b = 0; b < MMSE_NT; ++b) G[a][b] = make_double2(a == b ? lam : 0.0, 0.0);
-        }
-        const double* hk = mp.H + (((size_t)blk * N + k) * n_r) * n_t * 2;
-        for (int rx = 0; rx < n_r; ++rx) {
-            double2 h[MMSE_NT];
-#pragma unroll
-            for (int a = 0; a < MMSE_NT; ++a)
-                h[a] = (a < n_t) ? make_double2(hk[((size_t)rx * n_t + a) * 2], hk[((size_t)rx * n_t + a) * 2 + 1])
-                                 : make_double2(0.0, 0.0);
-            const double2 yv = Y[(size_t)rx * N + k];
-#pragma unroll
-            for (int a = 0; a < MMSE_NT; ++a) {
-                const double2 hc = make_double2(h[a].x, -h[a].y);
-                const double2 t = cmul(hc, yv);
-                rhs[a].x += t.x; rhs[a].y += t.y;
-#pragma unroll
-                for (int b = 0; b < MMSE_NT; ++b) {
-                    const double2 u = cmul(hc, h[b]);
-                    G[a][b].x += u.x; G[a][b].y += u.y;
-                }
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < MMSE_NT; ++a)
-            if (a >= n_t) G[a][a] = make_double2(1.0, 0.0);       // padding antennas: identity rows
-        // Gaussian elimination (G is Hermitian positive definite: no pivoting needed)
-#pragma unroll
-        for (int c = 0; c < MMSE_NT; ++c) {
-            const double2 piv = G[c][c];
-#pragma unroll
-            for (int rr = c + 1; rr < MMSE_NT; ++rr) {
-                const double2 f = cdiv(G[rr][c], piv);
-#pragma unroll
-                for (int cc = c; cc < MMSE_NT; ++cc) {
-                    const double2 t = cmul(f, G[c][cc]);
-                    G[rr][cc].x -= t.x; G[rr][cc].y -= t.y;
-                }
-                const double2 t = cmul(f, rhs[c]);
-                rhs[rr].x -= t.x; rhs[rr].y -= t.y;
-            }
-        }
         double2 x[MMSE_NT];
-#pragma unroll
-        for (int c = MMSE_NT - 1; c >= 0; --c) {
-            double2 acc = rhs[c];
-#pragma unroll
-            for (int cc = c + 1; cc < MMSE_NT; ++cc) {
-                const double2 t = cmul(G[c][cc], x[cc]);
-                acc.x -= t.x; acc.y -= t.y;
-            }
-            x[c] = cdiv(acc, G[c][c]);
-        }
+        mmse_solve_point(mp.H + (((size_t)blk * N + k) * n_r) * n_t * 2, Y, N, k, n_t, n_r, lam, x);
 #pragma unroll
         for (int tx = 0; tx < MMSE_NT; ++tx) {
             if (tx >= n_t) continue;
@@ -221,7 +148,7 @@ int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream) {
 int launch_mmse_detect(const MmseParams& mp, hipStream_t stream) {
     if (mp.n_t > MMSE_NT) return -1;
     const size_t lds = sizeof(double2) * ((size_t)mp.n_r * mp.n_sub + mp.n_sub / 2);
-    if (lds > 150 * 1024) return -1;
+    if (lds > MMSE_LDS_MAX) return -1;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmse_detect_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;

@@ -178,6 +178,15 @@ struct MmseParams {
     const uint8_t* tx_bits;      // [B][N*m][n_t]
     long long* err; long long* bits; double* X_hat;
 };
+// the equaliser's output back in the time domain (esn_equalize.hip)
+struct EqRowsParams {
+    int n_frames, frames_per_group, n_sub, log2n, cp, pad, n_t, n_r;
+    const double* p_i; double no;
+    const double* H;             // complex [G][N][n_r][n_t]
+    const double* y_cp;          // complex [B][T][n_r]
+    void* U_eq;                  // [B][cp + N + pad][2 n_t], float64 or float32
+    double* X_hat;               // optional complex [B][N][n_t]
+};
 // decision-directed channel estimate (esn_chantrack.hip): estimate e reads frames e window .. e window + window - 1
 struct ChanTrackParams {
     int n_est, window, est_per_group, n_sub, log2n, cp, n_t, n_r, isi, m;

@@ -133,10 +133,14 @@ int launch_spectral_radius_split(const double* W, int n_sets, int n_res, int n_s
 int launch_gen_taps(const TapParams& tp, hipStream_t stream);
 int launch_gen_taps_doppler(const DopplerParams& dp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);
-// esn_baseline.hip
+// esn_baseline.hip; MMSE_LDS_MAX: the dynamic LDS one workgroup of mmse_detect_kernel / mmse_equalize_rows_kernel may ask for
+constexpr size_t MMSE_LDS_MAX = 150 * 1024;
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);
 int launch_mmse_detect(const MmseParams& mp, hipStream_t stream);
 int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream);
+// esn_equalize.hip: the LDS of one workgroup, a function of the shape alone (served up to MMSE_LDS_MAX)
+size_t equalize_rows_lds_bytes(int n_sub, int n_t, int n_r);
+int launch_equalize_rows(const EqRowsParams& ep, hipStream_t stream, bool io32);
 // esn_chanstat.hip
 int launch_channel_metrics(const ChanStatParams& cp, hipStream_t stream);
 // esn_coded.hip

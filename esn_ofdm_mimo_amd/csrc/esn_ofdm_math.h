@@ -5,6 +5,8 @@
 //       esn_remod.hip    the forward pass of detect_remod_kernel (its decimation-in-frequency inverse takes the stage
 //                        indices from here and keeps its own butterfly)
 //       esn_chantrack.hip, esn_baseline.hip (channel_estimate_kernel, mmse_detect_kernel)
+//       esn_equalize.hip mmse_equalize_rows_kernel: the spectrum of mmse_detect_kernel (esn_mmse_solve.h) and, on the
+//                        conjugated solution with the same table, N IFFT_N(X) = conj(FFT_N(conj X))
 //       esn_gen.hip      gen_frames_kernel, x = N IFFT_N(X): the conjugate table
 //   * the unit-power square QAM grid (norm, slicer, level, bits <-> index): the above and qam_llr_kernel (esn_coded.hip)
 //   * the error-counter tail of the generic kernels (detect, remod, mmse)

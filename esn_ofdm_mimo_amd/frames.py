@@ -198,6 +198,37 @@ class FrameSource:
                                                      _lib.stream_handle()), "esn_mmse_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
+    def equalize_rows(self, H, y, frames_per_block, ebno_db, pad=0, io="f64", want_xhat=False):
+        """The MMSE equaliser's output back in the time domain (esn_mmse_equalize_rows): y [B, T, n_r] complex128 and
+        H [G, N, n_r, n_t] -> U_eq [B, T + pad, 2 n_t], the rows z = sqrt(Pi) N IFFT(X) behind their cyclic prefix and
+        `pad` zero rows, Re/Im interleaved -- what an ESN behind the equaliser reads.  X is what mmse_detect_count
+        computes, bit for bit (want_xhat adds it, complex128 [B, N, n_t]).  io="f32": the rows rounded to float32."""
+        torch, p = self.torch, self.p
+        if io not in ("f64", "f32"):
+            raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
+        if int(pad) < 0:
+            raise ValueError(f"pad = {pad} must be non-negative")
+        if int(frames_per_block) < 1:
+            raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+        g, b = H.shape[0], y.shape[0]
+        if H.dtype != torch.complex128 or tuple(H.shape[1:]) != (p.n_sub, p.n_r, p.n_t):
+            raise ValueError(f"H must be complex128 [G, {p.n_sub}, {p.n_r}, {p.n_t}], not {H.dtype} {tuple(H.shape)}")
+        if y.dtype != torch.complex128 or tuple(y.shape[1:]) != (p.t_frame, p.n_r):
+            raise ValueError(f"y must be complex128 [B, {p.t_frame}, {p.n_r}], not {y.dtype} {tuple(y.shape)}")
+        if (b + int(frames_per_block) - 1) // int(frames_per_block) > g:
+            raise ValueError(f"{b} frames of {frames_per_block} per block need more than the {g} blocks of H")
+        f32 = io == "f32"
+        with torch.cuda.device(self.device):
+            p_i = self._per_group(p.p_i(ebno_db), g)
+            rows = torch.empty((b, p.t_frame + int(pad), 2 * p.n_t), dtype=torch.float32 if f32 else torch.float64,
+                               device=self.device)
+            xh = torch.empty((b, p.n_sub, p.n_t), dtype=torch.complex128, device=self.device) if want_xhat else None
+            name = "esn_mmse_equalize_rows_f32" if f32 else "esn_mmse_equalize_rows"
+            check(getattr(self.lib, name)(b, int(frames_per_block), p.n_sub, p.cp, int(pad), p.n_t, p.n_r, ptr(p_i),
+                                          p.no, ptr(H.contiguous()), ptr(y.contiguous()), ptr(rows), ptr(xh),
+                                          _lib.stream_handle()), name)
+        return (rows, xh) if want_xhat else rows
+
     def track_prior(self, ebno_db):
         """reg [isi] of track_channel: the MAP weight T No / (N Pi r_h[l]) of the exponential prior r_h that
         esn_channel_estimate shrinks with (exp(-l / (cp / 9)) normalised over cp + 1 taps), T = N + cp."""

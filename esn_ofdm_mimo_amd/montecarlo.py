@@ -33,6 +33,8 @@
     ensemble_point  one Eb/No point of a reservoir ensemble (ensemble.py, esn_detect_count_ens): K small ESNs per          points.py
                     block, each fitted on the block's pilot, outputs averaged before the FFT; member 0 is the ESN of a
                     DetectorSweep of the same seed
+    equalized_esn_point  one Eb/No point of a small ESN behind the LS-MMSE equaliser (FrameSource.equalize_rows,          points.py
+                    esn_mmse_equalize_rows): the equalised signal back in the time domain is the reservoir's input
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -47,4 +49,5 @@ from .points import fnn_point, fnn_weights  # noqa: F401
 from .points import cnn_point, cnn_weights  # noqa: F401
 from .points import lstm_point, lstm_weights  # noqa: F401
 from .points import ensemble_point  # noqa: F401
+from .points import equalized_esn_point  # noqa: F401
 from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters, stream_seed  # noqa: F401

@@ -5,7 +5,8 @@ through the sweep's bank as it stands; frames and ESN legs stay float64 / comple
 Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, uncoded, detected symbol by symbol with its
 channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
 only.  And elm_point / fnn_point / cnn_point / lstm_point: the windowed ELM (elm.py), FNN (fnn.py) and CNN (cnn.py) and
-the LSTM (lstm.py), the reference's pinv-trained and Adam-trained comparators, on the same frames."""
+the LSTM (lstm.py), the reference's pinv-trained and Adam-trained comparators, on the same frames; ensemble_point, K
+small ESNs averaged before the FFT; and equalized_esn_point, a small ESN behind the LS-MMSE equaliser."""
 from __future__ import annotations
 
 from .frames import _view_real, summarize_channel_metrics
@@ -570,3 +571,109 @@ def ensemble_point(src, ebno_db, snr_idx, n_blocks, *, n_members=4, n_reservoir=
                               reservoirs=reservoirs, pool=pool, io=io, first_block=first_block,
                               frames_per_block=frames_per_block, chunk_blocks=chunk_blocks, member_counts=member_counts)
     return (errors, nbits, merr) if member_counts else (errors, nbits)
+
+
+def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge=1e-5, method="auto", delay=0,
+                        spectral_radius=0.9, sparsity=0.1, noise=0.001, precision="f64", reservoirs="shared", pool=8,
+                        io="f64", first_block=0, frames_per_block=None, chunk_blocks=None, want_mmse=False,
+                        want_xhat=False):
+    """One Eb/No point of an ESN that stands behind the LS-MMSE equaliser, on the frames a DetectorSweep over the same
+    FrameSource seed and its baseline leg see: per chunk blocks_fast(with_ls_pilot=True), the pilot's channel estimate
+    (estimate_channel), FrameSource.equalize_rows on the dense pilot (one frame per group) and on the data frames --
+    the equalised signal back in the time domain, 2 n_t real columns -- and a ReservoirBank(2 n_t, 2 n_t, n_reservoir)
+    fitted on the pilot rows against the pre-PA pilot delayed by `delay` rows (transient delay + cp; pinv with ridge=None,
+    else `ridge`), then one predict over the chunk's data rows and the detector tail.
+
+    Input scaling is the sweep's input_scaler / sqrt(var_x), teacher scaling its teacher_scale.  The reservoir is the
+    host draw of the sweep (draw_reservoir(src.seed * 7919 + 17 + i): one set for "shared", `pool` sets picked by
+    global block for "per_block") and the state-noise streams are stream_seed(src.seed, snr_idx, leg), leg 0 for training
+    and 1 for detection: member 0's of ensemble_point.  The harvest is float64; `precision` and io ("f32": float32 rows
+    into and out of predict) are the prediction's.  One pilot per block, block fading or not; params.continuation and
+    n_t > 4 are refused.  Returns (errors, bits): int64 [n_blocks] on the device; with want_mmse also (errors, bits) of
+    esn_mmse_detect_count on the same frames and the same H.  The counters do not depend on chunk_blocks or on how
+    first_block cuts the blocks; nothing is read back inside the chunk loop (a flagged fit has the whole point redone
+    with method="qr" after it).  want_xhat is test support, not part of a sweep: it appends the detector tail's X_hat,
+    complex128 [n_blocks F, N, n_t], and keeps every chunk's alive until the end."""
+    import numpy as np
+    from .batched import ReservoirBank
+    from .sweep import draw_reservoir, stream_seed
+    if reservoirs not in ("shared", "per_block"):
+        raise ValueError(f"reservoirs must be 'shared' or 'per_block', not {reservoirs!r} (device-drawn reservoirs are "
+                         "not served behind the equaliser)")
+    if method not in ("auto", "qr", "chol"):
+        raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
+    if io not in ("f64", "f32"):
+        raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
+    if io == "f32" and precision == "f64":
+        raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
+    if ridge is not None and not float(ridge) >= 0:
+        raise ValueError(f"ridge = {ridge} must be None or non-negative")
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    if not isinstance(n_reservoir, int) or n_reservoir < 2:
+        raise ValueError(f"n_reservoir must be an integer of at least 2, not {n_reservoir!r}")
+    if not isinstance(delay, int) or delay < 0:
+        raise ValueError(f"delay must be a non-negative integer, not {delay!r}")
+    if reservoirs == "per_block" and int(pool) < 1:
+        raise ValueError(f"pool = {pool} must be positive")
+    torch, p = src.torch, src.p
+    if p.continuation:
+        raise ValueError("equalized_esn_point does not go with params.continuation: every frame is predicted from a "
+                         "zero state")
+    if p.n_t > 4:
+        raise ValueError(f"n_t = {p.n_t}: the equaliser kernels serve up to 4 transmit antennas")
+    n_io, n, d, t = 2 * p.n_t, n_reservoir, delay, p.t_frame
+    F = int(frames_per_block or p.coherence_symbols)
+    first_block, n_blocks = int(first_block), int(n_blocks)
+    chunk = int(chunk_blocks or min(n_blocks, 4096))
+    with np.errstate(all="ignore"):
+        ws = [draw_reservoir(n_io, n_io, n, float(spectral_radius), float(sparsity), src.seed * 7919 + 17 + i)
+              for i in range(1 if reservoirs == "shared" else int(pool))]
+    if not all(np.isfinite(w[0]).all() for w in ws):
+        raise ValueError(f"a drawn {n} x {n} reservoir has no finite spectral radius to scale to (all its eigenvalues "
+                         "are zero): take more units or a smaller sparsity")
+    bank = ReservoirBank(n_io, n_io, n, *(np.stack([w[j] for w in ws]) for j in range(3)), teacher_forcing=True,
+                         noise=noise, device=src.device)
+    seeds = [stream_seed(src.seed, snr_idx, leg) for leg in (0, 1)]
+    transient = d + p.cp
+    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    mm_err = torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
+    mm_bits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
+    flagged = torch.zeros((), dtype=torch.int64, device=src.device)
+    kept = []
+    for b0 in range(first_block, first_block + n_blocks, chunk):
+        g = min(chunk, first_block + n_blocks - b0)
+        lo = b0 - first_block
+        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
+        H = src.estimate_channel(data["pilot_bits"], data["pilot_y_ls"], ebno_db)
+        U = src.equalize_rows(H, data["pilot_y"], 1, ebno_db, pad=d)
+        rows = src.equalize_rows(H, data["data_y"], F, ebno_db, pad=d, io=io)
+        if want_mmse:
+            src.mmse_detect_count(H, data["data_y"], data["data_bits"], F, ebno_db, err=mm_err[lo:lo + g],
+                                  bits=mm_bits[lo:lo + g])
+        bank.set_scaling(torch.full((g, n_io), p.input_scaling(ebno_db), dtype=torch.float64, device=src.device), None,
+                         torch.full((g, n_io), p.teacher_scale, dtype=torch.float64, device=src.device), None)
+        D = torch.zeros((g, t + d, n_io), dtype=torch.float64, device=src.device)
+        D[:, d:d + t] = _view_real(data["pilot_x"])
+        bank.fit(U, D, transient=transient, precision="f64", noise_mode="counter", seed=seeds[0], method=method,
+                 group_offset=b0, ridge=None if ridge is None else float(ridge))
+        flagged += bank.fit_status.ne(0).sum()
+        Y = bank.predict(rows, F, T=t + d, transient=transient, precision=precision, noise_mode="counter", seed=seeds[1],
+                         group_offset=b0, io=io)
+        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
+        out = bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g],
+                                bits=nbits[lo:lo + g], want_xhat=want_xhat)
+        if want_xhat:
+            kept.append(torch.view_as_complex(out[2].view(g * F, p.n_sub, p.n_t, 2).contiguous()))
+    if method != "qr" and int(flagged) != 0:
+        return equalized_esn_point(src, ebno_db, snr_idx, n_blocks, n_reservoir=n_reservoir, ridge=ridge, method="qr",
+                                   delay=delay, spectral_radius=spectral_radius, sparsity=sparsity, noise=noise,
+                                   precision=precision, reservoirs=reservoirs, pool=pool, io=io, first_block=first_block,
+                                   frames_per_block=frames_per_block, chunk_blocks=chunk_blocks, want_mmse=want_mmse,
+                                   want_xhat=want_xhat)
+    return (errors, nbits) + ((mm_err, mm_bits) if want_mmse else ()) + ((torch.cat(kept),) if want_xhat else ())

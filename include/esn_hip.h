@@ -687,6 +687,27 @@ int esn_zf_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, i
                         long long* err_count, long long* bit_count, double* X_hat, void* stream);
 int esn_taps_to_freq(int n_blocks, int n_sub, int n_t, int n_r, int isi, const double* taps, double* H, void* stream);
 
+/* ---- The equaliser's output back in the time domain (extension: the input rows of an ESN that stands behind the
+ * LS-MMSE equaliser), float64.  Frame f belongs to group g = f / frames_per_group (p_i [groups], H [groups]):
+ *   Y_k[rx] = (1/N) sum_i y[cp + i][rx] e^{-2 pi i ik/N}              y_cp complex [B][cp + N][n_r]
+ *   X_k     = (H_k^H H_k + (no / Pi_g) I)^-1 H_k^H Y_k / sqrt(Pi_g)   the operations and order of esn_mmse_detect_count:
+ *             X_hat (optional, complex [B][N][n_t]) is bitwise what that entry point writes for the same inputs
+ *   z_i[tx] = sqrt(Pi_g) sum_k X_k[tx] e^{+2 pi i ik/N}               (N IFFT_N and the scaling of esn_detect_remod)
+ *   U_eq [B][cp + N + pad][2 n_t]: rows [0, cp) the last cp samples of z, rows [cp, cp + N) z, rows [cp + N, cp + N + pad)
+ *   zero; Re/Im interleaved per antenna -- the input layout of esn_predict_batch / esn_harvest_batch at n_in = 2 n_t.
+ * Every element is written; no counters, no atomics; a frame's outputs do not depend on what else is in the launch.
+ * The _f32 entry point writes the float64 value rounded to float32.  One workgroup per frame holds
+ * 16 (max(n_r, n_t) N + N/2) bytes of LDS (the Y image, which X then replaces, and the twiddle table), at most 150 KiB:
+ * n_r <= 74 at N = 128, n_r <= 4 at N = 2048.  Served: N a power of two in [2, 2048], n_t <= 4, 0 <= cp < N,
+ * 0 <= pad <= 2^20, n_r within that LDS, U_eq 16-byte (float32: 8-byte) aligned; anything else returns -1 before any HIP
+ * call, the limit in esn_last_error(). */
+int esn_mmse_equalize_rows(int n_frames, int frames_per_group, int n_sub, int cp, int pad, int n_t, int n_r,
+                           const double* p_i, double no, const double* H, const double* y_cp,
+                           double* U_eq, double* X_hat, void* stream);
+int esn_mmse_equalize_rows_f32(int n_frames, int frames_per_group, int n_sub, int cp, int pad, int n_t, int n_r,
+                               const double* p_i, double no, const double* H, const double* y_cp,
+                               float* U_eq, double* X_hat, void* stream);
+
 /* ---- Decision-directed channel estimate (extension: the MMSE baseline tracked through a block under Doppler), float64.
  * Estimate e is made from `window` frames stored consecutively, frames e window .. e window + window - 1, and belongs to
  * group e / est_per_group (p_i [groups], reg [groups][isi]).  With w = exp(-2 pi i / N), L = isi, Pi = p_i[group]:
