@@ -1,21 +1,18 @@
-"""ctypes binding of libesn_hip.so (include/esn_hip.h).  Fails loudly: a missing
-library or a missing GPU is an error, never a silent CPU path."""
+"""ctypes binding of libesn_hip.so, read from include/esn_hip.h: the header is the one statement of the C ABI.
+SIGNATURES, the enum constants and ABI_VERSION are parsed from it when this module is imported (regular expressions
+over plain C99 text; no compiler, no library and no GPU needed), so a new entry point is declared in the header,
+defined in csrc/esn_api.hip, and there is nothing to type here.  Fails loudly: a declaration the parser cannot type,
+a missing library or a missing GPU is an error, never a guess or a silent CPU path."""
 import ctypes as C
 import os
+import re
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ESN_HIP_LIB") or os.path.join(_PKG, "libesn_hip.so")   # env: tuning builds only
-
-F64, F32, F16, BF16 = 0, 1, 2, 3
-PRECISIONS = {"f64": F64, "f32": F32, "f16": F16, "bf16": BF16}
-NOISE_NONE, NOISE_TENSOR, NOISE_COUNTER = 0, 1, 2
-ABI_VERSION = 10
-MEM_DEVICE, MEM_HOST = 0, 1
-# enum esn_path, by value: the recurrence kernel a call dispatches to (recur_path below)
-PATHS = ("mfma", "skew16", "f64_valu", "f64_mfma", "cluster_f64", "big_predict", "big_harvest", "harvest_cluster")
+HEADER_PATH = os.path.join(_PKG, "..", "include", "esn_hip.h")
 
 
-class Shape(C.Structure):
+class Shape(C.Structure):                        # struct esn_shape; callers construct it positionally
     _fields_ = [("n_res", C.c_int), ("n_in", C.c_int), ("n_out", C.c_int),
                 ("teacher_forcing", C.c_int), ("n_wsets", C.c_int),
                 ("leak_rate", C.c_double)]       # extension: 0 or 1 = the reference's update (include/esn_hip.h)
@@ -25,168 +22,88 @@ class EsnHipError(RuntimeError):
     pass
 
 
-_vp, _dp, _ip = C.c_void_p, C.c_void_p, C.c_void_p   # device pointers travel as integers
-SIGNATURES = {
-    "esn_last_error": (C.c_char_p, []),
-    "esn_abi_version": (C.c_int, []),
-    "esn_debug_set": (C.c_int, [C.c_char_p, C.c_char_p]),
-    "esn_recur_path": (C.c_int, [C.c_int, C.c_int, C.POINTER(Shape), C.c_int, C.c_int, C.c_int]),
-    "esn_device_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                  C.c_char_p, C.c_int]),
-    "esn_tile_frames": (C.c_int, [C.c_int, C.POINTER(Shape)]),
-    "esn_packed_weights_bytes": (C.c_size_t, [C.c_int, C.POINTER(Shape)]),
-    "esn_packed_readout_bytes": (C.c_size_t, [C.c_int, C.POINTER(Shape)]),
-    "esn_pack_weights": (C.c_int, [C.c_int, C.POINTER(Shape), _dp, _dp, _dp, _vp, _vp]),
-    "esn_pack_readout": (C.c_int, [C.c_int, C.POINTER(Shape), C.c_int, _dp, _vp, _vp]),
-    "esn_predict_batch": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _vp, _dp, _dp, _dp, _dp, _dp,
-                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
-                                    C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _dp, _vp, C.c_size_t, _vp]),
-    "esn_predict_batch_f32": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _vp, _dp, _dp, _dp, _dp, _vp,
-                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
-                                        C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_size_t, _vp]),
-    "esn_predict_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(Shape), C.c_int, C.c_int]),
-    "esn_harvest_batch": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _dp, _dp, _dp, _dp, _dp, _dp,
-                                    C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _dp,
-                                    _vp, C.c_size_t, _vp]),
-    "esn_harvest_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(Shape), C.c_int]),
-    "esn_harvest_batch_f32": (C.c_int, [C.c_int, C.POINTER(Shape), _vp, _dp, _dp, _dp, _dp, _dp, _dp,
-                                        C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.c_uint64, C.c_uint64, _vp,
-                                        _vp, C.c_size_t, _vp]),
-    "esn_readout_solve_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "esn_readout_solve_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          _dp, _dp, _dp, _ip, _vp, _vp]),
-    "esn_readout_chol_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "esn_readout_solve_chol_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                               _dp, _dp, _dp, _ip, _vp, C.c_size_t, _vp]),
-    "esn_readout_solve_chol_batch_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                   _dp, _dp, _dp, _ip, _vp, C.c_size_t, _vp]),
-    # ridge read-out (extension): lambda [G][L] between t_shift and W_out; W_out [G][L][n_out][cols], status [G][L]
-    "esn_readout_solve_ridge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "esn_readout_solve_ridge_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                _dp, _dp, _dp, C.c_int, _dp, _ip, _vp, _vp]),
-    "esn_readout_chol_ridge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "esn_readout_solve_chol_ridge_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                     _dp, _dp, _dp, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
-    "esn_readout_solve_chol_ridge_batch_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                         _dp, _dp, _dp, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
-    # leave-one-out choice among L candidates: W_out [G][n_out][cols], score [G][L], choice [G], status [G][L]
-    "esn_readout_ridge_loo_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "esn_readout_ridge_loo_batch": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              _dp, _dp, _dp, C.c_int, _dp, _dp, _ip, _ip, _vp, C.c_size_t, _vp]),
-    "esn_readout_ridge_loo_batch_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                  _dp, _dp, _dp, C.c_int, _dp, _dp, _ip, _ip, _vp, C.c_size_t, _vp]),
-    # hold-out score of the candidates W [G][L][n_out][cols] on a pilot the fit has not seen: E, D, W, n_groups, T,
-    # transient, cols, n_out, t_scale, t_shift, n_ridge, status_in, score [G][L], choice [G], stream
-    "esn_readout_holdout_score": (C.c_int, [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            _dp, _dp, C.c_int, _ip, _dp, _ip, _vp]),
-    "esn_readout_holdout_score_f32": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                _dp, _dp, C.c_int, _ip, _dp, _ip, _vp]),
-    # running normal equations: E, D, n_groups, T, transient, cols, n_out, t_scale, t_shift, decay, Gm [G][cols][cols],
-    # Cm [G][n_out][cols], stream; and Gm, Cm, n_groups, cols, n_out, ridge [G][L], n_ridge, W_out [G][L][n_out][cols],
-    # status [G][L], workspace, workspace_bytes, stream
-    "esn_gram_accumulate": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double,
-                                      _dp, _dp, _vp]),
-    "esn_gram_accumulate_f32": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double,
-                                          _dp, _dp, _vp]),
-    "esn_gram_solve_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "esn_gram_solve": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
-    # reservoirs drawn on the device: W [S][n][n], W_in [S][n][n_in], W_fb [S][n][n_out], radius [S], status [S]
-    "esn_gen_reservoirs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int,
-                                     _dp, _dp, _dp, _dp, _vp]),
-    "esn_spectral_radius_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "esn_spectral_radius_batch": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
-    "esn_spectral_radius_split_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "esn_spectral_radius_split_batch": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, _dp, _ip, _vp, C.c_size_t, _vp]),
-    "esn_scale_reservoirs": (C.c_int, [_dp, C.c_int, C.c_int, C.c_double, _dp, _ip, _vp]),
-    "esn_gen_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp,
-                               C.c_uint64, C.c_uint64, _dp, _vp]),
-    # Jakes taps inside a coherence block: taps [n_blocks][n_sym][n_r][n_t][isi]; angles_in [links][paths][16][2]
-    "esn_gen_taps_doppler": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
-                                       C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, _vp]),
-    "esn_gen_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                 _dp, _dp, C.c_double, _dp, _vp, _dp, C.c_uint64, C.c_uint64, _vp, _dp, _dp, _vp]),
-    "esn_gen_frames_c64": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_int, _dp, _dp, C.c_double, _dp, _vp, _dp, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
-                                     _vp]),
-    "esn_channel_estimate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
-                                       C.c_double, _vp, _dp, C.c_int, _dp, _vp]),
-    "esn_mmse_detect_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
-                                        C.c_double, _dp, _dp, _vp, _vp, _vp, _dp, _vp]),
-    "esn_zf_detect_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
-                                      _dp, _dp, _vp, _vp, _vp, _dp, _vp]),
-    # equalised time-domain rows: n_frames, frames_per_group, N, cp, pad, n_t, n_r, p_i, no, H, y_cp, U_eq, X_hat, stream
-    "esn_mmse_equalize_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
-                                         C.c_double, _dp, _dp, _dp, _dp, _vp]),
-    "esn_mmse_equalize_rows_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
-                                             C.c_double, _dp, _dp, _vp, _dp, _vp]),
-    "esn_taps_to_freq": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp]),
-    "esn_channel_metrics": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp, _dp, _vp, _dp, _vp]),
-    # decision-directed channel estimate: y_cp, X_hat | bits, n_est, window, est_per_group, N, cp, n_t, n_r, isi, m, p_i,
-    # reg, taps, H, status, stream
-    "esn_channel_track": (C.c_int, [_dp, _dp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _vp]),
-    # windowed ELM: precision, n_in, n_hidden, window, bias_col, n_wsets, W_in, b, in_scale, in_shift, U, n_groups, T_in,
-    # T, group_offset, E, e_f32, e_cols, stream
-    "esn_elm_features": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp,
-                                   C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, C.c_int, C.c_int, _vp]),
-    # precision, n_in, n_hidden, window, bias_col, n_wsets, n_out, W_in, b, W_out, e_cols, in_scale, in_shift, t_scale,
-    # t_shift, U, n_frames, frames_per_group, T_in, T, transient, group_offset, Y, stream
-    "esn_elm_predict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
-                                  _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _dp,
-                                  _vp]),
-    # windowed FNN: n_in, n_hidden, window, n_out, n_groups, T -> bytes of esn_fnn_train's workspace
-    "esn_fnn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    # precision, n_in, n_hidden, window, n_out, n_isets, W1_0, b1_0, W2_0, b2_0, in_scale, in_shift, t_scale, t_shift, U,
-    # D, n_groups, T_in, T, transient, group_offset, epochs, lr, beta1, beta2, eps, W1, b1, W2, b2, loss, workspace,
-    # workspace_bytes, stream
-    "esn_fnn_train": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
-                                _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double,
-                                C.c_double, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _vp, C.c_size_t, _vp]),
-    # precision, n_in, n_hidden, window, n_out, W1, b1, W2, b2, in_scale, in_shift, t_scale, t_shift, U, n_frames,
-    # frames_per_group, T_in, T, transient, Y, stream
-    "esn_fnn_predict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
-                                  _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp]),
-    # windowed CNN: n_in, c1, c2, n_out, kernel, n_groups, n_frames, T -> bytes of the workspace of train / predict
-    "esn_cnn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    # precision, n_in, c1, c2, n_out, kernel, n_isets, W1_0, b1_0, W2_0, b2_0, W3_0, b3_0, in_scale, in_shift, t_scale,
-    # t_shift, U, D, n_groups, T_in, T, transient, group_offset, epochs, lr, beta1, beta2, eps, W1, b1, W2, b2, W3, b3,
-    # loss, workspace, workspace_bytes, stream
-    "esn_cnn_train": (C.c_int, [C.c_int] * 7 + [_dp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
-                                C.c_double, C.c_double, C.c_double, C.c_double] + [_dp] * 7 + [_vp, C.c_size_t, _vp]),
-    # precision, n_in, c1, c2, n_out, kernel, W1, b1, W2, b2, W3, b3, in_scale, in_shift, t_scale, t_shift, U, n_frames,
-    # frames_per_group, T_in, T, transient, Y, workspace, workspace_bytes, stream
-    "esn_cnn_predict": (C.c_int, [C.c_int] * 6 + [_dp] * 11 + [C.c_int] * 5 + [_dp, _vp, C.c_size_t, _vp]),
-    # LSTM comparator: n_in, n_hidden, n_out, n_groups, n_frames, T -> bytes of the workspace of train / predict
-    "esn_lstm_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    # precision, n_in, n_hidden, n_out, n_isets, W_ih_0, W_hh_0, b_ih_0, b_hh_0, W_fc_0, b_fc_0, in_scale, in_shift,
-    # t_scale, t_shift, U, D, n_groups, T_in, T, transient, group_offset, epochs, lr, beta1, beta2, eps, W_ih, W_hh, b_ih,
-    # b_hh, W_fc, b_fc, loss, workspace, workspace_bytes, stream
-    "esn_lstm_train": (C.c_int, [C.c_int] * 5 + [_dp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
-                                 C.c_double, C.c_double, C.c_double, C.c_double] + [_dp] * 7 + [_vp, C.c_size_t, _vp]),
-    # precision, n_in, n_hidden, n_out, W_ih, W_hh, b_ih, b_hh, W_fc, b_fc, in_scale, in_shift, t_scale, t_shift, U,
-    # n_frames, frames_per_group, T_in, T, transient, Y, workspace, workspace_bytes, stream
-    "esn_lstm_predict": (C.c_int, [C.c_int] * 4 + [_dp] * 11 + [C.c_int] * 5 + [_dp, _vp, C.c_size_t, _vp]),
-    "esn_ldpc_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "esn_qam_llr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _vp]),
-    "esn_ldpc_decode_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp,
-                                        C.c_double, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
-    "esn_detect_count": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
-                                   _vp, _vp, _dp, _vp]),
-    "esn_detect_count_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
-                                       _vp, _vp, _dp, _vp]),
-    # ensemble tail: Y [K, B, N, 2 n_t], K, B, F, N, n_t, m, p_i, weights, tx_bits, err, bits, member_err, X_hat, stream
-    "esn_detect_count_ens": (C.c_int, [_dp] + [C.c_int] * 6 + [_dp, _dp, _vp, _vp, _vp, _vp, _dp, _vp]),
-    "esn_detect_count_ens_f32": (C.c_int, [_vp] + [C.c_int] * 6 + [_dp, _dp, _vp, _vp, _vp, _vp, _dp, _vp]),
-    # decide and re-modulate: Y, B, F, N, cp, delay, n_t, m, p_i, tx_bits, err, bits, X_hat, dec_bits, D_hat, stream
-    "esn_detect_remod": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _vp,
-                                   _vp, _vp, _dp, _vp, _dp, _vp]),
-}
-# host-memory front ends: the arguments of esn_X behind a leading esn_mem_kind (include/esn_hip.h)
-for _name in ("esn_pack_weights", "esn_pack_readout", "esn_predict_batch", "esn_harvest_batch",
-              "esn_readout_solve_batch", "esn_detect_count"):
-    SIGNATURES[_name + "_mem"] = (C.c_int, [C.c_int] + SIGNATURES[_name][1])
-SIGNATURES["esn_device_alloc"] = (C.c_void_p, [C.c_size_t])
-SIGNATURES["esn_device_free"] = (C.c_int, [C.c_void_p])
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "unsigned int": C.c_uint, "double": C.c_double,
+            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "long long": C.c_longlong,
+            "unsigned long long": C.c_ulonglong}
+# pointers travel as integers (c_void_p: device pointers, streams, NULL) but for these two pointees
+_POINTEES = {"char": C.c_char_p, "esn_shape_t": C.POINTER(Shape)}
+
+
+def strip_header(text):
+    """C99 text without block comments, line comments and preprocessor lines."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    return re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", " ", text, flags=re.M)
+
+
+def _ctype(decl, where):
+    """ctypes type of one return type or parameter (its name, if any, included)."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return _POINTEES.get(" ".join(words[:words.index("*")]), C.c_void_p)
+    if words[:1] == ["enum"] and len(words) in (2, 3):
+        return C.c_int
+    for n in (len(words), len(words) - 1):       # unnamed, then named
+        if " ".join(words[:n]) in _SCALARS and all(w.isidentifier() for w in words[n:]):
+            return _SCALARS[" ".join(words[:n])]
+    raise EsnHipError(f"{where}: cannot type `{' '.join(decl.split())}`; teach esn_ofdm_mimo_amd/_lib.py the type")
+
+
+def parse_signatures(text):
+    """{name: (restype, argtypes)} of every `ret esn_name(args);` of a header text."""
+    text = strip_header(text)
+    out = {}
+    for statement in re.split(r"[;{}]", text):
+        m = re.fullmatch(r"([^()]*?)\b(esn_\w+)\s*\(([^()]*)\)\s*", statement)
+        if not m:
+            continue                             # enumerators, struct members, extern "C"; `missed` below names the rest
+        ret, name, args = m.groups()
+        args = [] if args.strip() == "void" else args.split(",")
+        out[name] = (_ctype(ret, name), [_ctype(a, name) for a in args])
+    missed = sorted(set(re.findall(r"\b(esn_\w+)\s*\(", text)) - set(out))
+    if missed:
+        raise EsnHipError(f"cannot read the declaration of {', '.join(missed)}")
+    return out
+
+
+def parse_enums(text):
+    """{enum tag: {enumerator: value}} of a header text."""
+    out = {}
+    for tag, body in re.findall(r"\benum\s+(\w+)\s*\{([^{}]*)\}", strip_header(text)):
+        out[tag], value = {}, -1
+        for item in filter(str.strip, body.split(",")):
+            name, _, given = item.partition("=")
+            value = int(given, 0) if given.strip() else value + 1
+            out[tag][name.strip()] = value
+    return out
+
+
+def parse_define(text, name):
+    """Integer value of `#define name value` in a header text."""
+    m = re.search(r"^[ \t]*#[ \t]*define[ \t]+%s[ \t]+(-?\w+)[ \t]*$" % re.escape(name),
+                  re.sub(r"/\*.*?\*/", " ", text, flags=re.S), flags=re.M)
+    if not m:
+        raise EsnHipError(f"{name} is not defined")
+    return int(m.group(1), 0)
+
+
+with open(HEADER_PATH) as _f:
+    _HEADER = _f.read()
+SIGNATURES = parse_signatures(_HEADER)
+# the one override: esn_device_info fills three host ints, passed with byref(c_int()); every other pointer is an address
+SIGNATURES["esn_device_info"][1][:3] = [C.POINTER(C.c_int)] * 3
+ENUMS = parse_enums(_HEADER)
+ABI_VERSION = parse_define(_HEADER, "ESN_ABI_VERSION")
+
+F64, F32, F16, BF16 = (ENUMS["esn_precision"][k] for k in ("ESN_F64", "ESN_F32", "ESN_F16", "ESN_BF16"))
+PRECISIONS = {"f64": F64, "f32": F32, "f16": F16, "bf16": BF16}
+NOISE_NONE, NOISE_TENSOR, NOISE_COUNTER = (ENUMS["esn_noise_mode"][k] for k in
+                                           ("ESN_NOISE_NONE", "ESN_NOISE_TENSOR", "ESN_NOISE_COUNTER"))
+MEM_DEVICE, MEM_HOST = (ENUMS["esn_mem_kind"][k] for k in ("ESN_MEM_DEVICE", "ESN_MEM_HOST"))
+# enum esn_path, by value: the recurrence kernel a call dispatches to (recur_path below)
+PATHS = tuple(k[len("ESN_PATH_"):].lower() for k, v in sorted(ENUMS["esn_path"].items(), key=lambda kv: kv[1]))
+if sorted(ENUMS["esn_path"].values()) != list(range(len(PATHS))):
+    raise EsnHipError("enum esn_path must count 0, 1, 2, ...: PATHS is indexed by value")
 
 _lib = None
 

@@ -77,7 +77,9 @@ typedef struct esn_shape {
 
 const char* esn_last_error(void);
 
-/* ABI version (bumped on any signature change). */
+/* ABI version (bumped on any signature change): stated here only.  esn_abi_version() returns the value the library was
+ * built with; a binding compares the two. */
+#define ESN_ABI_VERSION 10
 int esn_abi_version(void);
 
 /* Tuning / diagnostic knobs for benchmarks and A/B tests (no counterpart in the reference).  The

@@ -1,10 +1,9 @@
 """The boundary is a plain-C ABI: include/esn_hip.h must compile as C (gcc -std=c99 -pedantic) and a
 C program must link against libesn_hip.so and call the host-only entry points (no GPU needed)."""
 import os
-import subprocess
 import sys
 
-import pytest
+import c_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,19 +37,7 @@ int main(void) {
 
 
 def test_header_is_c_and_library_links_from_c(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "abi.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "abi"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "abi", C_SRC)
     assert "ok" in r.stdout
 
 

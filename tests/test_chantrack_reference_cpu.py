@@ -4,17 +4,16 @@ solution of the stacked, regularised system, noise-free spectra give the taps ba
 by the binding, and returns every unserved shape and a wrong X_hat / bits pair before a device is touched; the ABI
 number stays 10; baseline_tracking_point refuses its arguments before it touches its FrameSource."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import c_abi  # noqa: E402
 import chantrack_ref as cr  # noqa: E402
 from oracle.esn_oracle import unit_qam  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -52
 
 # W, N, n_t, n_r, L, m
@@ -178,21 +177,9 @@ int main(void) {
 
 
 def test_entry_point_links_from_c99_and_validates_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
     rows = "\n".join('    if (call(%s) != -1 || !said("%s")) return %d;' % (", ".join(str(v) for v in row), word, 2 + i)
                      for i, (row, word) in enumerate(BAD))
-    src = tmp_path / "ct.c"
-    src.write_text(C_SRC % rows)
-    exe = tmp_path / "ct"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "ct", C_SRC % rows)
     assert "chantrack abi ok" in r.stdout
 
 

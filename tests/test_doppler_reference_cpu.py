@@ -10,9 +10,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import c_abi  # noqa: E402
 import doppler_ref as dr  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FD, SYMBOLS = 0.01, (0, 10, 20, 38, 60, 76)
 
@@ -83,19 +82,7 @@ int main(void) {
 
 
 def test_entry_point_links_from_c99_and_validates_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "dop.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "dop"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "dop", C_SRC)
     assert "doppler abi ok" in r.stdout
 
 

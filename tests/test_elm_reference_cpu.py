@@ -9,13 +9,13 @@ ELM output (rows [0, N) of the un-cut output) decodes at chance, the aligned sli
 Both entry points are plain C, typed by the binding, and return every unserved shape and null pointer before a device is
 touched; the ABI number stays; elm_point refuses its arguments before it touches its FrameSource."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import c_abi  # noqa: E402
 import elm_ref  # noqa: E402
 from oracle import esn_oracle as eo  # noqa: E402
 
@@ -179,23 +179,11 @@ int main(void) {
 
 
 def test_entry_points_link_from_c99_and_validate_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
     rows = ['    if (predict(%s) != %d || !said("esn_elm_predict", "%s")) return %d;'
             % (", ".join(str(v) for v in row), code, word, 2 + i) for i, (row, code, word) in enumerate(BAD)]
     rows += ['    if (features(%s) != %d || !said("esn_elm_features", "%s")) return %d;'
              % (", ".join(str(v) for v in row), code, word, 100 + i) for i, (row, code, word) in enumerate(F_BAD)]
-    src = tmp_path / "elm.c"
-    src.write_text(C_SRC % "\n".join(rows))
-    exe = tmp_path / "elm"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "elm", C_SRC % "\n".join(rows))
     assert "elm abi ok" in r.stdout
 
 

@@ -2,12 +2,9 @@
 10 -- whose argument checks answer -1 with their text before anything touches a device; and the NumPy ensemble
 (tests/ensemble_ref.py) reproduces the finding the feature rests on: at one pilot, four 256-unit ESNs averaged before
 the FFT beat one 512-unit ESN of the same recurrence FLOPs."""
-import os
-import subprocess
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import c_abi
 
 ENS_NAMES = ("esn_detect_count_ens", "esn_detect_count_ens_f32")
 
@@ -72,19 +69,7 @@ int main(void) {
 
 
 def test_ensemble_entry_points_link_from_c99_and_validate_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "ens.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "ens"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "ens", C_SRC)
     assert "ensemble abi ok" in r.stdout
 
 

@@ -3,18 +3,15 @@ detector, against NumPy's own inverse transform and against mathematics; the arg
 (esn_mmse_equalize_rows[_f32], plain C additions: the ABI version stays 10) from a stand-alone C program; the
 ValueErrors of montecarlo.equalized_esn_point; and the finding the feature rests on, pinned on the NumPy chain: a small
 ESN behind the LS-MMSE equaliser makes at most 0.6 of the equaliser's own bit errors at 21 dB."""
-import os
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import c_abi
 import equalize_ref as qr
 from oracle import baselines as bl
 from oracle.ofdm_frames import LinkConfig, make_frame, modulate, tdlb_mimo_taps
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SHAPES = [dict(), dict(n_t=2, n_r=2, n_sub=16), dict(n_t=1, n_r=1, n_sub=4, isi=1), dict(n_t=4, n_r=8, n_sub=16)]
 
@@ -188,20 +185,7 @@ int main(void) {
 
 
 def test_equalize_entry_points_link_from_c99_and_name_their_limits(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "eq.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "eq"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-L", "/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir,
-           "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "eq", C_SRC, extra_link=("-L", "/opt/rocm/lib", "-lamdhip64"))
     assert "equalize abi ok" in r.stdout
 
 

@@ -5,11 +5,11 @@ every refused call answered -1 / -2 with the function's name before anything tou
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import c_abi
 import gram_ref
 import multipilot_ref
 import tracking_ref
@@ -177,17 +177,5 @@ int main(void) {
 
 
 def test_gram_entry_points_link_from_c99_and_validate_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "gram.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "gram"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "gram", C_SRC)
     assert "gram abi ok" in r.stdout

@@ -1,10 +1,7 @@
 """The float32 / complex64 I/O entry points (esn_predict_batch_f32, esn_detect_count_f32, esn_gen_frames_c64) are
 plain C: a C99 program declares them by use through include/esn_hip.h, links against libesn_hip.so and gets the
 argument errors (-1) and the unserved precision (-2) back before anything touches a device."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import c_abi
 
 C_SRC = r'''
 #include <stdio.h>
@@ -49,19 +46,7 @@ int main(void) {
 
 
 def test_io32_entry_points_link_from_c99_and_validate_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "io32.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "io32"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "io32", C_SRC)
     assert "io32 abi ok" in r.stdout
 
 

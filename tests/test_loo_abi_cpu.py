@@ -2,10 +2,7 @@
 program declares them through include/esn_hip.h, links against libesn_hip.so and gets the argument errors (-1) and
 the unserved Gram dimension (-2, with the limit in the text) back before anything touches a device.  They are
 additions: the ABI version stays 10."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import c_abi
 
 LOO_NAMES = ("esn_readout_ridge_loo_workspace_bytes", "esn_readout_ridge_loo_batch", "esn_readout_ridge_loo_batch_f32")
 
@@ -74,19 +71,7 @@ int main(void) {
 
 
 def test_loo_entry_points_link_from_c99_and_validate_without_a_device(tmp_path):
-    from esn_ofdm_mimo_amd import build
-    lib = build.build_library(verbose=False)
-    src = tmp_path / "loo.c"
-    src.write_text(C_SRC)
-    exe = tmp_path / "loo"
-    libdir = os.path.dirname(lib)
-    cmd = ["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-           "-o", str(exe), "-L", libdir, "-lesn_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    r = c_abi.compile_and_run(tmp_path, "loo", C_SRC)
     assert "loo abi ok" in r.stdout
 
 

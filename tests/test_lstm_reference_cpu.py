@@ -12,13 +12,12 @@ import functools
 import hashlib
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import c_abi  # noqa: E402
 import lstm_ref  # noqa: E402
 from lstm_ref import NAMES  # noqa: E402
 from esn_ofdm_mimo_amd import _lib, build, lstm  # noqa: E402
@@ -229,7 +228,7 @@ def test_refusals_need_no_device():
     assert rc == -1 and "workspace" in msg, (rc, msg)
 
 
-def test_c99_program_includes_the_header_and_links():
+def test_c99_program_includes_the_header_and_links(tmp_path):
     prog = ('#include "esn_hip.h"\n#include <stdio.h>\n'
             "int main(void) {\n"
             "    size_t n = esn_lstm_workspace_bytes(4, 100, 4, 1, 0, 74);\n"
@@ -239,16 +238,5 @@ def test_c99_program_includes_the_header_and_links():
             "    int rp = esn_lstm_predict(ESN_F64, 4, 129, 4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 74, 74, 0, 0, 0, 0, 0);\n"
             '    printf("%d %zu %zu %d %d\\n", esn_abi_version(), n, z, rc, rp);\n'
             "    return 0;\n}\n")
-    with tempfile.TemporaryDirectory() as tmp:
-        c_file, exe = os.path.join(tmp, "t.c"), os.path.join(tmp, "t")
-        open(c_file, "w").write(prog)
-        pkg = os.path.dirname(build.build_library(verbose=False))
-        r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c_file,
-                            "-o", exe, "-L", pkg, "-lesn_hip", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        env = dict(os.environ, LD_LIBRARY_PATH=pkg + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-        r = subprocess.run([exe], capture_output=True, text=True, env=env)
-        assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
-        out = r.stdout.split()
+    out = c_abi.compile_and_run(tmp_path, "t", prog).stdout.split()
     assert out[0] == "10" and int(out[1]) > 0 and out[2] == "0" and out[3] == "-1" and out[4] == "-1", out
