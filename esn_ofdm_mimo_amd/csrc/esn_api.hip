@@ -1001,7 +1001,11 @@ int esn_channel_estimate(int n_blocks, int n_sub, int cp, int n_t, int n_r, int 
     c.n_blocks = n_blocks; c.n_sub = n_sub; c.log2n = l2; c.cp = cp; c.n_t = n_t; c.n_r = n_r; c.isi = isi;
     c.m = bits_per_sym; c.p_i = p_i; c.no = no; c.pilot_bits = pilot_bits; c.y_ls_cp = y_ls_cp; c.H = H;
     c.ls_only = ls_only ? 1 : 0;
-    return hip_fail(launch_channel_estimate(c, (hipStream_t)stream), "esn_channel_estimate");
+    int e = launch_channel_estimate(c, (hipStream_t)stream);
+    if (e == -1)
+        return fail(-2, "esn_channel_estimate: N=%d n_t=%d isi=%d needs %zu bytes of LDS, %zu are served", n_sub, n_t, isi,
+                    channel_estimate_lds_bytes(n_sub, n_t, isi), MMSE_LDS_MAX);
+    return hip_fail(e, "esn_channel_estimate");
 }
 
 static int linear_detect(const char* who, int zf, int n_frames, int frames_per_group, int n_sub, int cp, int n_t, int n_r,

@@ -139,8 +139,17 @@ int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
+// Yf[N], full[N], hls[N / n_t + 1], ctd[isi], tw[N / 2]
+size_t channel_estimate_lds_bytes(int n_sub, int n_t, int isi) {
+    return sizeof(double2) * ((size_t)2 * n_sub + n_sub / n_t + 1 + isi + n_sub / 2);
+}
+
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream) {
-    const size_t lds = sizeof(double2) * ((size_t)2 * cp.n_sub + cp.n_sub / cp.n_t + 1 + cp.isi + cp.n_sub / 2);
+    const size_t lds = channel_estimate_lds_bytes(cp.n_sub, cp.n_t, cp.isi);
+    if (lds > MMSE_LDS_MAX) return -1;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(channel_estimate_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(channel_estimate_kernel, dim3(cp.n_blocks * cp.n_r), dim3(256), lds, stream, cp);
     return (int)hipGetLastError();
 }

@@ -135,6 +135,8 @@ int launch_gen_taps_doppler(const DopplerParams& dp, hipStream_t stream);
 int launch_gen_frames(const FrameGenParams& fp, hipStream_t stream, bool c64 = false);
 // esn_baseline.hip; MMSE_LDS_MAX: the dynamic LDS one workgroup of mmse_detect_kernel / mmse_equalize_rows_kernel may ask for
 constexpr size_t MMSE_LDS_MAX = 150 * 1024;
+// the LDS of one workgroup of channel_estimate_kernel, a function of the shape alone (served up to MMSE_LDS_MAX; -1 beyond)
+size_t channel_estimate_lds_bytes(int n_sub, int n_t, int isi);
 int launch_channel_estimate(const ChanEstParams& cp, hipStream_t stream);
 int launch_mmse_detect(const MmseParams& mp, hipStream_t stream);
 int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream);

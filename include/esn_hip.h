@@ -668,7 +668,9 @@ int esn_gen_frames_c64(int n_frames, int frames_per_block, int n_sub, int cp, in
  *                        inter/extrapolation, IFFT -> isi taps, diagonal MMSE shrinkage, DFT
  *                        (Demo_MIMO_4x8_Sionna_CDL_ESN_v2.py:358-382); ls_only = 1 stops at the interpolated LS
  *                        estimate, the H_LS the block-fading drivers feed their LS-ZF detector
- *                        (OFDM_MIMO_2-2_NBF_LDPC.py:321-333,457).
+ *                        (OFDM_MIMO_2-2_NBF_LDPC.py:321-333,457).  isi <= 64 and N / n_t >= 2, else -1; one workgroup
+ *                        holds 16 (2N + N/n_t + 1 + isi + N/2) bytes of LDS (90,256 at N = 2048, n_t = 4, isi = 8): a
+ *                        shape beyond the 150 KiB served is -2 with the byte count in esn_last_error().
  * esn_mmse_detect_count  y_cp complex [B][T][n_r] -> X = (H^H H + No/Pi I)^-1 H^H Y / sqrt(Pi) per
  *                        subcarrier (:40-45, :444-448), hard decision + error count as in
  *                        esn_detect_count; n_t <= 4.  X_hat complex [B][N][n_t] optional.

@@ -60,7 +60,7 @@ def pilot_frames(cfg: LinkConfig, ebno_db, taps, rng):
 
     def tx_chain(xf):
         xt = n * np.fft.ifft(xf, axis=0)
-        xc = np.concatenate([xt[-cfg.cp:], xt], axis=0) * sp
+        xc = (np.concatenate([xt[-cfg.cp:], xt], axis=0) if cfg.cp > 0 else xt) * sp     # cp = 0: no prefix
         return xc, xc / np.sqrt(1 + (np.abs(xc) / a) ** 2)
 
     x_cp, x_pa = tx_chain(x_p)

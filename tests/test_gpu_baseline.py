@@ -4,7 +4,8 @@ Deterministic leg: esn_channel_estimate / esn_mmse_detect_count against oracle/b
 the same pilot / data frames (1e-9; integer error counts bit-exact).
 Statistical leg: HIP generator -> HIP channel estimate -> HIP MMSE detector over the reference's
 Eb/No grid against the reference's OWN published curve (column MMSE_uncoded of results_ber.csv) --
-this pins generator and baseline together on the GPU."""
+this pins generator and baseline together on the GPU.
+The ragged shapes (n_t that does not divide N, n_r < n_t, isi 1 to 64, N up to 2048, m in 2..8) are in tests/test_gpu_link_shapes.py."""
 import numpy as np
 import pytest
 

@@ -9,7 +9,8 @@ tests/test_philox_reference_cpu.py checks the model (known answers, distribution
 tests/test_gpu_philox_streams.py compares each kernel drawing for itself with the kernel fed the model.
 What is pinned here is that the HIP generator equals the oracle restatement; the oracle's recipe and
 the generator are each held to the reference drivers' own loop statements, sample for sample, by the
-loop_*.npz fixtures (tests/test_oracle_driver_loop.py, tests/test_gpu_driver_loop.py)."""
+loop_*.npz fixtures (tests/test_oracle_driver_loop.py, tests/test_gpu_driver_loop.py).
+The ragged shapes (n_t = 3, odd n_r, isi != 8, T < 64, N = 1024 / 2048, complex64 stores) are in tests/test_gpu_link_shapes.py."""
 import math
 
 import numpy as np
