@@ -1,7 +1,9 @@
 """The frame side of the Monte-Carlo harness (montecarlo.py tells the whole chain): FrameSource, the HIP frame generator
 with the baseline equalisers and channel metrics that read its taps and frames; percentiles_linear and
 summarize_channel_metrics, the per-Eb/No channel record reduced on the device; _view_real / complex_as_io, complex
-frames as the interleaved real rows the ESN reads.  torch is imported where it is used: no GPU is needed to import."""
+frames as the interleaved real rows the ESN reads; pilot_rows and group_scalings, the padded pilot rows and the
+scalings of a chunk of blocks, for the sweep and the points alike.  torch is imported where it is used: no GPU is needed
+to import."""
 from __future__ import annotations
 
 from . import _lib
@@ -32,6 +34,10 @@ class FrameSource:
     def _per_group(self, value, g):
         """float64 [g] on the device, every entry `value`: the kernels take Pi and the clip level per group."""
         return self.torch.full((g,), value, dtype=self.torch.float64, device=self.device)
+
+    def p_i(self, ebno_db, g):
+        """Pi of g blocks at this Eb/No, float64 [g] on the device: the generator scales by it, the tails divide by it."""
+        return self._per_group(self.p.p_i(ebno_db), g)
 
     def taps(self, n_blocks, snr_idx, first_block, gains=None):
         """[G, n_r, n_t, isi] complex128.  Link l of block b draws from counter (first_block + b)."""
@@ -68,7 +74,7 @@ class FrameSource:
         g = taps.shape[0]
         b = g * frames_per_block
         with torch.cuda.device(self.device):
-            p_i = self._per_group(p.p_i(ebno_db), g)
+            p_i = self.p_i(ebno_db, g)
             a_clip = self._per_group(p.a_clip(ebno_db), g)
             bits = torch.empty((b, p.n_sub * p.m, p.n_t), dtype=torch.uint8, device=self.device)
             x_cp = torch.empty((b, p.t_frame, p.n_t), dtype=cdt, device=self.device) if want_x else None
@@ -155,7 +161,7 @@ class FrameSource:
         torch, p = self.torch, self.p
         g = pilot_bits.shape[0]
         with torch.cuda.device(self.device):
-            p_i = self._per_group(p.p_i(ebno_db), g)
+            p_i = self.p_i(ebno_db, g)
             H = torch.empty((g, p.n_sub, p.n_r, p.n_t), dtype=torch.complex128, device=self.device)
             check(self.lib.esn_channel_estimate(g, p.n_sub, p.cp, p.n_t, p.n_r, p.isi, p.m, ptr(p_i), p.no,
                                                 ptr(pilot_bits.contiguous()), ptr(pilot_y_ls.contiguous()),
@@ -180,7 +186,7 @@ class FrameSource:
         torch, p = self.torch, self.p
         g, b = H.shape[0], data_y.shape[0]
         with torch.cuda.device(self.device):
-            p_i = self._per_group(p.p_i(ebno_db), g)
+            p_i = self.p_i(ebno_db, g)
             if err is None:
                 err = torch.zeros(g, dtype=torch.int64, device=self.device)
             if bits is None:
@@ -219,7 +225,7 @@ class FrameSource:
             raise ValueError(f"{b} frames of {frames_per_block} per block need more than the {g} blocks of H")
         f32 = io == "f32"
         with torch.cuda.device(self.device):
-            p_i = self._per_group(p.p_i(ebno_db), g)
+            p_i = self.p_i(ebno_db, g)
             rows = torch.empty((b, p.t_frame + int(pad), 2 * p.n_t), dtype=torch.float32 if f32 else torch.float64,
                                device=self.device)
             xh = torch.empty((b, p.n_sub, p.n_t), dtype=torch.complex128, device=self.device) if want_xhat else None
@@ -254,7 +260,7 @@ class FrameSource:
         n_est = y_cp.shape[0] // int(window)
         g = (n_est + int(est_per_group) - 1) // int(est_per_group)
         with torch.cuda.device(self.device):
-            p_i = self._per_group(p.p_i(ebno_db), g)
+            p_i = self.p_i(ebno_db, g)
             row = self._track_reg.get(float(ebno_db))      # one upload per Eb/No: the tracking loop calls per data symbol
             if row is None:
                 row = self._track_reg[float(ebno_db)] = torch.tensor(self.track_prior(ebno_db), dtype=torch.float64,
@@ -281,7 +287,7 @@ class FrameSource:
         if H.dtype != torch.complex128 or tuple(H.shape[2:]) != (p.n_r, p.n_t):
             raise ValueError(f"H must be complex128 [G, N, {p.n_r}, {p.n_t}], not {H.dtype} {tuple(H.shape)}")
         with torch.cuda.device(self.device):
-            p_i = self._per_group(p.p_i(ebno_db), g)
+            p_i = self.p_i(ebno_db, g)
             cond = torch.empty((g, n), dtype=torch.float64, device=self.device)
             rank = torch.empty((g, n), dtype=torch.uint8, device=self.device)
             cap = torch.empty((g,), dtype=torch.float64, device=self.device)
@@ -332,3 +338,26 @@ def _view_real(z):
 
 
 complex_as_io = _view_real
+
+
+def pilot_rows(pilot_y, pilot_x, delay, out=None):
+    """The zero-padded training rows of pilots: pilot_y complex128 [..., t, n_r] and pilot_x [..., t, n_t] -> float64
+    (U [..., t + d, 2 n_r], D [..., t + d, 2 n_t]), d = delay: pilot_y in rows [0, t) of U, the teacher pilot_x in rows
+    [d, d + t) of D, zeros elsewhere.  out=(U, D): buffers of that shape to fill instead of new ones (the padding rows
+    are never written, so they can be kept between calls).  pilot_y=None: D alone, (None, D)."""
+    import torch
+    t, d = pilot_x.shape[-2], delay
+    U, D = out or (None if z is None else torch.zeros((*z.shape[:-2], t + d, 2 * z.shape[-1]), dtype=torch.float64,
+                                                      device=z.device) for z in (pilot_y, pilot_x))
+    if pilot_y is not None:
+        U[..., :t, :] = _view_real(pilot_y)
+    D[..., d:d + t, :] = _view_real(pilot_x)
+    return U, D
+
+
+def group_scalings(g, n_in, in_scale, n_out, t_scale, device):
+    """set_scaling's arguments for g groups of one input and one teacher scale: ([g, n_in], None, [g, n_out], None)."""
+    import torch
+    return (torch.full((g, n_in), in_scale, dtype=torch.float64, device=device), None,
+            torch.full((g, n_out), t_scale, dtype=torch.float64, device=device), None)
+

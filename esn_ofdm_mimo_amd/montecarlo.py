@@ -23,16 +23,17 @@
                     reference's pinv-trained comparator, on the frames a DetectorSweep of the same seed detects
     fnn_point       the same for the windowed FNN (fnn.py, esn_fnn_train / esn_fnn_predict), the reference's          points.py
                     Adam-trained comparator: one training per block, all 50 epochs in one launch; the chunk loop is
-                    elm_point's (points._windowed_point); what the three Adam-trained points share -- optimiser and
-                    shape checks, shared or per-block initial sets, the training of a chunk -- is points._trained_point
-                    over a trained.TrainedBank
+                    elm_point's (points._windowed_point over points._chunks and frames.pilot_rows); what the three
+                    Adam-trained points share -- optimiser and shape checks, shared or per-block initial sets, the
+                    training of a chunk -- is points._trained_point over a trained.TrainedBank
     cnn_point       the same for the windowed CNN (cnn.py, esn_cnn_train / esn_cnn_predict), the reference's          points.py
                     three-layer Conv1d comparator, float64 throughout
     lstm_point      the same for the LSTM (lstm.py, esn_lstm_train / esn_lstm_predict), the reference's recurrent          points.py
                     comparator (its RNN curve), float64 throughout
     ensemble_point  one Eb/No point of a reservoir ensemble (ensemble.py, esn_detect_count_ens): K small ESNs per          points.py
                     block, each fitted on the block's pilot, outputs averaged before the FFT; member 0 is the ESN of a
-                    DetectorSweep of the same seed
+                    DetectorSweep of the same seed (sweep.reservoir_seed, host_reservoir_bank, fit_e_dtype); a flagged fit
+                    has it, elm_point or equalized_esn_point redone with the QR solve (points._retry_with_qr)
     equalized_esn_point  one Eb/No point of a small ESN behind the LS-MMSE equaliser (FrameSource.equalize_rows,          points.py
                     esn_mmse_equalize_rows): the equalised signal back in the time domain is the reservoir's input
 

@@ -6,10 +6,57 @@ Beside them baseline_tracking_point: the LS-MMSE baseline of one Eb/No point, un
 channel estimate re-made after every data symbol (what DetectorSweep(track=...) is to the ESN); it needs a FrameSource
 only.  And elm_point / fnn_point / cnn_point / lstm_point: the windowed ELM (elm.py), FNN (fnn.py) and CNN (cnn.py) and
 the LSTM (lstm.py), the reference's pinv-trained and Adam-trained comparators, on the same frames; ensemble_point, K
-small ESNs averaged before the FFT; and equalized_esn_point, a small ESN behind the LS-MMSE equaliser."""
+small ESNs averaged before the FFT; and equalized_esn_point, a small ESN behind the LS-MMSE equaliser.  The uncoded points
+share _check_block_args, _check_esn_point_args, _chunks and _retry_with_qr here, frames.pilot_rows / group_scalings
+and, with DetectorSweep, sweep.reservoir_seed / host_reservoirs / host_reservoir_bank / fit_e_dtype."""
 from __future__ import annotations
 
-from .frames import _view_real, summarize_channel_metrics
+import numpy as np
+
+from . import reservoirs as _reservoirs
+from .batched import ReservoirBank
+from .frames import _view_real, group_scalings, pilot_rows, summarize_channel_metrics
+from .readout import _lambdas
+from .sweep import (DetectorSweep, check_io, fit_e_dtype, host_reservoir_bank, host_reservoirs, reservoir_seed,
+                    stream_seed)
+
+
+def _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block):
+    """What every uncoded point refuses of its block range."""
+    if int(n_blocks) < 1 or int(first_block) < 0:
+        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
+    if chunk_blocks is not None and int(chunk_blocks) < 1:
+        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
+    if frames_per_block is not None and int(frames_per_block) < 1:
+        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+
+
+def _check_esn_point_args(method, io, precision, ridge, ridge_grid=None):
+    """What the points that fit a reservoir's read-out refuse alike."""
+    if method not in ("auto", "qr", "chol"):
+        raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
+    check_io(io, precision)
+    if ridge is not None and ridge_grid is not None:
+        raise ValueError("give ridge or ridge_grid, not both")
+    if ridge is not None and not float(ridge) >= 0:
+        raise ValueError(f"ridge = {ridge} must be None or non-negative")
+
+
+def _chunks(first_block, n_blocks, chunk):
+    """The chunks of blocks first_block .. first_block + n_blocks - 1, at most `chunk` blocks each: yields (b0, g, lo) --
+    the chunk's first global block, its length, and where its counters start in a point's [n_blocks] vectors."""
+    first_block, end = int(first_block), int(first_block) + int(n_blocks)
+    for b0 in range(first_block, end, chunk):
+        yield b0, min(chunk, end - b0), b0 - first_block
+
+
+def _retry_with_qr(body, method):
+    """The result of body(method), a point's chunk loop, which returns (result, flagged fits); a point with a flagged fit
+    is redone as a whole, once, with method "qr".  int(flagged) is the point's one host read."""
+    result, flagged = body(method)
+    if method != "qr" and int(flagged) != 0:
+        result, flagged = body("qr")
+    return result
 
 
 def _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, salt):
@@ -59,21 +106,13 @@ def baseline_tracking_point(src, ebno_db, snr_idx, n_blocks, frames_per_block=No
         raise ValueError(f"track must be None, 'decisions' or 'genie', not {track!r}")
     if not isinstance(window, int) or not 1 <= window <= 8:
         raise ValueError(f"window must be an integer in 1..8, not {window!r}")
-    if int(n_blocks) < 1 or int(first_block) < 0:
-        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
-    if chunk_blocks is not None and int(chunk_blocks) < 1:
-        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
-    if frames_per_block is not None and int(frames_per_block) < 1:
-        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
     torch, p = src.torch, src.p
-    F = int(frames_per_block or p.coherence_symbols)
-    chunk = int(chunk_blocks or n_blocks)
-    errors = torch.zeros(F, dtype=torch.int64, device=src.device)
-    nbits = torch.zeros(F, dtype=torch.int64, device=src.device)
+    F, chunk = int(frames_per_block or p.coherence_symbols), int(chunk_blocks or n_blocks)
+    errors, nbits = (torch.zeros(F, dtype=torch.int64, device=src.device) for _ in range(2))
     failed = torch.zeros((), dtype=torch.int64, device=src.device)
     kept = []
-    for b0 in range(int(first_block), int(first_block) + int(n_blocks), chunk):
-        g = min(chunk, int(first_block) + int(n_blocks) - b0)
+    for b0, g, _ in _chunks(first_block, n_blocks, chunk):
         d = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
         H = src.estimate_channel(d["pilot_bits"], d["pilot_y_ls"], ebno_db)
         if track is None:
@@ -204,12 +243,7 @@ def _check_windowed_point_args(slice, weights, precision, window, n_blocks, firs
         raise ValueError(f"precision must be 'f64' or 'f16', not {precision!r}")
     if not isinstance(window, int) or not 1 <= window <= 16:
         raise ValueError(f"window must be an integer in 1..16, not {window!r}")
-    if int(n_blocks) < 1 or int(first_block) < 0:
-        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
-    if chunk_blocks is not None and int(chunk_blocks) < 1:
-        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
-    if frames_per_block is not None and int(frames_per_block) < 1:
-        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
 
 
 def _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision, slice, train):
@@ -219,40 +253,28 @@ def _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_blo
     set_scaling(*scaling), inputs and teacher scaled by 1 / sqrt(var_x) -- then one predict over the chunk's data
     frames, cut as `slice` says, and the detector tail into that chunk's part of the counters.  Returns (errors, bits):
     int64 [n_blocks] on the device; nothing is read back."""
-    import numpy as np
     torch, p = src.torch, src.p
-    n_in, n_out = 2 * p.n_r, 2 * p.n_t
-    F = int(frames_per_block or p.coherence_symbols)
-    first_block, n_blocks = int(first_block), int(n_blocks)
+    n_in, n_out, T = 2 * p.n_r, 2 * p.n_t, p.t_frame + p.delay
+    F, n_blocks = int(frames_per_block or p.coherence_symbols), int(n_blocks)
     chunk = int(chunk_blocks or min(n_blocks, 4096))
-    d, T = p.delay, p.t_frame + p.delay
-    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
+    errors, nbits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) for _ in range(2))
     scale = 1.0 / np.sqrt(p.var_x(ebno_db))
-    for b0 in range(first_block, first_block + n_blocks, chunk):
-        g = min(chunk, first_block + n_blocks - b0)
+    for b0, g, lo in _chunks(first_block, n_blocks, chunk):
         data = src.blocks_fast(ebno_db, snr_idx, b0, g, F)
-        scaling = (torch.full((g, n_in), scale, dtype=torch.float64, device=src.device), None,
-                   torch.full((g, n_out), scale, dtype=torch.float64, device=src.device), None)
-        U = torch.zeros((g, T, n_in), dtype=torch.float64, device=src.device)
-        D = torch.zeros((g, T, n_out), dtype=torch.float64, device=src.device)
-        U[:, :p.t_frame] = _view_real(data["pilot_y"])
-        D[:, d:] = _view_real(data["pilot_x"])
-        bank = train(U, D, scaling, b0, g)
+        U, D = pilot_rows(data["pilot_y"], data["pilot_x"], p.delay)
+        bank = train(U, D, group_scalings(g, n_in, scale, n_out, scale, src.device), b0, g)
         dy = _view_real(data["data_y"])
         if slice == "aligned":
             Y = bank.predict(dy, F, T=T, transient=p.forget, precision=precision)
         else:
             Y = bank.predict(dy, F, T=T, transient=0, precision=precision)[:, :p.n_sub].contiguous()
-        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
-        lo = b0 - first_block
-        bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g])
+        bank.detect_count(Y, data["data_bits"], src.p_i(ebno_db, g), F, p.n_sub, p.n_t, p.m,
+                          err=errors[lo:lo + g], bits=nbits[lo:lo + g])
     return errors, nbits
 
 
 def _stack_sets(sets):
     """Per-block parameter sets, each a tuple of arrays -> one tuple of arrays [len(sets), ...]."""
-    import numpy as np
     return tuple(np.stack(a) for a in zip(*sets))
 
 
@@ -285,7 +307,6 @@ def _trained_point(src, ebno_db, snr_idx, n_blocks, shape_error, make_bank, draw
 def elm_weights(n_hidden, k, gain, seed, block=None):
     """W_in = gain U(-1, 1) [n_hidden, k], then b = U(-1, 1) [n_hidden], from RandomState(seed) -- or, for the set of
     one global block, RandomState([seed, block])."""
-    import numpy as np
     rs = np.random.RandomState(seed if block is None else [seed, block])
     return gain * rs.uniform(-1, 1, (n_hidden, k)), rs.uniform(-1, 1, n_hidden)
 
@@ -318,38 +339,36 @@ def elm_point(src, ebno_db, snr_idx, n_blocks, *, n_hidden=512, window=8, gain=0
     if k > 256:
         raise ValueError(f"window * 2 n_r = {k}: the ELM kernels serve up to 256")
     shared = elm_weights(n_hidden, k, gain, seed) if weights == "shared" else None
-    bank = None
-    flagged = src.torch.zeros((), dtype=src.torch.int64, device=src.device)
 
-    def train(U, D, scaling, b0, g):
-        nonlocal bank
-        if shared is None:
-            W_in, b = _stack_sets([elm_weights(n_hidden, k, gain, seed, b0 + i) for i in range(g)])
-        else:
-            W_in, b = shared
-        if bank is None:
-            bank = ElmBank(n_in, n_out, n_hidden, window, W_in, b, n_groups=g, device=src.device)
-        elif shared is None:
-            bank.set_weights(W_in, b)
-        bank.set_scaling(*scaling)
-        bank.fit(U, D, transient=transient, method=method, ridge=ridge, repair=False)
-        flagged.add_(bank.fit_status.ne(0).sum())
-        return bank
+    def point(method):
+        bank = None
+        flagged = src.torch.zeros((), dtype=src.torch.int64, device=src.device)
 
-    errors, nbits = _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks,
-                                    precision, slice, train)
-    if method != "qr" and int(flagged) != 0:
-        return elm_point(src, ebno_db, snr_idx, n_blocks, n_hidden=n_hidden, window=window, gain=gain, ridge=ridge,
-                         method="qr", precision=precision, slice=slice, weights=weights, first_block=first_block,
-                         seed=seed, frames_per_block=frames_per_block, chunk_blocks=chunk_blocks)
-    return errors, nbits
+        def train(U, D, scaling, b0, g):
+            nonlocal bank
+            if shared is None:
+                W_in, b = _stack_sets([elm_weights(n_hidden, k, gain, seed, b0 + i) for i in range(g)])
+            else:
+                W_in, b = shared
+            if bank is None:
+                bank = ElmBank(n_in, n_out, n_hidden, window, W_in, b, n_groups=g, device=src.device)
+            elif shared is None:
+                bank.set_weights(W_in, b)
+            bank.set_scaling(*scaling)
+            bank.fit(U, D, transient=transient, method=method, ridge=ridge, repair=False)
+            flagged.add_(bank.fit_status.ne(0).sum())
+            return bank
+
+        return _windowed_point(src, ebno_db, snr_idx, n_blocks, first_block, frames_per_block, chunk_blocks, precision,
+                               slice, train), flagged
+
+    return _retry_with_qr(point, method)
 
 
 def fnn_weights(n_hidden, k, n_out, seed, block=None):
     """(W1 [n_hidden, k], b1, W2 [n_out, n_hidden], b2), each U(+-1 / sqrt(fan_in)) -- the distribution of
     torch.nn.Linear -- drawn in that order from RandomState(seed) or, for the set of one global block,
     RandomState([seed, block])."""
-    import numpy as np
     rs = np.random.RandomState(seed if block is None else [seed, block])
     a1, a2 = 1.0 / np.sqrt(k), 1.0 / np.sqrt(n_hidden)
     return (rs.uniform(-a1, a1, (n_hidden, k)), rs.uniform(-a1, a1, n_hidden),
@@ -383,7 +402,6 @@ def cnn_weights(channels, kernel, n_in, n_out, seed, block=None):
     """(W1 [c1, n_in, k], b1, W2 [c2, c1, k], b2, W3 [n_out, c2, k], b3), each U(+-1 / sqrt(fan_in)) with
     fan_in = c_in k -- the distribution of torch.nn.Conv1d -- drawn in that order from RandomState(seed) or, for the set
     of one global block, RandomState([seed, block])."""
-    import numpy as np
     rs = np.random.RandomState(seed if block is None else [seed, block])
     c = (n_in, channels[0], channels[1], n_out)
     out = []
@@ -422,7 +440,6 @@ def lstm_weights(n_hidden, n_in, n_out, seed, block=None):
     """(W_ih [4H, n_in], W_hh [4H, H], b_ih [4H], b_hh [4H], W_fc [n_out, H], b_fc [n_out]), each U(+-1 / sqrt(H)) -- the
     distribution of torch.nn.LSTM and of torch.nn.Linear(H, .) -- drawn in that order from RandomState(seed) or, for the
     set of one global block, RandomState([seed, block])."""
-    import numpy as np
     rs = np.random.RandomState(seed if block is None else [seed, block])
     a, h = 1.0 / np.sqrt(n_hidden), n_hidden
     return tuple(rs.uniform(-a, a, s) for s in ((4 * h, n_in), (4 * h, h), (4 * h,), (4 * h,), (n_out, h), (n_out,)))
@@ -471,106 +488,69 @@ def ensemble_point(src, ebno_db, snr_idx, n_blocks, *, n_members=4, n_reservoir=
     is refused.  Returns (errors, bits): int64 [n_blocks] on the device, and with member_counts also int64
     [n_blocks, K], each member's own errors on the same frames.  chunk_blocks defaults to min(n_blocks, 4096 // K) --
     a chunk holds K slabs of Y -- and under "fresh" to what keeps K reservoirs per block within the sweep's budget.
-    The counters do not depend on chunk_blocks or on how
-    first_block cuts the blocks; nothing is read back inside the chunk loop (a flagged fit has the whole point redone
-    with method="qr" after it)."""
-    import numpy as np
-    from . import reservoirs as _reservoirs
-    from .batched import ReservoirBank
+    The counters do not depend on chunk_blocks or on how first_block cuts the blocks; nothing is read back inside the
+    chunk loop (a flagged fit has the whole point redone with method="qr" after it: _retry_with_qr)."""
     from .ensemble import MAX_MEMBERS, EnsembleBank
-    from .readout import _lambdas
-    from .sweep import DetectorSweep, draw_reservoir, stream_seed
     K = n_members
     if not isinstance(K, int) or not 1 <= K <= MAX_MEMBERS:
         raise ValueError(f"n_members must be an integer in 1..{MAX_MEMBERS}, not {n_members!r}")
     if reservoirs not in ("shared", "per_block", "fresh"):
         raise ValueError(f"reservoirs must be 'shared', 'per_block' or 'fresh', not {reservoirs!r}")
-    if method not in ("auto", "qr", "chol"):
-        raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
-    if io not in ("f64", "f32"):
-        raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
-    if io == "f32" and precision == "f64":
-        raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
-    if ridge is not None and ridge_grid is not None:
-        raise ValueError("give ridge or ridge_grid, not both")
-    if ridge is not None and not float(ridge) >= 0:
-        raise ValueError(f"ridge = {ridge} must be None or non-negative")
-    if int(n_blocks) < 1 or int(first_block) < 0:
-        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
-    if chunk_blocks is not None and int(chunk_blocks) < 1:
-        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
-    if frames_per_block is not None and int(frames_per_block) < 1:
-        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    _check_esn_point_args(method, io, precision, ridge, ridge_grid)
+    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
     torch, p = src.torch, src.p
     if p.continuation:
         raise ValueError("ensemble_point does not go with params.continuation: every member predicts from a zero state")
     n_in, n_out, n = 2 * p.n_r, 2 * p.n_t, int(n_reservoir)
-    F = int(frames_per_block or p.coherence_symbols)
-    first_block, n_blocks = int(first_block), int(n_blocks)
+    F, n_blocks = int(frames_per_block or p.coherence_symbols), int(n_blocks)
     chunk = int(chunk_blocks or min(n_blocks, max(1, 4096 // K)))      # (Y holds K slabs per chunk)
     res_args = (n_in, n_out, n, float(spectral_radius), float(sparsity))
-    res_seed = [src.seed * 7919 + 17 + MEMBER_SEED_STRIDE * k for k in range(K)]
-    kw = dict(teacher_forcing=True, noise=noise, device=src.device)
-    fresh = reservoirs == "fresh"
-    if fresh:
-        if chunk_blocks is None:        # K reservoirs per block live on the device for the length of a chunk
-            per_block = K * DetectorSweep.FRESH_BYTES_PER_BLOCK_N2 * n * n
-            chunk = min(chunk, max(1, DetectorSweep.FRESH_BUDGET_BYTES // per_block))
-        ens = None
-    else:
-        banks = []
-        for k in range(K):
-            ws = [draw_reservoir(n_in, n_out, n, res_args[3], res_args[4], res_seed[k] + i)
-                  for i in range(1 if reservoirs == "shared" else int(pool))]
-            banks.append(ReservoirBank(n_in, n_out, n, *(np.stack([w[j] for w in ws]) for j in range(3)), **kw))
-        ens = EnsembleBank(banks)
+    res_seed = [reservoir_seed(src.seed) + MEMBER_SEED_STRIDE * k for k in range(K)]
+    kw, fresh = dict(noise=noise, device=src.device), reservoirs == "fresh"
+    if fresh and chunk_blocks is None:        # K reservoirs per block live on the device for the length of a chunk
+        per_block = K * DetectorSweep.FRESH_BYTES_PER_BLOCK_N2 * n * n
+        chunk = min(chunk, max(1, DetectorSweep.FRESH_BUDGET_BYTES // per_block))
     grid_t = None
     if ridge_grid is not None:
         grid_t = _lambdas(torch, src.device, np.array(ridge_grid, dtype=np.float64).reshape(-1), 1, grid=True)[0][0]
     seeds = [[stream_seed(src.seed, snr_idx, leg + (k << MEMBER_LEG_SHIFT)) for k in range(K)] for leg in (0, 1)]
-    d, t = p.delay, p.t_frame
-    rows, cols = t + d - p.forget, n + n_in
-    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    merr = torch.zeros((n_blocks, K), dtype=torch.int64, device=src.device) if member_counts else None
-    flagged = torch.zeros((), dtype=torch.int64, device=src.device)
-    for b0 in range(first_block, first_block + n_blocks, chunk):
-        g = min(chunk, first_block + n_blocks - b0)
-        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, io="c64" if io == "f32" else "c128")
-        if fresh:       # block b in slot b % g, the set the kernels pick for it under group_offset = b0
-            sets = [_reservoirs.generate(*res_args, seed=res_seed[k], first_set=b0, n_sets=g, device=src.device,
-                                         check_status=method == "qr", n_squarings=24) for k in range(K)]
-            if ens is None:
-                ens = EnsembleBank([ReservoirBank(n_in, n_out, n, *s[:3], **kw) for s in sets])
-            else:
-                for m, s in zip(ens.members, sets):
-                    m.set_weights(*s[:3])
-            for s in sets:
-                flagged += s[4].ne(0).sum()
-        ens.set_scaling(torch.full((g, n_in), p.input_scaling(ebno_db), dtype=torch.float64, device=src.device), None,
-                        torch.full((g, n_out), p.teacher_scale, dtype=torch.float64, device=src.device), None)
-        U = torch.zeros((g, t + d, n_in), dtype=torch.float64, device=src.device)
-        D = torch.zeros((g, t + d, n_out), dtype=torch.float64, device=src.device)
-        U[:, :t] = _view_real(data["pilot_y"])
-        D[:, d:d + t] = _view_real(data["pilot_x"])
-        chol = method == "chol" or (method == "auto" and ens.members[0].chol_fits(rows, cols))
-        e_dtype = "f32" if (chol and fit_precision in ("f16", "bf16")) else "f64"
-        ens.fit(U, D, transient=p.forget, precision=fit_precision, noise_mode="counter", seed=seeds[0], method=method,
-                e_dtype=e_dtype, group_offset=b0, ridge=None if ridge is None else float(ridge), ridge_grid=grid_t)
-        flagged += ens.fit_status.ne(0).sum()
-        Y = ens.predict(_view_real(data["data_y"]), F, T=t + d, transient=p.forget, precision=precision,
-                        noise_mode="counter", seed=seeds[1], group_offset=b0, io=io)
-        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
-        lo = b0 - first_block
-        ens.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g], bits=nbits[lo:lo + g],
-                         member_err=None if merr is None else merr[lo:lo + g])
-    if method != "qr" and int(flagged) != 0:
-        return ensemble_point(src, ebno_db, snr_idx, n_blocks, n_members=K, n_reservoir=n_reservoir,
-                              spectral_radius=spectral_radius, sparsity=sparsity, noise=noise, precision=precision,
-                              fit_precision=fit_precision, method="qr", ridge=ridge, ridge_grid=ridge_grid,
-                              reservoirs=reservoirs, pool=pool, io=io, first_block=first_block,
-                              frames_per_block=frames_per_block, chunk_blocks=chunk_blocks, member_counts=member_counts)
-    return (errors, nbits, merr) if member_counts else (errors, nbits)
+    T = p.t_frame + p.delay
+
+    def point(method):
+        ens = None
+        if not fresh:
+            n_sets = 1 if reservoirs == "shared" else int(pool)
+            ens = EnsembleBank([host_reservoir_bank(*res_args, [res_seed[k] + i for i in range(n_sets)], **kw)
+                                for k in range(K)])
+        errors, nbits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) for _ in range(2))
+        merr = torch.zeros((n_blocks, K), dtype=torch.int64, device=src.device) if member_counts else None
+        flagged = torch.zeros((), dtype=torch.int64, device=src.device)
+        for b0, g, lo in _chunks(first_block, n_blocks, chunk):
+            data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, io="c64" if io == "f32" else "c128")
+            if fresh:       # block b in slot b % g, the set the kernels pick for it under group_offset = b0
+                sets = [_reservoirs.generate(*res_args, seed=res_seed[k], first_set=b0, n_sets=g, device=src.device,
+                                             check_status=method == "qr", n_squarings=24) for k in range(K)]
+                if ens is None:
+                    ens = EnsembleBank([ReservoirBank(n_in, n_out, n, *s[:3], teacher_forcing=True, **kw) for s in sets])
+                else:
+                    for m, s in zip(ens.members, sets):
+                        m.set_weights(*s[:3])
+                for s in sets:
+                    flagged += s[4].ne(0).sum()
+            ens.set_scaling(*group_scalings(g, n_in, p.input_scaling(ebno_db), n_out, p.teacher_scale, src.device))
+            U, D = pilot_rows(data["pilot_y"], data["pilot_x"], p.delay)
+            e_dtype = fit_e_dtype(ens.members[0], method, fit_precision, T - p.forget, n + n_in)
+            ens.fit(U, D, transient=p.forget, precision=fit_precision, noise_mode="counter", seed=seeds[0], method=method,
+                    e_dtype=e_dtype, group_offset=b0, ridge=None if ridge is None else float(ridge), ridge_grid=grid_t)
+            flagged += ens.fit_status.ne(0).sum()
+            Y = ens.predict(_view_real(data["data_y"]), F, T=T, transient=p.forget, precision=precision,
+                            noise_mode="counter", seed=seeds[1], group_offset=b0, io=io)
+            ens.detect_count(Y, data["data_bits"], src.p_i(ebno_db, g), F, p.n_sub, p.n_t, p.m,
+                             err=errors[lo:lo + g], bits=nbits[lo:lo + g],
+                             member_err=None if merr is None else merr[lo:lo + g])
+        return ((errors, nbits, merr) if member_counts else (errors, nbits)), flagged
+
+    return _retry_with_qr(point, method)
 
 
 def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge=1e-5, method="auto", delay=0,
@@ -594,26 +574,11 @@ def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge
     first_block cuts the blocks; nothing is read back inside the chunk loop (a flagged fit has the whole point redone
     with method="qr" after it).  want_xhat is test support, not part of a sweep: it appends the detector tail's X_hat,
     complex128 [n_blocks F, N, n_t], and keeps every chunk's alive until the end."""
-    import numpy as np
-    from .batched import ReservoirBank
-    from .sweep import draw_reservoir, stream_seed
     if reservoirs not in ("shared", "per_block"):
         raise ValueError(f"reservoirs must be 'shared' or 'per_block', not {reservoirs!r} (device-drawn reservoirs are "
                          "not served behind the equaliser)")
-    if method not in ("auto", "qr", "chol"):
-        raise ValueError(f"method must be 'auto', 'qr' or 'chol', not {method!r}")
-    if io not in ("f64", "f32"):
-        raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
-    if io == "f32" and precision == "f64":
-        raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
-    if ridge is not None and not float(ridge) >= 0:
-        raise ValueError(f"ridge = {ridge} must be None or non-negative")
-    if int(n_blocks) < 1 or int(first_block) < 0:
-        raise ValueError(f"n_blocks = {n_blocks} must be positive and first_block = {first_block} non-negative")
-    if chunk_blocks is not None and int(chunk_blocks) < 1:
-        raise ValueError(f"chunk_blocks = {chunk_blocks} must be positive")
-    if frames_per_block is not None and int(frames_per_block) < 1:
-        raise ValueError(f"frames_per_block = {frames_per_block} must be positive")
+    _check_esn_point_args(method, io, precision, ridge)
+    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
     if not isinstance(n_reservoir, int) or n_reservoir < 2:
         raise ValueError(f"n_reservoir must be an integer of at least 2, not {n_reservoir!r}")
     if not isinstance(delay, int) or delay < 0:
@@ -626,54 +591,43 @@ def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge
                          "zero state")
     if p.n_t > 4:
         raise ValueError(f"n_t = {p.n_t}: the equaliser kernels serve up to 4 transmit antennas")
-    n_io, n, d, t = 2 * p.n_t, n_reservoir, delay, p.t_frame
-    F = int(frames_per_block or p.coherence_symbols)
-    first_block, n_blocks = int(first_block), int(n_blocks)
+    n_io, n, d, T, transient = 2 * p.n_t, n_reservoir, delay, p.t_frame + delay, delay + p.cp
+    F, n_blocks = int(frames_per_block or p.coherence_symbols), int(n_blocks)
     chunk = int(chunk_blocks or min(n_blocks, 4096))
     with np.errstate(all="ignore"):
-        ws = [draw_reservoir(n_io, n_io, n, float(spectral_radius), float(sparsity), src.seed * 7919 + 17 + i)
-              for i in range(1 if reservoirs == "shared" else int(pool))]
-    if not all(np.isfinite(w[0]).all() for w in ws):
+        sets = host_reservoirs(n_io, n_io, n, float(spectral_radius), float(sparsity),
+                               [reservoir_seed(src.seed) + i for i in range(1 if reservoirs == "shared" else int(pool))])
+    if not np.isfinite(sets[0]).all():
         raise ValueError(f"a drawn {n} x {n} reservoir has no finite spectral radius to scale to (all its eigenvalues "
                          "are zero): take more units or a smaller sparsity")
-    bank = ReservoirBank(n_io, n_io, n, *(np.stack([w[j] for w in ws]) for j in range(3)), teacher_forcing=True,
-                         noise=noise, device=src.device)
     seeds = [stream_seed(src.seed, snr_idx, leg) for leg in (0, 1)]
-    transient = d + p.cp
-    errors = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    nbits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device)
-    mm_err = torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
-    mm_bits = torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
-    flagged = torch.zeros((), dtype=torch.int64, device=src.device)
-    kept = []
-    for b0 in range(first_block, first_block + n_blocks, chunk):
-        g = min(chunk, first_block + n_blocks - b0)
-        lo = b0 - first_block
-        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
-        H = src.estimate_channel(data["pilot_bits"], data["pilot_y_ls"], ebno_db)
-        U = src.equalize_rows(H, data["pilot_y"], 1, ebno_db, pad=d)
-        rows = src.equalize_rows(H, data["data_y"], F, ebno_db, pad=d, io=io)
-        if want_mmse:
-            src.mmse_detect_count(H, data["data_y"], data["data_bits"], F, ebno_db, err=mm_err[lo:lo + g],
-                                  bits=mm_bits[lo:lo + g])
-        bank.set_scaling(torch.full((g, n_io), p.input_scaling(ebno_db), dtype=torch.float64, device=src.device), None,
-                         torch.full((g, n_io), p.teacher_scale, dtype=torch.float64, device=src.device), None)
-        D = torch.zeros((g, t + d, n_io), dtype=torch.float64, device=src.device)
-        D[:, d:d + t] = _view_real(data["pilot_x"])
-        bank.fit(U, D, transient=transient, precision="f64", noise_mode="counter", seed=seeds[0], method=method,
-                 group_offset=b0, ridge=None if ridge is None else float(ridge))
-        flagged += bank.fit_status.ne(0).sum()
-        Y = bank.predict(rows, F, T=t + d, transient=transient, precision=precision, noise_mode="counter", seed=seeds[1],
-                         group_offset=b0, io=io)
-        p_i = torch.full((g,), p.p_i(ebno_db), dtype=torch.float64, device=src.device)
-        out = bank.detect_count(Y, data["data_bits"], p_i, F, p.n_sub, p.n_t, p.m, err=errors[lo:lo + g],
-                                bits=nbits[lo:lo + g], want_xhat=want_xhat)
-        if want_xhat:
-            kept.append(torch.view_as_complex(out[2].view(g * F, p.n_sub, p.n_t, 2).contiguous()))
-    if method != "qr" and int(flagged) != 0:
-        return equalized_esn_point(src, ebno_db, snr_idx, n_blocks, n_reservoir=n_reservoir, ridge=ridge, method="qr",
-                                   delay=delay, spectral_radius=spectral_radius, sparsity=sparsity, noise=noise,
-                                   precision=precision, reservoirs=reservoirs, pool=pool, io=io, first_block=first_block,
-                                   frames_per_block=frames_per_block, chunk_blocks=chunk_blocks, want_mmse=want_mmse,
-                                   want_xhat=want_xhat)
-    return (errors, nbits) + ((mm_err, mm_bits) if want_mmse else ()) + ((torch.cat(kept),) if want_xhat else ())
+
+    def point(method):
+        bank = ReservoirBank(n_io, n_io, n, *sets, teacher_forcing=True, noise=noise, device=src.device)
+        errors, nbits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) for _ in range(2))
+        mm_err, mm_bits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
+                           for _ in range(2))
+        flagged = torch.zeros((), dtype=torch.int64, device=src.device)
+        kept = []
+        for b0, g, lo in _chunks(first_block, n_blocks, chunk):
+            data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
+            H = src.estimate_channel(data["pilot_bits"], data["pilot_y_ls"], ebno_db)
+            U = src.equalize_rows(H, data["pilot_y"], 1, ebno_db, pad=d)
+            rows = src.equalize_rows(H, data["data_y"], F, ebno_db, pad=d, io=io)
+            if want_mmse:
+                src.mmse_detect_count(H, data["data_y"], data["data_bits"], F, ebno_db, err=mm_err[lo:lo + g],
+                                      bits=mm_bits[lo:lo + g])
+            bank.set_scaling(*group_scalings(g, n_io, p.input_scaling(ebno_db), n_io, p.teacher_scale, src.device))
+            _, D = pilot_rows(None, data["pilot_x"], d)
+            bank.fit(U, D, transient=transient, precision="f64", noise_mode="counter", seed=seeds[0], method=method,
+                     group_offset=b0, ridge=None if ridge is None else float(ridge))
+            flagged += bank.fit_status.ne(0).sum()
+            Y = bank.predict(rows, F, T=T, transient=transient, precision=precision, noise_mode="counter", seed=seeds[1],
+                             group_offset=b0, io=io)
+            out = bank.detect_count(Y, data["data_bits"], src.p_i(ebno_db, g), F, p.n_sub, p.n_t, p.m,
+                                    err=errors[lo:lo + g], bits=nbits[lo:lo + g], want_xhat=want_xhat)
+            if want_xhat:
+                kept.append(torch.view_as_complex(out[2].view(g * F, p.n_sub, p.n_t, 2).contiguous()))
+        return (errors, nbits) + ((mm_err, mm_bits) if want_mmse else ()) + ((torch.cat(kept),) if kept else ()), flagged
+
+    return _retry_with_qr(point, method)

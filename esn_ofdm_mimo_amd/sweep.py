@@ -1,7 +1,9 @@
 """The sweep of the Monte-Carlo harness (montecarlo.py tells the whole chain): draw_reservoir, the reference's host-side
-draw; blocks_for_rank and reduce_counters, the rank split and the path's one collective; RadiusCache and ChunkLayout,
-two named parts of DetectorSweep, the SNR sweep over Monte-Carlo blocks.  torch comes from _lib.require_gpu() or a
-local import: no GPU is needed to import."""
+draw, with reservoir_seed, host_reservoirs and host_reservoir_bank (the pool of a sweep or a point as a bank) and
+fit_e_dtype, which the points of points.py share; blocks_for_rank and reduce_counters, the rank split and the path's one
+collective; check_io and check_sweep_options, every refusal of DetectorSweep(...), made before the device is opened;
+RadiusCache and ChunkLayout, two named parts of DetectorSweep, the SNR sweep over Monte-Carlo blocks.  torch comes from
+_lib.require_gpu() or a local import: no GPU is needed to import."""
 from __future__ import annotations
 
 import numpy as np
@@ -9,7 +11,7 @@ import numpy as np
 from . import _lib
 from . import reservoirs as _reservoirs
 from .batched import ReservoirBank
-from .frames import FrameSource, _view_real
+from .frames import FrameSource, _view_real, pilot_rows
 from .link import LinkParams
 from .readout import _lambdas
 
@@ -43,6 +45,84 @@ def draw_reservoir(n_in, n_out, n_res, spectral_radius, sparsity, seed):
     w[rs.rand(n_res, n_res) < sparsity] = 0
     w *= spectral_radius / np.max(np.abs(np.linalg.eigvals(w)))
     return w, rs.rand(n_res, n_in) * 2 - 1, rs.rand(n_res, n_out) * 2 - 1
+
+
+def reservoir_seed(seed):
+    """Seed of the first reservoir set of the sweep with seed `seed`: set i of a pool is drawn from reservoir_seed + i."""
+    return seed * 7919 + 17
+
+
+def host_reservoirs(n_in, n_out, n_res, spectral_radius, sparsity, seeds):
+    """draw_reservoir of every seed, stacked: (W [S, n, n], W_in [S, n, n_in], W_feedb [S, n, n_out])."""
+    ws = [draw_reservoir(n_in, n_out, n_res, spectral_radius, sparsity, s) for s in seeds]
+    return tuple(np.stack([w[k] for w in ws]) for k in range(3))
+
+
+def host_reservoir_bank(n_in, n_out, n_res, spectral_radius, sparsity, seeds, **bank_kw):
+    """The teacher-forced ReservoirBank of the host draws of `seeds`, one weight set per seed."""
+    return ReservoirBank(n_in, n_out, n_res, *host_reservoirs(n_in, n_out, n_res, spectral_radius, sparsity, seeds),
+                         teacher_forcing=True, **bank_kw)
+
+
+def fit_e_dtype(bank, method, fit_precision, rows, cols):
+    """Element type of the extended states of a fit of [rows, cols] systems: float32 on the all-GPU fast path (fp16 / bf16
+    harvest + Cholesky, asked for or what "auto" picks at this shape) -- the state columns are exactly representable, the
+    fit is unchanged to ~1e-7 -- else float64."""
+    chol = method == "chol" or (method == "auto" and bank.chol_fits(rows, cols))
+    return "f32" if (chol and fit_precision in ("f16", "bf16")) else "f64"
+
+
+def check_io(io, precision):
+    if io not in ("f64", "f32"):
+        raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
+    if io == "f32" and precision == "f64":
+        raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
+
+
+def check_sweep_options(params, precision, solve_method, train_ebno, io, ridge, ridge_grid, radius, radius_precision,
+                        track, track_window, n_pilots, track_forget):
+    """What DetectorSweep refuses, from its options and the link alone: no device is touched."""
+    check_io(io, precision)
+    gram = solve_method == "gram"
+    if not 0.0 <= float(track_forget) <= 1.0:
+        raise ValueError(f"track_forget must lie in [0, 1], not {track_forget}")
+    if track not in (None, "decisions", "genie"):
+        raise ValueError(f"track must be None, 'decisions' or 'genie', not {track!r}")
+    if track is not None:
+        if int(track_window) < 1:
+            raise ValueError(f"track_window must be at least 1 (the training sets a re-fit sees), not {track_window}")
+        grid_refused = ridge_grid is not None and not (gram and int(n_pilots) >= 2)
+        for name, given in (("ridge_grid", grid_refused), ("train_ebno", train_ebno is not None),
+                            ("params.continuation", params.continuation), ("io='f32'", io == "f32")):
+            if given:
+                raise ValueError(f"track={track!r} does not go with {name}: the re-fits are plain pinv / ridge solves "
+                                 "on float64 frames of the actual Eb/No, every frame from a fresh state")
+    if int(n_pilots) != n_pilots or int(n_pilots) < 1:
+        raise ValueError(f"n_pilots must be a whole number of at least 1, not {n_pilots!r}")
+    if gram and ridge is None and ridge_grid is None:
+        raise ValueError("solve_method='gram' needs ridge or ridge_grid: the normal equations of fewer rows than "
+                         "columns have no pinv solution")
+    if gram and ridge_grid is not None and int(n_pilots) == 1:
+        raise ValueError("solve_method='gram' chooses among ridge_grid on a held-out pilot: it needs n_pilots >= 2")
+    if gram and params.continuation:
+        raise ValueError("solve_method='gram' does not go with params.continuation: every pilot is fitted from a zero "
+                         "state and no training-final state is kept")
+    if int(n_pilots) > 1:
+        for name, given in (("track", track is not None and not gram), ("train_ebno", train_ebno is not None),
+                            ("params.continuation", params.continuation)):
+            if given:
+                raise ValueError(f"n_pilots={n_pilots} does not go with {name}: several pilots are fitted once, at "
+                                 "the actual Eb/No, each from a zero state")
+    if ridge is not None and ridge_grid is not None:
+        raise ValueError("give ridge or ridge_grid, not both")
+    if int(n_pilots) > 1 and ridge_grid is not None and not 1 <= np.size(ridge_grid) <= ReservoirBank.HOLDOUT_MAX_GRID:
+        raise ValueError(f"ridge_grid holds {np.size(ridge_grid)} candidates, the hold-out choice takes 1 to "
+                         f"{ReservoirBank.HOLDOUT_MAX_GRID}")
+    if radius not in ("host", "device"):
+        raise ValueError(f"radius must be 'host' or 'device', not {radius!r}")
+    if radius_precision not in _reservoirs.RADIUS_PRECISIONS:
+        raise ValueError(f"radius_precision must be one of {sorted(_reservoirs.RADIUS_PRECISIONS)}, "
+                         f"not {radius_precision!r}")
 
 
 def stream_seed(seed, snr_idx, leg):
@@ -197,79 +277,31 @@ class DetectorSweep:
         state-noise legs and keys are those of the other solve methods.  train_ebno, params.continuation and io="f32"
         stay refused with track, and so does ridge_grid with one pilot; params.continuation is refused in this mode at
         any n_pilots (every pilot is fitted from a zero state: no training-final state exists)."""
-        if io not in ("f64", "f32"):
-            raise ValueError(f"io must be 'f64' or 'f32', not {io!r}")
-        if io == "f32" and precision == "f64":
-            raise ValueError("io='f32' needs precision f32, f16 or bf16 (the float64 kernels read and write float64)")
-        self.io = io
-        gram = solve_method == "gram"
-        if not 0.0 <= float(track_forget) <= 1.0:
-            raise ValueError(f"track_forget must lie in [0, 1], not {track_forget}")
-        self.track_forget = float(track_forget)
-        if track not in (None, "decisions", "genie"):
-            raise ValueError(f"track must be None, 'decisions' or 'genie', not {track!r}")
-        if track is not None:
-            if int(track_window) < 1:
-                raise ValueError(f"track_window must be at least 1 (the training sets a re-fit sees), not {track_window}")
-            grid_refused = ridge_grid is not None and not (gram and int(n_pilots) >= 2)
-            for name, given in (("ridge_grid", grid_refused), ("train_ebno", train_ebno is not None),
-                                ("params.continuation", params.continuation), ("io='f32'", io == "f32")):
-                if given:
-                    raise ValueError(f"track={track!r} does not go with {name}: the re-fits are plain pinv / ridge solves "
-                                     "on float64 frames of the actual Eb/No, every frame from a fresh state")
-        self.track, self.track_window = track, int(track_window)
+        check_sweep_options(params, precision, solve_method, train_ebno, io, ridge, ridge_grid, radius, radius_precision,
+                            track, track_window, n_pilots, track_forget)
+        self.io, self.track_forget = io, float(track_forget)
+        self.track, self.track_window, self.n_pilots = track, int(track_window), int(n_pilots)
         self.keep_track_xhat, self.track_xhat = False, None
-        if int(n_pilots) != n_pilots or int(n_pilots) < 1:
-            raise ValueError(f"n_pilots must be a whole number of at least 1, not {n_pilots!r}")
-        if gram and ridge is None and ridge_grid is None:
-            raise ValueError("solve_method='gram' needs ridge or ridge_grid: the normal equations of fewer rows than "
-                             "columns have no pinv solution")
-        if gram and ridge_grid is not None and int(n_pilots) == 1:
-            raise ValueError("solve_method='gram' chooses among ridge_grid on a held-out pilot: it needs n_pilots >= 2")
-        if gram and params.continuation:
-            raise ValueError("solve_method='gram' does not go with params.continuation: every pilot is fitted from a zero "
-                             "state and no training-final state is kept")
-        if int(n_pilots) > 1:
-            for name, given in (("track", track is not None and not gram), ("train_ebno", train_ebno is not None),
-                                ("params.continuation", params.continuation)):
-                if given:
-                    raise ValueError(f"n_pilots={n_pilots} does not go with {name}: several pilots are fitted once, at "
-                                     "the actual Eb/No, each from a zero state")
-            if ridge is not None and ridge_grid is not None:
-                raise ValueError("give ridge or ridge_grid, not both")
-            if ridge_grid is not None and not 1 <= np.size(ridge_grid) <= ReservoirBank.HOLDOUT_MAX_GRID:
-                raise ValueError(f"ridge_grid holds {np.size(ridge_grid)} candidates, the hold-out choice takes 1 to "
-                                 f"{ReservoirBank.HOLDOUT_MAX_GRID}")
-        self.n_pilots = int(n_pilots)
         torch = _lib.require_gpu()
         self.torch, self.p = torch, params
         self.rank, self.world = rank, world_size
         self.precision, self.fit_precision = precision, fit_precision
-        self.solve_method = solve_method
-        self.ridge = ridge
-        if ridge is not None and ridge_grid is not None:
-            raise ValueError("give ridge or ridge_grid, not both")
+        self.solve_method, self.ridge = solve_method, ridge
         self.ridge_grid = None if ridge_grid is None else np.array(ridge_grid, dtype=np.float64).reshape(-1)
         self.ridge_choice_counts = {}
         self.symbol_counts, self.symbol_error_counts = bool(symbol_counts), {}
         self.train_ebno = train_ebno      # not None: every ESN is trained at this fixed Eb/No (SURVEY Q14)
         self.n_in, self.n_out, self.n_res = 2 * params.n_r, 2 * params.n_t, n_reservoir
-        self.seed = seed
+        self.seed, self.reservoir_seed = seed, reservoir_seed(seed)
         self.src = FrameSource(params, device, seed)
         self.device = self.src.device
         # the candidates on the device, copied once: [L]
         self._grid_t = None if ridge_grid is None else _lambdas(torch, self.device, self.ridge_grid, 1, grid=True)[0][0]
         self._ebno = self._train_bufs = self._fit_io = self._cont = None     # set_snr / train leave these
-        if radius not in ("host", "device"):
-            raise ValueError(f"radius must be 'host' or 'device', not {radius!r}")
-        if radius_precision not in _reservoirs.RADIUS_PRECISIONS:
-            raise ValueError(f"radius_precision must be one of {sorted(_reservoirs.RADIUS_PRECISIONS)}, "
-                             f"not {radius_precision!r}")
         self.radius_precision, self.radius_squarings = radius_precision, int(radius_squarings)
         self.fresh_radius_cache, self.fresh_radius_hits, self._radius_cache = bool(fresh_radius_cache), 0, None
         self.reservoirs = reservoirs
         self._res_args = (self.n_in, self.n_out, int(n_reservoir), float(spectral_radius), float(sparsity))
-        self.reservoir_seed = seed * 7919 + 17
         self.bank = self._make_bank(pool, radius, noise)
 
     @property
@@ -286,21 +318,17 @@ class DetectorSweep:
         """The bank of the constructor: "fresh" holds block 0's reservoir until the first chunk swaps its own in;
         "shared" / "per_block" hold 1 / `pool` sets, set i drawn from reservoir_seed + i on the host or, with
         radius="device", from the same uniforms scaled on the device."""
-        torch = self.torch
-        n_in, n_out, n, rho, sparsity = self._res_args
+        n_in, n_out, n = self._res_args[:3]
         kw = dict(teacher_forcing=True, noise=noise, device=self.device)
         if self.reservoirs == "fresh":
-            bank = ReservoirBank.generate(*self._res_args, seed=self.reservoir_seed, first_set=0, n_sets=1,
+            return ReservoirBank.generate(*self._res_args, seed=self.reservoir_seed, first_set=0, n_sets=1,
                                           radius_precision=self.radius_precision, n_squarings=self.radius_squarings, **kw)
-        else:
-            seeds = [self.reservoir_seed + i for i in range(1 if self.reservoirs == "shared" else int(pool))]
-            if radius == "device":
-                sets = [self._device_scaled(s) for s in seeds]
-                bank = ReservoirBank(n_in, n_out, n, np.zeros((n, n)), np.zeros((n, n_in)), np.zeros((n, n_out)), **kw)
-                bank.set_weights(*(torch.cat([w[k] for w in sets]) for k in range(3)))
-            else:
-                ws = [draw_reservoir(n_in, n_out, n, rho, sparsity, s) for s in seeds]
-                bank = ReservoirBank(n_in, n_out, n, *(np.stack([w[k] for w in ws]) for k in range(3)), **kw)
+        seeds = [self.reservoir_seed + i for i in range(1 if self.reservoirs == "shared" else int(pool))]
+        if radius == "host":
+            return host_reservoir_bank(*self._res_args, seeds, noise=noise, device=self.device)
+        sets = [self._device_scaled(s) for s in seeds]
+        bank = ReservoirBank(n_in, n_out, n, np.zeros((n, n)), np.zeros((n, n_in)), np.zeros((n, n_out)), **kw)
+        bank.set_weights(*(self.torch.cat([w[k] for w in sets]) for k in range(3)))
         return bank
 
     def _device_scaled(self, seed):
@@ -354,7 +382,7 @@ class DetectorSweep:
         ones_out = torch.ones((n_groups, self.n_out), dtype=torch.float64, device=self.device)
         self.bank.set_scaling(ones_in * p.input_scaling(ebno_db if scale_ebno is None else scale_ebno), None,
                               ones_out * p.teacher_scale, None)
-        self.p_i = torch.full((n_groups,), p.p_i(ebno_db), dtype=torch.float64, device=self.device)
+        self.p_i = self.src.p_i(ebno_db, n_groups)
         self._ebno = ebno_db
 
     def ridge_at(self, ebno_db):
@@ -370,23 +398,15 @@ class DetectorSweep:
     def train(self, pilot_y, pilot_x, seed=0, group_offset=0):
         """helper_mimo_esn_generic.py:58-86 for G blocks: delay d, nForget = d + CP, one harvest + solve.
         group_offset = global index of the first block (noise key and weight set follow the global block)."""
-        torch, p = self.torch, self.p
-        d = p.delay
+        p, d = self.p, self.p.delay
         g, t = pilot_y.shape[0], pilot_y.shape[1]
         # zero-padded pilot buffers are kept between calls of the same shape (the padding rows are never written)
-        io = self._train_bufs
-        if io is None or io[0].shape != (g, t + d, self.n_in):
-            io = self._train_bufs = (torch.zeros((g, t + d, self.n_in), dtype=torch.float64, device=self.device),
-                                     torch.zeros((g, t + d, self.n_out), dtype=torch.float64, device=self.device))
-        U, D = io
-        U[:, :t] = _view_real(pilot_y)
-        D[:, d:d + t] = _view_real(pilot_x)
+        kept = self._train_bufs
+        fits = kept is not None and kept[0].shape == (g, t + d, self.n_in)
+        U, D = self._train_bufs = pilot_rows(pilot_y, pilot_x, d, out=kept if fits else None)
         self._fit_io = (U, D, p.forget)
-        # float32 extended states on the all-GPU fast path (fp16/bf16 harvest + Cholesky): the state
-        # columns are exactly representable, the fit is unchanged to ~1e-7
-        rows, cols = t + d - p.forget, self.bank.n_reservoir + self.n_in
-        chol = self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
-        e_dtype = self._fit_e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
+        e_dtype = self._fit_e_dtype = fit_e_dtype(self.bank, self.solve_method, self.fit_precision, t + d - p.forget,
+                                                  self.bank.n_reservoir + self.n_in)
         E = self.bank.fit(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
                           seed=seed, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,
                           ridge=self.ridge_at(self._ebno), ridge_grid=self._grid_t)
@@ -406,17 +426,12 @@ class DetectorSweep:
         """train for P pilots per block: pilots_y [G, P, T, n_r], pilots_x [G, P, T, n_t] (blocks_fast(n_pilots=P)),
         through ReservoirBank.fit_pilots.  Returns the stacked extended states [G, P rows, cols]; fit_io becomes
         (None, the stacked teacher, 0), which is what repair_fit needs."""
-        torch, p = self.torch, self.p
-        d = p.delay
-        g, P, t = pilots_y.shape[:3]
-        U = torch.zeros((g, P, t + d, self.n_in), dtype=torch.float64, device=self.device)
-        D = torch.zeros((g, P, t + d, self.n_out), dtype=torch.float64, device=self.device)
-        U[:, :, :t] = _view_real(pilots_y)
-        D[:, :, d:d + t] = _view_real(pilots_x)
-        rows, cols = P * (t + d - p.forget), self.bank.n_reservoir + self.n_in
+        p, d = self.p, self.p.delay
+        P, t = pilots_y.shape[1:3]
+        U, D = pilot_rows(pilots_y, pilots_x, d)
         gram = self.solve_method == "gram"          # (the accumulate kernel reads float32 states as the Cholesky ones do)
-        chol = gram or self.solve_method == "chol" or (self.solve_method == "auto" and self.bank.chol_fits(rows, cols))
-        e_dtype = self._fit_e_dtype = "f32" if (chol and self.fit_precision in ("f16", "bf16")) else "f64"
+        e_dtype = self._fit_e_dtype = fit_e_dtype(self.bank, "chol" if gram else self.solve_method, self.fit_precision,
+                                                  P * (t + d - p.forget), self.bank.n_reservoir + self.n_in)
         seeds = [self.stream_seed(snr_idx, 0)] + [self.stream_seed(snr_idx, self.PILOT_LEG0 + q) for q in range(1, P)]
         E = self.bank.fit_pilots(U, D, transient=p.forget, precision=self.fit_precision, noise_mode="counter",
                                  seed=seeds, method=self.solve_method, e_dtype=e_dtype, group_offset=group_offset,

@@ -1,7 +1,8 @@
 """The Monte-Carlo harness computes what the commit named in tests/golden/sweep_parent_counters.json computed: for one
 small sweep per constructor arm and per branch of a chunk, and for the two coded comparison points, every counter,
-fits_repaired, the bytes of W_out and the per-candidate, per-symbol and cache-hit counts are equal entry for entry
-(cases and recorder: tools/record_sweep_counters.py).  Each sweep runs once."""
+fits_repaired, the bytes of W_out and the per-candidate, per-symbol and cache-hit counts are equal entry for entry, and
+so are the per-block counters of the seven uncoded comparison points over one full and one short chunk
+(cases and recorder: tools/record_sweep_counters.py).  Each sweep and each point runs once."""
 import functools
 import importlib.util
 import json
@@ -17,7 +18,7 @@ _spec = importlib.util.spec_from_file_location("record_sweep_counters",
 rec = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(rec)
 
-NAMES = list(rec.CASES) + [rec.POINTS_CASE]
+NAMES = list(rec.CASES) + [rec.POINTS_CASE] + list(rec.POINT_CASES)
 
 
 @functools.lru_cache(maxsize=None)

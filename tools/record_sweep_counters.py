@@ -1,7 +1,8 @@
-"""Records what small DetectorSweep runs and the two coded comparison points produce -- the int64 counters, fits_repaired,
-the SHA-256 of the bank's W_out after the run and, where a case has them, ridge_choice_counts, symbol_error_counts and
-fresh_radius_hits -- into tests/golden/sweep_parent_counters.json for tests/test_gpu_sweep_counters.py: a rewrite of the
-Monte-Carlo harness that is meant to keep its results keeps every one of these entries.  Needs a GPU.
+"""Records what small DetectorSweep runs, the two coded comparison points and the seven uncoded comparison points produce
+-- the int64 counters, fits_repaired, the SHA-256 of the bank's W_out after the run and, where a case has them,
+ridge_choice_counts, symbol_error_counts and fresh_radius_hits; of an uncoded point its counters per block -- into
+tests/golden/sweep_parent_counters.json for tests/test_gpu_sweep_counters.py: a rewrite of the Monte-Carlo harness that
+is meant to keep its results keeps every one of these entries.  Needs a GPU.
 
 Run it from the tree of the commit whose results are to be pinned (the package next to this tool is the one loaded):
 
@@ -11,7 +12,9 @@ Every case runs twice and the file is written only if the two runs agree: a case
 recorded commit pins nothing.  One case per constructor arm and per branch of a chunk (CASES); unless a case says
 otherwise: LinkParams.block_fading(n_t=2, n_r=2, n_sub=64) with three data symbols per pilot, n_reservoir 64, seed 7,
 run([6, 18] dB, 6 blocks per point, chunks of 4), so every point has one full and one short chunk and no cluster kernel
-or workspace path is involved.  The coded points use LdpcCode(64 * 4 = 256, 4, 8, seed=11).
+or workspace path is involved.  The coded points use LdpcCode(64 * 4 = 256, 4, 8, seed=11).  The uncoded points
+(POINT_CASES) run at 18 dB on FrameSource(small_link(), seed 7): 6 blocks from block 2 on in chunks of 4, three data
+frames per block -- again one full and one short chunk, and a first block that is not 0.
 
 The reservoirs of most cases are drawn on the host through np.linalg.eigvals, which follows the host's LAPACK; for these
 the file also holds the SHA-256 of the drawn W (host_draw_digest, computed here without the package), so that a
@@ -71,11 +74,34 @@ CASES = {
     "siso_continuation": (siso_link, dict(n_reservoir=32), {}),
     "rank_1_of_2": (small_link, dict(rank=1, world_size=2), {}),
     "bench_link": (bench_link, dict(), dict(frames_per_block=2)),
+    "track_decisions": (small_link, dict(track="decisions", track_window=2, symbol_counts=True), {}),
+    "track_genie": (small_link, dict(track="genie", ridge=1e-3, symbol_counts=True), {}),
+    "pilots3_grid": (small_link, dict(n_pilots=3, ridge_grid=[1e-6, 1e-3, 1e-1]), {}),
+    "gram_track": (small_link, dict(solve_method="gram", ridge=1e-3, n_pilots=2, track="decisions", track_forget=0.9,
+                                    symbol_counts=True), {}),
+    "chol_f16": (small_link, dict(solve_method="chol", fit_precision="f16", precision="f16"), {}),
 }
 DEVICE_DRAWN = ("fresh_cache", "fresh_no_cache", "fresh_f16x2", "device_radius_per_block")
 POINTS_CASE = "coded_points"
-HOST_DRAWN = tuple(k for k in CASES if k not in DEVICE_DRAWN) + (POINTS_CASE,)
 POINTS_POOL = 3
+POINT_EBNO, POINT_SNR_IDX = 18.0, 1
+POINT_BLOCKS = dict(n_blocks=6, first_block=2, chunk_blocks=4, frames_per_block=3)
+# name: (function of esn_ofdm_mimo_amd.montecarlo, its keywords beyond POINT_BLOCKS)
+POINT_CASES = {
+    "baseline_tracking_point": ("baseline_tracking_point", dict(track="decisions", window=2)),
+    "elm_point": ("elm_point", dict(n_hidden=16, window=4, weights="per_block", ridge=1e-3)),
+    "fnn_point": ("fnn_point", dict(n_hidden=16, window=4, epochs=3, weights="per_block")),
+    "cnn_point": ("cnn_point", dict(channels=(4, 8), kernel=3, epochs=3)),
+    "lstm_point": ("lstm_point", dict(n_hidden=8, epochs=3, slice="reference")),
+    "ensemble_point_shared": ("ensemble_point", dict(n_members=2, n_reservoir=32, reservoirs="shared",
+                                                     member_counts=True)),
+    "ensemble_point_fresh_f16_io32": ("ensemble_point", dict(n_members=2, n_reservoir=32, reservoirs="fresh",
+                                                             precision="f16", fit_precision="f16", io="f32")),
+    "equalized_esn_point": ("equalized_esn_point", dict(n_reservoir=8, reservoirs="per_block", pool=2, want_mmse=True)),
+}
+# the host draws of the points that have one: name -> (n_reservoir, seeds beyond SEED * 7919 + 17)
+POINT_HOST_DRAWS = {"ensemble_point_shared": (32, (0, 104729)), "equalized_esn_point": (8, (0, 1))}
+HOST_DRAWN = tuple(k for k in CASES if k not in DEVICE_DRAWN) + (POINTS_CASE,) + tuple(POINT_HOST_DRAWS)
 
 
 def _sha(a):
@@ -86,15 +112,17 @@ def host_draw_digest(name):
     """SHA-256 of the W matrices the case's constructor draws on the host, stacked: the reference's recipe (uniform - 0.5,
     sparsify, scale by max |eigvals|) with the sweep's seeds, written out here so that it does not pass through the
     package under test.  No GPU."""
-    if name == POINTS_CASE:
-        n_res, n_sets, seed = N_RES, POINTS_POOL, SEED
+    if name in POINT_HOST_DRAWS:
+        n_res, offsets = POINT_HOST_DRAWS[name]
+    elif name == POINTS_CASE:
+        n_res, offsets = N_RES, range(POINTS_POOL)
     else:
         _, kw, _ = CASES[name]
-        n_res, seed = kw.get("n_reservoir", N_RES), SEED
-        n_sets = kw.get("pool", 8) if kw.get("reservoirs", "shared") == "per_block" else 1
+        n_res = kw.get("n_reservoir", N_RES)
+        offsets = range(kw.get("pool", 8) if kw.get("reservoirs", "shared") == "per_block" else 1)
     ws = []
-    for i in range(n_sets):
-        rs = np.random.RandomState(seed * 7919 + 17 + i)
+    for i in offsets:
+        rs = np.random.RandomState(SEED * 7919 + 17 + i)
         w = rs.rand(n_res, n_res) - 0.5
         w[rs.rand(n_res, n_res) < 0.1] = 0
         ws.append(w * (0.9 / np.max(np.abs(np.linalg.eigvals(w)))))
@@ -153,7 +181,19 @@ def points_record():
                              "train_fixed": _sha(fixed.bank.W_out.cpu().numpy())}}
 
 
+def point_record(name):
+    """One uncoded comparison point: what it returns, as lists (of the baseline's dict: errors, bits and failed)."""
+    from esn_ofdm_mimo_amd import montecarlo as mc
+    fn, kw = POINT_CASES[name]
+    out = getattr(mc, fn)(mc.FrameSource(small_link(), seed=SEED), POINT_EBNO, POINT_SNR_IDX, **POINT_BLOCKS, **kw)
+    if isinstance(out, dict):
+        return {"errors": out["errors"].tolist(), "bits": out["bits"].tolist(), "failed": int(out["failed"])}
+    return {"outputs": [t.cpu().numpy().tolist() for t in out]}
+
+
 def record(name):
+    if name in POINT_CASES:
+        return point_record(name)
     return points_record() if name == POINTS_CASE else sweep_record(name)
 
 
@@ -164,12 +204,12 @@ def main():
     args = ap.parse_args()
     import torch
     cases = {}
-    for name in list(CASES) + [POINTS_CASE]:
+    for name in list(CASES) + [POINTS_CASE] + list(POINT_CASES):
         first, second = record(name), record(name)
         if first != second:
             sys.exit(f"{name}: two runs of this tree differ, nothing written\n{first}\n{second}")
         cases[name] = first
-        print(f"{name}: {first.get('counters', '')}", flush=True)
+        print(f"{name}: {first.get('counters', first.get('outputs', ''))}", flush=True)
     doc = {"commit": args.commit, "numpy": np.__version__, "torch": torch.__version__,
            "device": torch.cuda.get_device_name(0), "seed": SEED,
            "host_draw_sha256": {name: host_draw_digest(name) for name in HOST_DRAWN}, "cases": cases}
