@@ -86,6 +86,45 @@ class DetectorTail:
                      ptr(xh), _lib.stream_handle()), "esn_detect_count_f32" if y32 else "esn_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
+    def detect_llr(self, Y, tx_bits, p_i, frames_per_group, n_sub, n_t, bits_per_sym, weights=None, bias=None,
+                   err=None, bits=None, want_xhat=False):
+        """detect_count and, in the same launch, the soft outputs of its X_hat (esn_detect_llr; a float32 Y goes to
+        esn_detect_llr_f32): the frame's decision-directed sigma2 [B] and llr [B, n_t, N m] = weights (d1 - d0)(X_hat /
+        bias) / sigma2 in the decoder's layout, weights / bias float64 [G, N, n_t] (FrameSource.mmse_sinr) or None = 1:
+        what LdpcCode.llrs gives on that X_hat, which never goes to memory unless want_xhat.  tx_bits None: nothing is
+        counted.  Returns (err, bits, llr, sigma2[, X_hat]); err / bits are None without tx_bits."""
+        torch = self.torch
+        y32 = getattr(Y, "dtype", None) in (torch.float32, np.float32)
+        Y = _as_dev(Y, torch, self.device, torch.float32 if y32 else None)
+        b, fpg = Y.shape[0], int(frames_per_group)
+        if fpg < 1:
+            raise ValueError(f"frames_per_group = {frames_per_group} must be positive")
+        g = (b + fpg - 1) // fpg
+        p_i = _as_dev(p_i, torch, self.device)
+        tx_bits = _as_dev(tx_bits, torch, self.device, dtype=torch.uint8)
+        for name, t in (("weights", weights), ("bias", bias)):     # as LdpcCode.llrs: float64 as given, never cast
+            if t is not None and (getattr(t, "dtype", None) not in (torch.float64, np.float64) or len(t.shape) != 3
+                                  or tuple(t.shape[1:]) != (n_sub, n_t) or t.shape[0] < g):
+                raise ValueError(f"{name} must be float64 [G >= {g}, {n_sub}, {n_t}], not "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        weights, bias = _as_dev(weights, torch, self.device), _as_dev(bias, torch, self.device)
+        with torch.cuda.device(self.device):
+            if tx_bits is not None:
+                if err is None:
+                    err = torch.zeros(g, dtype=torch.int64, device=self.device)
+                if bits is None:
+                    bits = torch.zeros(g, dtype=torch.int64, device=self.device)
+            else:
+                err = bits = None
+            xh = torch.empty((b, n_sub, 2 * n_t), dtype=torch.float64, device=self.device) if want_xhat else None
+            llr = torch.empty((b, n_t, n_sub * int(bits_per_sym)), dtype=torch.float64, device=self.device)
+            s2 = torch.empty(b, dtype=torch.float64, device=self.device)
+            name = "esn_detect_llr_f32" if y32 else "esn_detect_llr"
+            check(getattr(self.lib, name)(ptr(Y), b, fpg, int(n_sub), int(n_t), int(bits_per_sym), ptr(p_i), ptr(tx_bits),
+                                          ptr(err), ptr(bits), ptr(weights), ptr(bias), ptr(llr), ptr(s2), ptr(xh),
+                                          _lib.stream_handle()), name)
+        return (err, bits, llr, s2) + ((xh,) if want_xhat else ())
+
     def detect_remod(self, Y, tx_bits, p_i, frames_per_group, n_sub, cp, delay, n_t, bits_per_sym,
                      err=None, bits=None, want_xhat=False, want_bits=False):
         """detect_count and, in the same launch, the decisions re-modulated (esn_detect_remod): Y [B, N, 2 n_t] float64

@@ -10,7 +10,9 @@ call sites ``Demo_MIMO_4x8_Sionna_CDL_ESN_v2.py:250,495-496,505-506``).  What is
                             the reference's code differs from run to run; only the ensemble is fixed).
   * ``encode``              ``G.dot(u) % 2`` (:90-93)            -> ``esn_ldpc_encode``
   * ``llrs``                ``qam_llrs_maxlog`` + ``est_sigma2_from_decision`` (:66-93, :459-469)
-                                                                 -> ``esn_qam_llr``
+                                                                 -> ``esn_qam_llr``; with weights / bias (an
+                            extension: the MMSE equaliser's SINR per subcarrier and stream, FrameSource.mmse_sinr)
+                                                                 -> ``esn_qam_llr_weighted``
   * ``fit_calibration``     ``fit_logreg_1d`` (:108-119, :513-523): 400 plain gradient steps from
                             (1, 0), lr 0.1, l2 1e-3 -- per-SNR host logic of the driver, run as
                             torch tensor ops on the device (4 scalars per bit position).
@@ -94,16 +96,34 @@ class LdpcCode:
         return bits
 
     # ------------------------------------------------------------------ receiver side
-    def llrs(self, x_hat, bits_per_sym):
-        """x_hat complex128 [B, N, n_t] -> (llr float64 [B, n_t, N*m], sigma2 [B])."""
+    def llrs(self, x_hat, bits_per_sym, weights=None, bias=None, frames_per_group=1):
+        """x_hat complex128 [B, N, n_t] -> (llr float64 [B, n_t, N*m], sigma2 [B]).  weights / bias float64 [G, N, n_t]
+        (FrameSource.mmse_sinr; frame f reads group f // frames_per_group): llr = weights (d1 - d0)(x_hat / bias) /
+        sigma2 through esn_qam_llr_weighted, sigma2 unchanged; both None: esn_qam_llr."""
         torch = self.torch
         x_hat = x_hat.contiguous()
         b, n_sub, n_t = x_hat.shape
+        flat = weights is None and bias is None
+        if not flat:
+            if int(frames_per_group) < 1:
+                raise ValueError(f"frames_per_group = {frames_per_group} must be positive")
+            g = (b + int(frames_per_group) - 1) // int(frames_per_group)
+            for name, t in (("weights", weights), ("bias", bias)):
+                if t is not None and (t.dtype != torch.float64 or t.dim() != 3 or tuple(t.shape[1:]) != (n_sub, n_t)
+                                      or t.shape[0] < g):
+                    raise ValueError(f"{name} must be float64 [G >= {g}, {n_sub}, {n_t}], not {t.dtype} {tuple(t.shape)}")
+            weights = None if weights is None else weights.to(self.device).contiguous()
+            bias = None if bias is None else bias.to(self.device).contiguous()
         with torch.cuda.device(self.device):
             llr = torch.empty((b, n_t, n_sub * bits_per_sym), dtype=torch.float64, device=self.device)
             s2 = torch.empty(b, dtype=torch.float64, device=self.device)
-            check(self.lib.esn_qam_llr(b, n_sub, n_t, bits_per_sym, ptr(x_hat), ptr(llr), ptr(s2),
-                                       _lib.stream_handle()), "esn_qam_llr")
+            if flat:
+                check(self.lib.esn_qam_llr(b, n_sub, n_t, bits_per_sym, ptr(x_hat), ptr(llr), ptr(s2),
+                                           _lib.stream_handle()), "esn_qam_llr")
+            else:
+                check(self.lib.esn_qam_llr_weighted(b, int(frames_per_group), n_sub, n_t, bits_per_sym, ptr(x_hat),
+                                                    ptr(weights), ptr(bias), ptr(llr), ptr(s2), _lib.stream_handle()),
+                      "esn_qam_llr_weighted")
         return llr, s2
 
     def fit_calibration(self, llr, bits, bits_per_sym, maxiter=400, lr=0.1, l2=1e-3):

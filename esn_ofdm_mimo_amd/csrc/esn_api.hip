@@ -1441,6 +1441,91 @@ int esn_qam_llr(int n_frames, int n_sub, int n_t, int bits_per_sym, const double
     return hip_fail(launch_qam_llr(lp, (hipStream_t)stream), "esn_qam_llr");
 }
 
+// ---- SINR-weighted soft outputs (esn_soft.hip): every refusal below comes before any HIP call
+static int check_soft_shape(const char* who, int n_sub, int n_t, int* log2n) {
+    if (int rc = check_n_sub(who, n_sub, log2n)) return rc;
+    if (n_t < 1 || n_t > 4) return fail(-1, "%s: n_t=%d, 1 to 4 are served", who, n_t);
+    return 0;
+}
+static int check_soft_frames(const char* who, int n_frames, int frames_per_group, int bits_per_sym) {
+    if (n_frames <= 0) return fail(-1, "%s: n_frames=%d must be positive", who, n_frames);
+    if (frames_per_group <= 0) return fail(-1, "%s: frames_per_group=%d must be positive", who, frames_per_group);
+    return check_square_qam(who, bits_per_sym);
+}
+
+int esn_mmse_sinr(int n_blocks, int n_sub, int n_t, int n_r, const double* p_i, double no, const double* H, double* w,
+                  double* mu, double* gamma_mean, void* stream) {
+    const char* who = "esn_mmse_sinr";
+    int l2;
+    if (int rc = check_soft_shape(who, n_sub, n_t, &l2)) return rc;
+    if (n_blocks <= 0 || n_r <= 0) return fail(-1, "%s: n_blocks=%d and n_r=%d must be positive", who, n_blocks, n_r);
+    if (!p_i || !H) return fail(-1, "%s: p_i or H is null", who);
+    if (!w || !mu) return fail(-1, "%s: w or mu is null", who);
+    SinrParams sp;
+    sp.n_blocks = n_blocks; sp.n_sub = n_sub; sp.n_t = n_t; sp.n_r = n_r; sp.p_i = p_i; sp.no = no; sp.H = H;
+    sp.w = w; sp.mu = mu; sp.gamma_mean = gamma_mean;
+    return hip_fail(launch_mmse_sinr(sp, (hipStream_t)stream), who);
+}
+
+int esn_qam_llr_weighted(int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym, const double* X_hat,
+                         const double* w, const double* mu, double* llr, double* sigma2, void* stream) {
+    const char* who = "esn_qam_llr_weighted";
+    int l2;
+    if (int rc = check_soft_shape(who, n_sub, n_t, &l2)) return rc;
+    if (int rc = check_soft_frames(who, n_frames, frames_per_group, bits_per_sym)) return rc;
+    if (!X_hat) return fail(-1, "%s: X_hat is null", who);
+    if (!llr) return fail(-1, "%s: llr is null", who);
+    SoftLlrParams sp;
+    sp.l.n_frames = n_frames; sp.l.n_sub = n_sub; sp.l.n_t = n_t; sp.l.m = bits_per_sym; sp.l.X_hat = X_hat;
+    sp.l.llr = llr; sp.l.sigma2 = sigma2; sp.frames_per_group = frames_per_group; sp.w = w; sp.mu = mu;
+    return hip_fail(launch_qam_llr_weighted(sp, (hipStream_t)stream), who);
+}
+
+size_t esn_detect_llr_lds_bytes(int n_sub, int n_t) {
+    return (n_sub > 0 && n_t > 0) ? detect_llr_lds_bytes(n_sub, n_t) : 0;
+}
+
+static int detect_llr_common(const char* who, bool io32, const void* Y, int n_frames, int frames_per_group, int n_sub,
+                             int n_t, int bits_per_sym, const double* p_i, const uint8_t* tx_bits, long long* err_count,
+                             long long* bit_count, const double* w, const double* mu, double* llr, double* sigma2,
+                             double* X_hat, void* stream) {
+    int l2;
+    if (int rc = check_soft_shape(who, n_sub, n_t, &l2)) return rc;
+    if (int rc = check_soft_frames(who, n_frames, frames_per_group, bits_per_sym)) return rc;
+    if (!Y || !p_i) return fail(-1, "%s: Y or p_i is null", who);
+    if (!llr) return fail(-1, "%s: llr is null", who);
+    if (tx_bits && (!err_count || !bit_count)) return fail(-1, "%s: tx_bits given without err_count / bit_count", who);
+    if (((uintptr_t)Y & (io32 ? 7 : 15)) != 0) return fail(-1, "%s: Y must be %d-byte aligned", who, io32 ? 8 : 16);
+    if (X_hat && ((uintptr_t)X_hat & 15) != 0) return fail(-1, "%s: X_hat must be 16-byte aligned", who);
+    DetectLlrParams lp;
+    DetectParams& dp = lp.d;
+    if (io32) dp.Y32 = static_cast<const float*>(Y); else dp.Y = static_cast<const double*>(Y);
+    dp.n_frames = n_frames; dp.frames_per_group = frames_per_group; dp.n_sub = n_sub; dp.log2n = l2; dp.n_t = n_t;
+    dp.m = bits_per_sym; dp.p_i = p_i; dp.tx_bits = tx_bits; dp.err = err_count; dp.bits = bit_count; dp.X_hat = X_hat;
+    dp.na_wg = n_t;
+    lp.w = w; lp.mu = mu; lp.llr = llr; lp.sigma2 = sigma2;
+    const int e = launch_detect_llr(lp, (hipStream_t)stream, io32);
+    if (e == -1)                                             // the launcher's check; no served shape reaches it
+        return fail(-2, "%s: N=%d n_t=%d needs 16 (n_t (N + 1) + N/2) = %zu bytes of LDS, %zu are served: use "
+                    "esn_detect_count with X_hat and esn_qam_llr_weighted", who, n_sub, n_t,
+                    detect_llr_lds_bytes(n_sub, n_t), MMSE_LDS_MAX);
+    return hip_fail(e, who);
+}
+
+int esn_detect_llr(const double* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                   const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                   const double* w, const double* mu, double* llr, double* sigma2, double* X_hat, void* stream) {
+    return detect_llr_common("esn_detect_llr", false, Y, n_frames, frames_per_group, n_sub, n_t, bits_per_sym, p_i,
+                             tx_bits, err_count, bit_count, w, mu, llr, sigma2, X_hat, stream);
+}
+
+int esn_detect_llr_f32(const float* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                       const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                       const double* w, const double* mu, double* llr, double* sigma2, double* X_hat, void* stream) {
+    return detect_llr_common("esn_detect_llr_f32", true, Y, n_frames, frames_per_group, n_sub, n_t, bits_per_sym, p_i,
+                             tx_bits, err_count, bit_count, w, mu, llr, sigma2, X_hat, stream);
+}
+
 int esn_ldpc_decode_count(int n_cw, int n, int k, int m_checks, int n_edges, const int* chk_ptr, const int* edge_var,
                           const int* var_ptr, const int* var_edge, const double* y, double snr_db, int maxiter,
                           const uint8_t* u_true, int cw_per_group, uint8_t* x_out, long long* err_count,

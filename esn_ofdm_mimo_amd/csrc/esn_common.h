@@ -282,6 +282,28 @@ struct LlrParams {
     double* llr;             // [B][n_t][N*m]
     double* sigma2;          // optional [B]
 };
+// SINR-weighted soft outputs (esn_soft.hip)
+struct SinrParams {
+    int n_blocks, n_sub, n_t, n_r;
+    const double* p_i; double no;
+    const double* H;         // complex [G][N][n_r][n_t]
+    double* w;               // [G][N][n_t] SINR over the block's mean SINR
+    double* mu;              // [G][N][n_t] bias 1 - t
+    double* gamma_mean;      // optional [G]
+};
+struct SoftLlrParams {
+    LlrParams l;             // frames, shape, X_hat, llr, sigma2 as qam_llr_kernel reads them
+    int frames_per_group;
+    const double* w;         // [G][N][n_t], or nullptr: 1
+    const double* mu;        // [G][N][n_t], or nullptr: 1
+};
+struct DetectLlrParams {
+    DetectParams d;          // tx_bits may be nullptr (nothing is counted; err and bits are then not touched)
+    const double* w;         // as SoftLlrParams
+    const double* mu;
+    double* llr;             // [B][n_t][N*m]
+    double* sigma2;          // optional [B]
+};
 struct LdpcDecodeParams {
     int n_cw, n, k, m_checks, n_edges, maxiter, cw_per_group;
     double var;              // 10^(-snr_db/10)

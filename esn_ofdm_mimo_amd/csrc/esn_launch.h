@@ -149,6 +149,13 @@ int launch_channel_metrics(const ChanStatParams& cp, hipStream_t stream);
 int launch_ldpc_encode(const LdpcEncodeParams& ep, hipStream_t stream);
 int launch_qam_llr(const LlrParams& lp, hipStream_t stream);
 int launch_ldpc_decode(const LdpcDecodeParams& dp, hipStream_t stream);
+// esn_soft.hip; detect_llr_lds_bytes: the LDS of one workgroup of detect_llr_kernel (all n_t rows [N + 1] and N/2
+// twiddles, double2), a function of the shape alone; launch_detect_llr returns -1 where it passes MMSE_LDS_MAX, before any
+// HIP call -- the one check of it, which the entry point reports as -2 with the figures
+int launch_mmse_sinr(const SinrParams& sp, hipStream_t stream);
+int launch_qam_llr_weighted(const SoftLlrParams& lp, hipStream_t stream);
+size_t detect_llr_lds_bytes(int n_sub, int n_t);
+int launch_detect_llr(const DetectLlrParams& dp, hipStream_t stream, bool io32);
 // esn_detect.hip; detect_geometry: the launch of the generic detector kernels (detect_count_kernel, detect_remod_kernel) --
 // as many antennas per workgroup as fit LDS (rows [na][N + 1] and N/2 twiddles, double2), one workgroup per (frame,
 // chunk of antennas), 32 threads per antenna; false where not even one antenna fits

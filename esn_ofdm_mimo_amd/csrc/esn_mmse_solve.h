@@ -1,6 +1,7 @@
 // The per-subcarrier linear solve of the baseline equaliser, written once for the kernels that need X on the chip:
 //   esn_baseline.hip   mmse_detect_kernel (slices X and counts), channel_estimate_kernel (cdiv)
 //   esn_equalize.hip   mmse_equalize_rows_kernel (turns X back into time-domain rows)
+//   esn_soft.hip       mmse_sinr_kernel (mmse_sinr_point: the solve's bias and SINR per stream, no Y)
 // Both go through mmse_spectrum and mmse_solve_point, and the library is built with -ffp-contract=off, so they compile
 // the same operations on the same operands: X_hat of the two kernels is bit-identical.
 #pragma once
@@ -92,6 +93,72 @@ __device__ __forceinline__ void mmse_solve_point(const double* hk, const double2
             acc.x -= t.x; acc.y -= t.y;
         }
         x[c] = cdiv(acc, G[c][c]);
+    }
+}
+
+// t[tx] = lam [(H_k^H H_k + lam I)^-1]_{tx tx}, the error share of stream tx behind the solve above (bias 1 - t, SINR
+// (1 - t) / t): the same Gram matrix by the same operations, eliminated against the identity, one back substitution per
+// column.  t[tx] for tx >= n_t is lam (their rows are the identity); the caller clamps
+__device__ __forceinline__ void mmse_sinr_point(const double* hk, int n_t, int n_r, double lam, double (&t)[MMSE_NT]) {
+    double2 G[MMSE_NT][MMSE_NT], B[MMSE_NT][MMSE_NT];
+#pragma unroll
+    for (int a = 0; a < MMSE_NT; ++a)
+#pragma unroll
+        for (int b = 0; b < MMSE_NT; ++b) {
+            G[a][b] = make_double2(a == b ? lam : 0.0, 0.0);
+            B[a][b] = make_double2(a == b ? 1.0 : 0.0, 0.0);
+        }
+    for (int rx = 0; rx < n_r; ++rx) {
+        double2 h[MMSE_NT];
+#pragma unroll
+        for (int a = 0; a < MMSE_NT; ++a)
+            h[a] = (a < n_t) ? make_double2(hk[((size_t)rx * n_t + a) * 2], hk[((size_t)rx * n_t + a) * 2 + 1])
+                             : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int a = 0; a < MMSE_NT; ++a) {
+            const double2 hc = make_double2(h[a].x, -h[a].y);
+#pragma unroll
+            for (int b = 0; b < MMSE_NT; ++b) {
+                const double2 u = cmul(hc, h[b]);
+                G[a][b].x += u.x; G[a][b].y += u.y;
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < MMSE_NT; ++a)
+        if (a >= n_t) G[a][a] = make_double2(1.0, 0.0);
+#pragma unroll
+    for (int c = 0; c < MMSE_NT; ++c) {
+        const double2 piv = G[c][c];
+#pragma unroll
+        for (int rr = c + 1; rr < MMSE_NT; ++rr) {
+            const double2 f = cdiv(G[rr][c], piv);
+#pragma unroll
+            for (int cc = c; cc < MMSE_NT; ++cc) {
+                const double2 u = cmul(f, G[c][cc]);
+                G[rr][cc].x -= u.x; G[rr][cc].y -= u.y;
+            }
+#pragma unroll
+            for (int j = 0; j <= c; ++j) {                    // B stays lower triangular
+                const double2 u = cmul(f, B[c][j]);
+                B[rr][j].x -= u.x; B[rr][j].y -= u.y;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MMSE_NT; ++j) {                       // column j of the inverse, down to its row j
+        double2 z[MMSE_NT];
+#pragma unroll
+        for (int c = MMSE_NT - 1; c >= j; --c) {
+            double2 acc = B[c][j];
+#pragma unroll
+            for (int cc = c + 1; cc < MMSE_NT; ++cc) {
+                const double2 u = cmul(G[c][cc], z[cc]);
+                acc.x -= u.x; acc.y -= u.y;
+            }
+            z[c] = cdiv(acc, G[c][c]);
+        }
+        t[j] = lam * z[j].x;
     }
 }
 

@@ -8,7 +8,8 @@
 //       esn_equalize.hip mmse_equalize_rows_kernel: the spectrum of mmse_detect_kernel (esn_mmse_solve.h) and, on the
 //                        conjugated solution with the same table, N IFFT_N(X) = conj(FFT_N(conj X))
 //       esn_gen.hip      gen_frames_kernel, x = N IFFT_N(X): the conjugate table
-//   * the unit-power square QAM grid (norm, slicer, level, bits <-> index): the above and qam_llr_kernel (esn_coded.hip)
+//   * the unit-power square QAM grid (norm, slicer, level, bits <-> index): the above and qam_llr_kernel (esn_coded.hip);
+//     the max-log distance of one axis (qam_axis_llr): the soft kernels of esn_soft.hip
 //   * the error-counter tail of the generic kernels (detect, remod, mmse)
 //   * H[k] = sum_j c[j] exp(-2 pi i jk / N): channel_estimate_kernel, taps_to_freq_kernel
 // The library is built with -ffp-contract=off: every product and sum below is rounded on its own, so kernels that go
@@ -96,6 +97,22 @@ __device__ __forceinline__ int det_slice(double v, double norm, int side) {   //
 }
 __device__ __forceinline__ double det_level(int i, int side, double norm) {  // level i of the grid
     return (double)(2 * i - (side - 1)) / norm;
+}
+// lev[a] = det_level(a), a < side (side <= 32), by the whole workgroup; a barrier must follow before the table is read
+__device__ __forceinline__ void qam_levels(double* lev, int side, double norm) {
+    for (int a = threadIdx.x; a < side; a += blockDim.x) lev[a] = det_level(a, side, norm);
+}
+// max-log distance difference d1 - d0 of bit bb of one axis at coordinate t: d1 / d0 the smallest squared distance to a
+// level whose index has bit bb set / clear (the operations of qam_llr_kernel on the levels of qam_levels -- the division
+// by norm is taken once per workgroup, not once per level and bit; positive = bit 0 is nearer)
+__device__ __forceinline__ double qam_axis_llr(double t, int bb, int side, const double* lev) {
+    double d0 = 1e300, d1 = 1e300;
+    for (int a = 0; a < side; ++a) {
+        const double d = t - lev[a];
+        const double dd = d * d;
+        if ((a >> bb) & 1) d1 = fmin(d1, dd); else d0 = fmin(d0, dd);
+    }
+    return d1 - d0;
 }
 // index of the m bits b[0], b[stride], ..
 __device__ __forceinline__ int det_bits_index(const uint8_t* b, size_t stride, int m) {

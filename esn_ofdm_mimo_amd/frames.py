@@ -204,6 +204,23 @@ class FrameSource:
                                                      _lib.stream_handle()), "esn_mmse_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
+    def mmse_sinr(self, H, ebno_db):
+        """What the MMSE equaliser under H [G, N, n_r, n_t] does to every stream of every subcarrier (esn_mmse_sinr):
+        with t = lam [(H_k^H H_k + lam I)^-1]_ii, lam = No / Pi, returns (w, mu, gamma_mean) -- mu = 1 - t the bias,
+        w the SINR (1 - t) / t over the block's mean SINR gamma_mean [G]; w and mu float64 [G, N, n_t], what
+        LdpcCode.llrs and the banks' detect_llr take as weights and bias."""
+        torch, p = self.torch, self.p
+        if H.dtype != torch.complex128 or H.dim() != 4 or tuple(H.shape[1:]) != (p.n_sub, p.n_r, p.n_t):
+            raise ValueError(f"H must be complex128 [G, {p.n_sub}, {p.n_r}, {p.n_t}], not {H.dtype} {tuple(H.shape)}")
+        g = H.shape[0]
+        with torch.cuda.device(self.device):
+            p_i = self.p_i(ebno_db, g)
+            w, mu = (torch.empty((g, p.n_sub, p.n_t), dtype=torch.float64, device=self.device) for _ in range(2))
+            mean = torch.empty((g,), dtype=torch.float64, device=self.device)
+            check(self.lib.esn_mmse_sinr(g, p.n_sub, p.n_t, p.n_r, ptr(p_i), p.no, ptr(H.contiguous()), ptr(w), ptr(mu),
+                                         ptr(mean), _lib.stream_handle()), "esn_mmse_sinr")
+        return w, mu, mean
+
     def equalize_rows(self, H, y, frames_per_block, ebno_db, pad=0, io="f64", want_xhat=False):
         """The MMSE equaliser's output back in the time domain (esn_mmse_equalize_rows): y [B, T, n_r] complex128 and
         H [G, N, n_r, n_t] -> U_eq [B, T + pad, 2 n_t], the rows z = sqrt(Pi) N IFFT(X) behind their cyclic prefix and

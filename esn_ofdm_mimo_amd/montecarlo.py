@@ -36,6 +36,8 @@
                     has it, elm_point or equalized_esn_point redone with the QR solve (points._retry_with_qr)
     equalized_esn_point  one Eb/No point of a small ESN behind the LS-MMSE equaliser (FrameSource.equalize_rows,          points.py
                     esn_mmse_equalize_rows): the equalised signal back in the time domain is the reservoir's input
+    coded_equalized_point  its coded leg: coded_ber_point's payloads through that chain and the fused soft tail          points.py
+                    (detect_llr, esn_detect_llr), LLRs flat or weighted by the equaliser's SINR (FrameSource.mmse_sinr)
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -51,4 +53,5 @@ from .points import cnn_point, cnn_weights  # noqa: F401
 from .points import lstm_point, lstm_weights  # noqa: F401
 from .points import ensemble_point  # noqa: F401
 from .points import equalized_esn_point  # noqa: F401
+from .points import coded_equalized_point  # noqa: F401
 from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters, stream_seed  # noqa: F401

@@ -59,14 +59,14 @@ def _retry_with_qr(body, method):
     return result
 
 
-def _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, salt):
-    """The coded data of G blocks with F data frames each: info bits u [G F, n_t, k] from a generator keyed by
-    (seed, snr_idx, salt), their code words tx_bits [G F, N m, n_t], the blocks' taps, the pilot (bits, x, y), the
-    LS-pattern pilot and the data frames that carry tx_bits."""
-    torch, p, src = sweep.torch, sweep.p, sweep.src
-    gen = torch.Generator(device=sweep.device)
+def _coded_block_data(src, code, ebno_db, snr_idx, G, F, seed, salt):
+    """The coded data of G blocks with F data frames each out of the FrameSource src: info bits u [G F, n_t, k] from a
+    generator keyed by (seed, snr_idx, salt), their code words tx_bits [G F, N m, n_t], the blocks' taps, the pilot
+    (bits, x, y), the LS-pattern pilot and the data frames that carry tx_bits."""
+    torch, p = src.torch, src.p
+    gen = torch.Generator(device=src.device)
     gen.manual_seed((seed * 1000003 + snr_idx * 7919 + salt) % (2 ** 63 - 1))
-    u = torch.randint(0, 2, (G * F, p.n_t, code.k), generator=gen, device=sweep.device, dtype=torch.uint8)
+    u = torch.randint(0, 2, (G * F, p.n_t, code.k), generator=gen, device=src.device, dtype=torch.uint8)
     tx_bits = code.encode(u, p.n_t)
     taps = src.taps(G, snr_idx, 0)
     pilot = src.frames(taps, 1, ebno_db, snr_idx, 0, 0, want_x=True)
@@ -163,7 +163,7 @@ def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=No
     sweep._require_block_fading("coded_ber_point")
     p, src = sweep.p, sweep.src
     F, G = frames_per_block or p.coherence_symbols, n_blocks
-    u, tx_bits, _, (pbits, px, py), py_ls, dy = _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, 12345)
+    u, tx_bits, _, (pbits, px, py), py_ls, dy = _coded_block_data(src, code, ebno_db, snr_idx, G, F, seed, 12345)
     (e_esn, n_esn), x_esn = _esn_leg(sweep, ebno_db, py, px, dy, tx_bits, F, snr_idx, seed)
     # LS/MMSE baseline
     H = src.estimate_channel(pbits, py_ls, ebno_db)
@@ -171,13 +171,18 @@ def coded_ber_point(sweep, code, ebno_db, snr_idx, n_blocks, frames_per_block=No
     out = dict(ESN_uncoded=float(e_esn.sum()) / float(n_esn.sum()), MMSE_uncoded=float(e_mm.sum()) / float(n_mm.sum()))
     n_cal = max(1, int(round(cal_frac * G))) * F                             # frames used for calibration
     for name, xhat in (("ESN", x_esn), ("MMSE", x_mm)):
-        llr, _ = code.llrs(xhat, p.m)
-        a, b = code.fit_calibration(llr[:n_cal], tx_bits[:n_cal], p.m)
-        err, nb = code.decode_count(llr[n_cal:].contiguous(), a, b, u[n_cal:], p.n_t * F, p.m)
-        out[name + "_coded"] = float(err.sum()) / max(float(nb.sum()), 1.0)
-        out["a_" + name.lower()] = a.cpu().numpy()
-        out["b_" + name.lower()] = b.cpu().numpy()
+        _calibrated_leg(out, name, code, code.llrs(xhat, p.m)[0], tx_bits, u, n_cal, p.n_t * F, p.m)
     return out
+
+
+def _calibrated_leg(out, name, code, llr, tx_bits, u, n_cal, cw_per_group, m):
+    """The coded BER of one detector into out[name + "_coded"], with its calibration out["a_" / "b_" + name.lower()]:
+    fit_calibration on the first n_cal frames of llr [B, n_t, N m], decode_count on the rest."""
+    a, b = code.fit_calibration(llr[:n_cal], tx_bits[:n_cal], m)
+    err, nb = code.decode_count(llr[n_cal:].contiguous(), a, b, u[n_cal:], cw_per_group, m)
+    out[name + "_coded"] = float(err.sum()) / max(float(nb.sum()), 1.0)
+    out["a_" + name.lower()] = a.cpu().numpy()
+    out["b_" + name.lower()] = b.cpu().numpy()
 
 
 def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None, decode_every=4, llr_scale=1.5,
@@ -200,7 +205,7 @@ def block_fading_point(sweep, code, ebno_db, snr_idx, n_blocks, fixed_sweep=None
     torch, p, src = sweep.torch, sweep.p, sweep.src
     L = p.coherence_symbols
     F, G = L - 1, n_blocks
-    u, tx_bits, taps, (pbits, px, py), py_ls, dy = _coded_block_data(sweep, code, ebno_db, snr_idx, G, F, seed, 4242)
+    u, tx_bits, taps, (pbits, px, py), py_ls, dy = _coded_block_data(src, code, ebno_db, snr_idx, G, F, seed, 4242)
     xhat = {}
     err = {}
     err["ESN_matched"], xhat["ESN_matched"] = _esn_leg(sweep, ebno_db, py, px, dy, tx_bits, F, snr_idx, seed)
@@ -553,6 +558,55 @@ def ensemble_point(src, ebno_db, snr_idx, n_blocks, *, n_members=4, n_reservoir=
     return _retry_with_qr(point, method)
 
 
+def _equalized_esn_sets(who, src, n_blocks, n_reservoir, ridge, method, delay, spectral_radius, sparsity, precision,
+                        reservoirs, pool, io, first_block, frames_per_block, chunk_blocks):
+    """What equalized_esn_point and coded_equalized_point (`who`) refuse alike, then the host-drawn reservoir sets."""
+    if reservoirs not in ("shared", "per_block"):
+        raise ValueError(f"reservoirs must be 'shared' or 'per_block', not {reservoirs!r} (device-drawn reservoirs are "
+                         "not served behind the equaliser)")
+    _check_esn_point_args(method, io, precision, ridge)
+    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
+    if not isinstance(n_reservoir, int) or n_reservoir < 2:
+        raise ValueError(f"n_reservoir must be an integer of at least 2, not {n_reservoir!r}")
+    if not isinstance(delay, int) or delay < 0:
+        raise ValueError(f"delay must be a non-negative integer, not {delay!r}")
+    if reservoirs == "per_block" and int(pool) < 1:
+        raise ValueError(f"pool = {pool} must be positive")
+    p = src.p
+    if p.continuation:
+        raise ValueError(f"{who} does not go with params.continuation: every frame is predicted from a zero state")
+    if p.n_t > 4:
+        raise ValueError(f"n_t = {p.n_t}: the equaliser kernels serve up to 4 transmit antennas")
+    n_io, n = 2 * p.n_t, n_reservoir
+    with np.errstate(all="ignore"):
+        sets = host_reservoirs(n_io, n_io, n, float(spectral_radius), float(sparsity),
+                               [reservoir_seed(src.seed) + i for i in range(1 if reservoirs == "shared" else int(pool))])
+    if not np.isfinite(sets[0]).all():
+        raise ValueError(f"a drawn {n} x {n} reservoir has no finite spectral radius to scale to (all its eigenvalues "
+                         "are zero): take more units or a smaller sparsity")
+    return sets
+
+
+def _equalized_esn_chunk(src, bank, H, pilot_y, pilot_x, data_y, ebno_db, F, b0, *, delay, ridge, method, precision, io,
+                         seeds):
+    """The detector chain behind the equaliser on one chunk of g = H.shape[0] blocks from global block b0 on: the
+    equalised rows of the dense pilot and of the data frames, `bank` fitted on the pilot rows against the pre-PA pilot
+    delayed by `delay` rows, one predict over the data rows.  Returns (Y, flagged): what a detector tail reads, and how
+    many of the chunk's fits the kernel flagged (a device scalar)."""
+    p, g, n_io = src.p, H.shape[0], 2 * src.p.n_t
+    T, transient = p.t_frame + delay, delay + p.cp
+    U = src.equalize_rows(H, pilot_y, 1, ebno_db, pad=delay)
+    rows = src.equalize_rows(H, data_y, F, ebno_db, pad=delay, io=io)
+    bank.set_scaling(*group_scalings(g, n_io, p.input_scaling(ebno_db), n_io, p.teacher_scale, src.device))
+    _, D = pilot_rows(None, pilot_x, delay)
+    bank.fit(U, D, transient=transient, precision="f64", noise_mode="counter", seed=seeds[0], method=method,
+             group_offset=b0, ridge=None if ridge is None else float(ridge))
+    flagged = bank.fit_status.ne(0).sum()
+    Y = bank.predict(rows, F, T=T, transient=transient, precision=precision, noise_mode="counter", seed=seeds[1],
+                     group_offset=b0, io=io)
+    return Y, flagged
+
+
 def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge=1e-5, method="auto", delay=0,
                         spectral_radius=0.9, sparsity=0.1, noise=0.001, precision="f64", reservoirs="shared", pool=8,
                         io="f64", first_block=0, frames_per_block=None, chunk_blocks=None, want_mmse=False,
@@ -574,36 +628,16 @@ def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge
     first_block cuts the blocks; nothing is read back inside the chunk loop (a flagged fit has the whole point redone
     with method="qr" after it).  want_xhat is test support, not part of a sweep: it appends the detector tail's X_hat,
     complex128 [n_blocks F, N, n_t], and keeps every chunk's alive until the end."""
-    if reservoirs not in ("shared", "per_block"):
-        raise ValueError(f"reservoirs must be 'shared' or 'per_block', not {reservoirs!r} (device-drawn reservoirs are "
-                         "not served behind the equaliser)")
-    _check_esn_point_args(method, io, precision, ridge)
-    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
-    if not isinstance(n_reservoir, int) or n_reservoir < 2:
-        raise ValueError(f"n_reservoir must be an integer of at least 2, not {n_reservoir!r}")
-    if not isinstance(delay, int) or delay < 0:
-        raise ValueError(f"delay must be a non-negative integer, not {delay!r}")
-    if reservoirs == "per_block" and int(pool) < 1:
-        raise ValueError(f"pool = {pool} must be positive")
+    sets = _equalized_esn_sets("equalized_esn_point", src, n_blocks, n_reservoir, ridge, method, delay, spectral_radius,
+                               sparsity, precision, reservoirs, pool, io, first_block, frames_per_block, chunk_blocks)
     torch, p = src.torch, src.p
-    if p.continuation:
-        raise ValueError("equalized_esn_point does not go with params.continuation: every frame is predicted from a "
-                         "zero state")
-    if p.n_t > 4:
-        raise ValueError(f"n_t = {p.n_t}: the equaliser kernels serve up to 4 transmit antennas")
-    n_io, n, d, T, transient = 2 * p.n_t, n_reservoir, delay, p.t_frame + delay, delay + p.cp
+    n_io = 2 * p.n_t
     F, n_blocks = int(frames_per_block or p.coherence_symbols), int(n_blocks)
     chunk = int(chunk_blocks or min(n_blocks, 4096))
-    with np.errstate(all="ignore"):
-        sets = host_reservoirs(n_io, n_io, n, float(spectral_radius), float(sparsity),
-                               [reservoir_seed(src.seed) + i for i in range(1 if reservoirs == "shared" else int(pool))])
-    if not np.isfinite(sets[0]).all():
-        raise ValueError(f"a drawn {n} x {n} reservoir has no finite spectral radius to scale to (all its eigenvalues "
-                         "are zero): take more units or a smaller sparsity")
     seeds = [stream_seed(src.seed, snr_idx, leg) for leg in (0, 1)]
 
     def point(method):
-        bank = ReservoirBank(n_io, n_io, n, *sets, teacher_forcing=True, noise=noise, device=src.device)
+        bank = ReservoirBank(n_io, n_io, n_reservoir, *sets, teacher_forcing=True, noise=noise, device=src.device)
         errors, nbits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) for _ in range(2))
         mm_err, mm_bits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
                            for _ in range(2))
@@ -612,18 +646,13 @@ def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge
         for b0, g, lo in _chunks(first_block, n_blocks, chunk):
             data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
             H = src.estimate_channel(data["pilot_bits"], data["pilot_y_ls"], ebno_db)
-            U = src.equalize_rows(H, data["pilot_y"], 1, ebno_db, pad=d)
-            rows = src.equalize_rows(H, data["data_y"], F, ebno_db, pad=d, io=io)
             if want_mmse:
                 src.mmse_detect_count(H, data["data_y"], data["data_bits"], F, ebno_db, err=mm_err[lo:lo + g],
                                       bits=mm_bits[lo:lo + g])
-            bank.set_scaling(*group_scalings(g, n_io, p.input_scaling(ebno_db), n_io, p.teacher_scale, src.device))
-            _, D = pilot_rows(None, data["pilot_x"], d)
-            bank.fit(U, D, transient=transient, precision="f64", noise_mode="counter", seed=seeds[0], method=method,
-                     group_offset=b0, ridge=None if ridge is None else float(ridge))
-            flagged += bank.fit_status.ne(0).sum()
-            Y = bank.predict(rows, F, T=T, transient=transient, precision=precision, noise_mode="counter", seed=seeds[1],
-                             group_offset=b0, io=io)
+            Y, bad = _equalized_esn_chunk(src, bank, H, data["pilot_y"], data["pilot_x"], data["data_y"], ebno_db, F, b0,
+                                          delay=delay, ridge=ridge, method=method, precision=precision, io=io,
+                                          seeds=seeds)
+            flagged += bad
             out = bank.detect_count(Y, data["data_bits"], src.p_i(ebno_db, g), F, p.n_sub, p.n_t, p.m,
                                     err=errors[lo:lo + g], bits=nbits[lo:lo + g], want_xhat=want_xhat)
             if want_xhat:
@@ -631,3 +660,60 @@ def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge
         return (errors, nbits) + ((mm_err, mm_bits) if want_mmse else ()) + ((torch.cat(kept),) if kept else ()), flagged
 
     return _retry_with_qr(point, method)
+
+
+def coded_equalized_point(src, code, ebno_db, snr_idx, n_blocks, *, llr="sinr", n_reservoir=8, ridge=1e-5, delay=0,
+                          cal_frac=0.3, seed=0, method="auto", spectral_radius=0.9, sparsity=0.1, noise=0.001,
+                          precision="f64", reservoirs="shared", pool=8, io="f64", frames_per_block=None, want_xhat=False):
+    """One Eb/No point of the coded comparison for the ESN behind the LS-MMSE equaliser: the payloads, taps, pilot and
+    data frames of coded_ber_point (_coded_block_data: same generator key, salt 12345), the pilot's channel estimate,
+    the detector chain of equalized_esn_point (_equalized_esn_chunk: same reservoir draw, state-noise streams
+    stream_seed(src.seed, snr_idx, leg) + seed) into the fused soft tail (detect_llr), and the LS-MMSE detector on the
+    same frames (mmse_detect_count, LdpcCode.llrs); then, per detector, the logistic calibration fitted on the first
+    cal_frac of the blocks and sum-product decoding of the rest, as coded_ber_point.
+
+    llr="flat": one decision-directed sigma^2 per frame for every symbol of it, the reference's LLRs -- the MMSE leg is
+    then coded_ber_point's, bit for bit.  llr="sinr": the LLRs of both detectors weighted by the equaliser's SINR per
+    subcarrier and stream over the block's mean, on the symbol with the equaliser's bias taken out
+    (FrameSource.mmse_sinr on the same H); the uncoded columns do not depend on it.  The raw SINR as the scale is not
+    offered: LLRs of magnitude 10^3 make the calibration's gradient steps diverge from 15 dB on.
+
+    One chunk: all n_blocks blocks at once, block 0 first.  Refused arguments are equalized_esn_point's.  Returns
+    coded_ber_point's dictionary: ESN_uncoded, MMSE_uncoded, ESN_coded, MMSE_coded, a_esn, b_esn, a_mmse, b_mmse;
+    want_xhat (test support) adds x_esn, the soft tail's X_hat, complex128 [n_blocks F, N, n_t]."""
+    if llr not in ("sinr", "flat"):
+        raise ValueError(f"llr must be 'sinr' or 'flat', not {llr!r}")
+    if not 0.0 < float(cal_frac) < 1.0:
+        raise ValueError(f"cal_frac = {cal_frac} must be inside (0, 1)")
+    sets = _equalized_esn_sets("coded_equalized_point", src, n_blocks, n_reservoir, ridge, method, delay, spectral_radius,
+                               sparsity, precision, reservoirs, pool, io, 0, frames_per_block, None)
+    torch, p = src.torch, src.p
+    n_io, G = 2 * p.n_t, int(n_blocks)
+    F = int(frames_per_block or p.coherence_symbols)
+    n_cal = max(1, int(round(cal_frac * G))) * F                             # frames used for calibration
+    if n_cal >= G * F:
+        raise ValueError(f"n_blocks = {G} leaves no block to decode behind the {n_cal // F} calibration blocks")
+    if code.n != p.n_sub * p.m:
+        raise ValueError(f"the code's length {code.n} is not the frame's N m = {p.n_sub * p.m} bits per stream")
+    seeds = [stream_seed(src.seed, snr_idx, leg) + int(seed) for leg in (0, 1)]
+    u, tx_bits, _, (pbits, px, py), py_ls, dy = _coded_block_data(src, code, ebno_db, snr_idx, G, F, seed, 12345)
+    H = src.estimate_channel(pbits, py_ls, ebno_db)
+    w, mu = src.mmse_sinr(H, ebno_db)[:2] if llr == "sinr" else (None, None)
+    e_mm, n_mm, x_mm = src.mmse_detect_count(H, dy, tx_bits, F, ebno_db, want_xhat=True)
+    llr_mm = code.llrs(x_mm, p.m, weights=w, bias=mu, frames_per_group=F)[0]
+
+    def esn_leg(method):
+        bank = ReservoirBank(n_io, n_io, n_reservoir, *sets, teacher_forcing=True, noise=noise, device=src.device)
+        Y, flagged = _equalized_esn_chunk(src, bank, H, py, px, dy, ebno_db, F, 0, delay=delay, ridge=ridge,
+                                          method=method, precision=precision, io=io, seeds=seeds)
+        return bank.detect_llr(Y, tx_bits, src.p_i(ebno_db, G), F, p.n_sub, p.n_t, p.m, weights=w, bias=mu,
+                               want_xhat=want_xhat), flagged
+
+    tail = _retry_with_qr(esn_leg, method)
+    e_esn, n_esn, llr_esn = tail[:3]
+    out = dict(ESN_uncoded=float(e_esn.sum()) / float(n_esn.sum()), MMSE_uncoded=float(e_mm.sum()) / float(n_mm.sum()))
+    for name, l in (("ESN", llr_esn), ("MMSE", llr_mm)):
+        _calibrated_leg(out, name, code, l, tx_bits, u, n_cal, p.n_t * F, p.m)
+    if want_xhat:
+        out["x_esn"] = torch.view_as_complex(tail[4].view(G * F, p.n_sub, p.n_t, 2).contiguous())
+    return out

@@ -988,6 +988,42 @@ int esn_ldpc_decode_count(int n_cw, int n, int k, int m_checks, int n_edges,
                           const double* y, double snr_db, int maxiter, const uint8_t* u_true, int cw_per_group,
                           uint8_t* x_out, long long* err_count, long long* bit_count, void* stream);
 
+/* ---- SINR-weighted soft outputs behind the LS-MMSE equaliser (extension: the reference gives every symbol of a frame
+ * one decision-directed sigma^2), float64.  Plain additions: the ABI version stays.
+ * esn_mmse_sinr          per block g, subcarrier k and stream i, with lam = no / p_i[g] and H_k = H[g][k] ([n_r][n_t]):
+ *                          t = lam [(H_k^H H_k + lam I)^-1]_ii clamped to [1e-12, 1 - 1e-12]; the Gram matrix by the
+ *                          operations of esn_mmse_detect_count
+ *                          mu = 1 - t   the equaliser's bias,   gamma = (1 - t) / t   its SINR
+ *                          w  = gamma / gamma_mean[g], gamma_mean[g] the mean of gamma over the block's N n_t entries,
+ *                          summed in an order the shape alone decides (no atomics)
+ *                        w, mu [G][N][n_t]; gamma_mean [G] optional (NULL).  One workgroup per block.
+ * esn_qam_llr_weighted   sigma2[f] bitwise that of esn_qam_llr (taken on X_hat as it is), then, for frame f of group
+ *                        g = f / frames_per_group,
+ *                          llr[f][i][k m + b] = w[g][k][i] (d1 - d0)(X_hat[f][k][i] / mu[g][k][i]) / sigma2[f]
+ *                        with the max-log distances, sign (positive = bit 0) and layout of esn_qam_llr.  w or mu NULL: 1;
+ *                        both NULL: llr is bitwise that of esn_qam_llr.
+ * esn_detect_llr[_f32]   the fused soft tail: esn_detect_count[_f32] on Y (err_count, bit_count and the optional X_hat
+ *                        are bitwise that entry point's) and esn_qam_llr_weighted on its X_hat (llr and sigma2 bitwise),
+ *                        one workgroup per frame, X_hat never in memory unless asked for.  tx_bits may be NULL: nothing is
+ *                        counted.  Every element of llr is written; no atomics but the two counters.  One workgroup holds
+ *                        esn_detect_llr_lds_bytes(N, n_t) = 16 (n_t (N + 1) + N/2) bytes of LDS; beyond 150 KiB the call
+ *                        returns -2 and the caller takes esn_detect_count with X_hat, then esn_qam_llr_weighted.
+ * Served: N a power of two in [2, 2048], 1 <= n_t <= 4, any n_r >= 1, bits_per_sym even in [2, 10]; anything else returns
+ * -1 before any HIP call, the argument named in esn_last_error().  (All of that fits the LDS: 147 520 bytes at N = 2048,
+ * n_t = 4.) */
+int esn_mmse_sinr(int n_blocks, int n_sub, int n_t, int n_r, const double* p_i, double no, const double* H,
+                  double* w, double* mu, double* gamma_mean, void* stream);
+int esn_qam_llr_weighted(int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                         const double* X_hat, const double* w, const double* mu, double* llr, double* sigma2,
+                         void* stream);
+size_t esn_detect_llr_lds_bytes(int n_sub, int n_t);
+int esn_detect_llr(const double* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                   const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                   const double* w, const double* mu, double* llr, double* sigma2, double* X_hat, void* stream);
+int esn_detect_llr_f32(const float* Y, int n_frames, int frames_per_group, int n_sub, int n_t, int bits_per_sym,
+                       const double* p_i, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                       const double* w, const double* mu, double* llr, double* sigma2, double* X_hat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
