@@ -9,7 +9,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libesn_hip.so")
 SOURCES = ["esn_api.hip", "esn_host.hip", "esn_pack.hip", "esn_recur_f64.hip", "esn_recur_f64_mfma.hip", "esn_recur_mfma.hip",
            "esn_big_predict.hip", "esn_big_harvest.hip", "esn_recur_cluster.hip", "esn_recur_mfma_f32.hip", "esn_recur_mfma_f16.hip", "esn_recur_mfma_bf16.hip", "esn_recur_skew16.hip", "esn_harvest_cluster.hip",
-           "esn_solve_qr.hip", "esn_solve_chol.hip", "esn_solve_chol_big.hip", "esn_loo.hip", "esn_holdout.hip", "esn_gram.hip", "esn_detect.hip", "esn_ensemble.hip", "esn_remod.hip", "esn_gen.hip", "esn_reservoir.hip", "esn_specrad_split.hip", "esn_baseline.hip", "esn_equalize.hip", "esn_chantrack.hip", "esn_chanstat.hip", "esn_coded.hip", "esn_soft.hip",
+           "esn_solve_qr.hip", "esn_solve_chol.hip", "esn_solve_chol_big.hip", "esn_loo.hip", "esn_holdout.hip", "esn_gram.hip", "esn_detect.hip", "esn_ensemble.hip", "esn_remod.hip", "esn_gen.hip", "esn_reservoir.hip", "esn_specrad_split.hip", "esn_baseline.hip", "esn_equalize.hip", "esn_dcc.hip", "esn_chantrack.hip", "esn_chanstat.hip", "esn_coded.hip", "esn_soft.hip",
            "esn_elm.hip", "esn_fnn.hip", "esn_cnn.hip", "esn_lstm.hip"]
 # -fno-slp-vectorize: SLP turns adjacent float32 adds/fmas into v_pk_*_f32, which issue far slower
 # than two scalar ops beside MFMAs (measured: predict kernel 13.97 -> 13.42 ms)

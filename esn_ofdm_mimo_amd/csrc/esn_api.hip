@@ -1080,6 +1080,42 @@ int esn_mmse_equalize_rows_f32(int n_frames, int frames_per_group, int n_sub, in
                          no, H, y_cp, U_eq, X_hat, stream);
 }
 
+// ---- amplifier-aware LS-MMSE (esn_dcc.hip): every refusal below comes before any HIP call
+size_t esn_mmse_dcc_lds_bytes(int n_sub, int n_t, int n_r) {
+    if (n_sub <= 0 || n_t <= 0 || n_r <= 0) return 0;
+    return mmse_dcc_lds_bytes(n_sub, n_t, n_r);
+}
+
+int esn_mmse_dcc_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, int n_t, int n_r, int bits_per_sym,
+                              int n_iter, const double* p_i, const double* a_clip, double no, const double* H,
+                              const double* y_cp, const uint8_t* tx_bits, long long* err_count, long long* bit_count,
+                              long long* err_iter, double* X_hat, void* stream) {
+    const char* who = "esn_mmse_dcc_detect_count";
+    if (!p_i) return fail(-1, "%s: p_i is NULL", who);
+    if (!a_clip) return fail(-1, "%s: a_clip is NULL", who);
+    if (!H) return fail(-1, "%s: H is NULL", who);
+    if (!y_cp) return fail(-1, "%s: y_cp is NULL", who);
+    if (tx_bits && (!err_count || !bit_count)) return fail(-1, "%s: tx_bits needs err_count and bit_count", who);
+    if (!tx_bits && !X_hat) return fail(-1, "%s: tx_bits and X_hat are both NULL: nothing to compute", who);
+    int l2;
+    if (int rc = check_n_sub(who, n_sub, &l2)) return rc;
+    if (n_frames <= 0) return fail(-1, "%s: n_frames=%d must be positive", who, n_frames);
+    if (frames_per_group <= 0) return fail(-1, "%s: frames_per_group=%d must be positive", who, frames_per_group);
+    if (cp < 0 || cp >= n_sub) return fail(-1, "%s: cp=%d must be in [0, N) with N=%d", who, cp, n_sub);
+    if (n_t < 1 || n_t > 4) return fail(-1, "%s: n_t=%d must be in [1, 4]", who, n_t);
+    if (n_r < 1) return fail(-1, "%s: n_r=%d must be positive", who, n_r);
+    if (int rc = check_square_qam(who, bits_per_sym)) return rc;
+    if (mmse_dcc_lds_bytes(n_sub, n_t, n_r) > MMSE_LDS_MAX)
+        return fail(-1, "%s: N=%d n_t=%d n_r=%d needs 16 ((n_r + 2 n_t) N + N/2) = %zu bytes of LDS, %zu are served", who,
+                    n_sub, n_t, n_r, mmse_dcc_lds_bytes(n_sub, n_t, n_r), MMSE_LDS_MAX);
+    if (n_iter < 0 || n_iter > DCC_MAX_ITER) return fail(-1, "%s: n_iter=%d must be in [0, %d]", who, n_iter, DCC_MAX_ITER);
+    DccParams d;
+    d.n_frames = n_frames; d.frames_per_group = frames_per_group; d.n_sub = n_sub; d.log2n = l2; d.cp = cp; d.n_t = n_t;
+    d.n_r = n_r; d.m = bits_per_sym; d.n_iter = n_iter; d.p_i = p_i; d.a_clip = a_clip; d.no = no; d.H = H; d.y_cp = y_cp;
+    d.tx_bits = tx_bits; d.err = err_count; d.bits = bit_count; d.err_iter = err_iter; d.X_hat = X_hat;
+    return hip_fail(launch_mmse_dcc(d, (hipStream_t)stream), who);
+}
+
 int esn_channel_track(const double* y_cp, const double* X_hat, const uint8_t* bits, int n_est, int window,
                       int est_per_group, int n_sub, int cp, int n_t, int n_r, int isi, int bits_per_sym,
                       const double* p_i, const double* reg, double* taps, double* H, int* status, void* stream) {

@@ -187,6 +187,19 @@ struct EqRowsParams {
     void* U_eq;                  // [B][cp + N + pad][2 n_t], float64 or float32
     double* X_hat;               // optional complex [B][N][n_t]
 };
+// the MMSE detector with decision-aided cancellation of the amplifier's distortion (esn_dcc.hip)
+struct DccParams {
+    int n_frames, frames_per_group, n_sub, log2n, cp, n_t, n_r, m, n_iter;
+    const double* p_i;           // [groups]
+    const double* a_clip;        // [groups]
+    double no;
+    const double* H;             // complex [G][N][n_r][n_t]
+    const double* y_cp;          // complex [B][T][n_r]
+    const uint8_t* tx_bits;      // [B][N*m][n_t], or nullptr: nothing is counted
+    long long* err; long long* bits;
+    long long* err_iter;         // optional [groups][n_iter + 1]
+    double* X_hat;               // optional complex [B][N][n_t]
+};
 // decision-directed channel estimate (esn_chantrack.hip): estimate e reads frames e window .. e window + window - 1
 struct ChanTrackParams {
     int n_est, window, est_per_group, n_sub, log2n, cp, n_t, n_r, isi, m;

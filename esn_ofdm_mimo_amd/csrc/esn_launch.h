@@ -143,6 +143,11 @@ int launch_taps_to_freq(const TapsFreqParams& tp, hipStream_t stream);
 // esn_equalize.hip: the LDS of one workgroup, a function of the shape alone (served up to MMSE_LDS_MAX)
 size_t equalize_rows_lds_bytes(int n_sub, int n_t, int n_r);
 int launch_equalize_rows(const EqRowsParams& ep, hipStream_t stream, bool io32);
+// esn_dcc.hip: the LDS of one workgroup, a function of the shape alone (served up to MMSE_LDS_MAX; -1 beyond); DCC_MAX_ITER:
+// the cancellation passes one launch serves
+constexpr int DCC_MAX_ITER = 8;
+size_t mmse_dcc_lds_bytes(int n_sub, int n_t, int n_r);
+int launch_mmse_dcc(const DccParams& dp, hipStream_t stream);
 // esn_chanstat.hip
 int launch_channel_metrics(const ChanStatParams& cp, hipStream_t stream);
 // esn_coded.hip

@@ -2,8 +2,9 @@
 //   esn_baseline.hip   mmse_detect_kernel (slices X and counts), channel_estimate_kernel (cdiv)
 //   esn_equalize.hip   mmse_equalize_rows_kernel (turns X back into time-domain rows)
 //   esn_soft.hip       mmse_sinr_kernel (mmse_sinr_point: the solve's bias and SINR per stream, no Y)
-// Both go through mmse_spectrum and mmse_solve_point, and the library is built with -ffp-contract=off, so they compile
-// the same operations on the same operands: X_hat of the two kernels is bit-identical.
+//   esn_dcc.hip        mmse_dcc_kernel (X0, and once per cancellation pass on H D in place of Y)
+// Those with a Y go through mmse_spectrum and mmse_solve_point, and the library is built with -ffp-contract=off, so they compile
+// the same operations on the same operands: their X_hat is bit-identical.
 #pragma once
 #include "esn_common.h"
 #include "esn_ofdm_math.h"

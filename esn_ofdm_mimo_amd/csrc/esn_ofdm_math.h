@@ -7,6 +7,8 @@
 //       esn_chantrack.hip, esn_baseline.hip (channel_estimate_kernel, mmse_detect_kernel)
 //       esn_equalize.hip mmse_equalize_rows_kernel: the spectrum of mmse_detect_kernel (esn_mmse_solve.h) and, on the
 //                        conjugated solution with the same table, N IFFT_N(X) = conj(FFT_N(conj X))
+//       esn_dcc.hip      mmse_dcc_kernel: that spectrum, and per cancellation pass the same pair of transforms on the
+//                        decisions and on the amplifier's predicted distortion
 //       esn_gen.hip      gen_frames_kernel, x = N IFFT_N(X): the conjugate table
 //   * the unit-power square QAM grid (norm, slicer, level, bits <-> index): the above and qam_llr_kernel (esn_coded.hip);
 //     the max-log distance of one axis (qam_axis_llr): the soft kernels of esn_soft.hip

@@ -204,6 +204,49 @@ class FrameSource:
                                                      _lib.stream_handle()), "esn_mmse_detect_count")
         return (err, bits, xh) if want_xhat else (err, bits)
 
+    def mmse_dcc_detect_count(self, H, data_y, data_bits, frames_per_block, ebno_db, n_iter=2, a_clip=None, err=None,
+                              bits=None, want_xhat=False, want_iter_counts=False):
+        """The LS-MMSE detector with n_iter passes of decision-aided cancellation of the amplifier's distortion
+        (esn_mmse_dcc_detect_count): slice, re-modulate, pass the decisions through x / sqrt(1 + (|x|/A)^2), subtract the
+        predicted distortion behind the same equaliser.  n_iter=0 is mmse_detect_count bit for bit.  a_clip: None, the
+        generator's p.a_clip(ebno_db) for every group; a number, or float64 [G] (host or device), a clip level of the
+        caller's -- a wrong one is allowed (mismatch studies), a non-finite or non-positive one is not.  data_bits=None:
+        nothing is counted (then want_xhat must be set).  Returns (err, bits[, X_hat][, err_iter]): the counters of
+        X^{n_iter} per group, X_hat complex128 [B, N, n_t], err_iter int64 [G, n_iter + 1] the errors of X^0 .. X^{n_iter}."""
+        torch, p = self.torch, self.p
+        n_iter = int(n_iter)
+        if not 0 <= n_iter <= 8:
+            raise ValueError(f"n_iter = {n_iter} must be in 0..8")
+        g, b = H.shape[0], data_y.shape[0]
+        if data_bits is None and not want_xhat:
+            raise ValueError("data_bits=None counts nothing: ask for X_hat")
+        with torch.cuda.device(self.device):
+            p_i = self.p_i(ebno_db, g)
+            if a_clip is None:
+                a_clip = self._per_group(p.a_clip(ebno_db), g)
+            else:
+                host = torch.as_tensor(a_clip, dtype=torch.float64).reshape(-1).cpu()
+                if host.numel() not in (1, g):
+                    raise ValueError(f"a_clip must be one number or one per group ({g}), not {host.numel()} entries")
+                if not bool((torch.isfinite(host) & (host > 0)).all()):
+                    raise ValueError("a_clip must be finite and positive")
+                a_clip = host.expand(g).contiguous().to(self.device)
+            if data_bits is not None:
+                if err is None:
+                    err = torch.zeros(g, dtype=torch.int64, device=self.device)
+                if bits is None:
+                    bits = torch.zeros(g, dtype=torch.int64, device=self.device)
+            it = torch.zeros((g, n_iter + 1), dtype=torch.int64, device=self.device) \
+                if want_iter_counts and data_bits is not None else None
+            xh = torch.empty((b, p.n_sub, p.n_t), dtype=torch.complex128, device=self.device) if want_xhat else None
+            check(self.lib.esn_mmse_dcc_detect_count(b, int(frames_per_block), p.n_sub, p.cp, p.n_t, p.n_r, p.m, n_iter,
+                                                     ptr(p_i), ptr(a_clip), p.no, ptr(H.contiguous()),
+                                                     ptr(data_y.contiguous()),
+                                                     ptr(None if data_bits is None else data_bits.contiguous()),
+                                                     ptr(err), ptr(bits), ptr(it), ptr(xh), _lib.stream_handle()),
+                  "esn_mmse_dcc_detect_count")
+        return (err, bits) + ((xh,) if want_xhat else ()) + ((it,) if want_iter_counts else ())
+
     def mmse_sinr(self, H, ebno_db):
         """What the MMSE equaliser under H [G, N, n_r, n_t] does to every stream of every subcarrier (esn_mmse_sinr):
         with t = lam [(H_k^H H_k + lam I)^-1]_ii, lam = No / Pi, returns (w, mu, gamma_mean) -- mu = 1 - t the bias,

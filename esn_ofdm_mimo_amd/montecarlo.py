@@ -38,6 +38,9 @@
                     esn_mmse_equalize_rows): the equalised signal back in the time domain is the reservoir's input
     coded_equalized_point  its coded leg: coded_ber_point's payloads through that chain and the fused soft tail          points.py
                     (detect_llr, esn_detect_llr), LLRs flat or weighted by the equaliser's SINR (FrameSource.mmse_sinr)
+    dcc_point       one Eb/No point of the amplifier-aware LS-MMSE baseline (FrameSource.mmse_dcc_detect_count,          points.py
+                    esn_mmse_dcc_detect_count): decision-aided cancellation of the amplifier's distortion, on the frames
+                    and the channel estimate of equalized_esn_point
 
 The reference redraws a reservoir per coherence block from the global RNG; the sweep
 supports that ("per_block" reservoirs from a pre-drawn pool) and the shared-reservoir mode the
@@ -54,4 +57,5 @@ from .points import lstm_point, lstm_weights  # noqa: F401
 from .points import ensemble_point  # noqa: F401
 from .points import equalized_esn_point  # noqa: F401
 from .points import coded_equalized_point  # noqa: F401
+from .points import dcc_point  # noqa: F401
 from .sweep import DetectorSweep, blocks_for_rank, draw_reservoir, reduce_counters, stream_seed  # noqa: F401

@@ -662,6 +662,43 @@ def equalized_esn_point(src, ebno_db, snr_idx, n_blocks, *, n_reservoir=8, ridge
     return _retry_with_qr(point, method)
 
 
+def dcc_point(src, ebno_db, snr_idx, n_blocks, *, n_iter=2, a_clip_db_error=0.0, first_block=0, frames_per_block=None,
+              chunk_blocks=None, want_mmse=False):
+    """One Eb/No point of the amplifier-aware LS-MMSE baseline (FrameSource.mmse_dcc_detect_count: n_iter passes of
+    decision-aided cancellation of the amplifier's distortion), on the frames equalized_esn_point sees: per chunk
+    blocks_fast(with_ls_pilot=True) and the pilot's channel estimate (estimate_channel).  The detector is told the clip
+    level p.a_clip(ebno_db) times 10^(a_clip_db_error / 20): 0 the generator's own, anything else a mismatch study.
+    Returns (errors, bits, iter_errors): int64 [n_blocks], [n_blocks] and [n_iter + 1] on the device -- the counters of
+    X^{n_iter} per block and the point's bit errors after 0 .. n_iter passes; with want_mmse also (errors, bits) of
+    esn_mmse_detect_count on the same frames and the same H, which n_iter=0 equals bit for bit.  The counters do not
+    depend on chunk_blocks or on how first_block cuts the blocks; nothing is read back.  n_t > 4 is refused."""
+    _check_block_args(n_blocks, first_block, chunk_blocks, frames_per_block)
+    if not isinstance(n_iter, int) or not 0 <= n_iter <= 8:
+        raise ValueError(f"n_iter must be an integer in 0..8, not {n_iter!r}")
+    if not np.isfinite(float(a_clip_db_error)):
+        raise ValueError(f"a_clip_db_error = {a_clip_db_error} must be finite")
+    torch, p = src.torch, src.p
+    if p.n_t > 4:
+        raise ValueError(f"n_t = {p.n_t}: the equaliser kernels serve up to 4 transmit antennas")
+    F, n_blocks = int(frames_per_block or p.coherence_symbols), int(n_blocks)
+    chunk = int(chunk_blocks or min(n_blocks, 4096))
+    a_clip = p.a_clip(ebno_db) * 10.0 ** (float(a_clip_db_error) / 20.0)
+    errors, nbits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) for _ in range(2))
+    mm_err, mm_bits = (torch.zeros(n_blocks, dtype=torch.int64, device=src.device) if want_mmse else None
+                       for _ in range(2))
+    iter_errors = torch.zeros(n_iter + 1, dtype=torch.int64, device=src.device)
+    for b0, g, lo in _chunks(first_block, n_blocks, chunk):
+        data = src.blocks_fast(ebno_db, snr_idx, b0, g, F, with_ls_pilot=True)
+        H = src.estimate_channel(data["pilot_bits"], data["pilot_y_ls"], ebno_db)
+        if want_mmse:
+            src.mmse_detect_count(H, data["data_y"], data["data_bits"], F, ebno_db, err=mm_err[lo:lo + g],
+                                  bits=mm_bits[lo:lo + g])
+        out = src.mmse_dcc_detect_count(H, data["data_y"], data["data_bits"], F, ebno_db, n_iter=n_iter, a_clip=a_clip,
+                                        err=errors[lo:lo + g], bits=nbits[lo:lo + g], want_iter_counts=True)
+        iter_errors += out[2].sum(dim=0)
+    return (errors, nbits, iter_errors) + ((mm_err, mm_bits) if want_mmse else ())
+
+
 def coded_equalized_point(src, code, ebno_db, snr_idx, n_blocks, *, llr="sinr", n_reservoir=8, ridge=1e-5, delay=0,
                           cal_frac=0.3, seed=0, method="auto", spectral_radius=0.9, sparsity=0.1, noise=0.001,
                           precision="f64", reservoirs="shared", pool=8, io="f64", frames_per_block=None, want_xhat=False):

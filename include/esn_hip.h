@@ -712,6 +712,35 @@ int esn_mmse_equalize_rows_f32(int n_frames, int frames_per_group, int n_sub, in
                                const double* p_i, double no, const double* H, const double* y_cp,
                                float* U_eq, double* X_hat, void* stream);
 
+/* ---- Amplifier-aware LS-MMSE (extension: a classical baseline that knows the transmit amplifier), float64.  The frame
+ * recipe passes x through x / sqrt(1 + (|x|/A)^2), A = a_clip; this detector slices, re-modulates, passes its decisions
+ * through that amplifier and subtracts the distortion it predicts, n_iter times, inside one launch.  Frame f belongs to
+ * group g = f / frames_per_group (p_i, a_clip [groups], H [groups]); lam = no / Pi_g, A = a_clip[g], side = 2^(m/2):
+ *   Y_k, X0_k   exactly as esn_mmse_detect_count: X0 is bitwise its X_hat
+ *   for it = 1 .. n_iter:
+ *     S_k[tx]  = the grid point nearest X^{it-1}_k[tx] (slicer and levels of esn_detect_count)
+ *     xt_i[tx] = sqrt(Pi_g) sum_k S_k[tx] e^{+2 pi i ik/N}, i < N (no prefix)
+ *     d_i[tx]  = xt_i / sqrt(1 + (|xt_i|/A)^2) - xt_i
+ *     D_k[tx]  = (1 / (N sqrt(Pi_g))) sum_i d_i[tx] e^{-2 pi i ik/N}
+ *     X^it_k   = X0_k - (H_k^H H_k + lam I)^-1 H_k^H (H_k D_k)
+ *   slicer, bit errors and counters of esn_mmse_detect_count on X^{n_iter}: n_iter = 0 is that entry point bit for bit,
+ *   counters and X_hat.  X_hat (optional, complex [B][N][n_t]) is X^{n_iter}.
+ * err_iter (optional, [groups][n_iter + 1], added to like err_count) takes the bit errors of X^0 .. X^{n_iter}, from the
+ * slicer passes the loop makes anyway.  tx_bits may be NULL: then no counter is touched (err_count, bit_count and err_iter
+ * may be NULL too) and X_hat must be given.  Every sum runs in an order the shape alone decides: a frame's X_hat and error
+ * counts are bitwise the same alone and in any batch.  One workgroup per frame holds esn_mmse_dcc_lds_bytes(N, n_t, n_r) =
+ * 16 ((n_r + 2 n_t) N + N/2) bytes of LDS (Y / H D, X0, the work rows, the twiddle table): 33,792 at N = 128 and 4x8,
+ * 135,168 at N = 512 and 4x8.  Served: N a power of two in [2, 2048], 1 <= n_t <= 4, n_r >= 1, 0 <= cp < N,
+ * 0 <= n_iter <= 8, even bits_per_sym in [2, 10], LDS within 150 KiB; anything else returns -1 before any HIP call, the
+ * argument named in esn_last_error().  a_clip lives in device memory and is not read by the host: its entries must be
+ * finite and positive (a huge A switches the correction off: d = 0). */
+size_t esn_mmse_dcc_lds_bytes(int n_sub, int n_t, int n_r);
+int esn_mmse_dcc_detect_count(int n_frames, int frames_per_group, int n_sub, int cp, int n_t, int n_r,
+                              int bits_per_sym, int n_iter, const double* p_i, const double* a_clip, double no,
+                              const double* H, const double* y_cp, const uint8_t* tx_bits,
+                              long long* err_count, long long* bit_count, long long* err_iter, double* X_hat,
+                              void* stream);
+
 /* ---- Decision-directed channel estimate (extension: the MMSE baseline tracked through a block under Doppler), float64.
  * Estimate e is made from `window` frames stored consecutively, frames e window .. e window + window - 1, and belongs to
  * group e / est_per_group (p_i [groups], reg [groups][isi]).  With w = exp(-2 pi i / N), L = isi, Pi = p_i[group]:
